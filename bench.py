@@ -1,10 +1,17 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json's metric on MI355X: protein-ligand graphs/s for one full SINGA training step
-(zero_grad -> forward -> CrossEntropy -> backward -> [grad all-reduce] -> clip(inf) -> Adam), plus the achieved
-HBM GB/s of the fused alpha-scale + rotate-back + scatter kernel ("scatter-TP", k10) and of gather+rotate (k4)
-against the roofline, plus the CPU oracle timed on this box's host cores.
+(zero_grad -> forward -> CrossEntropy -> backward -> [grad all-reduce] -> clip(inf) -> Adam).  With --full also the
+achieved HBM GB/s of the fused alpha-scale + rotate-back + scatter kernel ("scatter-TP", k10) and of gather+rotate (k4)
+against the roofline, and the CPU oracle timed on this box's host cores.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3_b128_l4] [--scaling weak|strong] [--sweep]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps, optionally writes what the last timed step computed
+(--dump-outputs) and prints the result line.  --full adds every other measurement and check: the per-batch preparation
+and Laplacian-encoding times, the strong-split shard (N = 1), the instrumented eager and in-graph roofline passes, the other
+BASELINE workloads, the CPU-oracle baseline with its HIP-vs-oracle gate and, for N > 1, the weak figure and the
+all-reduce overlap comparison.
 
 Default workload = BASELINE.json configs[2]: 128 CrossDocked-shaped ragged synthetic graphs,
 l_max = 4, full step, one GPU.  N > 1: one rank per GPU over RCCL.  Launched by the driver under torch.distributed.run
@@ -12,7 +19,7 @@ the ranks are taken from the environment; launched bare (`python bench.py --gpus
 processes before touching the GPU and relays rank 0's JSON line.  `--scaling weak` (default): every rank trains on its
 own 128 graphs; `--scaling strong` = BASELINE.json configs[3] (config 4): the SAME 128-graph batch is split over the
 ranks by edge count (dp.shard_ranges_by_cost) and the gradients are combined token-weighted.
-Prints ONE JSON line on rank 0.  Exit code 3 (after the line) if the HIP path's loss or total gradient norm on the
+Prints ONE JSON line on rank 0.  --full: exit code 3 (after the line) if the HIP path's loss or total gradient norm on the
 CPU-oracle sample is further than 1e-4 relative from the oracle's (north_star's tolerance).
 `--sweep`: N = 1, 2, 4, 8 (as many as there are GPUs) back to back, every N a fresh child process, one combined line.
 """
@@ -42,6 +49,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg3_b128_l4")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline figure (see the module docstring); the "
+                         "options below that tune those measurements only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy: its loss and gradient norm, "
+                         "and a fixed sample of the updated parameters and of their gradients")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="N > 1 only.  Default strong = BASELINE.json configs[3] (the SAME batch split over the ranks); the "
                          "weak figure (every rank its own full batch) is then measured too and reported under 'weak'")
@@ -406,6 +419,34 @@ def median(xs):
     return 0.5 * (xs[(n - 1) // 2] + xs[n // 2]) if n else None
 
 
+DUMP_PER_TENSOR = 4096      # elements sampled per parameter: 724 tensors at L = 4 -> at most 12 MB per sampled array
+
+
+def dump_outputs(model, engine, loss, out_dir):
+    """What a caller of the timed step holds after its last call: the returned loss, the gradient norm it clipped with, the
+    updated parameters and their gradients.  The full model is 85 MB per array at L = 4, so every parameter contributes
+    all of its elements or DUMP_PER_TENSOR of them at positions drawn by a fixed seed (the same positions in every run and
+    build); parameters that take no gradient contribute zeros to grads.npy.  float64 scalars, float32 samples."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    gen = torch.Generator().manual_seed(0)
+    params, grads = [], []
+    with torch.no_grad():
+        for p in model.parameters():
+            n = p.numel()
+            idx = torch.arange(n) if n <= DUMP_PER_TENSOR else torch.randperm(n, generator=gen)[:DUMP_PER_TENSOR].sort().values
+            idx = idx.to(p.device)
+            params.append(p.detach().reshape(-1)[idx].float().cpu())
+            g = p.grad
+            grads.append(g.detach().reshape(-1)[idx].float().cpu() if g is not None else torch.zeros(idx.numel()))
+    arrays = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+              "grad_norm": np.array([float(engine.grad_norm)], dtype=np.float64),
+              "params": torch.cat(params).numpy(), "grads": torch.cat(grads).numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def sweep(args):
     """N = 1, 2, 4, 8 (<= visible GPUs) back to back, every N a fresh child process started before this process touches the
     GPU (it never does).  N = 1 runs with SINGA_RCCL_SELFTEST=1, i.e. through the same process-group code path as N > 1 (a
@@ -504,9 +545,10 @@ def roofline_rows(recs, L, tags_k=("k10_fwd", "k10_bwd", "k4_fwd", "k4_bwd_rad",
 
 
 def run_workload(R, workload, steps, warmup, main=True):
-    """One workload through the step engine: generation, warm-up / capture, the timed region, and the measurements around
-    it.  main: the workload `value` is quoted on (strong proxy, eager roofline pass, N > 1 extras); otherwise the lighter
-    set reported under `other_workloads`.  Returns a dict of results; the model / engine are dropped on return."""
+    """One workload through the step engine: generation, warm-up / capture, the timed region, and - with --full - the
+    measurements around it.  main: the workload `value` is quoted on (its outputs are dumped; with --full: strong proxy,
+    eager roofline pass, N > 1 extras); otherwise the lighter set reported under `other_workloads`.  Returns a dict of
+    results; the model / engine are dropped on return."""
     import copy
     import gc
     from singa_amd import dp, graph as G, ops
@@ -517,6 +559,7 @@ def run_workload(R, workload, steps, warmup, main=True):
     from singa_amd.optim import Adam
 
     args, world, rank, dev, multi, selftest, scaling, log = R.args, R.world, R.rank, R.dev, R.multi, R.selftest, R.scaling, R.log
+    full = args.full
     L, kw, base_ids, n_parent = G.resolve_workload(workload)
     n_graphs = len(base_ids)
     cfg = load_config(lmax=L)
@@ -571,7 +614,7 @@ def run_workload(R, workload, steps, warmup, main=True):
     # the run's initial parameters, for the CPU oracle (and for the HIP path's own loss / gradient norm on the CPU sample,
     # computed at the very end of the run)
     state_file = None
-    if main and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and main and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import tempfile
         state_file = os.path.join(tempfile.mkdtemp(prefix="singa_bench_"), "init_state.pt")
         torch.save({k: v.cpu() for k, v in model.state_dict().items()}, state_file)
@@ -605,25 +648,32 @@ def run_workload(R, workload, steps, warmup, main=True):
         exposed = median([a.elapsed_time(b) for a, b in engine.comm_events])
     engine.comm_events = None
     log(f"timed {steps} steps in {elapsed:.3f} s, median step {median(per_step):.3f} ms ({engine.captures} graph capture(s) so far)")
-    # how much of a step is per-batch graph preparation (edge sorting, kNN graphs, dense maps) - measured
-    # separately, it is already inside every timed step
-    torch.cuda.synchronize()
-    t_p = time.perf_counter()
-    for _ in range(3):
-        EF_layers._edge_cache.clear()
-        batch.extras.pop("prepared", None)
-        model.prepare(batch)
-    torch.cuda.synchronize()
-    prepare_ms = (time.perf_counter() - t_p) / 3 * 1e3
-    # the Laplacian positional encoding of one batch (reference: dgl.lap_pe inside forward, GAN:71,77), timed
-    # on its own (it is inside every timed step already)
-    torch.cuda.synchronize()
-    t_p = time.perf_counter()
-    for _ in range(3):
-        for nt, et in ((G.PA, G.E_PP), (G.LA, G.E_LL)):
-            G.laplacian_pe_batched(batch[et]["edge_index"], batch[nt]["batch"], batch.num_graphs, cfg.model.encoder.lap_dim)
-    torch.cuda.synchronize()
-    lap_pe_ms = (time.perf_counter() - t_p) / 3 * 1e3
+    dumped = None
+    if main and rank == 0 and args.dump_outputs:
+        # before anything below runs a step of its own (the eager roofline pass updates the parameters)
+        dumped = dump_outputs(model, engine, loss, args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
+    prepare_ms = lap_pe_ms = None
+    if full:
+        # how much of a step is per-batch graph preparation (edge sorting, kNN graphs, dense maps) - measured
+        # separately, it is already inside every timed step
+        torch.cuda.synchronize()
+        t_p = time.perf_counter()
+        for _ in range(3):
+            EF_layers._edge_cache.clear()
+            batch.extras.pop("prepared", None)
+            model.prepare(batch)
+        torch.cuda.synchronize()
+        prepare_ms = (time.perf_counter() - t_p) / 3 * 1e3
+        # the Laplacian positional encoding of one batch (reference: dgl.lap_pe inside forward, GAN:71,77),
+        # timed on its own (it is inside every timed step already)
+        torch.cuda.synchronize()
+        t_p = time.perf_counter()
+        for _ in range(3):
+            for nt, et in ((G.PA, G.E_PP), (G.LA, G.E_LL)):
+                G.laplacian_pe_batched(batch[et]["edge_index"], batch[nt]["batch"], batch.num_graphs, cfg.model.encoder.lap_dim)
+        torch.cuda.synchronize()
+        lap_pe_ms = (time.perf_counter() - t_p) / 3 * 1e3
 
     res = {"workload": workload, "L": L, "kw": kw, "ids": ids, "base_ids": base_ids, "n_graphs": n_graphs, "n_nodes": n_nodes,
            "n_edges": n_edges, "graphs_per_step": graphs_per_step, "elapsed": elapsed, "per_step": per_step, "own_ms": own_ms,
@@ -632,7 +682,7 @@ def run_workload(R, workload, steps, warmup, main=True):
            "two_phase": bool(getattr(engine, "two_phase", False)), "exposed_ms": exposed, "lap_in_step": lap_in_step,
            "weak": None, "proxy": None, "roof": None, "overlap": None, "per_rank": None, "rccl_ranks": None,
            "host_submit_ms": host_submit_ms, "host_prefetch_ms": host_prefetch_ms,
-           "host_cpu_ms": host_cpu_ms}
+           "host_cpu_ms": host_cpu_ms, "dumped": dumped}
 
     # ---- N > 1: who ran where (the first thing to look at when a scaling point looks wrong)
     if multi:
@@ -651,11 +701,11 @@ def run_workload(R, workload, steps, warmup, main=True):
 
     # ---- N > 1: the overlapped (two-phase) order next to the default one.  Same initial state, same batches, dropout off,
     # the same number of steps in both orders: step time, exposed all-reduce time, and the parameters afterwards must agree.
-    if main and world > 1 and not args.no_overlap_check and use_graph:
+    if full and main and world > 1 and not args.no_overlap_check and use_graph:
         res["overlap"] = overlap_check(R, model, opt, batches, ids, n_graphs, scaling, cfg, bucket, log)
 
     # ---- N > 1, strong split: the weak figure too (every rank its own full batch), same engine, its own captures
-    if main and world > 1 and scaling == "strong" and args.scaling is None:
+    if full and main and world > 1 and scaling == "strong" and args.scaling is None:
         reducer.clear_shard_weight()
         w_ids = [i + rank * n_parent for i in base_ids]
         w_batches = make_batches(w_ids, n_parent * world, 2)
@@ -671,7 +721,7 @@ def run_workload(R, workload, steps, warmup, main=True):
         del w_batches
 
     # ---- N = 1, default workload: the shard ONE rank of the 8-GPU strong split (config 4) would own, timed on this GPU
-    if main and world == 1 and not multi and use_graph and args.proxy_steps > 0 and args.proxy_workload in G.WORKLOADS \
+    if full and main and world == 1 and not multi and use_graph and args.proxy_steps > 0 and args.proxy_workload in G.WORKLOADS \
             and G.WORKLOADS[args.proxy_workload].get("parent") == workload:
         _, _, p_ids, _ = G.resolve_workload(args.proxy_workload)
         p_batches = make_batches(p_ids, n_parent, D)
@@ -690,7 +740,7 @@ def run_workload(R, workload, steps, warmup, main=True):
         del p_batches
 
     # ---- instrumented eager pass: the same step run eagerly with start/stop events attached to every tagged dispatch
-    if main and args.roofline_steps > 0:
+    if full and main and args.roofline_steps > 0:
         if use_graph:
             engine.release()              # give the graph pool back before the eager instrumented steps
         engine.eager_step(batch)          # one un-instrumented eager step first (allocator warm-up)
@@ -758,7 +808,7 @@ def run_workload(R, workload, steps, warmup, main=True):
     # are refused under capture by this ROCm build), replayed a few times.  In a CHILD process (one GPU, after this workload's
     # memory has been handed back): an instrumented capture is not the product path, and whatever goes wrong in it must not
     # take the measured line down with it.
-    if use_graph and args.ingraph_steps > 0 and world == 1 and not multi and rank == 0:
+    if full and use_graph and args.ingraph_steps > 0 and world == 1 and not multi and rank == 0:
         recs, err = ingraph_child(args, workload)
         if recs is not None:
             per_graph, big_g, n_union_g = roofline_rows(recs, L)
@@ -939,7 +989,7 @@ def main():
     # configs[4], so that the driver's record carries them - value, median step, k10 roofline fraction inside the replayed step,
     # Laplacian-encoding time and peak HBM
     others = {}
-    if world == 1 and not multi and not args.eager and args.workload == "cfg3_b128_l4" and args.other_workloads:
+    if args.full and world == 1 and not multi and not args.eager and args.workload == "cfg3_b128_l4" and args.other_workloads:
         for wl in [w for w in args.other_workloads.split(",") if w]:
             if wl not in G.WORKLOADS or wl == args.workload:
                 continue
@@ -1052,7 +1102,9 @@ def main():
                                       if bucket else "one resident batch per GPU, its graph structure rebuilt every step"),
                           "captures_in_timed_region": res["captures_timed"],
                           "prepare": "in step" if args.no_prefetch else "prefetched on a second stream during the previous step",
-                          "prepare_ms_of_step": round(res["prepare_ms"], 2), "lap_pe_ms": round(res["lap_pe_ms"], 2),
+                          # (--full only: separate timings, not parts of the headline measurement)
+                          "prepare_ms_of_step": round(res["prepare_ms"], 2) if res["prepare_ms"] is not None else None,
+                          "lap_pe_ms": round(res["lap_pe_ms"], 2) if res["lap_pe_ms"] is not None else None,
                           "lap_pe": ("recomputed inside every step (preparation phase, prefetch stream) by the library's batched "
                                      "eigensolver singa_lap_eig; lap_pe_ms = the same computation timed on its own"
                                      if res["lap_in_step"] else
@@ -1064,7 +1116,10 @@ def main():
                                              if res["two_phase"] else
                                              "one bucketed all-reduce after the backward pass" if multi else "none (one rank)")},
                "final_loss": round(res["final_loss"], 5), "roofline": roof,
-               "peak_hbm_gb": res["peak_hbm_gb"], "peak_hbm_reserved_gb": res["peak_hbm_reserved_gb"], "hbm_total_gb": res["hbm_total_gb"]}
+               "peak_hbm_gb": res["peak_hbm_gb"], "peak_hbm_reserved_gb": res["peak_hbm_reserved_gb"], "hbm_total_gb": res["hbm_total_gb"],
+               "full": bool(args.full)}
+        if res["dumped"] is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": res["dumped"]}
         if multi:
             out["rccl_ranks"] = res["rccl_ranks"]
             out["per_rank"] = res["per_rank"]

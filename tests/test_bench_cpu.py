@@ -82,3 +82,31 @@ def test_weight_gradient_split_model():
             w = tiles * S
             fill = w / (-(-w // 512) * 512)
             assert fill > 0.9, (rows, tiles, S, fill)
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """bench.dump_outputs (host logic, CPU-held model at the bench's l_max): loss / gradient norm in float64, parameter and
+    gradient samples in float32 at the same positions in every call, zeros for parameters without a gradient, and the
+    whole dump far below the 64 MB bound even at L = 4."""
+    import types
+    import numpy as np
+    import torch
+    from singa_amd.config import load_config
+    from singa_amd.model.GAN import SINGA
+    torch.manual_seed(0)
+    model = SINGA(load_config(lmax=4), device="cpu")
+    ps = list(model.parameters())
+    for i, p in enumerate(ps):
+        if i % 5:
+            p.grad = torch.full_like(p, float(i))
+    engine = types.SimpleNamespace(grad_norm=torch.tensor(2.5))
+    shapes = bench.dump_outputs(model, engine, torch.tensor(1.75), str(tmp_path / "a"))
+    bench.dump_outputs(model, engine, torch.tensor(1.75), str(tmp_path / "b"))
+    load = lambda d, n: np.load(os.path.join(tmp_path, d, f"{n}.npy"))
+    assert load("a", "loss").dtype == np.float64 and float(load("a", "loss")[0]) == 1.75 and float(load("a", "grad_norm")[0]) == 2.5
+    n = sum(min(p.numel(), bench.DUMP_PER_TENSOR) for p in ps)
+    assert shapes["params"] == shapes["grads"] == [n]
+    for name in ("params", "grads"):
+        assert load("a", name).dtype == np.float32 and np.array_equal(load("a", name), load("b", name))
+    assert set(np.unique(load("a", "grads")).tolist()) == {float(i) for i in range(len(ps)) if i % 5} | {0.0}
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) < 64e6

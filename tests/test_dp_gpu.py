@@ -141,24 +141,31 @@ def test_strong_split_of_a_config3_batch_equals_the_union(tmp_path):
         assert abs((n0 * a + n1 * b) / (n0 + n1) - r) < 2e-4 * abs(r), (l0, l1, ref_l)
 
 
-def test_rccl_selftest_one_rank_bench():
+def test_rccl_selftest_one_rank_bench(tmp_path):
     """The N-rank code path of bench.py on a ONE-rank RCCL communicator (SINGA_RCCL_SELFTEST=1): process group on `nccl`,
     same-init check, collective capture decision over the side gloo group, barriers, the bucketed all-reduce between the
     replayed forward+backward graph and the optimizer graph, max-over-ranks timing.  (More ranks need more GPUs: RCCL
-    refuses two ranks on one device.)  The run must produce a normal bench line that moved the gradient payload."""
+    refuses two ranks on one device.)  The run must produce a normal bench line that moved the gradient payload, and
+    --dump-outputs must write the last timed step's loss, gradient norm and parameter / gradient samples."""
     import json
     import subprocess
+    import numpy as np
     env = dict(os.environ, SINGA_RCCL_SELFTEST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
+    dump = str(tmp_path / "out")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2_b32_l2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--roofline-steps", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       timeout=600)
+                        "--no-cpu-baseline", "--roofline-steps", "0", "--dump-outputs", dump], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["final_loss"] == line["final_loss"]
     assert "RCCL self-test" in line["config"]["parallelism"]
     assert line["config"]["grad_allreduce_bytes"] > 60e6            # the L = 2 model's 64 MB of gradients went through RCCL
+    out = {n: np.load(os.path.join(dump, f"{n}.npy")) for n in ("loss", "grad_norm", "params", "grads")}
+    assert abs(float(out["loss"][0]) - line["final_loss"]) < 1e-4 and float(out["grad_norm"][0]) > 0
+    assert out["params"].dtype == np.float32 and out["params"].shape == out["grads"].shape
+    assert np.isfinite(out["params"]).all() and np.isfinite(out["grads"]).all() and np.abs(out["grads"]).max() > 0
 
 
 def test_two_rank_bench_line_explains_itself():
@@ -172,7 +179,7 @@ def test_two_rank_bench_line_explains_itself():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "SINGA_RCCL_SELFTEST"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg2_b32_l2", "--steps", "4",
-                        "--warmup", "1", "--roofline-steps", "0", "--ingraph-steps", "0"], env=env, stdout=subprocess.PIPE,
+                        "--warmup", "1", "--full", "--roofline-steps", "0", "--ingraph-steps", "0"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -1,15 +1,12 @@
 """Host-side data layer (CPU): collate semantics, synthetic generator determinism, Laplacian PE (single vs batched),
-and - only where the reference checkout is mounted - reading its pickled example graphs without torch_geometric."""
+and reading the reference's pickled example graphs (stored as tests/golden/example_*.pt) without torch_geometric."""
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from singa_amd import graph as G
 from tests.helpers import GOLDEN, NAMES
-
-REF_EXAMPLE = "/root/reference/example"
 
 
 def test_collate_offsets_and_ptr():
@@ -64,10 +61,9 @@ def test_laplacian_pe_batched_matches_per_graph():
             assert np.abs(np.linalg.eigvalsh(ritz) - w[1:9]).max() < 1e-5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLE), reason="reference checkout not mounted (GPU box)")
 def test_load_reference_pt_without_pyg():
     for n in NAMES:
-        g = G.load_reference_pt(os.path.join(REF_EXAMPLE, f"{n}.pt"), with_lap=False)
+        g = G.load_reference_pt(os.path.join(GOLDEN, f"example_{n}.pt"), with_lap=False)
         z = np.load(os.path.join(GOLDEN, f"graph_{n}.npz"))
         assert np.array_equal(g[G.PA]["x"].numpy(), z["x_p"]) and np.array_equal(g[G.E_LP]["edge_index"].numpy(), z["ei_lp"])
         assert np.array_equal(g["atomicnum"][G.LA].numpy(), z["z_l"])
