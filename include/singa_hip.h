@@ -176,6 +176,31 @@ int singa_dec_cross_attn(const float* y, const float* wq_t, const float* bq, con
 int singa_dec_ffn(const float* z, const float* w1_t, const float* b1, const float* w2_t, const float* b2, const float* gamma,
                   const float* beta, int R, float* out, float eps, void* stream);
 
+/* Token choice of sampled generation (singa_amd/model/Sampling.py; the reference only has beam search): one launch per
+ * decoding step draws the next token of every row from logits[rows][V] (raw projection outputs, 1 <= V <= 1024) and keeps
+ * the rows' state on the device.  The rule, per row, with u = uniforms[t][row] in [0, 1):
+ *   1. tau == 0: the allowed index of the largest logit z, the lowest index among equals; u is not read.
+ *   2. otherwise s_i = z_i / tau; the allowed tokens are ranked by descending s, equal values by ascending index.
+ *   3. top_k > 0 keeps ranks < top_k.  Then, with q = softmax of s over the tokens still kept, top_p < 1 keeps a token iff the
+ *      mass of the tokens ranked strictly before it is < top_p (rank 0 always stays).
+ *   4. over the kept tokens in vocabulary index order, F_i = inclusive running sum of exp(s_i - max s) / total; the token is
+ *      the smallest kept i with F_i > u, or the last kept index if rounding leaves none.
+ *   5. its log-probability is log-softmax of the unmodified z (tau = 1, no filter, no mask) at that token.
+ * allowed[V]: bytes, 0 = never drawn (null: all allowed); tau >= 0; top_k >= 0 (0 = off); top_p in (0, 1] (1 = off).
+ * Step t = *pos - pos_offset is read on the device (pos: the int64 position counter of the KV caches), so the launch can be
+ * replayed from a captured graph; steps outside 0 .. T - 2 write nothing.  uniforms[>= T - 1][rows].  State, all updated here:
+ *   tokens[rows][T] int64: column t + 1 receives the token;      next[rows] int64: the same token, the next step's input;
+ *   finished[rows] bytes, length[rows], sum_logp[rows]: a row that draws `eos` is finished from the next step on: it then
+ *     emits `pad` and its length (tokens drawn, `eos` included) and summed log-probability stay as they are;
+ *   live[1]: decremented once per row when it finishes (the caller starts it at the number of unfinished rows);
+ *   tok_logp[rows][T] (optional, may be null): column t + 1 receives the token's log-probability (0 for finished rows).
+ * The logits are expected to be finite.  SINGA_E_SHAPE: V outside 1..1024, tau < 0, top_k < 0, top_p outside (0, 1], T < 2,
+ * eos / pad outside [0, V). */
+int singa_sample_token(const float* logits, const float* uniforms, const unsigned char* allowed, const long long* pos,
+                       int pos_offset, int rows, int V, int T, float tau, int top_k, float top_p, int eos, int pad,
+                       unsigned char* finished, int32_t* length, float* sum_logp, long long* tokens, long long* next,
+                       int32_t* live, float* tok_logp, void* stream);
+
 /* k15c — the two per-edge MLPs of the CProMG graph attention (reference model/CProMG.py:41-48 `weight_k_net`,
  * `weight_v_net` = Linear -> ShiftedSoftplus -> Linear, applied at CP:58 and CP:68): wk[E,HK] and wv[E,HV] from
  * attr[E,CIN] in one pass on the f32 MFMA, hidden activations never stored.  Weight matrices in nn.Linear's own layout:

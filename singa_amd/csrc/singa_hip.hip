@@ -1511,6 +1511,180 @@ __global__ void __launch_bounds__(1024) dec_ffn_kernel(const float* __restrict__
     if (t < 256) out[(long long)r * 256 + t] = res;
 }
 
+// ------------------------------------------------------------------------------------------------ token choice of sampled generation
+// singa_sample_token (include/singa_hip.h states the rule): one wavefront per row of raw logits, the row in registers -
+// lane l holds tokens l, l + 64, ... (NPL of them, V <= 64 NPL) - and no LDS: what log-softmax, sort, cumsum, masked
+// renormalisation, multinomial, gather and the row bookkeeping would do in a dozen library launches is one pass.
+//   * ranking without a sort: the rank of token i is the number of tokens j "before" it (s_j > s_i, or equal and j < i) and
+//     the top-p mass in front of it is the sum of their e_j; both come from one loop over j in which (s_j, e_j) is a
+//     wave-uniform v_readlane broadcast.  Everything ranked before a kept token is kept as well, so the loop does not need
+//     to know top-k's outcome.  Skipped when neither filter is on.
+//   * the draw: inclusive wave scan (6 __shfl_up steps per 64 tokens, carry between the NPL groups) of the kept e_i in
+//     vocabulary order, the first F_i > u found with a wave minimum over the hit indices.
+// expf / logf are the accurate ones: the reported log-probability has to hold the fp32 bound of a V-term log-sum-exp.
+#ifndef SINGA_EMUL      // (cross-lane: not part of the sequential CPU emulation build of tests/emul)
+__device__ __forceinline__ int wave_min64i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max64i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float lane_bcast_f(float v, int lane) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+}
+
+template <int NPL>
+__global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
+                                                           const unsigned char* __restrict__ allowed,
+                                                           const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
+                                                           float tau, int top_k, float top_p, int eos, int pad,
+                                                           unsigned char* __restrict__ finished, int32_t* __restrict__ length,
+                                                           float* __restrict__ sum_logp, long long* __restrict__ tokens,
+                                                           long long* __restrict__ next, int32_t* __restrict__ live,
+                                                           float* __restrict__ tok_logp) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                           // wave-uniform from here on
+    const long long t = *pos - pos_offset;                             // decoding step: reads uniforms[t], writes column t + 1
+    if (t < 0 || t + 1 >= T) return;
+    const long long slot = (long long)row * T + t + 1;
+    if (finished[row]) {
+        if (lane == 0) {
+            tokens[slot] = pad;
+            next[row] = pad;
+            if (tok_logp) tok_logp[slot] = 0.f;
+        }
+        return;
+    }
+    const float NEG = -INFINITY;
+    float z[NPL];
+    bool ok[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int i = k * 64 + lane;
+        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
+        ok[k] = i < V && (!allowed || allowed[i]);
+    }
+    // the model's own log-sum-exp (tau = 1, nothing filtered)
+    float zmax = NEG;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
+    zmax = wave_max64(zmax);
+    float zsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
+    const float lse = zmax + logf(wave_sum64(zsum));
+
+    int tok;
+    if (tau == 0.f) {                                                  // greedy: largest allowed logit, lowest index among equals
+        float bv = NEG;
+        int bi = INT32_MAX;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k)
+            if (ok[k] && (bi == INT32_MAX || z[k] > bv)) bv = z[k], bi = k * 64 + lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (oi != INT32_MAX && (bi == INT32_MAX || ov > bv || (ov == bv && oi < bi))) bv = ov, bi = oi;
+        }
+        tok = bi;
+    } else {
+        float s[NPL], e[NPL];
+        bool keep[NPL];
+        float smax = NEG;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            s[k] = ok[k] ? z[k] / tau : NEG;
+            smax = fmaxf(smax, s[k]);
+        }
+        smax = wave_max64(smax);
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            e[k] = ok[k] ? expf(s[k] - smax) : 0.f;
+            keep[k] = ok[k];
+        }
+        if (top_k > 0 || top_p < 1.f) {
+            int rank[NPL];
+            float before[NPL];
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) rank[k] = 0, before[k] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < NPL; ++kk) {
+                const int n = min(64, V - kk * 64);                    // a masked token (s = -inf, e = 0) is never "before" an allowed one
+                for (int l = 0; l < n; ++l) {
+                    const float sj = lane_bcast_f(s[kk], l), ej = lane_bcast_f(e[kk], l);
+                    const int j = kk * 64 + l;
+#pragma unroll
+                    for (int k = 0; k < NPL; ++k) {
+                        const bool b = sj > s[k] || (sj == s[k] && j < k * 64 + lane);
+                        rank[k] += b ? 1 : 0;
+                        before[k] += b ? ej : 0.f;
+                    }
+                }
+            }
+            if (top_k > 0) {
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) keep[k] = keep[k] && rank[k] < top_k;
+            }
+            if (top_p < 1.f) {                                         // q = softmax over what top-k left; rank 0 has nothing before it
+                float part = 0.f;
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) part += keep[k] ? e[k] : 0.f;
+                const float total = wave_sum64(part);
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) keep[k] = keep[k] && before[k] / total < top_p;
+            }
+        }
+        float part = 0.f;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) part += keep[k] ? e[k] : 0.f;
+        const float total = wave_sum64(part);
+        const float u = uniforms[t * rows + row];
+        float carry = 0.f;
+        int hit = INT32_MAX, last = -1;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            float x = keep[k] ? e[k] : 0.f;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float y = __shfl_up(x, o, 64);
+                if (lane >= o) x += y;
+            }
+            if (keep[k]) {
+                last = k * 64 + lane;
+                if (hit == INT32_MAX && (carry + x) / total > u) hit = last;
+            }
+            carry += lane_bcast_f(x, 63);
+        }
+        hit = wave_min64i(hit);
+        tok = hit != INT32_MAX ? hit : wave_max64i(last);
+    }
+    tok = tok < 0 || tok >= V ? pad : tok;                             // no allowed token at all: nothing sensible to draw
+    // the chosen token's own logit: it sits in lane tok % 64, register tok / 64
+    float zt = 0.f;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k)
+        if (tok >> 6 == k) zt = lane_bcast_f(z[k], tok & 63);
+    if (lane == 0) {
+        const float lp = zt - lse;
+        tokens[slot] = tok;
+        next[row] = tok;
+        if (tok_logp) tok_logp[slot] = lp;
+        sum_logp[row] += lp;
+        length[row] += 1;
+        if (tok == eos) {
+            finished[row] = 1;
+            atomicSub(live, 1);
+        }
+    }
+}
+#endif
+
 
 // ------------------------------------------------------------------------------------------------ CProMG edge MLPs on MFMA
 // W_k = L2k(ssp(L1k(attr))), W_v = L2v(ssp(L1v(attr))) for every kNN edge (CP:41-48, 58, 68): two chained GEMMs per net
@@ -6451,6 +6625,36 @@ int singa_dec_ffn(const float* z, const float* w1_t, const float* b1, const floa
     if (R <= 0) return SINGA_OK;
     hipLaunchKernelGGL(dec_ffn_kernel, dim3(R), dim3(1024), 0, (hipStream_t)stream, z, w1_t, b1, w2_t, b2, gamma, beta, out, eps);
     return check_launch("dec_ffn");
+}
+
+int singa_sample_token(const float* logits, const float* uniforms, const unsigned char* allowed, const long long* pos,
+                       int pos_offset, int rows, int V, int T, float tau, int top_k, float top_p, int eos, int pad,
+                       unsigned char* finished, int32_t* length, float* sum_logp, long long* tokens, long long* next,
+                       int32_t* live, float* tok_logp, void* stream) {
+    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live)
+        return fail(SINGA_E_NULL, "sample_token: null pointer");
+    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token: vocabulary of 1..1024 tokens");
+    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token: temperature must be >= 0");
+    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token: top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token: top_p must be in (0, 1]");
+    if (T < 2 || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
+        return fail(SINGA_E_SHAPE, "sample_token: T >= 2 columns, eos / pad inside the vocabulary");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "sample_token: not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
+    hipLaunchKernelGGL(sample_token_kernel<NPL>, grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, \
+                       top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp)
+    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
+    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
+    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
+    else SINGA_SAMPLE_LAUNCH(16);
+#undef SINGA_SAMPLE_LAUNCH
+    return check_launch("sample_token");
+#endif
 }
 
 int singa_edge_mlp_fwd(const float* attr, const float* w1tk, const float* b1k, const float* w2tk, const float* b2k,

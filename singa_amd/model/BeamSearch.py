@@ -69,7 +69,10 @@ class KVDecoder:
     the chosen tokens, all decoder layers, vocabulary projection, log-softmax, candidate top-k) is therefore one HIP
     graph, captured once per search and replayed per token."""
 
-    def __init__(self, decoder, projection, enc_outputs, enc_pad_mask, beams, max_positions, vocab_size, fused=True):
+    def __init__(self, decoder, projection, enc_outputs, enc_pad_mask, beams, max_positions, vocab_size, fused=True,
+                 search_buffers=True):
+        """search_buffers=False leaves out the beam step's own input / output buffers (`step_in`, `step_out`, `logp`): the
+        sampling loop (model/Sampling.py) only uses `token_input` / `prop_input` / `advance`."""
         self.dec, self.proj, self.beams, self.V = decoder, projection, beams, vocab_size
         a0, f0 = decoder.layers[0].dec_self_attn, decoder.layers[0].pos_ffn
         # the step kernels are built for the shipped decoder geometry; anything else takes the library path
@@ -109,12 +112,14 @@ class KVDecoder:
         self.v = torch.zeros(n, self.R, self.heads, max_positions, self.dv, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)            # next position to be written
         self.slots = torch.arange(max_positions, device=dev)
+        self.graph = None
+        if not search_buffers:
+            return
         # the step's inputs (scores, tokens, source rows - one row each, as doubles: exact for fp32 and for indices) and
         # outputs (2*beams ranked candidate scores and flat beam*vocab indices per protein), fixed addresses
         self.step_in = torch.zeros(3, self.R, dtype=torch.float64, device=dev)
         self.step_out = torch.zeros(2, B, 2 * beams, dtype=torch.float64, device=dev)
         self.logp = torch.zeros(self.R, vocab_size, device=dev)
-        self.graph = None
 
     def reset(self):
         self.pos.zero_()

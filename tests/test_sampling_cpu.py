@@ -1,0 +1,100 @@
+"""Sampled generation, the part that runs without a GPU: the argument errors of `singa_sample_token` through the built
+library, the float64 restatement of its rule (tests/sampling_rule.py) against a literal brute-force reading on tiny
+vocabularies, and `sample` / `ops.sample_token` refusing CPU tensors.  The kernel itself uses cross-lane operations (wave
+scans, lane broadcasts) and is therefore, like `singa_lap_pe`, not part of the sequential emulation build: it is compared
+with the restatement on the GPU (tests/test_sampling_gpu.py)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests.sampling_rule import brute_force, choose
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__
+    __graft_entry__.build()
+    from singa_amd import _capi
+    return _capi.bind(__graft_entry__.LIB)
+
+
+def test_sample_token_argument_errors_without_gpu(lib):
+    """Validation happens before any HIP call: SINGA_E_NULL = -1, SINGA_E_SHAPE as the other entry points return it."""
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)                 # never dereferenced: every call below fails its checks
+    shape = lib.singa_edge_mlp_fwd(*([p] * 11), 1, 1, 1, 1, None)       # a known SINGA_E_SHAPE
+    assert shape not in (0, -1)
+
+    def call(V=116, tau=1.0, top_k=0, top_p=1.0, T=8, eos=3, pad=4, logits=p, live=p):
+        return lib.singa_sample_token(logits, p, None, p, 2, 4, V, T, tau, top_k, top_p, eos, pad, p, p, p, p, p, live, None, None)
+
+    assert call(logits=None) == -1 and call(live=None) == -1
+    assert b"sample_token" in lib.singa_last_error_string()
+    for bad in (dict(V=0), dict(V=1025), dict(V=-3), dict(top_p=0.0), dict(top_p=1.5), dict(top_p=-0.1), dict(tau=-0.5),
+                dict(top_k=-1), dict(T=1), dict(eos=116), dict(pad=-1), dict(tau=float("nan")), dict(top_p=float("nan"))):
+        assert call(**bad) == shape, bad
+    assert b"sample_token" in lib.singa_last_error_string()
+    # valid arguments and no rows: nothing to launch
+    assert lib.singa_sample_token(p, p, None, p, 2, 0, 116, 8, 1.0, 0, 1.0, 3, 4, p, p, p, p, p, p, None, None) == 0
+    assert lib.singa_sample_token(p, p, None, p, 2, 0, 1024, 8, 0.0, 7, 1e-6, 3, 4, p, p, p, p, p, p, p, None) == 0
+
+
+def test_restatement_matches_brute_force_on_tiny_vocabularies():
+    rs = np.random.RandomState(0)
+    n = 0
+    for V in (1, 2, 3, 5, 6):
+        for _ in range(120):
+            z = rs.uniform(-3, 3, V)
+            if rs.rand() < 0.4 and V > 1:                 # exact ties
+                z[rs.randint(V)] = z[rs.randint(V)]
+            allowed = None
+            if rs.rand() < 0.3 and V > 1:
+                allowed = rs.rand(V) < 0.6
+                allowed[rs.randint(V)] = True
+            tau = [0.0, 0.5, 1.0, 2.0][rs.randint(4)]
+            top_k = [0, 1, 2, V, V + 3][rs.randint(5)]
+            top_p = [1.0, 0.9, 0.5, 1e-6][rs.randint(4)]
+            u = [0.0, 1 - 2.0 ** -24, rs.rand(), rs.rand()][rs.randint(4)]
+            tok, logp, _ = choose(z, u, tau, top_k, top_p, allowed)
+            assert tok == brute_force(z, u, tau, top_k, top_p, allowed), (V, z, u, tau, top_k, top_p, allowed)
+            assert abs(logp - np.log(np.exp(z[tok]) / np.exp(z).sum())) < 1e-12
+            assert allowed is None or allowed[tok]
+            n += 1
+    assert n == 600
+
+
+def test_restatement_known_cases():
+    z = np.log(np.array([0.1, 0.4, 0.2, 0.3]))
+    assert choose(z, 0.0, 1.0, 0, 1.0)[0] == 0 and choose(z, 0.1 - 1e-9, 1.0, 0, 1.0)[0] == 0  # F = .1 .5 .7 1
+    assert choose(z, 0.1 + 1e-9, 1.0, 0, 1.0)[0] == 1
+    assert choose(z, 0.69, 1.0, 0, 1.0)[0] == 2 and choose(z, 0.999, 1.0, 0, 1.0)[0] == 3
+    assert choose(z, 0.9, 0.0, 0, 1.0)[0] == 1                                              # greedy ignores u
+    assert choose(z, 0.99, 1.0, 2, 1.0)[0] == 3 and choose(z, 0.5, 1.0, 2, 1.0)[0] == 1     # top-2 = {1, 3}: F = 4/7, 1
+    # top-p 0.5: ranks 1, 3, 2, 0 with masses before 0, .4, .7, .9 -> {1, 3} kept; after top-2 the same by renormalised mass
+    assert choose(z, 0.99, 1.0, 0, 0.5)[0] == 3 and choose(z, 0.0, 1.0, 0, 0.5)[0] == 1
+    assert choose(z, 0.99, 1.0, 0, 0.4 - 1e-9)[0] == 1                                      # the mass before rank 1 is .4
+    assert choose(z, 0.99, 1.0, 0, 0.4 + 1e-9)[0] == 3
+    assert choose(z, 0.99, 1.0, 0, 1.0, allowed=[1, 1, 1, 0])[0] == 2                       # F = 1/7, 5/7, 1 over {0, 1, 2}
+    assert choose([1.0, 2.0, 2.0, 0.0], 0.3, 0.0, 0, 1.0)[0] == 1                           # lowest index among equals
+    assert choose([1.0, 2.0, 2.0, 0.0], 0.9, 1.0, 1, 1.0)[0] == 1                           # rank by index among equals
+    tok, logp, amb = choose(z, 0.5 + 1e-7, 1.0, 0, 1.0, eps=1e-5)
+    assert tok == 2 and amb and abs(logp - np.log(0.2)) < 1e-12
+    assert not choose(z, 0.45, 1.0, 0, 1.0, eps=1e-5)[2]
+
+
+def test_sampling_refuses_cpu_tensors():
+    import torch
+
+    from singa_amd import ops
+    from singa_amd.config import Config
+    from singa_amd.model.Sampling import sample
+    ex = Config()
+    ex.protein_atom_feature = torch.zeros(4, 8)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        sample(None, ["&", "$", "^"], 2, 1, 8, ex, device="cpu")
+    state = {"tokens": torch.zeros(2, 4, dtype=torch.int64), "next": torch.zeros(2, dtype=torch.int64),
+             "finished": torch.zeros(2, dtype=torch.uint8), "length": torch.zeros(2, dtype=torch.int32),
+             "sum_logp": torch.zeros(2), "live": torch.zeros(1, dtype=torch.int32)}
+    with pytest.raises(RuntimeError, match="GPU only"):
+        ops.sample_token(torch.zeros(2, 3), torch.zeros(4, 2), torch.zeros(1, dtype=torch.int64), 1, state)

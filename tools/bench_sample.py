@@ -1,0 +1,121 @@
+#!/usr/bin/env python
+"""Throughput of sampled generation (singa_amd/model/Sampling.py) in gen.py's configuration - one protein pocket of 200
+atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket with random-init weights, next to the beam
+step of `tools/bench_beam.py` measured in the same process on the same pocket.
+
+    python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table]
+
+Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
+20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
+per step, and their ratio); with `--table` also both decoder paths at rows = 20, 128, 512, 2048 (the table `fused=None`
+picks from, profiles/sampling/README.md).  A generation is timed as a whole - encoder, cache set-up, graph capture and
+every step - and divided by its steps, as bench_beam.py does.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=128, help="samples drawn for the pocket in one call")
+    ap.add_argument("--max-length", type=int, default=201)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fused", choices=["auto", "k17", "library"], default="auto")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--table", action="store_true")
+    args = ap.parse_args()
+    import __graft_entry__
+    __graft_entry__.build()
+    from singa_amd import graph as G
+    from singa_amd.config import Config, load_config
+    from singa_amd.model.BeamSearch import beam_search
+    from singa_amd.model.CProMG import DenseMap, knn_graph
+    from singa_amd.model.GAN import SINGA
+    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample
+    dev = torch.device("cuda", 0)
+    cfg = load_config(lmax=2)
+    torch.manual_seed(cfg.train.seed)
+    model = SINGA(cfg, device=dev).eval()
+    voc = list(cfg.model.decoder.smiVoc)
+    with torch.no_grad():
+        # as bench_beam.py: keep '$' from ending a run early, so that every run decodes max_length tokens
+        model.model.decoder.layers[-1].pos_ffn.layer_norm.bias[0] = 10.0
+        model.model.projection.weight[voc.index("$")] = 0.0
+        model.model.projection.weight[voc.index("$"), 0] = -3.0
+    b = G.collate([G.synthetic_graph(500)]).to(dev)
+    model.prepare(b)
+    with torch.no_grad():
+        feat = model.embedding(b, gen_mode=True)[G.PA].embedding.reshape(b[G.PA]["x"].shape[0], -1)
+    ex = Config()
+    batch = b[G.PA]["batch"]
+    ex.protein_element_batch, ex.protein_atom_feature, ex.protein_pos = batch, feat, b[G.PA]["pos"]
+    ex.protein_atom_laplacian = b[G.PA]["lap_pe"]
+    knn = knn_graph(b[G.PA]["pos"], cfg.model.encoder.knn, batch, 1, DenseMap(batch, 1))
+    ex.protein_knn = knn[:, knn[0] >= 0]
+    T = args.max_length
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        steps = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / steps
+
+    def run_sample(rows, fused):
+        tr = {}
+        prop = torch.ones(rows, 3, device=dev)
+        sample(model, voc, rows, 1, T, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+               suppress=("$",), generator=gen, fused=fused, trace=tr)
+        run_sample.path = tr["path"]
+        return tr["steps"]
+
+    def run_beam():
+        return beam_search(model, voc, 20, 1, T, 1, ex, torch.ones(20, 3, device=dev), device=dev).shape[1] - 1
+
+    def entry(rows, ms):
+        return {"rows": rows, "ms_per_step": round(ms, 4), "new_tokens_per_s": round(rows / ms * 1e3, 1),
+                "sequences_per_s": round(rows / (ms * (T - 1)) * 1e3, 2)}
+
+    fused = {"auto": None, "k17": True, "library": False}[args.fused]
+    run_beam(), run_sample(20, None), run_sample(args.rows, fused)           # warm-up: library initialisation, code objects
+    beam_ms, samp_ms = [], []
+    for _ in range(max(args.reps, 5)):                                        # interleaved: both see the same machine state
+        beam_ms.append(timed(run_beam))
+        samp_ms.append(timed(lambda: run_sample(20, None)))
+    path20 = run_sample.path
+    bm, sm = statistics.median(beam_ms), statistics.median(samp_ms)
+    main_ms = statistics.median(timed(lambda: run_sample(args.rows, fused)) for _ in range(args.reps))
+    res = {"metric": "sample_new_tokens_per_s", "unit": "tokens/s", "steps": T - 1, "path": run_sample.path}
+    res.update(entry(args.rows, main_ms))
+    res["value"] = res["new_tokens_per_s"]
+    res["at_20_rows"] = {"sample_ms_per_step": round(sm, 4), "beam_ms_per_step": round(bm, 4), "sample_over_beam": round(sm / bm, 4),
+                         "sample_path": path20, "generations_each": len(beam_ms),
+                         "sample_runs_ms": [round(x, 4) for x in samp_ms], "beam_runs_ms": [round(x, 4) for x in beam_ms]}
+    res["config"] = {"workload": "gen.py: 1 pocket (200 atoms), property prompt", "max_length": T, "temperature": args.temperature,
+                     "top_k": args.top_k, "top_p": args.top_p, "launch": "hipGraph replay per step",
+                     "fused_none_picks": "k17 at every row count" if FUSED_MAX_ROWS is None else f"k17 up to {FUSED_MAX_ROWS} rows, library above"}
+    if args.table:
+        table = []
+        for rows in (20, 128, 512, 2048):
+            for name, f in (("k17", True), ("library", False)):
+                run_sample(rows, f)
+                ms = statistics.median(timed(lambda: run_sample(rows, f)) for _ in range(3 if rows >= 512 else args.reps))
+                table.append(dict(entry(rows, ms), path=name))
+        res["table"] = table
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,7 @@
 """Static audit of the library's gfx950 code for two patterns that cost memory round trips inside loops:
 a load followed (within three instructions) by s_waitcnt vmcnt(0), and loads behind per-element branches.
 Compiles singa_hip.hip to assembly and prints, per kernel: such load->wait pairs, all vmcnt(0) waits, loads, branches.
-    python tools/isa_audit.py [top N]"""
+    python tools/isa_audit.py [top N] [name filter]      (e.g. `isa_audit.py 40 sample_token`: the token-choice kernels)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = os.path.join(tempfile.gettempdir(), "singa_audit.s")
@@ -36,7 +36,8 @@ for (k, body), name in zip(kern.items(), names):
                 if ins[j].startswith(LOAD):
                     break
     rows.append((ser, w0, loads, br, name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")))
-rows.sort(reverse=True)
+flt = sys.argv[2] if len(sys.argv) > 2 else ""
+rows = sorted((r for r in rows if flt in r[4]), reverse=True)
 print("load->vmcnt(0)  vmcnt(0)  loads  branches  kernel")
 for r in rows[:int(sys.argv[1]) if len(sys.argv) > 1 else 40]:
     print("%10d %10d %6d %9d   %s" % r)
