@@ -284,14 +284,16 @@ class _RotateBackScatter(torch.autograd.Function):
         CH = y0.shape[1] // lay.seg_rows[0]
         assert y1.shape[1] == lay.seg_rows[1] * CH and y2.shape[1] == lay.seg_rows[2] * CH
         assert alpha.shape == (es.E, heads) and wr.shape == (es.E, lay.WSZ)
+        ctx.save_for_backward(y0, y1, y2, alpha, wr)
+        ctx.es, ctx.heads, ctx.L, ctx.M, ctx.CH = es, heads, L, M, CH
+        if es.E == 0:                             # an edge type without edges: empty tensors have no address to hand over
+            return torch.zeros(es.n_dst, lay.K, CH, device=y0.device, dtype=torch.float32)
         out = torch.empty(es.n_dst, lay.K, CH, device=y0.device, dtype=torch.float32)
         seg, n = _segs3((y0, y1, y2), lay.seg_rows, CH)
         if PROFILE_ON:
             _lib.lib().singa_prof_hint_edges(es.E)
         _chk(_lib.lib().singa_rotate_back_scatter_fwd(seg, n, _p(alpha), _p(wr), _p(es.row_ptr), _p(out), es.n_dst, CH,
                                                       heads, L, M, 0, 1.0, _stream()), "singa_rotate_back_scatter_fwd")
-        ctx.save_for_backward(y0, y1, y2, alpha, wr)
-        ctx.es, ctx.heads, ctx.L, ctx.M, ctx.CH = es, heads, L, M, CH
         return out
 
     @staticmethod
@@ -299,6 +301,8 @@ class _RotateBackScatter(torch.autograd.Function):
         y0, y1, y2, alpha, wr = ctx.saved_tensors
         es, heads, L, M, CH = ctx.es, ctx.heads, ctx.L, ctx.M, ctx.CH
         lay = so3.layout(L, M)
+        if es.E == 0:
+            return torch.zeros_like(y0), torch.zeros_like(y1), torch.zeros_like(y2), torch.zeros_like(alpha), None, None, None, None, None
         g = g.contiguous()
         widths = [y0.shape[1], y1.shape[1], y2.shape[1]]
         gY = torch.empty(es.E, sum(widths), device=g.device, dtype=torch.float32)   # the three gradients as column blocks
@@ -362,6 +366,9 @@ class _SegmentSoftmax(torch.autograd.Function):
         y = torch.empty_like(x)
         N = row_ptr.numel() - 1
         ctx.dense = int(x.shape[1] == 4 and x.shape[0] >= 16 * N)      # >= 16 edges per segment on average: wave per segment
+        if x.shape[0] == 0:                       # no edges: nothing to normalise (and an empty tensor has no address)
+            ctx.save_for_backward(y, row_ptr)
+            return y
         _chk(_lib.lib().singa_segment_softmax_fwd(_p(x), _p(row_ptr), _p(y), N, x.shape[1], eps, ctx.dense, _stream()),
              "singa_segment_softmax_fwd")
         ctx.save_for_backward(y, row_ptr)
@@ -373,6 +380,8 @@ class _SegmentSoftmax(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.empty_like(y)
         N = row_ptr.numel() - 1
+        if y.shape[0] == 0:
+            return gx, None, None
         _chk(_lib.lib().singa_segment_softmax_bwd(_p(y), _p(gy), _p(row_ptr), _p(gx), N, y.shape[1], ctx.dense, _stream()),
              "singa_segment_softmax_bwd")
         return gx, None, None
@@ -390,10 +399,12 @@ class _SegmentWSum(torch.autograd.Function):
         _dev(w, v, row_ptr)
         E, H, F = v.shape
         N = row_ptr.numel() - 1
+        ctx.save_for_backward(w, v, row_ptr)
+        if E == 0:                                # no edges: every segment sums to zero (and empty tensors have no address)
+            return torch.zeros(N, H, F, device=v.device, dtype=torch.float32)
         out = torch.empty(N, H, F, device=v.device, dtype=torch.float32)
         _chk(_lib.lib().singa_segment_wsum_fwd(_p(w), _p(v), _p(row_ptr), _p(out), N, H, F, _stream()),
              "singa_segment_wsum_fwd")
-        ctx.save_for_backward(w, v, row_ptr)
         return out
 
     @staticmethod
@@ -403,6 +414,8 @@ class _SegmentWSum(torch.autograd.Function):
         E, H, F = v.shape
         N = row_ptr.numel() - 1
         gw, gv = torch.empty_like(w), torch.empty_like(v)
+        if E == 0:
+            return gw, gv, None
         _chk(_lib.lib().singa_segment_wsum_bwd(_p(g), _p(w), _p(v), _p(row_ptr), _p(gw), _p(gv), N, H, F, _stream()),
              "singa_segment_wsum_bwd")
         return gw, gv, None
@@ -735,6 +748,10 @@ class _EdgeLogits(torch.autograd.Function):
         _dev(qp, wk, hk, cterm)
         N, H, D = qp.shape
         qk = torch.empty(wk.shape[0], H, device=qp.device, dtype=torch.float32)
+        ctx.edges, ctx.scale = edges, scale
+        if wk.shape[0] == 0:                      # no edges: no logits (and empty tensors have no address to hand over)
+            ctx.save_for_backward(qp, wk, hk)
+            return qk
         _chk(_lib.lib().singa_edge_logits_fwd(_p(qp), _p(wk), _p(hk), _p(cterm), _p(edges.row_ptr), _p(edges.col32),
                                               _p(qk), N, H, D, scale, _stream()), "singa_edge_logits_fwd")
         ctx.save_for_backward(qp, wk, hk)
@@ -748,6 +765,8 @@ class _EdgeLogits(torch.autograd.Function):
         g = g.contiguous()
         g_qp, g_wk, g_hk = torch.empty_like(qp), torch.empty_like(wk), torch.empty_like(hk)
         g_c = torch.empty(N, H, device=g.device, dtype=torch.float32)
+        if wk.shape[0] == 0:
+            return g_qp.zero_(), g_wk, g_hk.zero_(), g_c.zero_(), None, None
         _chk(_lib.lib().singa_edge_logits_bwd(_p(g), _p(qp), _p(wk), _p(hk), _p(e.row_ptr), _p(e.col32), _p(e.col_ptr),
                                               _p(e.eperm), _p(e.row32), _p(g_qp), _p(g_wk), _p(g_hk), _p(g_c), N, H, D,
                                               ctx.scale, _stream()), "singa_edge_logits_bwd")
@@ -766,6 +785,10 @@ class _GatherWSum(torch.autograd.Function):
         _dev(alpha, wv, hv)
         N, H, F = hv.shape
         out = torch.empty(N, H, F, device=hv.device, dtype=torch.float32)
+        ctx.edges = edges
+        if alpha.shape[0] == 0:                   # no edges: every node sums to zero (and empty tensors have no address)
+            ctx.save_for_backward(alpha, wv, hv)
+            return out.zero_()
         _chk(_lib.lib().singa_gather_wsum_fwd(_p(alpha), _p(wv), _p(hv), _p(edges.row_ptr), _p(edges.col32), _p(out), N,
                                               H, F, _stream()), "singa_gather_wsum_fwd")
         ctx.save_for_backward(alpha, wv, hv)
@@ -779,6 +802,8 @@ class _GatherWSum(torch.autograd.Function):
         N, H, F = hv.shape
         g = g.contiguous()
         g_a, g_wv, g_hv = torch.empty_like(alpha), torch.empty_like(wv), torch.empty_like(hv)
+        if alpha.shape[0] == 0:
+            return g_a, g_wv, g_hv.zero_(), None
         _chk(_lib.lib().singa_gather_wsum_bwd(_p(g), _p(alpha), _p(wv), _p(hv), _p(e.row_ptr), _p(e.col32), _p(e.col_ptr),
                                               _p(e.eperm), _p(e.row32), _p(g_a), _p(g_wv), _p(g_hv), N, H, F, _stream()),
              "singa_gather_wsum_bwd")

@@ -26,6 +26,43 @@ def rel_err(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def rowwise_err(got, want, report=None):
+    """max over rows r of |got_r - want_r| / max(|want_r|, median_r |want_r|), both as float64 on the CPU, reshaped to
+    [rows, -1] (rows = the leading axis: edges, nodes, decoder rows, parameter rows; a 1-D tensor is ONE row).  An error
+    confined to a few rows is not diluted by the row count as in one global relative norm; the median floor keeps a
+    near-zero reference row from deciding the test.  `report`: a label - prints the value and the row it was found in."""
+    got = torch.as_tensor(got).detach().cpu().double()
+    want = torch.as_tensor(want).detach().cpu().double()
+    assert got.shape == want.shape, (tuple(got.shape), tuple(want.shape))
+    if want.numel() == 0:
+        return 0.0
+    rows = want.shape[0] if want.dim() > 1 else 1
+    got, want = got.reshape(rows, -1), want.reshape(rows, -1)
+    ref = want.norm(dim=1)
+    err = (got - want).norm(dim=1) / torch.maximum(ref, ref.median()).clamp_min(1e-300)
+    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))        # NaN / inf in `got`: a failure
+    worst = int(err.argmax())
+    if report is not None:
+        print(f"{report}: rowwise_err {float(err[worst]):.3e} at row {worst} of {rows}")
+    return float(err[worst])
+
+
+def cpu_f64(fn, inputs, grad_outs, wrt=None, device=None):
+    """Evaluate `fn` on float64 CPU copies of `inputs` (the CPU reference of a kernel: same formula as the reference's
+    torch code, computed away from the GPU) and return (outputs, gradients w.r.t. inputs[wrt]) - as float64 CPU tensors, or
+    as float32 tensors on `device`."""
+    ins = [t.detach().cpu().double().requires_grad_(True) if (torch.is_tensor(t) and t.is_floating_point()) else
+           (t.cpu() if torch.is_tensor(t) else t) for t in inputs]
+    outs = fn(*ins)
+    single = torch.is_tensor(outs)
+    outs_l = [outs] if single else list(outs)
+    gos = [g.detach().cpu().double() for g in ([grad_outs] if torch.is_tensor(grad_outs) else grad_outs)]
+    idx = range(len(ins)) if wrt is None else wrt
+    grads = torch.autograd.grad(outs_l, [ins[i] for i in idx], gos)
+    to = (lambda t: t.detach()) if device is None else (lambda t: t.detach().float().to(device))
+    return (to(outs) if single else [to(o) for o in outs_l]), [to(g) for g in grads]
+
+
 def product_batch(names, z=None, device="cuda", with_lap=False):
     """Golden graphs as a singa_amd HeteroGraph batch; `z` (a golden npz) pins rot-mats / kNN lists / lap-PE."""
     import os as _os

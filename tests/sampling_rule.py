@@ -98,26 +98,30 @@ def oracle_logits(sd, voc, tokens, feat, pos, batch, lap, knn, prop, batch_size)
     return out[:, 1:].double().numpy()
 
 
-def check_against_oracle(tokens, uniforms, logits, eos, tau, top_k, top_p, eps=EPS):
+def check_against_oracle(tokens, uniforms, logits, eos, tau, top_k, top_p, eps=EPS, allowed=None):
     """Every live decision of `tokens` [rows, T] against the rule applied to the oracle's `logits` [rows, T - 1, V] and the
-    uniforms [T, rows] the kernel read.  -> dict: live decisions, ambiguous ones, unambiguous mismatches [(row, t, got, want)],
-    the oracle's log-probability of every drawn token [rows, T] (0 where the row was finished), lengths."""
+    uniforms [T, rows] the kernel read; `allowed` [V] (0 = never drawn) as handed to the kernel.  -> dict: live decisions,
+    ambiguous ones, unambiguous mismatches [(row, t, got, want)], the oracle's log-probability of every drawn token [rows, T]
+    (0 where the row was finished), lengths, and `checked` [rows, T] bool: column c holds True where the token of column c
+    was a live, unambiguous decision, i.e. one that was compared."""
     tokens, uniforms = np.asarray(tokens), np.asarray(uniforms, np.float64)
     R, T = tokens.shape
     live = amb = 0
     bad, lp = [], np.zeros((R, T))
     lengths = np.zeros(R, np.int64)
+    checked = np.zeros((R, T), bool)
     for r in range(R):
         for t in range(T - 1):
-            want, _, a = choose(logits[r, t], uniforms[t, r], tau, top_k, top_p, eps=eps, exact_ties=False)
+            want, _, a = choose(logits[r, t], uniforms[t, r], tau, top_k, top_p, allowed, eps=eps, exact_ties=False)
             got = int(tokens[r, t + 1])
             z = logits[r, t]
             lp[r, t + 1] = z[got] - (z.max() + np.log(np.exp(z - z.max()).sum()))
             live += 1
             lengths[r] += 1
             amb += a
+            checked[r, t + 1] = not a
             if not a and got != want:
                 bad.append((r, t, got, want))
             if got == eos:
                 break
-    return {"live": live, "ambiguous": amb, "bad": bad, "logp": lp, "lengths": lengths}
+    return {"live": live, "ambiguous": amb, "bad": bad, "logp": lp, "lengths": lengths, "checked": checked}

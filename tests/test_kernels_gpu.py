@@ -462,18 +462,9 @@ def test_edge_head_logits_and_activation():
 
 
 def cpu_f64(fn, inputs, grad_outs, wrt=None):
-    """Evaluate `fn` on float64 CPU copies of `inputs` (the CPU reference of a kernel: same formula as the reference's
-    torch code, computed away from the GPU) and return (outputs, gradients w.r.t. inputs[wrt]) as float32 CUDA tensors."""
-    ins = [t.detach().cpu().double().requires_grad_(True) if (torch.is_tensor(t) and t.is_floating_point()) else
-           (t.cpu() if torch.is_tensor(t) else t) for t in inputs]
-    outs = fn(*ins)
-    single = torch.is_tensor(outs)
-    outs_l = [outs] if single else list(outs)
-    gos = [g.detach().cpu().double() for g in ([grad_outs] if torch.is_tensor(grad_outs) else grad_outs)]
-    idx = range(len(ins)) if wrt is None else wrt
-    grads = torch.autograd.grad(outs_l, [ins[i] for i in idx], gos)
-    to = lambda t: t.detach().float().to(DEV)
-    return (to(outs) if single else [to(o) for o in outs_l]), [to(g) for g in grads]
+    """tests.helpers.cpu_f64 (the float64 CPU reference of a kernel) with the results as float32 CUDA tensors."""
+    from tests.helpers import cpu_f64 as f64
+    return f64(fn, inputs, grad_outs, wrt, device=DEV)
 
 
 @pytest.mark.parametrize("M", [1, 63, 56448])

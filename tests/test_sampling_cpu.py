@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.sampling_rule import brute_force, choose
+from tests.sampling_rule import brute_force, check_against_oracle, choose
 
 
 @pytest.fixture(scope="module")
@@ -81,6 +81,34 @@ def test_restatement_known_cases():
     tok, logp, amb = choose(z, 0.5 + 1e-7, 1.0, 0, 1.0, eps=1e-5)
     assert tok == 2 and amb and abs(logp - np.log(0.2)) < 1e-12
     assert not choose(z, 0.45, 1.0, 0, 1.0, eps=1e-5)[2]
+
+
+def test_check_against_oracle_with_an_allowed_mask():
+    """check_against_oracle on sequences drawn by the rule itself from synthetic logits: with the `allowed` mask the
+    sequences were drawn under, nothing disagrees and every unambiguous live decision is marked as checked; without it
+    (the default), the rule would have drawn suppressed tokens and the sequences disagree; a wrong token is reported."""
+    rs = np.random.RandomState(4)
+    R, T, V, eos = 6, 40, 12, 1
+    logits = rs.uniform(-2, 2, (R, T - 1, V))
+    logits[:, :, eos] += 2.0                                  # '$' is likely: suppressing it changes the draws
+    u = rs.rand(T, R)
+    allowed = np.ones(V, np.uint8)
+    allowed[[0, eos]] = 0
+    for setting in ((1.0, 0, 1.0), (0.8, 5, 0.9)):
+        tokens = np.zeros((R, T), np.int64)
+        for r in range(R):
+            for t in range(T - 1):
+                tokens[r, t + 1] = choose(logits[r, t], u[t, r], *setting, allowed)[0]
+        assert not np.isin(tokens[:, 1:], [0, eos]).any()
+        res = check_against_oracle(tokens, u, logits, eos, *setting, allowed=allowed)
+        assert not res["bad"] and res["live"] == R * (T - 1) and (res["lengths"] == T - 1).all()
+        assert res["checked"].shape == (R, T) and not res["checked"][:, 0].any()
+        assert int(res["checked"].sum()) == res["live"] - res["ambiguous"] and res["ambiguous"] <= 0.02 * res["live"]
+        assert check_against_oracle(tokens, u, logits, eos, *setting)["bad"]
+        wrong = tokens.copy()
+        r, t = np.argwhere(res["checked"])[len(np.argwhere(res["checked"])) // 2]
+        wrong[r, t] = 2 if wrong[r, t] != 2 else 3
+        assert (int(r), int(t) - 1) in [b[:2] for b in check_against_oracle(wrong, u, logits, eos, *setting, allowed=allowed)["bad"]]
 
 
 def test_sampling_refuses_cpu_tensors():
