@@ -30,21 +30,14 @@ class CGemm(C.Structure):
                 ("sigma", C.c_float)]
 
 
-def cgemm_probs(items):
-    arr = (CGemm * len(items))()
+def gemm_probs(items, struct=Gemm):
+    """items: list of dicts with the fields of `struct` (Gemm or CGemm; pointers as ints, missing fields 0) -> (ctypes array, n)"""
+    arr = (struct * len(items))()
     for g, it in zip(arr, items):
         for k, v in it.items():
             setattr(g, k, v)
     return arr, len(items)
 
-
-def gemm_probs(items):
-    """items: list of dicts with the fields of singa_gemm_t (pointers as ints, missing fields 0) -> (ctypes array, n)"""
-    arr = (Gemm * len(items))()
-    for g, it in zip(arr, items):
-        for k, v in it.items():
-            setattr(g, k, v)
-    return arr, len(items)
 
 _SIGS = {
     "singa_version": ([], I32),

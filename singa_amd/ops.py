@@ -6,7 +6,6 @@ inputs exactly as in the reference (`.detach()` at EF:490-491, 2351); backward k
 rotated intermediates.
 """
 import ctypes
-import os
 import math
 import warnings
 
@@ -99,53 +98,6 @@ def branch_stream(device=None):
     if dev not in _branch_streams:
         _branch_streams[dev] = torch.cuda.Stream(device=dev)
     return _branch_streams[dev]
-
-
-DW_SIDE_STREAM = os.environ.get("SINGA_DW_SIDE", "0") == "1"      # OFF: measured slower, see _dw_side
-
-
-class _dw_side:
-    """Context for the launches that produce a WEIGHT gradient while the parameter-gradient queue (_GradSink) is on: nothing
-    in the backward pass waits for them (only the queue's flush does), so they run on the model's second stream beside the
-    chain of input-gradient launches - at shard size (3-7 k rows) those are latency-bound 64 x 64-tile GEMMs that leave most
-    of every CU idle.  Fork: the second stream waits for everything issued so far on the current one (the incoming gradient);
-    join: _GradSink.flush.  Tensors the side launches read are handed to the allocator with record_stream.  No fork when
-    the queue is off (eager callers get their gradients returned), when already on the second stream (the ligand encoder's
-    and the hetero pass's backward run there).  OFF by default (SINGA_DW_SIDE=1 turns it on): correct (engine and GEMM suites
-    pass) but SLOWER in the replayed step - ~200 fork edges per step cost more than the overlap returns on this ROCm build:
-    config 3 150.8 -> 162.0 ms, the 17-graph shard 29.6 -> 40.7 ms (same box, back to back)."""
-
-    def __init__(self, *reads, params=()):
-        """reads: tensors the launches read; params: the parameters whose gradients they produce - the fork only happens
-        when ALL of them take their gradient through the queue (otherwise the caller reduces the partials right away)."""
-        self.reads, self.side, self.ctx = reads, None, None
-        self.direct = all(_GradSink.takes(p) for p in params if p is not None)
-
-    def __enter__(self):
-        if DW_SIDE_STREAM and _GradSink.on and self.direct:
-            cur = torch.cuda.current_stream()
-            side = branch_stream(cur.device)
-            if side != cur:
-                side.wait_stream(cur)
-                self.side, self.cur = side, cur
-                self.ctx = torch.cuda.stream(side)
-                self.ctx.__enter__()
-                _GradSink.forked = True
-        return self
-
-    def keep(self, *outs):
-        """outs: tensors allocated inside the context that the current stream reads later (at the flush)."""
-        if self.side is not None:
-            for t in outs:
-                t.record_stream(self.cur)
-
-    def __exit__(self, *exc):
-        if self.side is not None:
-            self.ctx.__exit__(*exc)
-            for t in self.reads:
-                if t is not None:
-                    t.record_stream(self.side)
-        return False
 
 
 def _p(t):
@@ -490,10 +442,8 @@ class _S2ActEdge(torch.autograd.Function):
         P, Q, A = _grid_factors(L, M, True, h0.device)
         E = h0.shape[0]
         out = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
-        seg, n = _capi.segs([(h0.data_ptr() + 4 * x_off, h0.stride(0), lay.seg_rows[0]),
-                             (h1.data_ptr(), h1.stride(0), lay.seg_rows[1]),
-                             (h2.data_ptr(), h2.stride(0), lay.seg_rows[2])])
-        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, ctypes.c_void_p(h0.data_ptr() + 4 * gate_off), h0.stride(0), _p(P),
+        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P),
                                             _p(Q), _p(A), _p(out), E, C, L, _stream()), "singa_s2act_sep_fwd")
         ctx.save_for_backward(h0, h1, h2)
         ctx.cfg = (gate_off, x_off, C, L, M)
@@ -509,10 +459,8 @@ class _S2ActEdge(torch.autograd.Function):
         E = h0.shape[0]
         gx = torch.empty(E, lay.KR * C, device=g.device, dtype=torch.float32)
         gg = torch.empty(E, C, device=g.device, dtype=torch.float32)
-        seg, n = _capi.segs([(h0.data_ptr() + 4 * x_off, h0.stride(0), lay.seg_rows[0]),
-                             (h1.data_ptr(), h1.stride(0), lay.seg_rows[1]),
-                             (h2.data_ptr(), h2.stride(0), lay.seg_rows[2])])
-        _chk(_lib.lib().singa_s2act_sep_bwd(seg, n, ctypes.c_void_p(h0.data_ptr() + 4 * gate_off), h0.stride(0), _p(P),
+        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+        _chk(_lib.lib().singa_s2act_sep_bwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P),
                                             _p(Q), _p(A), _p(g), _p(gx), _p(gg), E, C, L, _stream()),
              "singa_s2act_sep_bwd")
         n0, n1 = lay.seg_rows[0] * C, lay.seg_rows[1] * C
@@ -547,10 +495,8 @@ class _EdgeHead(torch.autograd.Function):
                                         _stream()), "singa_alpha_logits_fwd")
         P, Q, Az = _grid_factors(L, M, True, h0.device)
         act = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
-        seg, n = _capi.segs([(h0.data_ptr() + 4 * x_off, h0.stride(0), lay.seg_rows[0]),
-                             (h1.data_ptr(), h1.stride(0), lay.seg_rows[1]),
-                             (h2.data_ptr(), h2.stride(0), lay.seg_rows[2])])
-        _chk(lib.singa_s2act_sep_fwd(seg, n, ctypes.c_void_p(h0.data_ptr() + 4 * gate_off), h0.stride(0), _p(P), _p(Q),
+        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+        _chk(lib.singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
                                      _p(Az), _p(act), E, C, L, _stream()), "singa_s2act_sep_fwd")
         ctx.save_for_backward(h0, h1, h2, ln_w, ln_b, dot)
         ctx.cfg = (heads, A, C, L, M, eps)
@@ -580,15 +526,11 @@ class _EdgeHead(torch.autograd.Function):
         if g_dot is not None:
             g_dot = g_dot.view(heads, A)
         P, Q, Az = _grid_factors(L, M, True, h0.device)
-        seg, n = _capi.segs([(h0.data_ptr() + 4 * x_off, h0.stride(0), lay.seg_rows[0]),
-                             (h1.data_ptr(), h1.stride(0), lay.seg_rows[1]),
-                             (h2.data_ptr(), h2.stride(0), lay.seg_rows[2])])
-        gseg, _ = _capi.segs([(g_h0.data_ptr() + 4 * x_off, g_h0.stride(0), lay.seg_rows[0]),
-                              (g_h1.data_ptr(), g_h1.stride(0), lay.seg_rows[1]),
-                              (g_h2.data_ptr(), g_h2.stride(0), lay.seg_rows[2])])
+        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+        gseg, _ = _segs3((g_h0[:, x_off:], g_h1, g_h2), lay.seg_rows, C)
         if E > 0:
-            _chk(lib.singa_s2act_sep_bwd_seg(seg, n, ctypes.c_void_p(h0.data_ptr() + 4 * gate_off), h0.stride(0), _p(P), _p(Q),
-                                             _p(Az), _p(g_act), gseg, ctypes.c_void_p(g_h0.data_ptr() + 4 * gate_off),
+            _chk(lib.singa_s2act_sep_bwd_seg(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
+                                             _p(Az), _p(g_act), gseg, _p(g_h0[:, gate_off:]),
                                              g_h0.stride(0), E, C, L, _stream()), "singa_s2act_sep_bwd_seg")
         return (g_h0, g_h1, g_h2, g_lnw, g_lnb, g_dot, None, None, None, None, None, None)
 
@@ -1173,7 +1115,6 @@ class _GradSink:
     on = False
     found = None       # a dict while the engine records which parameters are produced by sink-aware backward functions
     jobs = []          # (src [M, n] kept alive until the flush, [(col0, flat .grad view)])
-    forked = False     # weight-gradient launches of this pass are running on the second stream (_dw_side): flush joins
     @staticmethod
     def takes(*params):
         """True when every given parameter can receive its gradient directly."""
@@ -1190,10 +1131,6 @@ class _GradSink:
 
     @staticmethod
     def flush():
-        if _GradSink.forked:
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(branch_stream(cur.device))
-            _GradSink.forked = False
         jobs, _GradSink.jobs = _GradSink.jobs, []
         jobs = [j for j in jobs if j[0].shape[0] > 0 and j[0].shape[1] > 0]
         if not jobs:
@@ -1270,9 +1207,6 @@ def bias_add(x, b):
     return _BiasAdd.apply(x, b)
 
 
-import os as _os
-
-
 class _rocblas:
     """Inside: torch's GEMMs go to rocBLAS (the `cublas` backend) instead of hipBLASLt.  Only the generic dense-attention
     branch (head sizes other than the shipped 32 / 64) still multiplies through the library, see _BmmSmall."""
@@ -1325,9 +1259,115 @@ def _rows(t):
     return t
 
 
+def _mat(t, what):
+    """(pointer, rows, columns, row pitch, rows per group, group pitch) of a GEMM operand given as a view: [rows, cols], or
+    [N, n, cols] = N groups of n rows (the 2l+1 coefficient rows of one degree, x[:, l*l:(l+1)**2]).  Raises where the view
+    cannot be addressed that way under the float4 rule of include/singa_hip.h: unit column stride, 16-byte aligned base,
+    pitches that are multiples of 4 floats."""
+    if t.dim() == 2:
+        (rows, cols), ld, grp, gld = t.shape, t.stride(0), 0, 0
+    elif t.dim() == 3:
+        (n, grp, cols), gld, ld = t.shape, t.stride(0), t.stride(1)
+        rows = n * grp
+    else:
+        raise RuntimeError(f"GEMM operand {what}: a 2-D or 3-D view, got {tuple(t.shape)}")
+    ptr = t.data_ptr()
+    bad = ("the columns are not contiguous" if t.stride(-1) != 1 else "the base is not 16-byte aligned" if ptr % 16 else
+           "the pitches are not multiples of 4 floats" if ld % 4 or gld % 4 else None)
+    if bad:
+        raise RuntimeError(f"GEMM operand {what}, shape {tuple(t.shape)}, strides {t.stride()}, address {ptr:#x}: {bad}")
+    return ptr, rows, cols, ld, grp, gld
+
+
+def _like_c(t, C, what):
+    """Pointer of an epilogue operand that the kernel addresses with C's pitches (the pitch of an axis of length 1 is never used)."""
+    pitches = all(st == sc for st, sc, n in zip(t.stride(), C.stride(), C.shape) if n > 1)
+    if t.shape != C.shape or not pitches or t.data_ptr() % 16:
+        raise RuntimeError(f"GEMM {what}: shape {tuple(t.shape)}, strides {t.stride()} must be those of the result "
+                         f"({tuple(C.shape)}, {C.stride()}), 16-byte aligned")
+    return t.data_ptr()
+
+
+def _extents(a_rc, b_rc, a, b, c, unit=""):
+    """(I, J, R) of c[I, J] = sum_r A(i, r) B(r, j) from the (rows, columns) of A, B and C in the given operand form
+    (a_rc: A is [I][R], else [R][I]; b_rc: B is [J][R], else [R][J]) - raises when the three disagree."""
+    (I, Ra), (J, Rb) = (a if a_rc else a[::-1]), (b if b_rc else b[::-1])
+    if Ra != Rb or c != (I, J):
+        raise RuntimeError(f"GEMM form ({int(a_rc)}, {int(b_rc)}): A {a}, B {b} and C {c} (rows, columns{unit}) disagree on I, J, R")
+    return I, J, Ra
+
+
+def _prob(A, B, C, a_rc, b_rc, bias=None, addend=None, mask=None, relu=False, asum=None):
+    """One singa_gemm_t record (the dict _gemm takes) from views of the operands: pointers, pitches and row grouping come
+    from the views (_mat), I, J, R from their shapes (_extents).  C of the (0, 0) form may be a [S, I, J] view of a slab
+    buffer: the dense partial results of S splits, c_split_stride = its stride(0); asum then a [S, I] view of the rows that
+    take the column sums of A.  bias [J]; addend / mask: views laid out like C.  Host checks only, no device work."""
+    a, ar, ac, lda, ag, agl = _mat(A, "A")
+    b, br, bc, ldb, bg, bgl = _mat(B, "B")
+    c, cr, cc, ldc, cg, cgl = _mat(C, "C")
+    slabs = C.dim() == 3 and not a_rc
+    I, J, R = _extents(a_rc, b_rc, (ar, ac), (br, bc), (cg, cc) if slabs else (cr, cc))
+    it = dict(a=a, lda=lda, b=b, ldb=ldb, c=c, ldc=ldc, I=I, J=J, R=R)
+    if ag:
+        it.update(a_group=ag, a_group_ld=agl)
+    if bg:
+        it.update(b_group=bg, b_group_ld=bgl)
+    if slabs:
+        if ldc != J or cgl < I * J:
+            raise RuntimeError(f"GEMM slabs {tuple(C.shape)}, strides {C.stride()}: dense [I, J] blocks that do not overlap")
+        it.update(c_split_stride=cgl)
+    elif cg:
+        it.update(c_group=cg, c_group_ld=cgl)
+    if bias is not None:
+        if bias.shape != (J,) or bias.stride(0) != 1 or bias.data_ptr() % 16:
+            raise RuntimeError(f"GEMM bias: a contiguous 16-byte aligned [{J}], got {tuple(bias.shape)}")
+        it.update(bias=bias.data_ptr())
+    if addend is not None:
+        it.update(addend=_like_c(addend, C, "addend"))
+    if mask is not None:
+        it.update(mask=_like_c(mask, C, "mask"))
+    if relu:
+        it.update(relu=1)
+    if asum is not None:
+        if (a_rc or ag or asum.dim() != 2 or asum.shape[1] != I or asum.stride(1) != 1
+                or (slabs and asum.shape[0] != C.shape[0])):
+            raise RuntimeError(f"GEMM asum {tuple(asum.shape)}: one contiguous row of I = {I} floats per split, (0, 0) form, plain A rows")
+        it.update(asum=asum.data_ptr(), asum_stride=asum.stride(0))
+    return it
+
+
+def _cprob(A, B, C, a_rc, b_rc, sigma):
+    """One singa_cgemm_t record (the dict _cgemm takes).  A, B, C: (real part, imaginary part) pairs of views - the caller
+    names the layout by how it halves the stored matrix: `X.chunk(2, 1)` for [x_+ | x_-] column halves, `w.chunk(2, 0)` for
+    [Wr; Wi] row halves.  a_im / b_im / c_im are the distances between the two parts; I, J, R count complex elements.  C of
+    the (0, 0) form may be a pair of [S, I, J] slab views as in _prob."""
+    parts = []
+    for (re, im), what in zip((A, B, C), "ABC"):
+        ptr, rows, cols, ld, grp, gld = _mat(re, what)
+        off = im.data_ptr() - ptr
+        if im.shape != re.shape or im.stride() != re.stride() or off % 16:
+            raise RuntimeError(f"complex GEMM operand {what}: the imaginary part {tuple(im.shape)}, strides {im.stride()} must be "
+                             f"laid out like the real part {tuple(re.shape)}, {re.stride()}, a multiple of 4 floats away")
+        parts.append((ptr, rows, cols, ld, grp, gld, off // 4))
+    (a, ar, ac, lda, ag, _, a_im), (b, br, bc, ldb, bg, _, b_im), (c, cr, cc, ldc, cg, cgl, c_im) = parts
+    slabs = cg > 0 and not a_rc
+    if ag or bg or (cg and not slabs):
+        raise RuntimeError("complex GEMM: plain rows only (no grouped operands)")
+    I, J, R = _extents(a_rc, b_rc, (ar, ac), (br, bc), (cg, cc) if slabs else (cr, cc), ", complex")
+    it = dict(a=a, lda=lda, a_im=a_im, b=b, ldb=ldb, b_im=b_im, c=c, ldc=ldc, c_im=c_im, I=I, J=J, R=R, sigma=sigma)
+    if slabs:
+        it.update(c_split_stride=cgl)
+    return it
+
+
 def _gemm(items, a_rc, b_rc, splits=1):
     arr, n = _capi.gemm_probs(items)
     _chk(_lib.lib().singa_gemm_f32(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), "singa_gemm_f32")
+
+
+def _cgemm(items, a_rc, b_rc, splits=1):
+    arr, n = _capi.gemm_probs(items, _capi.CGemm)
+    _chk(_lib.lib().singa_cgemm3m_f32(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), "singa_cgemm3m_f32")
 
 
 def _splits_for(rows, tiles=None):
@@ -1360,6 +1400,47 @@ def _splits_few(rows, tiles):
     return best
 
 
+def _dw_grads(probs, splits, cplx=False):
+    """The weight gradients of ONE split-reduction launch.  probs: [(A, B, weight parameter, bias parameter or None)] - the
+    (0, 0)-form products dW = A^T B over the rows of the views A [rows, out] and B [rows, in] (grouped rows allowed), whose
+    result is (a part of) the parameter in the parameter's own layout; problems in a row that name the same parameter fill it
+    front to back.  A bias parameter takes the column sums of A from the same launch (asum).  cplx: A = [g_r | g_i], B =
+    [x_+ | x_-] column halves, the result an fc weight [Wr; Wi] (singa_cgemm3m_f32, no bias).  The partial slabs of all
+    problems, then the asum rows, are the columns of one [splits, row] buffer that param_colsum adds up.
+    -> ([gradient per distinct weight parameter, shaped like it], [gradient per bias parameter]): None where the sum was
+    queued into .grad (_GradSink), zeros when there are no rows to reduce over."""
+    dims = [(A.shape[-1], B.shape[-1] // 2 if cplx else B.shape[-1]) for A, B, _, _ in probs]
+    sizes = [i * j for i, j in dims] + [i for (i, _), p in zip(dims, probs) if p[3] is not None]
+    targets, off = [], 0                   # (first column, columns, parameter) in the buffer's order
+    for sz, (_, _, w, _) in zip(sizes, probs):
+        if targets and targets[-1][2] is w:
+            targets[-1] = (targets[-1][0], targets[-1][1] + sz, w)
+        else:
+            targets.append((off, sz, w))
+        off += sz
+    nw = len(targets)
+    for sz, bias in zip(sizes[len(probs):], [p[3] for p in probs if p[3] is not None]):
+        targets.append((off, sz, bias))
+        off += sz
+    A0 = probs[0][0]
+    if A0.numel() == 0:
+        res = [torch.zeros(n, device=A0.device, dtype=torch.float32) for _, n, _ in targets]
+    else:
+        part = torch.empty(splits, off, device=A0.device, dtype=torch.float32)
+        blocks = part.split(sizes, 1)
+        asums = iter(blocks[len(probs):])
+        items = []
+        for (A, B, _, bias), (i, j), blk in zip(probs, dims, blocks):
+            slab = blk.as_strided((splits, i, j), (off, j, 1))      # (unflatten would make up a pitch for a single split)
+            if cplx:
+                items.append(_cprob(A.chunk(2, 1), B.chunk(2, 1), slab.chunk(2, 1), False, False, -1.0))
+            else:
+                items.append(_prob(A, B, slab, False, False, asum=next(asums) if bias is not None else None))
+        (_cgemm if cplx else _gemm)(items, False, False, splits)
+        res = param_colsum(part, targets)
+    return [g.view(p.shape) if g is not None else None for g, (_, _, p) in zip(res[:nw], targets)], res[nw:]
+
+
 def gemm_nt(x, w, bias=None, out=None):
     """y = x w^T (+ bias) on the library's own MFMA kernel; x [M, K] (row-strided views allowed), w [N, K]."""
     x, w = _rows(x), _rows(w)
@@ -1368,8 +1449,7 @@ def gemm_nt(x, w, bias=None, out=None):
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    _gemm([dict(a=x.data_ptr(), lda=x.stride(0), b=w.data_ptr(), ldb=w.stride(0), c=out.data_ptr(), ldc=out.stride(0),
-                bias=bias.data_ptr() if bias is not None else None, I=M, J=N, R=K)], True, True)
+    _gemm([_prob(x, w, out, True, True, bias=bias)], True, True)
     return out
 
 
@@ -1392,64 +1472,32 @@ class _SO2Linear3(torch.autograd.Function):
         outs = tuple(w.shape[0] for w in ws)
         assert all(w.shape[1] == k for w, k in zip(ws, ins))
         H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
-        items, ai, ci = [], 0, 0
-        for w, k, o, b in zip(ws, ins, outs, (b0, None, None)):
-            items.append(dict(a=X.data_ptr() + 4 * ai, lda=X.stride(0), b=w.data_ptr(), ldb=w.stride(0),
-                              c=H.data_ptr() + 4 * ci, ldc=H.stride(0), bias=b.data_ptr() if b is not None else None,
-                              I=E, J=o, R=k))
-            ai, ci = ai + k, ci + o
+        hs = H.split(outs, 1)
         if E > 0:
-            _gemm(items, True, True)
+            _gemm([_prob(x, w, h, True, True, bias=b) for x, w, h, b in zip(X.split(ins, 1), ws, hs, (b0, None, None))],
+                  True, True)
         ctx.save_for_backward(X, *ws)
-        ctx.ins, ctx.outs = ins, outs
-        o0, o1 = outs[0], outs[0] + outs[1]
-        return H[:, :o0], H[:, o0:o1], H[:, o1:]
+        ctx.ins = ins
+        return hs
 
     @staticmethod
     def backward(ctx, g0, g1, g2):
-        X, w0, w1, w2 = ctx.saved_tensors
-        ins, outs = ctx.ins, ctx.outs
+        X, *ws = ctx.saved_tensors
+        ins, outs = ctx.ins, tuple(w.shape[0] for w in ws)
         E = X.shape[0]
         gs = [_rows(g) for g in (g0, g1, g2)]
-        ws = (w0, w1, w2)
+        xs = X.split(ins, 1)
         gX = None
         if ctx.needs_input_grad[0]:
             gX = torch.empty_like(X)
-            items, ai = [], 0
-            for g, w, k, o in zip(gs, ws, ins, outs):       # dX_blk = g_blk @ w_blk: A = g [E, o] (RC), B = w [o, k] ([R][J])
-                items.append(dict(a=g.data_ptr(), lda=g.stride(0), b=w.data_ptr(), ldb=w.stride(0),
-                                  c=gX.data_ptr() + 4 * ai, ldc=gX.stride(0), I=E, J=k, R=o))
-                ai += k
-            if E > 0:
-                _gemm(items, True, False)
-        # dW_blk = g_blk^T X_blk: reduction over the edges, split over workgroups into dense partial slabs
-        sizes = [o * k for o, k in zip(outs, ins)]
-        tot = sum(sizes)
-        row = tot + outs[0]                      # + the m = 0 bias gradient: column sums of g0, taken inside the same launch
+            if E > 0:                                       # dX_blk = g_blk @ w_blk: A = g [E, o] (RC), B = w [o, k] ([R][J])
+                _gemm([_prob(g, w, gx, True, False) for g, w, gx in zip(gs, ws, gX.split(ins, 1))], True, False)
+        # dW_blk = g_blk^T X_blk: reduction over the edges, split over workgroups into dense partial slabs; the m = 0 bias
+        # gradient (column sums of g0) is taken inside the same launch
         S = _splits_for(E, sum(-(-o // 128) * -(-k // 128) for o, k in zip(outs, ins)))
-        part = torch.empty(S, row, device=X.device, dtype=torch.float32)
-        items, ai, off = [], 0, 0
-        for n, (g, k, o, sz) in enumerate(zip(gs, ins, outs, sizes)):
-            items.append(dict(a=g.data_ptr(), lda=g.stride(0), b=X.data_ptr() + 4 * ai, ldb=X.stride(0),
-                              c=part.data_ptr() + 4 * off, ldc=k, I=o, J=k, R=E, c_split_stride=row,
-                              asum=(part.data_ptr() + 4 * tot) if n == 0 else None, asum_stride=row))
-            ai, off = ai + k, off + sz
-        pw = ctx.params[:3]
-        if E > 0:
-            _gemm(items, False, False, S)
-            offs = [0, sizes[0], sizes[0] + sizes[1]]
-            res = param_colsum(part, [(off, sz, p) for off, sz, p in zip(offs, sizes, pw)] + [(tot, outs[0], ctx.params[3])])
-            gws, gb = res[:3], res[3]
-        else:
-            gws = list(torch.zeros(tot, device=X.device, dtype=torch.float32).split(sizes))
-            gb = torch.zeros(outs[0], device=X.device, dtype=torch.float32)
-        gws = [g.view(o, k) if g is not None else None for g, o, k in zip(gws, outs, ins)]
+        pw0, pw1, pw2, pb0 = ctx.params
+        gws, (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0), (gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], S)
         return gX, gws[0], gb, gws[1], gws[2], None, None
-
-
-def _cgemm(items, a_rc, b_rc, splits=1):
-    arr, n = _capi.cgemm_probs(items)
-    _chk(_lib.lib().singa_cgemm3m_f32(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), "singa_cgemm3m_f32")
 
 
 class _SO2Conv3M(torch.autograd.Function):
@@ -1470,74 +1518,41 @@ class _SO2Conv3M(torch.autograd.Function):
         outs = tuple(w.shape[0] for w in ws)
         assert ws[0].shape[1] == n0 and all(2 * w.shape[1] == k and w.shape[0] % 2 == 0 for w, k in zip(ws[1:], ins[1:]))
         H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
+        xs, hs = X.split(ins, 1), H.split(outs, 1)
         if E > 0:
-            _gemm([dict(a=X.data_ptr(), lda=X.stride(0), b=ws[0].data_ptr(), ldb=ws[0].stride(0), c=H.data_ptr(),
-                        ldc=H.stride(0), bias=b0.data_ptr(), I=E, J=outs[0], R=n0)], True, True)
-            items, ai, ci = [], n0, outs[0]
-            for w, k, o in zip(ws[1:], ins[1:], outs[1:]):
-                K, N = k // 2, o // 2
-                items.append(dict(a=X.data_ptr() + 4 * ai, lda=X.stride(0), a_im=K, b=w.data_ptr(), ldb=K, b_im=N * K,
-                                  c=H.data_ptr() + 4 * ci, ldc=H.stride(0), c_im=N, I=E, J=N, R=K, sigma=1.0))
-                ai, ci = ai + k, ci + o
-            _cgemm(items, True, True)
+            _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True)
+            # A = [x_+ | x_-], B = fc.weight [Wr; Wi], C = [out_r | out_i]
+            _cgemm([_cprob(x.chunk(2, 1), w.chunk(2, 0), h.chunk(2, 1), True, True, 1.0)
+                    for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True)
         ctx.save_for_backward(X, *ws)
-        ctx.ins, ctx.outs = ins, outs
-        o0, o1 = outs[0], outs[0] + outs[1]
-        return H[:, :o0], H[:, o0:o1], H[:, o1:]
+        ctx.ins = ins
+        return hs
 
     @staticmethod
     def backward(ctx, g0, g1, g2):
-        X, w0, w1, w2 = ctx.saved_tensors
-        ins, outs = ctx.ins, ctx.outs
+        X, *ws = ctx.saved_tensors
+        ins, outs = ctx.ins, tuple(w.shape[0] for w in ws)
         E = X.shape[0]
         gs = [_rows(g) for g in (g0, g1, g2)]
-        ws = (w0, w1, w2)
-        # weight gradients: reductions over the edges, split over workgroups into dense partial slabs (the fc weights' layouts)
-        sizes = [outs[0] * ins[0], outs[1] * ins[1] // 2, outs[2] * ins[2] // 2]
-        tot = sum(sizes)
-        # the two launches have few tiles each (conv1: 16 and 14): each gets the split count that fills the CUs
+        xs = X.split(ins, 1)
+        # weight gradients: reductions over the edges, split over workgroups into dense partial slabs (the fc weights' layouts).
+        # The two launches have few tiles each (conv1: 16 and 14): each gets the split count that fills the CUs.  They are
+        # issued in front of the input-gradient launches: nothing in the backward pass waits for them
         S0 = _splits_few(E, -(-outs[0] // 128) * -(-ins[0] // 128))
         Sc = _splits_few(E, sum(-(-(o // 2) // 128) * -(-(k // 2) // 64) for o, k in zip(outs[1:], ins[1:])))
-        pw = ctx.params[:3]
-        if E > 0:
-            row0, rowc = sizes[0] + outs[0], sizes[1] + sizes[2]
-            with _dw_side(X, *gs, params=ctx.params) as side:
-                part0 = torch.empty(S0, row0, device=X.device, dtype=torch.float32)
-                partc = torch.empty(Sc, rowc, device=X.device, dtype=torch.float32)
-                _gemm([dict(a=gs[0].data_ptr(), lda=gs[0].stride(0), b=X.data_ptr(), ldb=X.stride(0), c=part0.data_ptr(),
-                            ldc=ins[0], I=outs[0], J=ins[0], R=E, c_split_stride=row0, asum=part0.data_ptr() + 4 * sizes[0],
-                            asum_stride=row0)], False, False, S0)
-                items, ai, off = [], ins[0], 0
-                for g, k, o, sz in zip(gs[1:], ins[1:], outs[1:], sizes[1:]):
-                    K, N = k // 2, o // 2
-                    items.append(dict(a=g.data_ptr(), lda=g.stride(0), a_im=N, b=X.data_ptr() + 4 * ai, ldb=X.stride(0), b_im=K,
-                                      c=partc.data_ptr() + 4 * off, ldc=K, c_im=N * K, I=N, J=K, R=E, sigma=-1.0,
-                                      c_split_stride=rowc))
-                    ai, off = ai + k, off + sz
-                _cgemm(items, False, False, Sc)
-                side.keep(part0, partc)
-            r0 = param_colsum(part0, [(0, sizes[0], pw[0]), (sizes[0], outs[0], ctx.params[3])])
-            rc = param_colsum(partc, [(0, sizes[1], pw[1]), (sizes[1], sizes[2], pw[2])])
-            gws, gb = [r0[0], rc[0], rc[1]], r0[1]
-        else:
-            gws = list(torch.zeros(tot, device=X.device, dtype=torch.float32).split(sizes))
-            gb = torch.zeros(outs[0], device=X.device, dtype=torch.float32)
+        pw0, pw1, pw2, pb0 = ctx.params
+        (gw0,), (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0)], S0)
+        (gw1, gw2), _ = _dw_grads([(gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], Sc, cplx=True)
         gX = None
         if ctx.needs_input_grad[0]:
             gX = torch.empty_like(X)
             if E > 0:
-                _gemm([dict(a=gs[0].data_ptr(), lda=gs[0].stride(0), b=w0.data_ptr(), ldb=w0.stride(0), c=gX.data_ptr(),
-                            ldc=gX.stride(0), I=E, J=ins[0], R=outs[0])], True, False)
-                items, ai = [], ins[0]
-                for g, w, k, o in zip(gs[1:], ws[1:], ins[1:], outs[1:]):
-                    K, N = k // 2, o // 2
-                    items.append(dict(a=g.data_ptr(), lda=g.stride(0), a_im=N, b=w.data_ptr(), ldb=K, b_im=N * K,
-                                      c=gX.data_ptr() + 4 * ai, ldc=gX.stride(0), c_im=K, I=E, J=K, R=N, sigma=-1.0))
-                    ai += k
-                _cgemm(items, True, False)
-        shapes = [(outs[0], ins[0]), (outs[1], ins[1] // 2), (outs[2], ins[2] // 2)]
-        gws = [g.view(*sh) if g is not None else None for g, sh in zip(gws, shapes)]
-        return gX, gws[0], gb, gws[1], gws[2], None, None
+                gxs = gX.split(ins, 1)
+                _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False)
+                # A = [g_r | g_i], B = fc.weight [Wr; Wi] as [r = n][j = k], C = [dx_+ | dx_-]
+                _cgemm([_cprob(g.chunk(2, 1), w.chunk(2, 0), gx.chunk(2, 1), True, False, -1.0)
+                        for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False)
+        return gX, gw0, gb, gw1, gw2, None, None
 
 
 def so2_conv3m(X, w0, b0, w1, w2, n0, n1):
@@ -1548,6 +1563,22 @@ def so2_conv3m(X, w0, b0, w1, w2, n0, n1):
 def so2_linear3(X, w0, b0, w1, w2, n0, n1):
     """(X[:, :n0] w0^T + b0, X[:, n0:n0+n1] w1^T, X[:, n0+n1:] w2^T) - see _SO2Linear3."""
     return _SO2Linear3.apply(X, w0, b0, w1, w2, n0, n1)
+
+
+def _degrees(t, L):
+    """The row sets of the degrees 0..L of [N, K, C] coefficient rows: L + 1 views [N, 2l + 1, C] (one split call)."""
+    return t.split([2 * l + 1 for l in range(L + 1)], 1)
+
+
+def _so3_linear_probs(x, weight, out, L, b_rc, bias=None, addend=None):
+    """The launch of an SO3_LinearV2 on [N, K, C] rows: one problem per degree l, A = the degree's rows of x (a grouped row
+    set), B = weight[l], C = the same rows of out, so that the result is written in place.  b_rc: out = x weight[l]^T (the
+    forward product; bias on the l = 0 row, addend a tensor like out), else out = x weight[l] (the input gradient)."""
+    if weight.shape[0] != L + 1:
+        raise RuntimeError(f"SO3 linear: {weight.shape[0]} weight matrices for the degrees 0..{L}")
+    ads = _degrees(addend, L) if addend is not None else [None] * (L + 1)
+    return [_prob(a, w, c, True, b_rc, bias=bias if l == 0 else None, addend=ad)
+            for l, (a, w, c, ad) in enumerate(zip(_degrees(x, L), weight.unbind(0), _degrees(out, L), ads))]
 
 
 class _SO3Linear(torch.autograd.Function):
@@ -1573,18 +1604,8 @@ class _SO3Linear(torch.autograd.Function):
             # k11s: a 16-long contraction - VALU kernel, thread = output channel, whole 2 KB rows per store
             _chk(_lib.lib().singa_so3_skinny_expand(_p(x), _p(weight), cout * cin, cin, 1, _p(bias), _p(out), N, cout, L,
                                                     _stream()), "singa_so3_skinny_expand")
-        else:
-            items = []
-            for l in range(L + 1):
-                n = 2 * l + 1
-                items.append(dict(a=x.data_ptr() + 4 * l * l * cin, lda=cin, a_group=n, a_group_ld=K * cin,
-                                  b=weight.data_ptr() + 4 * l * cout * cin, ldb=cin,
-                                  c=out.data_ptr() + 4 * l * l * cout, ldc=cout, c_group=n, c_group_ld=K * cout,
-                                  bias=bias.data_ptr() if l == 0 else None,
-                                  addend=(addend.data_ptr() + 4 * l * l * cout) if addend is not None else None,
-                                  I=N * n, J=cout, R=cin))
-            if N > 0:
-                _gemm(items, True, True)
+        elif N > 0:
+            _gemm(_so3_linear_probs(x, weight, out, L, True, bias, addend), True, True)
         ctx.save_for_backward(x, weight)
         ctx.L = L
         return out
@@ -1607,16 +1628,8 @@ class _SO3Linear(torch.autograd.Function):
                 # k11s: d x = g expanded through weight[l][u][c] - again a 16-long contraction
                 _chk(lib.singa_so3_skinny_expand(_p(g), _p(weight), cout * cin, 1, cin, None, _p(gx), N, wide, L, _stream()),
                      "singa_so3_skinny_expand(dx)")
-            else:
-                items = []
-                for l in range(L + 1):
-                    n = 2 * l + 1
-                    items.append(dict(a=g.data_ptr() + 4 * l * l * cout, lda=cout, a_group=n, a_group_ld=K * cout,
-                                      b=weight.data_ptr() + 4 * l * cout * cin, ldb=cin,
-                                      c=gx.data_ptr() + 4 * l * l * cin, ldc=cin, c_group=n, c_group_ld=K * cin,
-                                      I=N * n, J=cin, R=cout))
-                if N > 0:
-                    _gemm(items, True, False)
+            elif N > 0:
+                _gemm(_so3_linear_probs(g, weight, gx, L, False), True, False)
         if skinny:
             # k11s: the weight gradient as a VALU reduction over whole 2 KB rows of the 512-channel tensor (16 -> 512:
             # small = x, big = g, rows [l][c][u] + the bias gradient; 512 -> 16: small = g, big = x, rows [l][u][c])
@@ -1634,22 +1647,8 @@ class _SO3Linear(torch.autograd.Function):
                 gb = param_colsum(g[:, 0, :], [(0, cout, ctx.params[1])])[0]
             return gx, (gw.view(L + 1, cout, cin) if gw is not None else None), gb, None, (g if ctx.has_addend else None)
         # dW_l = sum over the (node, row) pairs of degree l of g_row^T x_row
-        sz = cout * cin
-        S = _splits_for(N * (2 * L + 1))
-        part = torch.empty(S, (L + 1) * sz, device=x.device, dtype=torch.float32)
-        items = []
-        for l in range(L + 1):
-            n = 2 * l + 1
-            items.append(dict(a=g.data_ptr() + 4 * l * l * cout, lda=cout, a_group=n, a_group_ld=K * cout,
-                              b=x.data_ptr() + 4 * l * l * cin, ldb=cin, b_group=n, b_group_ld=K * cin,
-                              c=part.data_ptr() + 4 * l * sz, ldc=cin, I=cout, J=cin, R=N * n, c_split_stride=(L + 1) * sz))
-        if N > 0:
-            _gemm(items, False, False, S)
-            gw = param_colsum(part, [(0, (L + 1) * sz, ctx.params[0])])[0]
-            if gw is not None:
-                gw = gw.view(L + 1, cout, cin)
-        else:
-            gw = torch.zeros(L + 1, cout, cin, device=x.device, dtype=torch.float32)
+        (gw,), _ = _dw_grads([(gl, xl, ctx.params[0], None) for gl, xl in zip(_degrees(g, L), _degrees(x, L))],
+                             _splits_for(N * (2 * L + 1)))
         return gx, gw, param_colsum(g[:, 0, :], [(0, cout, ctx.params[1])])[0], None, (g if ctx.has_addend else None)
 
 
@@ -1684,17 +1683,8 @@ class _FFNTail(torch.autograd.Function):
             addend = addend.contiguous()
             _dev(addend)
             assert addend.shape == out.shape
-        items = []
-        for l in range(L + 1):
-            nl = 2 * l + 1
-            items.append(dict(a=a.data_ptr() + 4 * l * l * cin, lda=cin, a_group=nl, a_group_ld=K * cin,
-                              b=weight.data_ptr() + 4 * l * cout * cin, ldb=cin,
-                              c=out.data_ptr() + 4 * l * l * cout, ldc=cout, c_group=nl, c_group_ld=K * cout,
-                              bias=bias.data_ptr() if l == 0 else None,
-                              addend=(addend.data_ptr() + 4 * l * l * cout) if addend is not None else None,
-                              I=N * nl, J=cout, R=cin))
         if N > 0:
-            _gemm(items, True, True)
+            _gemm(_so3_linear_probs(a, weight, out, L, True, bias, addend), True, True)
         ctx.save_for_backward(h, gate, a, weight)
         ctx.L = L
         return out
@@ -1746,13 +1736,10 @@ class _GroupedLinear3(torch.autograd.Function):
         N, ig = h.shape[0], ws[0].shape[1]
         ogs = [w.shape[0] // heads for w in ws]
         outs = [torch.empty(N, heads, og, device=h.device, dtype=torch.float32) for og in ogs]
-        items = []
-        for w, o, og in zip(ws, outs, ogs):
-            for g in range(heads):
-                items.append(dict(a=h.data_ptr() + 4 * g * ig, lda=h.stride(0), b=w.data_ptr() + 4 * g * og * ig, ldb=ig,
-                                  c=o.data_ptr() + 4 * g * og, ldc=heads * og, I=N, J=og, R=ig))
         if N > 0:
-            _gemm(items, True, True)
+            hs = h.split(ig, 1)                                      # the heads' column blocks of h, row blocks of a weight
+            _gemm([_prob(hh, wh, oh, True, True) for w, o, og in zip(ws, outs, ogs)
+                   for hh, wh, oh in zip(hs, w.split(og, 0), o.unbind(1))], True, True)
         ctx.save_for_backward(h, *ws)
         ctx.heads, ctx.ogs = heads, ogs
         return tuple(outs)
@@ -1765,36 +1752,18 @@ class _GroupedLinear3(torch.autograd.Function):
         gs = [_rows(g.reshape(N, heads * og)) for g, og in zip((gk, gq, gv), ogs)]
         gh = None
         if ctx.needs_input_grad[0] and N > 0:
-            prev = None
+            prev = [None] * heads
             for g, w, og in zip(gs, ws, ogs):                        # dh += g_layer W_layer, head by head; chained through `addend`
-                cur = torch.empty(N, heads * ig, device=h.device, dtype=torch.float32)
-                items = []
-                for hd in range(heads):
-                    items.append(dict(a=g.data_ptr() + 4 * hd * og, lda=g.stride(0), b=w.data_ptr() + 4 * hd * og * ig, ldb=ig,
-                                      c=cur.data_ptr() + 4 * hd * ig, ldc=heads * ig, I=N, J=ig, R=og,
-                                      addend=(prev.data_ptr() + 4 * hd * ig) if prev is not None else None))
-                _gemm(items, True, False)
+                gh = torch.empty(N, heads * ig, device=h.device, dtype=torch.float32)
+                cur = gh.split(ig, 1)
+                _gemm([_prob(gg, wh, c, True, False, addend=ad)
+                       for gg, wh, c, ad in zip(g.split(og, 1), w.split(og, 0), cur, prev)], True, False)
                 prev = cur
-            gh = prev
         elif ctx.needs_input_grad[0]:
             gh = torch.zeros_like(h)
-        sizes = [heads * og * ig for og in ogs]
-        tot = sum(sizes)
-        if N > 0:
-            S = _tn_splits(N, max(ogs), ig)
-            part = torch.empty(S, tot, device=h.device, dtype=torch.float32)
-            items, off = [], 0
-            for g, og in zip(gs, ogs):
-                for hd in range(heads):                              # dW[layer][head] [og, ig] = g_head^T h_head
-                    items.append(dict(a=g.data_ptr() + 4 * hd * og, lda=g.stride(0), b=h.data_ptr() + 4 * hd * ig, ldb=h.stride(0),
-                                      c=part.data_ptr() + 4 * off, ldc=ig, I=og, J=ig, R=N, c_split_stride=tot))
-                    off += og * ig
-            _gemm(items, False, False, S)
-            offs = [0, sizes[0], sizes[0] + sizes[1]]
-            gws = param_colsum(part, [(o, sz, p) for o, sz, p in zip(offs, sizes, ctx.params)])
-            gws = [gw.view(p.shape) if gw is not None else None for gw, p in zip(gws, ctx.params)]
-        else:
-            gws = [torch.zeros_like(p) for p in ctx.params]
+        hs = h.split(ig, 1)                                          # dW[layer][head] [og, ig] = g_head^T h_head
+        gws, _ = _dw_grads([(gg, hh, p, None) for g, og, p in zip(gs, ogs, ctx.params) for gg, hh in zip(g.split(og, 1), hs)],
+                           _tn_splits(N, max(ogs), ig))
         return gh, gws[0], gws[1], gws[2], None
 
 
@@ -1845,9 +1814,7 @@ class _LinearOwn(torch.autograd.Function):
         if addend is not None:
             ad = addend.reshape(M, N).contiguous()
             _dev(ad)
-        _gemm([dict(a=x2.data_ptr(), lda=x2.stride(0), b=w2.data_ptr(), ldb=w2.stride(0), c=y.data_ptr(), ldc=N,
-                    bias=b.data_ptr() if b is not None else None, addend=ad.data_ptr() if ad is not None else None,
-                    I=M, J=N, R=K)], True, True)
+        _gemm([_prob(x2, w2, y, True, True, bias=b, addend=ad)], True, True)
         ctx.save_for_backward(x2, w2)
         ctx.xshape, ctx.has_bias, ctx.ashape = x.shape, b is not None, (addend.shape if addend is not None else None)
         return y.view(*x.shape[:-1], N)
@@ -1860,7 +1827,7 @@ class _LinearOwn(torch.autograd.Function):
         g2 = _rows(g.reshape(-1, N))
         wp, bp = ctx.params
         gx = gw = gb = None
-        # the weight gradient first: it may fork onto the second stream (_dw_side) and then only waits for what produced g
+        # the weight gradient first: nothing in the backward pass waits for it, the input gradient's launch follows it
         if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2] and M > 0:
             gw, gb = _tn_grad(g2, x2, wp, bp)                         # the bias gradient rides in the weight gradient's launch
         else:
@@ -1870,8 +1837,7 @@ class _LinearOwn(torch.autograd.Function):
                 gb = param_colsum(g2, [(0, N, bp)])[0]
         if ctx.needs_input_grad[0]:
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([dict(a=g2.data_ptr(), lda=g2.stride(0), b=w2.data_ptr(), ldb=w2.stride(0), c=gx.data_ptr(), ldc=K,
-                        I=M, J=K, R=N)], True, False)
+            _gemm([_prob(g2, w2, gx, True, False)], True, False)
             gx = gx.view(ctx.xshape)
         ga = g.reshape(ctx.ashape) if ctx.ashape is not None and ctx.needs_input_grad[3] else None
         return gx, gw, gb, ga
@@ -1890,8 +1856,7 @@ class _LinearNN(torch.autograd.Function):
         _dev(x2, w2)
         M = x2.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([dict(a=x2.data_ptr(), lda=x2.stride(0), b=w2.data_ptr(), ldb=w2.stride(0), c=y.data_ptr(), ldc=N, I=M, J=N, R=K)],
-              True, False)
+        _gemm([_prob(x2, w2, y, True, False)], True, False)
         ctx.save_for_backward(x2, w2)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], N)
@@ -1905,8 +1870,7 @@ class _LinearNN(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[0]:                  # dx = g W^T: W [K, N] is the [J][R] operand of the (1, 1) form
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([dict(a=g2.data_ptr(), lda=g2.stride(0), b=w2.data_ptr(), ldb=w2.stride(0), c=gx.data_ptr(), ldc=K,
-                        I=M, J=K, R=N)], True, True)
+            _gemm([_prob(g2, w2, gx, True, True)], True, True)
             gx = gx.view(ctx.xshape)
         if ctx.needs_input_grad[1]:                  # dW [K, N] = x^T g
             gw = _tn_grad(x2, g2, ctx.param)
@@ -1920,25 +1884,13 @@ def linear_nn(x, w):
 
 
 def _tn_grad(g2, x2, param, bias=None):
-    """dW[N, K] = g2^T x2 (reduction over the rows, split over workgroups) as partial slabs -> param_colsum: returns the
-    gradient shaped like `param`, or None when it was queued into param.grad.  (Tried and dropped in round 3: queueing the
+    """dW[N, K] = g2^T x2 (reduction over the rows, split over workgroups): the one-problem case of _dw_grads.  Returns the
+    gradient shaped like `param`, or None when it was queued into param.grad - and, with `bias`, the bias gradient (the
+    per-split column sums of g ride behind the slab) as a second result.  (Tried and dropped in round 3: queueing the
     products themselves and launching them 12 at a time - one split count and one tile shape for a mixed batch cost 12 ms
     per step at config 3 and gained nothing on the 17-graph shard, tools/lab/ab_bench.py.)"""
-    M, N = g2.shape
-    K = x2.shape[1]
-    S = _tn_splits(M, N, K)
-    row = N * K + (N if bias is not None else 0)         # the bias gradient's per-split column sums of g ride behind the slab
-    with _dw_side(g2, x2, params=(param, bias)) as side:
-        part = torch.empty(S, row, device=g2.device, dtype=torch.float32)
-        _gemm([dict(a=g2.data_ptr(), lda=g2.stride(0), b=x2.data_ptr(), ldb=x2.stride(0), c=part.data_ptr(), ldc=K,
-                    I=N, J=K, R=M, c_split_stride=row, asum=(part.data_ptr() + 4 * N * K) if bias is not None else None,
-                    asum_stride=row)], False, False, S)
-        side.keep(part)
-    if bias is not None:
-        gw, gb = param_colsum(part, [(0, N * K, param), (N * K, N, bias)])
-        return (gw.view(param.shape) if gw is not None else None), gb
-    gw = param_colsum(part, [(0, N * K, param)])[0]
-    return gw.view(param.shape) if gw is not None else None
+    (gw,), gb = _dw_grads([(g2, x2, param, bias)], _tn_splits(g2.shape[0], g2.shape[1], x2.shape[1]))
+    return (gw, gb[0]) if bias is not None else gw
 
 
 def _pad4(x, w):
@@ -1993,20 +1945,11 @@ class _LinearMulti(torch.autograd.Function):
         ns = [w.shape[0] for w in w2]
         tot = sum(ns)
         y = torch.empty(M, tot, device=x.device, dtype=torch.float32)
-        items, off = [], 0
-        for w, b, n in zip(w2, bs, ns):
-            items.append(dict(a=x2.data_ptr(), lda=x2.stride(0), b=w.data_ptr(), ldb=w.stride(0), c=y.data_ptr() + 4 * off,
-                              ldc=tot, bias=b.data_ptr() if b is not None else None, I=M, J=n, R=K))
-            off += n
-        _gemm(items, True, True)
+        ys = y.split(ns, 1)
+        _gemm([_prob(x2, w, yb, True, True, bias=b) for w, b, yb in zip(w2, bs, ys)], True, True)
         ctx.save_for_backward(x2, *w2)
         ctx.xshape, ctx.ns = x.shape, ns
-        lead = x.shape[:-1]
-        outs, off = [], 0
-        for n in ns:
-            outs.append(y[:, off:off + n].view(*lead, n))
-            off += n
-        return tuple(outs)
+        return tuple(yb.view(*x.shape[:-1], n) for yb, n in zip(ys, ns))
 
     @staticmethod
     def backward(ctx, *gs):
@@ -2020,38 +1963,24 @@ class _LinearMulti(torch.autograd.Function):
         fused = all(g.stride(1) == 1 and g.stride(0) == g2[0].stride(0) for g in g2) and g2[0].stride(0) >= tot
         off = 0
         for g, n in zip(g2, ns):
-            fused = fused and g.data_ptr() == g2[0].data_ptr() + 4 * off
+            fused = fused and g.data_ptr() - g2[0].data_ptr() == 4 * off
             off += n
         if fused and g2[0].data_ptr() % 16 == 0 and g2[0].stride(0) % 4 == 0:
-            G, ldg = g2[0], g2[0].stride(0)
+            G = g2[0].as_strided((M, tot), (g2[0].stride(0), 1))     # the buffer's first `tot` columns: all blocks side by side
         else:
             G = torch.cat(g2, 1)
-            ldg = tot
-        gp = G.data_ptr()
         gx = None
         if ctx.needs_input_grad[0]:
             wcat = torch.cat(w2, 0)                                  # [tot, K]: the reduction runs over all output columns
             gx = torch.empty(M, K, device=x2.device, dtype=torch.float32)
-            _gemm([dict(a=gp, lda=ldg, b=wcat.data_ptr(), ldb=K, c=gx.data_ptr(), ldc=K, I=M, J=K, R=tot)], True, False)
+            _gemm([_prob(G, wcat, gx, True, False)], True, False)
             gx = gx.view(ctx.xshape)
-        sizes = [n * K for n in ns]
-        S = _tn_splits(M, max(ns), K)
-        row = tot * K + tot                       # weight-gradient slabs + the bias gradients (column sums of G, same launch)
-        part = torch.empty(S, row, device=x2.device, dtype=torch.float32)
-        items, off, poff = [], 0, 0
-        for n, sz in zip(ns, sizes):
-            items.append(dict(a=gp + 4 * off, lda=ldg, b=x2.data_ptr(), ldb=x2.stride(0), c=part.data_ptr() + 4 * poff, ldc=K,
-                              I=n, J=K, R=M, c_split_stride=row, asum=part.data_ptr() + 4 * (tot * K + off), asum_stride=row))
-            off, poff = off + n, poff + sz
-        _gemm(items, False, False, S)
-        offs = [sum(sizes[:i]) for i in range(len(sizes))]
-        coff = [tot * K + sum(ns[:i]) for i in range(len(ns))]
-        res = param_colsum(part, [(o, sz, w) for o, sz, w in zip(offs, sizes, ws)] + [(o, n, b) for o, n, b in zip(coff, ns, bs)])
-        gws = [gw.view(w.shape) if gw is not None else None for gw, w in zip(res[:len(ns)], ws)]
-        gbs = res[len(ns):]
+        # weight-gradient slabs + the bias gradients (column sums of G, same launch)
+        gws, gbs = _dw_grads([(g, x2, w, b) for g, w, b in zip(G.split(ns, 1), ws, bs)], _tn_splits(M, max(ns), K))
+        gbs = iter(gbs)
         out = [gx]
-        for gw, gb in zip(gws, gbs):
-            out += [gw, gb]
+        for gw, b in zip(gws, bs):
+            out += [gw, next(gbs) if b is not None else None]
         return tuple(out)
 
 
@@ -2089,10 +2018,8 @@ class _PosFFN(torch.autograd.Function):
         M, N = x2.shape[0], a2.shape[0]
         h = torch.empty(M, H, device=x.device, dtype=torch.float32)
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([dict(a=x2.data_ptr(), lda=x2.stride(0), b=a1.data_ptr(), ldb=a1.stride(0), c=h.data_ptr(), ldc=H,
-                    bias=b1.data_ptr(), I=M, J=H, R=K, relu=1)], True, True)
-        _gemm([dict(a=h.data_ptr(), lda=H, b=a2.data_ptr(), ldb=a2.stride(0), c=y.data_ptr(), ldc=N, bias=b2.data_ptr(),
-                    I=M, J=N, R=H)], True, True)
+        _gemm([_prob(x2, a1, h, True, True, bias=b1, relu=True)], True, True)
+        _gemm([_prob(h, a2, y, True, True, bias=b2)], True, True)
         ctx.save_for_backward(x2, a1, a2, h)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], N)
@@ -2104,16 +2031,14 @@ class _PosFFN(torch.autograd.Function):
         H, N = a1.shape[0], a2.shape[0]
         g2 = _rows(g.reshape(-1, N))
         w1, b1, w2, b2 = ctx.params
-        gw2, gb2 = _tn_grad(g2, h, w2, b2)                 # (weight gradients first: they may fork onto the second stream)
+        gw2, gb2 = _tn_grad(g2, h, w2, b2)                 # (each weight gradient in front of the input gradient it goes with)
         dh = torch.empty(M, H, device=g.device, dtype=torch.float32)
-        _gemm([dict(a=g2.data_ptr(), lda=g2.stride(0), b=a2.data_ptr(), ldb=a2.stride(0), c=dh.data_ptr(), ldc=H,
-                    I=M, J=H, R=N, mask=h.data_ptr())], True, False)
+        _gemm([_prob(g2, a2, dh, True, False, mask=h)], True, False)
         gw1, gb1 = _tn_grad(dh, x2, w1, b1)
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([dict(a=dh.data_ptr(), lda=H, b=a1.data_ptr(), ldb=a1.stride(0), c=gx.data_ptr(), ldc=K, I=M, J=K, R=H)],
-                  True, False)
+            _gemm([_prob(dh, a1, gx, True, False)], True, False)
             gx = gx.view(ctx.xshape)
         return gx, gw1, gb1, gw2, gb2
 
