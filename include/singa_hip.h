@@ -9,6 +9,12 @@
  *     fp32 data, int32 indices; pointers are borrowed for the duration of the enqueue only;
  *   - functions only ENQUEUE work on `stream` (a hipStream_t passed as void*); no allocation, no synchronisation,
  *     no global mutable state after singa_init();
+ *   - outputs are written in full: every element of an output view is defined by the call whatever the memory held before,
+ *     and nothing outside the views (the gaps of a strided view included) is written.  Partial-sum buffers (`part`, gw_part /
+ *     gb_part, asum) are written in ALL rows their sizing function announces - rows without work hold zeros, so callers reduce
+ *     over all of them.  Accumulators (stats of singa_edge_frames, the destinations of singa_colsum_multi, g_w of
+ *     singa_block_weight_bwd with accumulate != 0, p / m / v / step of singa_adam_step, the state arrays of singa_sample_token,
+ *     one cache position of singa_dec_self_attn) and buffers called scratch / work are the only exceptions and say so;
  *   - return 0 on success, a negative SINGA_E* code for argument errors, a positive hipError_t for launch errors;
  *     singa_last_error_string() describes the last failure of the calling thread;
  *   - edges of one edge type are sorted by destination node: row_ptr[n]..row_ptr[n+1] are the edges into node n.
@@ -16,7 +22,8 @@
  * Coefficient orderings: node tensors are [N, K=(L+1)^2, C] l-primary; edge tensors between the
  * two rotations are "m-primary": [(l,0) l=0..L] ++ for m=1..M: [(l,+m) l=m..L] ++ [(l,-m) l=m..L], KR rows.
  * Reduced Wigner rows Wr[E, WSZ]: for l=0..L the rows |m|<=min(l,M) of the l-th Wigner block, row-major
- * [2*min(l,M)+1][2l+1]  (WSZ = 35 / 115 / 235 for L = 2 / 4 / 6 at M = 2).
+ * [2*min(l,M)+1][2l+1]: 35 / 115 / 235 coefficients for L = 2 / 4 / 6 at M = 2, padded with zeros to a record of
+ * WSZ = 36 / 116 / 236 floats (a multiple of 4: 16-byte aligned records; singa_dims reports WSZ).
  */
 #ifndef SINGA_HIP_H
 #define SINGA_HIP_H
@@ -66,7 +73,8 @@ int singa_dims(int lmax, int mmax, int* kr, int* wsz, int* rad_rows);
 int singa_edge_frames(const float* vec, const float* rnd, float* rot, float* stats, int E, void* stream);
 
 /* k2 — SO3_Rotation.set_wigner / RotationToWignerDMatrix / wigner_D (EF:485-528, 2207-2229):
- * rot[E,3,3] edge frames -> Wr[E,WSZ] reduced Wigner rows. */
+ * rot[E,3,3] edge frames -> Wr[E,WSZ] reduced Wigner rows.  All WSZ floats of every record are written, the pad floats
+ * behind the coefficients as 0: the caller does not clear Wr. */
 int singa_wigner_rows(const float* rot, float* wr, int E, int lmax, int mmax, void* stream);
 
 /* k3-k6 — _expand_edge x2 + cat + SO3_Rotation.rotate + _m_primary + radial multiply (EF:326-328,1116-1119,494-497,
@@ -426,10 +434,12 @@ int singa_rowdot_bwd(const float* g, const float* x, const float* b, float* gx, 
  * at model/GAN.py:71,77): for each of B graphs the kout (<= 8) eigenvectors after the smallest of its normalised Laplacian
  * I - D^-1/2 A D^-1/2 (A[src, dst] = 1 for every edge, repeats count once; D = in-degree clipped at 1; symmetrised), entry
  * of largest magnitude made positive, written as fp32 rows out[first[b] + i, 0..kout-1]; graphs with fewer than kout + 1
- * atoms get zero columns.  Edges: esrc / edst are LOCAL atom indices (0 .. nnodes[b] - 1), grouped by graph, graph b owning
- * eptr[b] .. eptr[b+1] - 1.  A: [B, ld, ld] doubles of scratch (ld >= max nnodes, <= 896; not initialised by the caller),
- * work: singa_lap_pe_work(B, ld) doubles.  One workgroup per graph; all O(n^3) work is per connected component (Householder
- * tridiagonalisation, Sturm multi-section, inverse iteration, back-transformation). */
+ * atoms get zero columns - written by the kernel: all kout columns of every graph's nnodes[b] rows are defined by the call
+ * and the caller does not clear `out`; rows of `out` that belong to no graph are not touched.  Edges: esrc / edst are LOCAL
+ * atom indices (0 .. nnodes[b] - 1), grouped by graph, graph b owning eptr[b] .. eptr[b+1] - 1.  A: [B, ld, ld] doubles of
+ * scratch (ld >= max nnodes, <= 896; not initialised by the caller), work: singa_lap_pe_work(B, ld) doubles.  One workgroup
+ * per graph; all O(n^3) work is per connected component (Householder tridiagonalisation, Sturm multi-section, inverse
+ * iteration, back-transformation). */
 int singa_lap_pe_work(int B, int ld);
 int singa_lap_pe(double* A, const int32_t* esrc, const int32_t* edst, const int32_t* eptr, const int32_t* nnodes, const int32_t* first,
                  double* work, float* out, int B, int ld, int kout, void* stream);

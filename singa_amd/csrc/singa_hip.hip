@@ -285,6 +285,10 @@ __global__ void wigner_rows_kernel(const float* __restrict__ rot, float* __restr
         float fk = (float)(l - k), fkk = (float)(l - kk);
         out[k] = Cc[k] * cosf(fk * gamma) + ((k != kk) ? Cc[kk] * sinf(fkk * gamma) : 0.f);
     }
+    // the record is padded to a multiple of 4 floats (so3_index.h); the thread of the last row writes the pad as zeros, so
+    // that the whole WSZ-float record is defined by this kernel and the caller need not clear it
+    if (r == I::KR - 1)
+        for (int k = I::w_off(L + 1); k < I::WSZ; ++k) wr[(long long)e * I::WSZ + k] = 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------ k3-k6: gather+rotate

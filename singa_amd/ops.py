@@ -158,7 +158,8 @@ def edge_frames(vec, rand, stats):
 def lap_pe(src, dst, eptr, num, start, n_total, mx, k=8):
     """n2: Laplacian positional encoding of every graph of a batch (reference model/CProMG.py:562-571; no gradient).
     src / dst: int32 LOCAL atom indices of the edges, grouped by graph; eptr [B + 1] the graphs' edge ranges; num [B]
-    atoms per graph; start [B] first row of each graph in the result; mx >= max(num).  -> fp32 [n_total, k]."""
+    atoms per graph; start [B] first row of each graph in the result (the graphs tile the n_total rows: a row that belongs to no
+    graph is not written); mx >= max(num).  -> fp32 [n_total, k]."""
     for t in (src, dst, eptr):
         if not t.is_cuda or t.dtype != torch.int32:
             raise RuntimeError("lap_pe: CUDA int32 edge arrays (no CPU path)")
@@ -170,7 +171,7 @@ def lap_pe(src, dst, eptr, num, start, n_total, mx, k=8):
     nn, st = num.to(torch.int32).contiguous(), start.to(torch.int32).contiguous()
     scratch = torch.empty(B * mx * mx, device=dev, dtype=torch.float64)           # only the components' diagonal blocks are touched
     work = torch.empty(max(lib.singa_lap_pe_work(B, mx), 1), device=dev, dtype=torch.float64)
-    out = torch.zeros(n_total, k, device=dev, dtype=torch.float32)
+    out = torch.empty(n_total, k, device=dev, dtype=torch.float32)   # the kernel writes all k columns of every graph's rows (zeros past n - 1)
     _chk(lib.singa_lap_pe(_p(scratch), _p(src), _p(dst), _p(eptr), _p(nn), _p(st), _p(work), _p(out), B, mx, k, _stream()),
          "singa_lap_pe")
     return out
@@ -182,7 +183,7 @@ def wigner_rows(rot, L, M=2):
     _dev(rot)
     lay = so3.layout(L, M)
     E = rot.shape[0]
-    wr = torch.zeros(E, lay.WSZ, device=rot.device, dtype=torch.float32)     # WSZ is padded to 16-byte records; pad floats = 0
+    wr = torch.empty(E, lay.WSZ, device=rot.device, dtype=torch.float32)     # WSZ is padded to 16-byte records; the kernel writes the pad floats (0)
     _chk(_lib.lib().singa_wigner_rows(_p(rot), _p(wr), E, L, M, _stream()), "singa_wigner_rows")
     return wr
 

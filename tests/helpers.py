@@ -247,3 +247,125 @@ class oracle_pinned_relu_ties:
     def __exit__(self, *exc):
         self._O.pos_ffn = self._orig
         return False
+
+
+# ------------------------------------------------------------------------------------------ write footprints of C ABI calls
+# The C ABI (include/singa_hip.h) works on caller-owned, possibly strided views.  An Arena carves all views of ONE call out of
+# one allocation, with poisoned guard bands around every view and poison in every gap of a strided view, so that a stray
+# write lands in memory of our own where it can be seen, a stray read that feeds a result shows up in the result, and nothing
+# faults.  Two canaries (two runs of the same call) tell "never written" from "written with the old value".
+ARENA_GUARD = 4096                                     # elements before and behind every view (16 KB of floats)
+_INT_VIEW = {torch.float32: torch.int32, torch.float64: torch.int64, torch.int32: torch.int32, torch.int64: torch.int64,
+             torch.uint8: torch.uint8}
+# bit patterns, as the integer type of the same width
+_CANARY = {"nan": {torch.float32: 0x7FC0BEEF, torch.float64: 0x7FF8DEADBEEFCAFE},          # quiet NaNs with a payload
+           "big": {torch.float32: 0x7149F2CA, torch.float64: 0x7E37E43C8800759C}}          # 1e30, 1e300
+_CANARY_INT = {torch.int32: -0x7452F00D, torch.int64: -0x7452F00D7452F00D, torch.uint8: 0xA5}   # outside any valid index / flag
+
+
+class ArenaView:
+    """One view of an Arena: `.t` is the strided tensor handed to the call, `.ptr` its address."""
+
+    def __init__(self, name, region, t, promised, role, snap):
+        self.name, self.region, self.t, self.promised, self.role, self.snap = name, region, t, promised, role, snap
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+
+class Arena:
+    """canary: "nan" or "big" (floating-point poison; integer buffers use one out-of-range pattern in both).
+
+    view(name, shape, ...) places a view and returns its ArenaView; roles:
+      "in"      read-only input, filled with `data`; its gaps and guards are poison, and it must come back unchanged;
+      "out"     every element (or every element of `promised`, a bool mask of the view's shape) must be written; the rest of the
+                view, its gaps and its guards must keep their bits;
+      "inout"   starts from `data` (accumulators, caches); compared by the caller against `initial (op) result`;
+      "scratch" memory the header calls uninitialised: poisoned, may be written anywhere inside the view.
+    report() -> ArenaReport after the call has finished."""
+
+    def __init__(self, device, canary, capacity=64 << 20, guard=ARENA_GUARD):
+        assert canary in _CANARY
+        self.device, self.canary, self.guard = torch.device(device), canary, guard
+        self.buf = torch.empty(capacity, dtype=torch.uint8, device=self.device)          # the ONE allocation
+        self.top, self.views = 0, {}
+
+    def poison(self, dtype):
+        return _CANARY[self.canary][dtype] if dtype.is_floating_point else _CANARY_INT[dtype]
+
+    def view(self, name, shape, dtype=torch.float32, strides=None, data=None, role="in", promised=None):
+        assert name not in self.views and role in ("in", "out", "inout", "scratch")
+        shape = tuple(int(s) for s in shape)
+        if strides is None:
+            strides, acc = [], 1
+            for s in reversed(shape):
+                strides.insert(0, acc)
+                acc *= max(s, 1)
+        strides = tuple(int(s) for s in strides)
+        numel = int(np.prod(shape)) if shape else 1
+        span = 1 + sum((s - 1) * st for s, st in zip(shape, strides)) if numel else 0
+        item = torch.empty(0, dtype=dtype).element_size()
+        n = span + 2 * self.guard
+        start = -(-self.top // 256) * 256
+        assert start + n * item <= self.buf.numel(), "arena capacity"
+        self.top = start + n * item
+        region = self.buf[start:start + n * item].view(dtype)
+        bits = region.view(_INT_VIEW[dtype])
+        bits.fill_(self.poison(dtype))
+        t = region.as_strided(shape, strides, region.storage_offset() + self.guard)
+        idx = torch.arange(n, device=self.device).as_strided(shape, strides, self.guard)
+        assert idx.unique().numel() == numel, "overlapping strides"
+        if role == "in" or role == "inout":
+            assert data is not None
+            t.copy_(torch.as_tensor(data).to(device=self.device, dtype=dtype).reshape(shape))
+        mask = torch.zeros(n, dtype=torch.bool, device=self.device)
+        if role == "scratch":
+            mask[self.guard:self.guard + span] = True
+        elif promised is None:
+            mask[idx.reshape(-1)] = True
+        else:
+            mask[idx[torch.as_tensor(promised, device=self.device).expand(shape)]] = True
+        v = ArenaView(name, region, t, mask, role, bits.clone())
+        self.views[name] = v
+        return v
+
+    def report(self):
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+        rep = ArenaReport()
+        for name, v in self.views.items():
+            bits = v.region.view(_INT_VIEW[v.region.dtype])
+            changed = bits != v.snap
+            stray = int((changed & ~v.promised).sum())
+            if stray:
+                where = int((changed & ~v.promised).nonzero()[0]) - self.guard
+                rep.stray[name] = (stray, where)                    # words outside the promise whose bits changed, first offset
+            if v.role == "in" and int((changed & v.promised).sum()):
+                rep.stray[name] = (int(changed.sum()), "input modified")
+            if v.role == "out":
+                left = int(((bits == self.poison(v.region.dtype)) & v.promised).sum())
+                if left:
+                    rep.unwritten[name] = left
+            if v.role in ("out", "inout"):
+                rep.bits[name] = bits[v.promised].cpu()
+                rep.out[name] = v.t.detach().clone().cpu()
+        return rep
+
+
+class ArenaReport:
+    def __init__(self):
+        self.stray, self.unwritten, self.bits, self.out = {}, {}, {}, {}
+
+
+def arena_runs(case, device, **kw):
+    """Run `case(arena)` (which places its views and makes the call) once per canary -> (report_nan, report_big, names of the
+    outputs whose promised elements are not bit-identical between the two runs, what `case` returned in the first run)."""
+    reps, ret = [], None
+    for canary in ("nan", "big"):
+        ar = Arena(device, canary, **kw)
+        r = case(ar)
+        ret = r if ret is None else ret
+        reps.append(ar.report())
+    differ = [n for n in reps[0].bits if not torch.equal(reps[0].bits[n], reps[1].bits[n])]
+    return reps[0], reps[1], differ, ret

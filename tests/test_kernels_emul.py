@@ -485,3 +485,17 @@ def test_block_weight(emul):
     acc = base.copy()
     assert emul.singa_block_weight_bwd(ptr(G.numpy()), ptr(acc), h, k, 1, None) == 0
     assert np.abs(acc - (base + w.grad.numpy())).max() < 1e-6
+
+
+# The write-footprint cases of tests/test_abi_footprint_gpu.py whose kernels the sequential emulation can run (no cross-lane,
+# workgroup-synchronised or matrix-core kernel): the same views between poisoned guard bands, the same four assertions.
+FOOTPRINT_CASES = ["adam_step", "bias_ssp_bwd", "bias_ssp_fwd", "block_weight_bwd", "block_weight_fwd", "colsum", "colsum_multi",
+                   "edge_frames", "gather_rotate_bwd", "gather_rotate_fwd", "gather_wsum_fwd", "knn_edge_attr", "ln_silu_bwd", "ln_silu_fwd",
+                   "rotate_back_scatter_bwd", "rotate_back_scatter_fwd", "s2act_bwd", "s2act_fwd", "s2act_sep_bwd", "s2act_sep_bwd_seg",
+                   "s2act_sep_fwd", "segment_wsum_fwd", "so3_skinny_expand", "so3_skinny_reduce", "wigner_rows"]
+
+
+@pytest.mark.parametrize("name", FOOTPRINT_CASES)
+def test_write_footprint(emul, name):
+    from tests import test_abi_footprint_gpu as fp
+    fp.run_case(name, fp.Env(emul, dev="cpu"))
