@@ -6,7 +6,10 @@ temperature / top-k / top-p; singa_amd/model/Sampling.py).
 
 The reference's PDB / docking front end is out of scope, so pockets come from `--data golden` (the three
 example graphs the reference bundles) or `--data synthetic`.  No chemistry toolkit is required: the sequences are written as
-they were decoded, without a validity filter.
+they were decoded, without a validity filter.  `--grammar smiles` (sample mode) removes the syntactic rejects where the token
+is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired ring-closure digits and no
+dangling bond symbol (include/singa_hip_gen.h states the rule).  Chemical validity - valence, aromaticity, duplicate ring
+bonds - is still not checked, and beam search is not constrained.
 
     python gen.py --config ./config/train.yml --ckpt logs/.../checkpoints/100.pt --data golden --mode sample \\
                   --num-samples 100 --temperature 0.9 --top-p 0.95 --seed 1
@@ -41,12 +44,15 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--grammar", choices=["none", "smiles"], default="none",
+                    help="sample: draw only tokens that keep the sequence a completable SMILES string")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--prop", type=float, nargs=3, default=[1.0, 1.0, 1.0], metavar=("V", "Q", "S"),
                     help="the property prompt: vina score below -7.5, QED above 0.6, SAS below 4 (1 = wanted)")
     ap.add_argument("--out", type=str, default=None, help="write the sequences here instead of stdout")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
+    assert args.grammar == "none" or args.mode == "sample", "--grammar constrains sampling only: beam search selects on the host"
     dev = torch.device(args.device if ":" in args.device else "cuda:0")
     torch.cuda.set_device(dev)
 
@@ -94,7 +100,8 @@ def main():
     if args.mode == "sample":
         gen = torch.Generator(device=dev).manual_seed(args.seed)
         tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
-                        top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr).cpu()
+                        top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
+                        grammar=None if args.grammar == "none" else args.grammar).cpu()
         lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
         print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
     else:

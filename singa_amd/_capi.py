@@ -134,11 +134,18 @@ _LAB_SIGS = {
 }
 LAB_EXPORTS = tuple(_LAB_SIGS)
 
+# include/singa_hip_gen.h: generation-time extensions (grammar-constrained sampling), outside the drop-in training ABI
+_GEN_SIGS = {
+    "singa_sample_token_grammar": ([P, P, P, P, P, I32, I32, I32, I32, F32, I32, F32, I32, I32] + [P] * 10, I32),
+    "singa_smiles_rule_host": ([P, P, P, I32, P, P], I32),
+}
+GEN_EXPORTS = tuple(_GEN_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
-    for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -21,6 +21,7 @@
 
 #include "../../include/singa_hip.h"
 #include "../../include/singa_hip_lab.h"
+#include "../../include/singa_hip_gen.h"
 #include "so3_index.h"
 
 namespace {
@@ -1526,6 +1527,44 @@ __global__ void __launch_bounds__(1024) dec_ffn_kernel(const float* __restrict__
 //   * the draw: inclusive wave scan (6 __shfl_up steps per 64 tokens, carry between the NPL groups) of the kept e_i in
 //     vocabulary order, the first F_i > u found with a wave minimum over the hit indices.
 // expf / logf are the accurate ones: the reported log-probability has to hold the fp32 bound of a V-term log-sum-exp.
+//
+// The SMILES rule of singa_sample_token_grammar (include/singa_hip_gen.h states it): one source for the kernel and for
+// singa_smiles_rule_host.  Integer operations on registers only; `c` is a class byte (low nibble class, high nibble digit).
+enum { SMI_NONE = 0, SMI_ATOM = 1, SMI_BOND = 2, SMI_OPEN = 3, SMI_CLOSE = 4, SMI_RING = 5, SMI_DOT = 6, SMI_EOS = 7,
+       SMI_START = 7, SMI_BONDX = 8 };                                 // classes 0-7; prev codes 1-6 as the classes, 7, 8
+
+__host__ __device__ inline int smiles_next(int st, int c) {            // the state after a token that may follow
+    const int cl = c & 15, bit = 1 << (c >> 4);
+    int prev = st & 15, depth = (st >> 4) & 63, ring = (st >> 10) & 511, here = (st >> 19) & 511;
+    const bool after_atom = prev == SMI_ATOM || prev == SMI_RING;
+    here = cl == SMI_ATOM ? 0 : cl == SMI_RING ? here | (bit & ~ring) : here;
+    ring = cl == SMI_RING ? ring ^ bit : ring;
+    depth += (cl == SMI_OPEN ? 1 : 0) - (cl == SMI_CLOSE ? 1 : 0);
+    prev = ((cl == SMI_BOND) & !after_atom) ? SMI_BONDX : cl;
+    return ((cl == SMI_NONE) | (cl >= SMI_EOS)) ? st : prev | depth << 4 | ring << 10 | here << 19;    // '$': the state stays
+}
+
+__host__ __device__ inline int smiles_need(int st) {                   // columns of the shortest completion, '$' included
+    const int prev = st & 15, depth = (st >> 4) & 63, ring = (st >> 10) & 511, here = (st >> 19) & 511;
+    const bool a = prev == SMI_START || prev == SMI_DOT || prev == SMI_BOND || prev == SMI_BONDX || prev == SMI_OPEN ||
+                   (ring != 0 && (prev == SMI_CLOSE || (ring & here) != 0));
+    return (a ? 1 : 0) + __builtin_popcount((unsigned)ring) + depth + 1;
+}
+
+// written without short-circuit operators and with one return: the class differs from lane to lane, and a branch on it
+// would run its sides one after the other
+__host__ __device__ inline bool smiles_allows(int st, int c, int rem) {
+    const int cl = c & 15, d = c >> 4;
+    const int prev = st & 15, depth = (st >> 4) & 63, ring = (st >> 10) & 511, here = (st >> 19) & 511;
+    const bool after_atom = (prev == SMI_ATOM) | (prev == SMI_RING), A = after_atom | (prev == SMI_CLOSE);
+    const bool opens = (after_atom | (prev == SMI_BOND)) & !(ring >> d & 1), closes = after_atom & (ring >> d & 1) & !(here >> d & 1);
+    const bool gram = (cl == SMI_ATOM) | ((cl == SMI_BOND) & (A | (prev == SMI_OPEN))) | ((cl == SMI_OPEN) & A & (depth < 63)) |
+                      ((cl == SMI_CLOSE) & A & (depth > 0)) | ((cl == SMI_DOT) & A) |
+                      ((cl == SMI_RING) & (d < 9) & (opens | closes));
+    const bool end = (cl == SMI_EOS) & A & (depth == 0) & (ring == 0);  // no budget: '$' needs no further column
+    return end | (gram & (rem >= smiles_need(smiles_next(st, c))));
+}
+
 #ifndef SINGA_EMUL      // (cross-lane: not part of the sequential CPU emulation build of tests/emul)
 __device__ __forceinline__ int wave_min64i(int v) {
 #pragma unroll
@@ -1541,7 +1580,10 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }
 
-template <int NPL>
+// GRAMMAR (singa_sample_token_grammar): the row's state word is read once (wave-uniform), the rule is ANDed into ok[] from the
+// class bytes of the lane's tokens, the choice below runs unchanged, and lane 0 stores the new state with the bookkeeping.
+// <NPL, false> is singa_sample_token: cls, gstate and allowed_logp are not read.
+template <int NPL, bool GRAMMAR>
 __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
                                                            const unsigned char* __restrict__ allowed,
                                                            const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
@@ -1549,7 +1591,8 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
                                                            unsigned char* __restrict__ finished, int32_t* __restrict__ length,
                                                            float* __restrict__ sum_logp, long long* __restrict__ tokens,
                                                            long long* __restrict__ next, int32_t* __restrict__ live,
-                                                           float* __restrict__ tok_logp) {
+                                                           float* __restrict__ tok_logp, const unsigned char* __restrict__ cls,
+                                                           int32_t* __restrict__ gstate, float* __restrict__ allowed_logp) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                           // wave-uniform from here on
@@ -1561,17 +1604,24 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
             tokens[slot] = pad;
             next[row] = pad;
             if (tok_logp) tok_logp[slot] = 0.f;
+            if (GRAMMAR && allowed_logp) allowed_logp[slot] = 0.f;
         }
         return;
     }
     const float NEG = -INFINITY;
     float z[NPL];
     bool ok[NPL];
+    int gs = 0, c[NPL];
+    if constexpr (GRAMMAR) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const int i = k * 64 + lane;
         z[k] = i < V ? logits[(long long)row * V + i] : NEG;
         ok[k] = i < V && (!allowed || allowed[i]);
+        if constexpr (GRAMMAR) {
+            c[k] = i < V ? cls[i] : 0;
+            ok[k] = ok[k] && smiles_allows(gs, c[k], (int)(T - 2 - t));
+        }
     }
     // the model's own log-sum-exp (tau = 1, nothing filtered)
     float zmax = NEG;
@@ -1582,6 +1632,13 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
     const float lse = zmax + logf(wave_sum64(zsum));
+    float alp = 0.f;                                                   // log of the model's mass on the effective mask
+    if (GRAMMAR && allowed_logp) {
+        float asum = 0.f;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) asum += ok[k] ? expf(z[k] - zmax) : 0.f;
+        alp = zmax + logf(wave_sum64(asum)) - lse;
+    }
 
     int tok;
     if (tau == 0.f) {                                                  // greedy: largest allowed logit, lowest index among equals
@@ -1668,13 +1725,22 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
         hit = wave_min64i(hit);
         tok = hit != INT32_MAX ? hit : wave_max64i(last);
     }
-    tok = tok < 0 || tok >= V ? pad : tok;                             // no allowed token at all: nothing sensible to draw
+    const bool drawn = tok >= 0 && tok < V;
+    tok = drawn ? tok : pad;                                           // no allowed token at all: nothing sensible to draw
     // the chosen token's own logit: it sits in lane tok % 64, register tok / 64
     float zt = 0.f;
+    int ct = 0;                                                        // and, under the grammar, its class byte
 #pragma unroll
     for (int k = 0; k < NPL; ++k)
-        if (tok >> 6 == k) zt = lane_bcast_f(z[k], tok & 63);
+        if (tok >> 6 == k) {
+            zt = lane_bcast_f(z[k], tok & 63);
+            if constexpr (GRAMMAR) ct = __builtin_amdgcn_readlane(c[k], tok & 63);
+        }
     if (lane == 0) {
+        if constexpr (GRAMMAR) {
+            if (drawn) gstate[row] = smiles_next(gs, ct);
+            if (allowed_logp) allowed_logp[slot] = alp;
+        }
         const float lp = zt - lse;
         tokens[slot] = tok;
         next[row] = tok;
@@ -6650,8 +6716,9 @@ int singa_sample_token(const float* logits, const float* uniforms, const unsigne
     const dim3 grid((rows + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    hipLaunchKernelGGL(sample_token_kernel<NPL>, grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, \
-                       top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp)
+    hipLaunchKernelGGL((sample_token_kernel<NPL, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
+                       T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp,                  \
+                       (const unsigned char*)nullptr, (int32_t*)nullptr, (float*)nullptr)
     if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
     else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
     else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
@@ -6659,6 +6726,49 @@ int singa_sample_token(const float* logits, const float* uniforms, const unsigne
 #undef SINGA_SAMPLE_LAUNCH
     return check_launch("sample_token");
 #endif
+}
+
+int singa_sample_token_grammar(const float* logits, const float* uniforms, const unsigned char* allowed,
+                               const unsigned char* cls, const long long* pos, int pos_offset, int rows, int V, int T, float tau,
+                               int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
+                               float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp,
+                               int32_t* gstate, float* allowed_logp, void* stream) {
+    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live || !cls || !gstate)
+        return fail(SINGA_E_NULL, "sample_token_grammar: null pointer");
+    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token_grammar: vocabulary of 1..1024 tokens");
+    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token_grammar: temperature must be >= 0");
+    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token_grammar: top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token_grammar: top_p must be in (0, 1]");
+    if (T < 3 || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
+        return fail(SINGA_E_SHAPE, "sample_token_grammar: T >= 3 columns, eos / pad inside the vocabulary");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "sample_token_grammar: not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
+    hipLaunchKernelGGL((sample_token_kernel<NPL, true>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
+                       T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,     \
+                       allowed_logp)
+    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
+    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
+    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
+    else SINGA_SAMPLE_LAUNCH(16);
+#undef SINGA_SAMPLE_LAUNCH
+    return check_launch("sample_token_grammar");
+#endif
+}
+
+int singa_smiles_rule_host(const unsigned char* cls, const int32_t* state, const int32_t* rem, int n, unsigned char* ok,
+                           int32_t* next_state) {
+    if (!cls || !state || !rem || !ok || !next_state) return fail(SINGA_E_NULL, "smiles_rule_host: null pointer");
+    if (n < 0) return fail(SINGA_E_SHAPE, "smiles_rule_host: n must be >= 0");
+    for (int i = 0; i < n; ++i) {
+        ok[i] = smiles_allows(state[i], cls[i], rem[i]) ? 1 : 0;
+        next_state[i] = ok[i] ? smiles_next(state[i], cls[i]) : state[i];
+    }
+    return SINGA_OK;
 }
 
 int singa_edge_mlp_fwd(const float* attr, const float* w1tk, const float* b1k, const float* w2tk, const float* b2k,

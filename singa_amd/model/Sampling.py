@@ -20,10 +20,17 @@ by its uniforms, on any device and at any row count.
 
 A live row that draws '^' or '&' carries on: to the KV-cached decoder they are tokens like any other (as in beam search, the
 caches have no padding mask).  `suppress=("&", "^")` keeps them from being drawn.
+
+`grammar="smiles"` constrains the draw to syntactically complete SMILES: the token choice then runs as
+`ops.sample_token_grammar` (kernel `singa_sample_token_grammar`; include/singa_hip_gen.h states the rule), which keeps one
+more word of state per row on the device and masks, per row, what cannot follow the row's prefix or could not be finished in
+the columns left.  Every row then ends in '$' before `max_length` and the text in front of it has balanced branches, paired
+ring-closure digits and no dangling bond symbol.  Syntax only: valence, aromaticity, duplicate ring bonds (C1C1), %nn
+closures and beam search are outside the rule (singa_amd/smiles.py).  The step stays one captured graph.
 """
 import torch
 
-from .. import ops
+from .. import ops, smiles
 from .BeamSearch import KVDecoder
 
 # Row count above which `fused=None` takes the library path (GEMMs that read a layer's weights once per step) instead of the
@@ -41,7 +48,7 @@ def cache_bytes(decoder, rows, positions):
 
 @torch.no_grad()
 def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0, top_k=0,
-           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None):
+           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None):
     """`num_samples` sequences for each of the `batch_size` pockets of `example`, drawn token by token from the model's own
     distribution reshaped by `temperature` (0 = greedy), `top_k` (0 = off) and `top_p` (1 = off).
 
@@ -55,7 +62,13 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     '$' if the model ended it before `max_length`, and is padded with '^'.  `trace`, if a dict, receives `lengths` (int32:
     tokens drawn per row, the '$' included, '&' not), `sum_logp` (f32: the model's own log-likelihood of the drawn tokens,
     temperature 1 and nothing filtered), `token_logp` [rows, max_length] (per drawn token), `uniforms`, `path`
-    ('k17' / 'library') and `steps` (tokens decoded before every row had ended)."""
+    ('k17' / 'library') and `steps` (tokens decoded before every row had ended).
+
+    `grammar="smiles"`: only tokens that keep the row a prefix of a syntactically complete SMILES string which still fits
+    into `max_length` (>= 3) are drawn, so every row ends with '$'.  `token_logp` / `sum_logp` stay the unconstrained model's;
+    `trace` also receives `allowed_logp` [rows, max_length]: log of the model's probability mass on the tokens the rule (and
+    `suppress`) allowed at that step, so that token_logp - allowed_logp is the log-probability under the constrained proposal.
+    ValueError for an unknown grammar, max_length < 3, or a `suppress` that removes every atom, '$', or ')' but not '('."""
     dev = torch.device(device)
     if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
         raise RuntimeError("sample runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
@@ -63,6 +76,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         raise ValueError(f"sample: num_samples >= 1, batch_size >= 1, max_length >= 2 (got {num_samples}, {batch_size}, {max_length})")
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError(f"sample: temperature >= 0, top_k >= 0, 0 < top_p <= 1 (got {temperature}, {top_k}, {top_p})")
+    cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
     tf = model.model
     voc = list(smiVoc)
     V = len(voc)
@@ -104,6 +118,10 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
              "sum_logp": torch.empty(rows, dtype=torch.float32, device=dev),
              "live": torch.empty(1, dtype=torch.int32, device=dev),
              "tok_logp": torch.empty(rows, max_length, dtype=torch.float32, device=dev)}
+    if grammar is not None:
+        cls = torch.as_tensor(cls).to(dev)
+        state["grammar"] = torch.empty(rows, dtype=torch.int32, device=dev)
+        state["allowed_logp"] = torch.empty(rows, max_length, dtype=torch.float32, device=dev)
 
     def start():
         state["tokens"].fill_(pad)
@@ -111,12 +129,18 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         state["next"].fill_(sos)
         state["finished"].zero_(), state["length"].zero_(), state["sum_logp"].zero_(), state["tok_logp"].zero_()
         state["live"].fill_(rows)
+        if grammar is not None:
+            state["grammar"].fill_(smiles.FRESH), state["allowed_logp"].zero_()
         kv.reset()
 
     def step():
         out = kv.advance(kv.token_input(state["next"]))
-        ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
-                         float(top_p), eos, pad, allowed)
+        if grammar is None:
+            ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
+                             float(top_p), eos, pad, allowed)
+        else:
+            ops.sample_token_grammar(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, cls, float(temperature),
+                                     int(top_k), float(top_p), eos, pad, allowed)
 
     replay = step
     if graph:
@@ -149,4 +173,6 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     if trace is not None:
         trace.update(lengths=state["length"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"], uniforms=uniforms,
                      path="k17" if kv.fused else "library", steps=steps)
+        if grammar is not None:
+            trace.update(allowed_logp=state["allowed_logp"])
     return state["tokens"]

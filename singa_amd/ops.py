@@ -810,12 +810,8 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams):
     return out
 
 
-def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0, allowed=None):
-    """The next token of every row, drawn on the device (`singa_sample_token`, include/singa_hip.h states the rule; inference
-    only, no autograd): one launch.  logits [R, V] f32 (raw projection outputs), uniforms [>= T - 1, R] f32 in [0, 1), pos: int64
-    device scalar, the step is pos - pos_offset.  `state`: dict of the rows' device state, updated in place - tokens [R, T] int64,
-    next [R] int64, finished [R] uint8, length [R] int32, sum_logp [R] f32, live [1] int32 and, optionally, tok_logp [R, T] f32.
-    allowed: [V] uint8, 0 = never drawn."""
+def _sample_token_views(what, logits, uniforms, pos, state, allowed, extra=()):
+    """The argument checks `sample_token` and `sample_token_grammar` share; `extra`: further (tensor, dtype, shape) triples."""
     _dev(logits, uniforms, state["sum_logp"], state["length"], state["live"], state.get("tok_logp"))
     R, V = logits.shape
     tokens, nxt, fin = state["tokens"], state["next"], state["finished"]
@@ -823,19 +819,48 @@ def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_
     for t, dt, shape in ((tokens, torch.int64, (R, T)), (nxt, torch.int64, (R,)), (fin, torch.uint8, (R,)),
                          (state["length"], torch.int32, (R,)), (state["sum_logp"], torch.float32, (R,)),
                          (state["live"], torch.int32, (1,)), (pos, torch.int64, None), (allowed, torch.uint8, (V,)),
-                         (state.get("tok_logp"), torch.float32, (R, T))):
+                         (state.get("tok_logp"), torch.float32, (R, T))) + tuple(extra):
         if t is None:
             continue
         if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
-            raise RuntimeError(f"sample_token: expected a contiguous {dt} GPU tensor of shape {shape}, got {t.dtype} "
+            raise RuntimeError(f"{what}: expected a contiguous {dt} GPU tensor of shape {shape}, got {t.dtype} "
                                f"{tuple(t.shape)} on {t.device}")
     if not (logits.is_contiguous() and uniforms.is_contiguous() and uniforms.dim() == 2 and uniforms.shape[1] == R
             and uniforms.shape[0] >= T - 1):
-        raise RuntimeError(f"sample_token: logits [R, V] and uniforms [>= T - 1, R] must be contiguous, got "
+        raise RuntimeError(f"{what}: logits [R, V] and uniforms [>= T - 1, R] must be contiguous, got "
                            f"{tuple(logits.shape)}, {tuple(uniforms.shape)} for T = {T}")
+    return R, V, T
+
+
+def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0, allowed=None):
+    """The next token of every row, drawn on the device (`singa_sample_token`, include/singa_hip.h states the rule; inference
+    only, no autograd): one launch.  logits [R, V] f32 (raw projection outputs), uniforms [>= T - 1, R] f32 in [0, 1), pos: int64
+    device scalar, the step is pos - pos_offset.  `state`: dict of the rows' device state, updated in place - tokens [R, T] int64,
+    next [R] int64, finished [R] uint8, length [R] int32, sum_logp [R] f32, live [1] int32 and, optionally, tok_logp [R, T] f32.
+    allowed: [V] uint8, 0 = never drawn."""
+    R, V, T = _sample_token_views("sample_token", logits, uniforms, pos, state, allowed)
     _chk(_lib.lib().singa_sample_token(_p(logits), _p(uniforms), _p(allowed), _p(pos), pos_offset, R, V, T, temperature, top_k, top_p,
-                                       eos, pad, _p(fin), _p(state["length"]), _p(state["sum_logp"]), _p(tokens), _p(nxt),
-                                       _p(state["live"]), _p(state.get("tok_logp")), _stream()), "singa_sample_token")
+                                       eos, pad, _p(state["finished"]), _p(state["length"]), _p(state["sum_logp"]),
+                                       _p(state["tokens"]), _p(state["next"]), _p(state["live"]), _p(state.get("tok_logp")),
+                                       _stream()), "singa_sample_token")
+
+
+def sample_token_grammar(logits, uniforms, pos, pos_offset, state, cls, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0,
+                         allowed=None):
+    """`sample_token` under the SMILES rule of include/singa_hip_gen.h (`singa_sample_token_grammar`): the mask is `allowed` AND
+    what the rule lets follow the row's state.  cls: [V] uint8 class bytes (`singa_amd.smiles.classify`); `state` as for
+    `sample_token`, plus grammar [R] int32 (the rows' packed rule state, `smiles.FRESH` for a fresh row; updated in place) and,
+    optionally, allowed_logp [R, T] f32 (log of the model's probability mass on the effective mask)."""
+    _dev(state["grammar"], state.get("allowed_logp"))
+    (R, V), T = logits.shape, state["tokens"].shape[1]
+    _sample_token_views("sample_token_grammar", logits, uniforms, pos, state, allowed,
+                                  ((cls, torch.uint8, (V,)), (state["grammar"], torch.int32, (R,)),
+                                   (state.get("allowed_logp"), torch.float32, (R, T))))
+    _chk(_lib.lib().singa_sample_token_grammar(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), pos_offset, R, V, T,
+                                               temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
+                                               _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]),
+                                               _p(state.get("tok_logp")), _p(state["grammar"]), _p(state.get("allowed_logp")),
+                                               _stream()), "singa_sample_token_grammar")
 
 
 class _MaskedSoftmax(torch.autograd.Function):

@@ -3,12 +3,15 @@
 atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket with random-init weights, next to the beam
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
-    python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table]
+    python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
 per step, and their ratio); with `--table` also both decoder paths at rows = 20, 128, 512, 2048 (the table `fused=None`
-picks from, profiles/sampling/README.md).  A generation is timed as a whole - encoder, cache set-up, graph capture and
+picks from, profiles/sampling/README.md); with `--grammar` also the k17 step under `grammar="smiles"` next to the plain one at
+rows = 20, 128, 2048, both timed in this process, runs interleaved (`grammar_table`; '$' is then not suppressed - the grammar
+needs it - but its logit keeps rows from ending before the budget forces them to: `steps` is reported).  A generation is timed
+as a whole - encoder, cache set-up, graph capture and
 every step - and divided by its steps, as bench_beam.py does.
 """
 import argparse
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--table", action="store_true")
+    ap.add_argument("--grammar", action="store_true", help="also time the grammar-constrained step (grammar_table)")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -73,11 +77,11 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 
-    def run_sample(rows, fused):
+    def run_sample(rows, fused, grammar=None):
         tr = {}
         prop = torch.ones(rows, 3, device=dev)
         sample(model, voc, rows, 1, T, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-               suppress=("$",), generator=gen, fused=fused, trace=tr)
+               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar)
         run_sample.path = tr["path"]
         return tr["steps"]
 
@@ -114,6 +118,18 @@ def main():
                 ms = statistics.median(timed(lambda: run_sample(rows, f)) for _ in range(3 if rows >= 512 else args.reps))
                 table.append(dict(entry(rows, ms), path=name))
         res["table"] = table
+    if args.grammar:
+        gtable = []
+        for rows in (20, 128, 2048):
+            run_sample(rows, True), run_sample(rows, True, "smiles")
+            plain, gram, steps = [], [], []
+            for _ in range(3 if rows >= 512 else args.reps):
+                plain.append(timed(lambda: run_sample(rows, True)))
+                gram.append(timed(lambda: steps.append(run_sample(rows, True, "smiles")) or steps[-1]))
+            gtable.append({"rows": rows, "path": "k17", "plain_ms_per_step": round(statistics.median(plain), 4),
+                           "grammar_ms_per_step": round(statistics.median(gram), 4), "grammar_steps": steps,
+                           "plain_runs_ms": [round(x, 4) for x in plain], "grammar_runs_ms": [round(x, 4) for x in gram]})
+        res["grammar_table"] = gtable
     print(json.dumps(res))
 
 
