@@ -9,10 +9,16 @@ example graphs the reference bundles) or `--data synthetic`.  No chemistry toolk
 they were decoded, without a validity filter.  `--grammar smiles` (sample mode) removes the syntactic rejects where the token
 is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired ring-closure digits and no
 dangling bond symbol (include/singa_hip_gen.h states the rule).  Chemical validity - valence, aromaticity, duplicate ring
-bonds - is still not checked, and beam search is not constrained.
+bonds - is still not checked, and beam search is not constrained.  `--prefix TEXT` (sample mode) starts every sequence with
+that fragment - a scaffold to continue; under `--grammar smiles` a fragment the rule refuses is an error before anything runs.
+`--mode score --molecules FILE` draws nothing: FILE holds lines of `pocket name<TAB>SMILES`, and every molecule's
+log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input.
 
     python gen.py --config ./config/train.yml --ckpt logs/.../checkpoints/100.pt --data golden --mode sample \\
                   --num-samples 100 --temperature 0.9 --top-p 0.95 --seed 1
+
+    python gen.py --data golden --mode sample --num-samples 100 --grammar smiles --prefix "c1ccc("
+    python gen.py --data golden --mode score --molecules library.tsv
 
 One line per sequence on stdout (or in `--out`), tab-separated: pocket name, the SMILES string between '&' and '$', the
 number of tokens decoded ('$' included), the summed log-probability of the sequence under the model.  Everything else that
@@ -37,7 +43,7 @@ def main():
     ap.add_argument("--data", choices=["golden", "synthetic"], default="golden")
     ap.add_argument("--pockets", type=int, default=3, help="number of pockets (synthetic data)")
     ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 4 or 6)")
-    ap.add_argument("--mode", choices=["beam", "sample"], default="sample")
+    ap.add_argument("--mode", choices=["beam", "sample", "score"], default="sample")
     ap.add_argument("--num-samples", type=int, default=100, help="sequences per pocket (sample)")
     ap.add_argument("--num-beams", type=int, default=20, help="beams per pocket (beam); the best hypothesis is written")
     ap.add_argument("--max-length", type=int, default=None, help="default: model.decoder.tgt_len + 1")
@@ -46,6 +52,9 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--grammar", choices=["none", "smiles"], default="none",
                     help="sample: draw only tokens that keep the sequence a completable SMILES string")
+    ap.add_argument("--prefix", type=str, default=None, help="sample: every sequence starts with this SMILES fragment")
+    ap.add_argument("--molecules", type=str, default=None,
+                    help="score: a file of lines `pocket name<TAB>SMILES` (further columns are ignored)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--prop", type=float, nargs=3, default=[1.0, 1.0, 1.0], metavar=("V", "Q", "S"),
                     help="the property prompt: vina score below -7.5, QED above 0.6, SAS below 4 (1 = wanted)")
@@ -53,6 +62,8 @@ def main():
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
     assert args.grammar == "none" or args.mode == "sample", "--grammar constrains sampling only: beam search selects on the host"
+    assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
+    assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
     dev = torch.device(args.device if ":" in args.device else "cuda:0")
     torch.cuda.set_device(dev)
 
@@ -63,7 +74,8 @@ def main():
     from singa_amd.model.BeamSearch import beam_search
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
-    from singa_amd.model.Sampling import sample
+    from singa_amd import smiles
+    from singa_amd.model.Sampling import sample, score
 
     cfg = load_config(args.config, lmax=args.lmax)
     torch.manual_seed(args.seed)
@@ -94,14 +106,33 @@ def main():
     knn = knn_graph(batch[G.PA]["pos"], cfg.model.encoder.knn, ids, B, DenseMap(ids, B))
     ex.protein_knn = knn[:, knn[0] >= 0]
 
+    if args.mode == "score":
+        wanted = [ln.rstrip("\n").split("\t")[:2] for ln in open(args.molecules) if ln.strip() and not ln.startswith("#")]
+        assert wanted and all(len(w) == 2 and w[0] in names for w in wanted), \
+            f"--molecules: every line is `pocket name<TAB>SMILES`, the pockets are {names}"
+        mols = [[smi for name, smi in wanted if name == n] for n in names]
+        grammar = None if args.grammar == "none" else args.grammar
+        res = score(model, voc, mols, B, ex, torch.tensor([args.prop], dtype=torch.float32) if cfg.train.num_props else None,
+                    device=dev, max_length=args.max_length, grammar=grammar)
+        print(f"# scored {len(wanted)} molecules for {B} pockets")
+        seen = {n: 0 for n in names}
+        lines = []
+        for name, smi in wanted:
+            b, i = names.index(name), seen[name]
+            seen[name] += 1
+            lines.append(f"{name}\t{smi}\t{res['length'][b][i]}\t{res['sum_logp'][b][i]:.6f}")
+        emit(args, lines)
+        return
+
     per = args.num_samples if args.mode == "sample" else args.num_beams
     prop = torch.tensor([args.prop] * (B * per), dtype=torch.float32, device=dev) if cfg.train.num_props else None
     tr = {}
     if args.mode == "sample":
         gen = torch.Generator(device=dev).manual_seed(args.seed)
+        forced = None if args.prefix is None else smiles.encode([args.prefix] * B, voc, max_length)
         tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
                         top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
-                        grammar=None if args.grammar == "none" else args.grammar).cpu()
+                        grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
         lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
         print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
     else:
@@ -118,6 +149,10 @@ def main():
                 break
             body.append(voc[t])
         lines.append(f"{names[r // per]}\t{''.join(body)}\t{lengths[r]}\t{logps[r]:.6f}")
+    emit(args, lines)
+
+
+def emit(args, lines):
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -141,11 +141,18 @@ _GEN_SIGS = {
 }
 GEN_EXPORTS = tuple(_GEN_SIGS)
 
+# include/singa_hip_force.h: forced tokens in sampled generation (scaffold continuation, scoring); a table of its own
+_FORCE_SIGS = {
+    "singa_sample_token_forced": ([P, P, P, P, P, I32, I32, I32, I32, F32, I32, F32, I32, I32] + [P] * 12, I32),
+}
+FORCE_EXPORTS = tuple(_FORCE_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
-    for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
+            list(_FORCE_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -22,6 +22,7 @@
 #include "../../include/singa_hip.h"
 #include "../../include/singa_hip_lab.h"
 #include "../../include/singa_hip_gen.h"
+#include "../../include/singa_hip_force.h"
 #include "so3_index.h"
 
 namespace {
@@ -1582,8 +1583,12 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
 
 // GRAMMAR (singa_sample_token_grammar): the row's state word is read once (wave-uniform), the rule is ANDed into ok[] from the
 // class bytes of the lane's tokens, the choice below runs unchanged, and lane 0 stores the new state with the bookkeeping.
-// <NPL, false> is singa_sample_token: cls, gstate and allowed_logp are not read.
-template <int NPL, bool GRAMMAR>
+// <NPL, false, *> is singa_sample_token: cls, gstate and allowed_logp are not read.
+// FORCED (singa_sample_token_forced, include/singa_hip_force.h): one wave-uniform 8-byte read of forced[row][t + 1]; a value
+// inside [0, V) replaces the choice (mask, filters and the uniform take no part) and the bookkeeping below runs unchanged;
+// the rank of the emitted token among the raw logits is one wave reduction over the registers the row already sits in.
+// <NPL, *, false> reads neither `forced` nor `rank`.
+template <int NPL, bool GRAMMAR, bool FORCED>
 __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
                                                            const unsigned char* __restrict__ allowed,
                                                            const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
@@ -1592,7 +1597,8 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
                                                            float* __restrict__ sum_logp, long long* __restrict__ tokens,
                                                            long long* __restrict__ next, int32_t* __restrict__ live,
                                                            float* __restrict__ tok_logp, const unsigned char* __restrict__ cls,
-                                                           int32_t* __restrict__ gstate, float* __restrict__ allowed_logp) {
+                                                           int32_t* __restrict__ gstate, float* __restrict__ allowed_logp,
+                                                           const long long* __restrict__ forced, int32_t* __restrict__ rank) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                           // wave-uniform from here on
@@ -1605,8 +1611,15 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
             next[row] = pad;
             if (tok_logp) tok_logp[slot] = 0.f;
             if (GRAMMAR && allowed_logp) allowed_logp[slot] = 0.f;
+            if (FORCED && rank) rank[slot] = 0;
         }
         return;
+    }
+    int given = -1;                                                    // FORCED: the token to take, -1 = this column is free
+    if constexpr (FORCED) {
+        const long long f = forced[slot];
+        const int lo = __builtin_amdgcn_readfirstlane((int)(f & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(f >> 32));
+        given = (hi == 0 && lo >= 0 && lo < V) ? lo : -1;
     }
     const float NEG = -INFINITY;
     float z[NPL];
@@ -1641,7 +1654,9 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
     }
 
     int tok;
-    if (tau == 0.f) {                                                  // greedy: largest allowed logit, lowest index among equals
+    if (FORCED && given >= 0) {
+        tok = given;
+    } else if (tau == 0.f) {                                           // greedy: largest allowed logit, lowest index among equals
         float bv = NEG;
         int bi = INT32_MAX;
 #pragma unroll
@@ -1736,10 +1751,25 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
             zt = lane_bcast_f(z[k], tok & 63);
             if constexpr (GRAMMAR) ct = __builtin_amdgcn_readlane(c[k], tok & 63);
         }
+    int above = 0;                                                     // FORCED: tokens ranked before the emitted one
+    if constexpr (FORCED) {
+        if (rank) {                                                    // (wave-uniform)
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                const int i = k * 64 + lane;
+                above += (i < V && (z[k] > zt || (z[k] == zt && i < tok))) ? 1 : 0;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+        }
+    }
     if (lane == 0) {
         if constexpr (GRAMMAR) {
             if (drawn) gstate[row] = smiles_next(gs, ct);
             if (allowed_logp) allowed_logp[slot] = alp;
+        }
+        if constexpr (FORCED) {
+            if (rank) rank[slot] = drawn ? above : -1;
         }
         const float lp = zt - lse;
         tokens[slot] = tok;
@@ -6716,9 +6746,10 @@ int singa_sample_token(const float* logits, const float* uniforms, const unsigne
     const dim3 grid((rows + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    hipLaunchKernelGGL((sample_token_kernel<NPL, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
+    hipLaunchKernelGGL((sample_token_kernel<NPL, false, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
                        T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp,                  \
-                       (const unsigned char*)nullptr, (int32_t*)nullptr, (float*)nullptr)
+                       (const unsigned char*)nullptr, (int32_t*)nullptr, (float*)nullptr, (const long long*)nullptr,                  \
+                       (int32_t*)nullptr)
     if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
     else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
     else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
@@ -6748,15 +6779,57 @@ int singa_sample_token_grammar(const float* logits, const float* uniforms, const
     const dim3 grid((rows + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    hipLaunchKernelGGL((sample_token_kernel<NPL, true>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
+    hipLaunchKernelGGL((sample_token_kernel<NPL, true, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
                        T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,     \
-                       allowed_logp)
+                       allowed_logp, (const long long*)nullptr, (int32_t*)nullptr)
     if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
     else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
     else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
     else SINGA_SAMPLE_LAUNCH(16);
 #undef SINGA_SAMPLE_LAUNCH
     return check_launch("sample_token_grammar");
+#endif
+}
+
+int singa_sample_token_forced(const float* logits, const float* uniforms, const unsigned char* allowed,
+                              const unsigned char* cls, const long long* pos, int pos_offset, int rows, int V, int T, float tau,
+                              int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
+                              float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp,
+                              int32_t* gstate, float* allowed_logp, const long long* forced, int32_t* rank, void* stream) {
+    const bool grammar = cls && gstate;
+    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live || !forced)
+        return fail(SINGA_E_NULL, "sample_token_forced: null pointer");
+    if (!grammar && (cls || gstate || allowed_logp))
+        return fail(SINGA_E_NULL, "sample_token_forced: cls and gstate go together (allowed_logp only with them)");
+    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token_forced: vocabulary of 1..1024 tokens");
+    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token_forced: temperature must be >= 0");
+    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token_forced: top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token_forced: top_p must be in (0, 1]");
+    if (T < (grammar ? 3 : 2) || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
+        return fail(SINGA_E_SHAPE, "sample_token_forced: T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "sample_token_forced: not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
+    do {                                                                                                                      \
+        if (grammar)                                                                                                          \
+            hipLaunchKernelGGL((sample_token_kernel<NPL, true, true>), grid, block, 0, st, logits, uniforms, allowed, pos,    \
+                               pos_offset, rows, V, T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, \
+                               live, tok_logp, cls, gstate, allowed_logp, forced, rank);                                      \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((sample_token_kernel<NPL, false, true>), grid, block, 0, st, logits, uniforms, allowed, pos,   \
+                               pos_offset, rows, V, T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, \
+                               live, tok_logp, cls, gstate, allowed_logp, forced, rank);                                      \
+    } while (0)
+    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
+    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
+    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
+    else SINGA_SAMPLE_LAUNCH(16);
+#undef SINGA_SAMPLE_LAUNCH
+    return check_launch("sample_token_forced");
 #endif
 }
 

@@ -27,6 +27,14 @@ more word of state per row on the device and masks, per row, what cannot follow 
 the columns left.  Every row then ends in '$' before `max_length` and the text in front of it has balanced branches, paired
 ring-closure digits and no dangling bond symbol.  Syntax only: valence, aromaticity, duplicate ring bonds (C1C1), %nn
 closures and beam search are outside the rule (singa_amd/smiles.py).  The step stays one captured graph.
+
+`forced=` gives tokens instead of drawing them: the token choice then runs as `ops.sample_token_forced` (kernel
+`singa_sample_token_forced`; include/singa_hip_force.h states the rule), which reads one more 8-byte word per row from a
+fixed device matrix indexed by the device-resident position - like the uniforms, so the step stays one captured graph - and,
+where that word is a token, takes it with the bookkeeping of a drawn one.  Forcing the first columns of a row continues a
+scaffold; forcing every column up to '$' scores a given molecule (`score`): the log-likelihood then comes from the same
+kernels, in the same order, as the `sum_logp` of a drawn row, so the two are comparable bit for bit.  The host validates what
+it forces (`smiles.check_forced`, through the library's own rule) before any device work; the kernel does not.
 """
 import torch
 
@@ -48,7 +56,7 @@ def cache_bytes(decoder, rows, positions):
 
 @torch.no_grad()
 def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0, top_k=0,
-           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None):
+           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None, forced=None):
     """`num_samples` sequences for each of the `batch_size` pockets of `example`, drawn token by token from the model's own
     distribution reshaped by `temperature` (0 = greedy), `top_k` (0 = off) and `top_p` (1 = off).
 
@@ -68,7 +76,16 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     into `max_length` (>= 3) are drawn, so every row ends with '$'.  `token_logp` / `sum_logp` stay the unconstrained model's;
     `trace` also receives `allowed_logp` [rows, max_length]: log of the model's probability mass on the tokens the rule (and
     `suppress`) allowed at that step, so that token_logp - allowed_logp is the log-probability under the constrained proposal.
-    ValueError for an unknown grammar, max_length < 3, or a `suppress` that removes every atom, '$', or ')' but not '('."""
+    ValueError for an unknown grammar, max_length < 3, or a `suppress` that removes every atom, '$', or ')' but not '('.
+
+    `forced`: int64 tensor or array [rows, max_length] or [batch_size, max_length] (one prefix per pocket, repeated for its
+    `num_samples` rows), `smiles.encode` builds it: a value inside the vocabulary in column c is the token of column c, given
+    instead of drawn - with the same bookkeeping, so `token_logp` / `sum_logp` hold the model's log-probability of it - and any
+    other value (-1) leaves the column to the draw.  A row's forced columns are one run from column 1: a scaffold to continue,
+    or, with its '$', a whole molecule to score (`score`).  `smiles.check_forced` refuses anything else, and under `grammar` a
+    prefix the rule does not allow or that cannot be finished in `max_length`, with a ValueError before any device work.
+    `trace` also receives `rank` [rows, max_length] int32: the rank of every emitted token among the row's raw logits (0 = the
+    arg-max; 0 behind a row's end).  Free columns are drawn exactly as without `forced`, from the same uniforms."""
     dev = torch.device(device)
     if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
         raise RuntimeError("sample runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
@@ -77,6 +94,14 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError(f"sample: temperature >= 0, top_k >= 0, 0 < top_p <= 1 (got {temperature}, {top_k}, {top_p})")
     cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
+    if forced is not None:
+        forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
+        forced = smiles.check_forced(forced, smiVoc, max_length, grammar)
+        if forced.shape[0] == batch_size and num_samples > 1:
+            forced = forced.repeat(num_samples, 0)
+        if forced.shape[0] != batch_size * num_samples:
+            raise ValueError(f"sample: forced has {forced.shape[0]} rows, expected {batch_size * num_samples} (or one per pocket: "
+                             f"{batch_size})")
     tf = model.model
     voc = list(smiVoc)
     V = len(voc)
@@ -122,6 +147,9 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         cls = torch.as_tensor(cls).to(dev)
         state["grammar"] = torch.empty(rows, dtype=torch.int32, device=dev)
         state["allowed_logp"] = torch.empty(rows, max_length, dtype=torch.float32, device=dev)
+    if forced is not None:
+        forced = torch.as_tensor(forced).to(dev).contiguous()          # uploaded once; the step indexes it with the device's position
+        state["rank"] = torch.empty(rows, max_length, dtype=torch.int32, device=dev)
 
     def start():
         state["tokens"].fill_(pad)
@@ -131,11 +159,17 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         state["live"].fill_(rows)
         if grammar is not None:
             state["grammar"].fill_(smiles.FRESH), state["allowed_logp"].zero_()
+        if forced is not None:
+            state["rank"].zero_()
         kv.reset()
 
     def step():
         out = kv.advance(kv.token_input(state["next"]))
-        if grammar is None:
+        if forced is not None:
+            ops.sample_token_forced(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, forced,
+                                    cls if grammar is not None else None, float(temperature), int(top_k), float(top_p), eos, pad,
+                                    allowed)
+        elif grammar is None:
             ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
                              float(top_p), eos, pad, allowed)
         else:
@@ -175,4 +209,58 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
                      path="k17" if kv.fused else "library", steps=steps)
         if grammar is not None:
             trace.update(allowed_logp=state["allowed_logp"])
+        if forced is not None:
+            trace.update(rank=state["rank"])
     return state["tokens"]
+
+
+def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda", max_length=None, grammar=None, fused=None):
+    """The model's own log-likelihood of given molecules: `molecules[b]` is the list of SMILES strings (or token lists, as
+    `smiles.encode` takes them) to score for pocket b of `example`; the lists may differ in length.  Every molecule is one row
+    of `sample` with all its columns forced up to and including '$', so a score comes from the same kernels, in the same
+    order, as the `sum_logp` that `sample` reports for a drawn row.  Shorter lists are padded with empty rows (forced to '$'
+    in column 1), which are dropped from the result.  `max_length`: default the longest molecule + 2 ('&' and '$').  `prop`:
+    [num_props] or [batch_size, num_props] (one prompt per pocket) or one row per molecule slot
+    [batch_size * longest list, num_props].
+
+    Returns a dict of per-pocket lists, one entry per molecule in the order given: `sum_logp` (float), `length` (tokens, the
+    '$' included), `token_logp` and `rank` (arrays of `length` entries: per token, '$' last; rank 0 = the model's arg-max,
+    so the mean of rank == 0 is the top-1 accuracy) and, under `grammar`, `allowed_logp`.  ValueError before any launch for a
+    molecule the vocabulary cannot spell, one that does not fit `max_length`, or, under `grammar`, one the rule refuses."""
+    dev = torch.device(device)
+    if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
+        raise RuntimeError("score runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
+    if len(molecules) != batch_size:
+        raise ValueError(f"score: one list of molecules per pocket: got {len(molecules)} lists for {batch_size} pockets")
+    voc = [str(v) for v in smiVoc]
+    per = max((len(m) for m in molecules), default=0)
+    if per < 1:
+        raise ValueError("score: no molecule to score")
+    items = []
+    for m in molecules:
+        items += [smiles.tokenize(x, voc) if isinstance(x, str) else list(x) for x in m] + [[]] * (per - len(m))
+    if max_length is None:
+        max_length = max(len(x) for x in items) + 2
+    forced = smiles.encode(items, voc, max_length, end=True)
+    if prop is not None:
+        prop = torch.as_tensor(prop).float().reshape(-1, torch.as_tensor(prop).shape[-1])
+        if prop.shape[0] == 1:
+            prop = prop.repeat(batch_size * per, 1)
+        elif prop.shape[0] == batch_size and per > 1:
+            prop = prop.repeat_interleave(per, 0)
+    tr = {}
+    sample(model, smiVoc, per, batch_size, max_length, example, prop, device=device, uniforms=torch.zeros(max_length, batch_size * per),
+           fused=fused, trace=tr, grammar=grammar, forced=forced)
+    keys = {"token_logp": "token_logp", "rank": "rank"}
+    if grammar is not None:
+        keys["allowed_logp"] = "allowed_logp"
+    host = {k: tr[v].cpu().numpy() for k, v in keys.items()}
+    lengths, sums = tr["lengths"].cpu().numpy(), tr["sum_logp"].cpu().numpy()
+    out = {k: [] for k in ("sum_logp", "length", *keys)}
+    for b, m in enumerate(molecules):
+        rows = range(b * per, b * per + len(m))
+        out["sum_logp"].append([float(sums[r]) for r in rows])
+        out["length"].append([int(lengths[r]) for r in rows])
+        for k in keys:
+            out[k].append([host[k][r, 1:1 + lengths[r]].copy() for r in rows])
+    return out

@@ -863,6 +863,30 @@ def sample_token_grammar(logits, uniforms, pos, pos_offset, state, cls, temperat
                                                _stream()), "singa_sample_token_grammar")
 
 
+def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=None, temperature=1.0, top_k=0, top_p=1.0, eos=0,
+                        pad=0, allowed=None):
+    """`sample_token` (cls=None) or `sample_token_grammar` (cls: [V] uint8 class bytes) with given tokens
+    (`singa_sample_token_forced`, include/singa_hip_force.h states the rule): forced [R, T] int64, contiguous, on the GPU - at
+    step t a row whose forced[row, t + 1] lies in [0, V) takes that token with the bookkeeping of a drawn one, any other row
+    chooses as the unforced op does, bit for bit.  `state` as for those ops (grammar [R] int32 and, optionally, allowed_logp
+    under the grammar) and, optionally, rank [R, T] int32: the rank of every emitted token among the row's raw logits."""
+    if state.get("rank") is not None:
+        _dev(state["rank"])
+    (R, V), T = logits.shape, state["tokens"].shape[1]
+    extra = ((forced, torch.int64, (R, T)), (state.get("rank"), torch.int32, (R, T)))
+    gstate = alp = None
+    if cls is not None:
+        gstate, alp = state["grammar"], state.get("allowed_logp")
+        _dev(gstate, alp)
+        extra += ((cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)), (alp, torch.float32, (R, T)))
+    _sample_token_views("sample_token_forced", logits, uniforms, pos, state, allowed, extra)
+    _chk(_lib.lib().singa_sample_token_forced(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), pos_offset, R, V, T,
+                                              temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
+                                              _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]),
+                                              _p(state.get("tok_logp")), _p(gstate), _p(alp), _p(forced), _p(state.get("rank")),
+                                              _stream()), "singa_sample_token_forced")
+
+
 class _MaskedSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, mask, scale, heads):

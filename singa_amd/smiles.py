@@ -6,6 +6,8 @@ the fresh state.
 Scope of the rule: syntax only - balanced branches, paired ring-closure digits, no dangling bond symbol, and a '$' before the
 columns run out.  Not covered: chemical validity (valence, aromaticity, duplicate ring bonds such as C1C1), %nn closures (the
 vocabulary has none), a bond symbol in front of a closing ring digit (never drawn), beam search."""
+import functools
+
 import numpy as np
 
 NONE, ATOM, BOND, OPEN, CLOSE, RING, DOT, EOS = range(8)        # token classes; prev codes 1-6 are the classes' own
@@ -64,3 +66,129 @@ def check_arguments(grammar, voc, max_length, suppress=()):
     if kept(OPEN) and not kept(CLOSE):
         raise ValueError("sample: suppress removes ')' while '(' stays; an opened branch could never be closed")
     return cls
+
+
+# ------------------------------------------------------------------------------------------------ forced tokens: the host side
+# `sample(..., forced=...)` / `score` (singa_amd/model/Sampling.py; include/singa_hip_force.h states what the kernel does with a
+# forced token): spelling text in the vocabulary, laying prefixes out as the matrix the kernel reads, and walking that matrix
+# through the library's own rule before anything is launched - the kernel takes a forced token whether or not the rule allows it.
+@functools.lru_cache(maxsize=8)
+def _spelling(voc):
+    """-> (the set of entries, first character -> the entries that start with it, longest first)"""
+    by_first = {}
+    for v in sorted(set(voc) - {""}, key=len, reverse=True):
+        by_first.setdefault(v[0], []).append(v)
+    return frozenset(voc), by_first
+
+
+def tokenize(text, voc):
+    """The vocabulary entries that spell `text`, greedily: a bracket atom whole, otherwise the longest entry that matches
+    ('Br' / 'Cl' before 'B' / 'C').  ValueError, naming the position, for text the vocabulary cannot spell."""
+    known, by_first = _spelling(tuple(str(v) for v in voc))
+    out, i = [], 0
+    while i < len(text):
+        if text[i] == "[":
+            j = text.find("]", i)
+            if j < 0:
+                raise ValueError(f"tokenize: '[' at position {i} of {text!r} is never closed")
+            tok = text[i:j + 1]
+            if tok not in known:
+                raise ValueError(f"tokenize: the vocabulary has no entry {tok!r} (position {i} of {text!r})")
+        else:
+            tok = next((v for v in by_first.get(text[i], ()) if text.startswith(v, i)), None)
+            if tok is None:
+                raise ValueError(f"tokenize: no vocabulary entry matches {text[i]!r} at position {i} of {text!r}")
+        out.append(tok)
+        i += len(tok)
+    return out
+
+
+def encode(items, voc, max_length, end=False):
+    """int64 [len(items), max_length], -1 where nothing is forced: column 0 is '&', columns 1..n the tokens of item i, column
+    n + 1 '$' if `end`.  An item is a string (`tokenize`) or a sequence of token strings or ids.  ValueError for an item that
+    does not fit into the columns."""
+    voc = [str(v) for v in voc]
+    index = {}
+    for i, v in enumerate(voc):
+        index.setdefault(v, i)                                         # as list.index: the first of equal entries
+    out = np.full((len(items), max_length), -1, np.int64)
+    for r, item in enumerate(items):
+        toks = tokenize(item, voc) if isinstance(item, str) else list(item)
+        ids = []
+        for c, t in enumerate(toks):
+            if isinstance(t, str):
+                if t not in index:
+                    raise ValueError(f"encode: item {r}, token {c}: the vocabulary has no entry {t!r}")
+                ids.append(index[t])
+            else:
+                if not 0 <= int(t) < len(voc):
+                    raise ValueError(f"encode: item {r}, token {c}: id {int(t)} is outside the vocabulary of {len(voc)}")
+                ids.append(int(t))
+        n = len(ids) + (1 if end else 0)
+        if n > max_length - 1:
+            raise ValueError(f"encode: item {r} takes {len(ids)} tokens{' and its $' if end else ''}; max_length = {max_length} "
+                             f"has {max_length - 1} columns after '&'")
+        out[r, 0] = index["&"]
+        out[r, 1:1 + len(ids)] = ids
+        if end:
+            out[r, 1 + len(ids)] = index["$"]
+    return out
+
+
+def check_forced(forced, voc, max_length, grammar=None):
+    """The argument check of `sample(..., forced=...)`, on the CPU: `forced` [rows, max_length] integers, a value outside the
+    vocabulary (-1) = a free column.  Column 0 must be '&' or free, a row's forced columns must be one run that starts at column
+    1 (no free column in front of a forced one), and nothing may be forced behind a forced '$'.  Under `grammar` every forced
+    token is walked through the library's rule (`singa_smiles_rule_host`: the functions the kernel evaluates), from the fresh
+    state with rem = max_length - 2 - t at step t, so a prefix that leaves too few columns to finish is refused as well.  One
+    exception: a row forced to '$' in column 1 is an empty row (what `score` pads ragged lists with) and passes under any
+    grammar.  ValueError names row, column and token of the first refusal; returns the matrix as a contiguous int64 array."""
+    voc = [str(v) for v in voc]
+    V = len(voc)
+    f = np.ascontiguousarray(np.asarray(forced))
+    if f.ndim != 2 or f.shape[1] != max_length or f.dtype.kind not in "iu":
+        raise ValueError(f"forced: an integer matrix [rows, max_length = {max_length}] is expected, got {f.dtype} {f.shape}")
+    f = f.astype(np.int64)
+    cls = check_arguments(grammar, voc, max_length)
+    is_f = (f >= 0) & (f < V)
+    name = lambda r, c: f"row {r}, column {c}, token {voc[f[r, c]]!r}"
+    bad0 = np.flatnonzero(is_f[:, 0] & (f[:, 0] != (voc.index("&") if "&" in voc else -1)))
+    if len(bad0):
+        raise ValueError(f"forced: {name(int(bad0[0]), 0)}: column 0 is the start token '&' (or free)")
+    n = np.where(is_f[:, 1:].all(1), max_length - 1, np.argmin(is_f[:, 1:], 1))          # length of the run from column 1
+    eos = voc.index("$") if "$" in voc else -1
+    for r in np.flatnonzero(is_f[:, 1:].sum(1) != n):
+        c = 1 + int(n[r]) + int(np.argmax(is_f[r, 1 + n[r]:]))
+        raise ValueError(f"forced: {name(int(r), c)} follows the free column {int(n[r]) + 1}: the forced columns of a row are one "
+                         f"run from column 1")
+    ended = np.zeros(len(f), bool)
+    state = np.full(len(f), FRESH, np.int32)
+    filler = (n >= 1) & (f[:, 1] == eos)
+    rule = None
+    if grammar is not None:
+        import ctypes
+
+        from . import _capi, _lib
+        rule = _lib.lib().singa_smiles_rule_host
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    for t in range(int(n.max()) if len(n) else 0):
+        on = np.flatnonzero(n > t)
+        tok = f[on, t + 1]
+        late = on[ended[on]]
+        if len(late):
+            r = int(late[0])
+            raise ValueError(f"forced: {name(r, t + 1)} stands behind the row's '$'")
+        if rule is not None:
+            c = np.ascontiguousarray(cls[tok])
+            st = np.ascontiguousarray(state[on])
+            rem = np.full(len(on), max_length - 2 - t, np.int32)
+            ok, nxt = np.zeros(len(on), np.uint8), np.zeros(len(on), np.int32)
+            _capi.check(_lib.lib(), rule(vp(c), vp(st), vp(rem), len(on), vp(ok), vp(nxt)), "singa_smiles_rule_host")
+            refused = on[(ok == 0) & ~filler[on]]
+            if len(refused):
+                r = int(refused[0])
+                raise ValueError(f"forced: {name(r, t + 1)}: the {grammar} rule does not let it follow "
+                                 f"{''.join(voc[i] for i in f[r, 1:t + 1])!r} with {max_length - 2 - t} columns left after it")
+            state[on] = nxt
+        ended[on] |= tok == eos
+    return f

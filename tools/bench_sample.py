@@ -3,14 +3,16 @@
 atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket with random-init weights, next to the beam
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
-    python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar]
+    python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
 per step, and their ratio); with `--table` also both decoder paths at rows = 20, 128, 512, 2048 (the table `fused=None`
 picks from, profiles/sampling/README.md); with `--grammar` also the k17 step under `grammar="smiles"` next to the plain one at
 rows = 20, 128, 2048, both timed in this process, runs interleaved (`grammar_table`; '$' is then not suppressed - the grammar
-needs it - but its logit keeps rows from ending before the budget forces them to: `steps` is reported).  A generation is timed
+needs it - but its logit keeps rows from ending before the budget forces them to: `steps` is reported); with `--forced` also
+the k17 step with a forced prefix of 5 tokens next to the plain one at rows = 20, 2048, interleaved (`forced_table`), and
+`score` on 2,048 molecules of 40 tokens for the pocket, timed as a whole call (`score_2048`: molecules / s).  A generation is timed
 as a whole - encoder, cache set-up, graph capture and
 every step - and divided by its steps, as bench_beam.py does.
 """
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--table", action="store_true")
     ap.add_argument("--grammar", action="store_true", help="also time the grammar-constrained step (grammar_table)")
+    ap.add_argument("--forced", action="store_true", help="also time the step with a forced prefix, and score() (forced_table)")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -46,7 +49,8 @@ def main():
     from singa_amd.model.BeamSearch import beam_search
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
-    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample
+    from singa_amd import smiles
+    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample, score
     dev = torch.device("cuda", 0)
     cfg = load_config(lmax=2)
     torch.manual_seed(cfg.train.seed)
@@ -77,11 +81,11 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 
-    def run_sample(rows, fused, grammar=None):
+    def run_sample(rows, fused, grammar=None, forced=None):
         tr = {}
         prop = torch.ones(rows, 3, device=dev)
         sample(model, voc, rows, 1, T, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar)
+               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar, forced=forced)
         run_sample.path = tr["path"]
         return tr["steps"]
 
@@ -130,6 +134,25 @@ def main():
                            "grammar_ms_per_step": round(statistics.median(gram), 4), "grammar_steps": steps,
                            "plain_runs_ms": [round(x, 4) for x in plain], "grammar_runs_ms": [round(x, 4) for x in gram]})
         res["grammar_table"] = gtable
+    if args.forced:
+        ftable = []
+        prefix = smiles.encode(["CCOCN"], voc, T)                               # 5 forced columns, then the free draw
+        for rows in (20, 2048):
+            run_sample(rows, True), run_sample(rows, True, forced=prefix)
+            plain, forc = [], []
+            for _ in range(3 if rows >= 512 else args.reps):
+                plain.append(timed(lambda: run_sample(rows, True)))
+                forc.append(timed(lambda: run_sample(rows, True, forced=prefix)))
+            ftable.append({"rows": rows, "path": "k17", "plain_ms_per_step": round(statistics.median(plain), 4),
+                           "forced_ms_per_step": round(statistics.median(forc), 4),
+                           "plain_runs_ms": [round(x, 4) for x in plain], "forced_runs_ms": [round(x, 4) for x in forc]})
+        res["forced_table"] = ftable
+        mols = [["CCOCN" * 8] * 2048]                                            # 40 tokens each, '$' the 41st
+        do_score = lambda: score(model, voc, mols, 1, ex, torch.ones(1, 3), device=dev, fused=True) and 1
+        do_score()
+        secs = [timed(do_score) / 1e3 for _ in range(3)]
+        res["score_2048"] = {"molecules": 2048, "tokens_each": 40, "seconds": [round(x, 4) for x in secs],
+                             "molecules_per_s": round(2048 / statistics.median(secs), 1)}
     print(json.dumps(res))
 
 
