@@ -2,7 +2,9 @@
 """Generation entrypoint, the counterpart of train.py for the reference's gen.py:156-196: embed the pockets with the
 equivariant embedding in `gen_mode`, then decode SMILES token sequences conditioned on them - with the reference's beam
 search (`--mode beam`, one sequence per pocket) or by sampling (`--mode sample`, `--num-samples` sequences per pocket with
-temperature / top-k / top-p; singa_amd/model/Sampling.py).
+temperature / top-k / top-p; singa_amd/model/Sampling.py).  `--mode distinct` samples WITHOUT replacement: `--num-samples`
+pairwise distinct sequences per pocket (stochastic beam search; `--temperature`, `--grammar` and `--seed` apply, top-k / top-p
+do not), best perturbed score first.
 
 The reference's PDB / docking front end is out of scope, so pockets come from `--data golden` (the three
 example graphs the reference bundles) or `--data synthetic`.  No chemistry toolkit is required: the sequences are written as
@@ -19,6 +21,7 @@ log-likelihood under the model for its pocket is written, in the same four colum
 
     python gen.py --data golden --mode sample --num-samples 100 --grammar smiles --prefix "c1ccc("
     python gen.py --data golden --mode score --molecules library.tsv
+    python gen.py --data golden --mode distinct --num-samples 100 --grammar smiles --seed 3
 
 One line per sequence on stdout (or in `--out`), tab-separated: pocket name, the SMILES string between '&' and '$', the
 number of tokens decoded ('$' included), the summed log-probability of the sequence under the model.  Everything else that
@@ -43,8 +46,8 @@ def main():
     ap.add_argument("--data", choices=["golden", "synthetic"], default="golden")
     ap.add_argument("--pockets", type=int, default=3, help="number of pockets (synthetic data)")
     ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 4 or 6)")
-    ap.add_argument("--mode", choices=["beam", "sample", "score"], default="sample")
-    ap.add_argument("--num-samples", type=int, default=100, help="sequences per pocket (sample)")
+    ap.add_argument("--mode", choices=["beam", "sample", "score", "distinct"], default="sample")
+    ap.add_argument("--num-samples", type=int, default=100, help="sequences per pocket (sample, distinct)")
     ap.add_argument("--num-beams", type=int, default=20, help="beams per pocket (beam); the best hypothesis is written")
     ap.add_argument("--max-length", type=int, default=None, help="default: model.decoder.tgt_len + 1")
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -61,7 +64,9 @@ def main():
     ap.add_argument("--out", type=str, default=None, help="write the sequences here instead of stdout")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
-    assert args.grammar == "none" or args.mode == "sample", "--grammar constrains sampling only: beam search selects on the host"
+    assert args.grammar == "none" or args.mode in ("sample", "distinct"), \
+        "--grammar constrains sampling only: beam search selects on the host"
+    assert args.mode != "distinct" or (args.top_k == 0 and args.top_p == 1.0), "--mode distinct takes no --top-k / --top-p"
     assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
     dev = torch.device(args.device if ":" in args.device else "cuda:0")
@@ -75,7 +80,7 @@ def main():
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
-    from singa_amd.model.Sampling import sample, score
+    from singa_amd.model.Sampling import sample, sample_distinct, score
 
     cfg = load_config(args.config, lmax=args.lmax)
     torch.manual_seed(args.seed)
@@ -124,7 +129,7 @@ def main():
         emit(args, lines)
         return
 
-    per = args.num_samples if args.mode == "sample" else args.num_beams
+    per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
     prop = torch.tensor([args.prop] * (B * per), dtype=torch.float32, device=dev) if cfg.train.num_props else None
     tr = {}
     if args.mode == "sample":
@@ -135,20 +140,31 @@ def main():
                         grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
         lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
         print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
+    elif args.mode == "distinct":
+        tokens = sample_distinct(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature,
+                                 suppress=("&", "^"), grammar=None if args.grammar == "none" else args.grammar, seed=args.seed,
+                                 trace=tr).cpu()
+        keep = tr["valid"].cpu().bool()                                       # a small tree leaves trailing slots empty
+        print(f"# {int(keep.sum())} distinct sequences for {B} pockets ({per} asked for each): {tr['steps']} steps")
+        rows = [r for r in range(B * per) if keep[r]]
+        tokens, names_of = tokens[keep], [names[r // per] for r in rows]
+        lengths, logps = tr["lengths"].cpu()[keep].tolist(), tr["sum_logp"].cpu()[keep].tolist()
     else:
         tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr).cpu()
         best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7
         lengths, logps = [len(h) for _, h in best], [s * len(h) ** 0.7 for s, h in best]
         per = 1
 
+    if args.mode != "distinct":
+        names_of = [names[r // per] for r in range(tokens.shape[0])]
     lines = []
     for r, row in enumerate(tokens.tolist()):
         body = []
-        for t in (row[1:1 + lengths[r]] if args.mode == "sample" else row[1:]):   # a sampled row is `lengths[r]` tokens long
+        for t in (row[1:1 + lengths[r]] if args.mode != "beam" else row[1:]):     # a sampled row is `lengths[r]` tokens long
             if t == eos or (t == pad and args.mode == "beam"):
                 break
             body.append(voc[t])
-        lines.append(f"{names[r // per]}\t{''.join(body)}\t{lengths[r]}\t{logps[r]:.6f}")
+        lines.append(f"{names_of[r]}\t{''.join(body)}\t{lengths[r]}\t{logps[r]:.6f}")
     emit(args, lines)
 
 

@@ -147,12 +147,23 @@ _FORCE_SIGS = {
 }
 FORCE_EXPORTS = tuple(_FORCE_SIGS)
 
+# include/singa_hip_swor.h: sampling without replacement (stochastic beam search, `sample_distinct`); a table of its own
+U64 = C.c_uint64
+_SWOR_SIGS = {
+    "singa_swor_noise_host": ([U64, P, P, P, I32, P, P, P], I32),
+    "singa_swor_work": ([I32, I32], C.c_longlong),
+    "singa_swor_expand": ([P, P, P, P, I32, I32, I32, I32, I32, F32, U64, P, I32] + [P] * 8 + [P], I32),
+    "singa_swor_select": ([P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32] + [P] * 13 + [P], I32),
+    "singa_swor_follow": ([P] * 8 + [I32] * 6 + [I64] * 4 + [P], I32),
+}
+SWOR_EXPORTS = tuple(_SWOR_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
-            list(_FORCE_SIGS.items()):
+            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -23,6 +23,7 @@
 #include "../../include/singa_hip_lab.h"
 #include "../../include/singa_hip_gen.h"
 #include "../../include/singa_hip_force.h"
+#include "../../include/singa_hip_swor.h"
 #include "so3_index.h"
 
 namespace {
@@ -1781,6 +1782,373 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
             finished[row] = 1;
             atomicSub(live, 1);
         }
+    }
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------ sampling without replacement
+// Stochastic beam search (include/singa_hip_swor.h states the rule).  The noise - Philox4x32-10 keyed by the seed, counted by
+// (prefix hash, token, stream) -, the uniform and the child hash are one source for the kernels and singa_swor_noise_host.
+__host__ __device__ inline uint32_t swor_philox(unsigned long long seed, unsigned long long hash, uint32_t v, uint32_t strm) {
+    uint32_t c0 = (uint32_t)hash, c1 = (uint32_t)(hash >> 32), c2 = v, c3 = strm;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__host__ __device__ inline float swor_uniform(uint32_t x) {           // in (0, 1): the rounding to 1 is taken back
+    const float u = ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-8f;
+    return u < 1.f ? u : 0.99999994f;
+}
+
+__host__ __device__ inline unsigned long long swor_child_hash(unsigned long long h, int v) {
+    unsigned long long z = h + (unsigned long long)(v + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// where singa_swor_select keeps the new row state until every parent has been read: offsets into `work`, 16-byte aligned
+struct SworWork {
+    long long hash, tokens, gumbel, prop, sum, toklogp, length, gstate, fin, bytes;
+    SworWork(long long rows, long long T) {
+        auto up = [](long long b) { return (b + 15) / 16 * 16; };
+        hash = 0;
+        tokens = hash + up(rows * 8);
+        gumbel = tokens + up(rows * T * 8);
+        prop = gumbel + up(rows * 4);
+        sum = prop + up(rows * 4);
+        toklogp = sum + up(rows * 4);
+        length = toklogp + up(rows * T * 4);
+        gstate = length + up(rows * 4);
+        fin = gstate + up(rows * 4);
+        bytes = fin + up(rows);
+    }
+};
+
+#ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
+// singa_swor_expand: one wave per row, the row's logits in registers as sample_token_kernel holds them (lane l: tokens l,
+// l + 64, ...).  lse and the model's log-probability are that kernel's expressions, so they carry the same bits.
+template <int NPL, bool GRAMMAR>
+__global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
+                                                          const unsigned char* __restrict__ cls, const long long* __restrict__ pos,
+                                                          int pos_offset, int rows, int kslots, int V, int T, float tau,
+                                                          unsigned long long seed, const uint32_t* __restrict__ streams, int pad,
+                                                          const float* __restrict__ gumbel, const float* __restrict__ prop_logp,
+                                                          const unsigned long long* __restrict__ hash,
+                                                          const unsigned char* __restrict__ finished,
+                                                          const int32_t* __restrict__ gstate, float* __restrict__ cand,
+                                                          float* __restrict__ cand_logp, float* __restrict__ cand_phi) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                           // wave-uniform from here on
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    const float NEG = -INFINITY;
+    const float G = gumbel[row], phi = prop_logp[row];
+    float* cr = cand + (long long)row * V;
+    float* lr = cand_logp + (long long)row * V;
+    float* pr = cand_phi + (long long)row * V;
+    if (!(G > NEG) || finished[row]) {                                 // dead: no candidate; finished: itself, emitting `pad`
+        const bool fin = G > NEG;
+        for (int i = lane; i < V; i += 64) {
+            const bool c = fin && i == pad;
+            cr[i] = c ? G : NEG, lr[i] = c ? 0.f : NEG, pr[i] = c ? phi : NEG;
+        }
+        return;
+    }
+    const unsigned long long hsh = hash[row];
+    const uint32_t strm = streams[row / kslots];
+    float z[NPL];
+    bool ok[NPL];
+    int gs = 0;
+    if constexpr (GRAMMAR) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int i = k * 64 + lane;
+        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
+        ok[k] = i < V && (!allowed || allowed[i]);
+        if constexpr (GRAMMAR) ok[k] = ok[k] && smiles_allows(gs, i < V ? cls[i] : 0, (int)(T - 2 - t));
+    }
+    // the model's own log-sum-exp (tau = 1, nothing filtered), as in sample_token_kernel
+    float zmax = NEG;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
+    zmax = wave_max64(zmax);
+    float zsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
+    const float lse = zmax + logf(wave_sum64(zsum));
+    // the proposal: log-softmax of z / tau over the mask
+    float s[NPL], smax = NEG;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        s[k] = ok[k] ? z[k] / tau : NEG;
+        smax = fmaxf(smax, s[k]);
+    }
+    smax = wave_max64(smax);
+    float part = 0.f;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) part += ok[k] ? expf(s[k] - smax) : 0.f;
+    const float lt = logf(wave_sum64(part));                           // (an empty mask: every ok[] is false below)
+    // The perturbation and the conditioning run in double precision: a child whose g lies within 1e-3 of the row's maximum
+    // has d = g - Z known to no better than the rounding of g itself, and log1p(-exp(d)) magnifies that by 1 / |d| - in
+    // fp32 to 5e-4 in g~ (measured), which is the margin the selection has to be decided by.  d is formed from
+    // h = (z / tau - max) + noise: phi and the log-sum-exp are common to the row and drop out of it.
+    double h[NPL], Zh = -INFINITY, sdmax = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        h[k] = ok[k] ? (double)z[k] / (double)tau : -INFINITY;         // z / tau without the fp32 rounding of the quotient
+        sdmax = fmax(sdmax, h[k]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sdmax = fmax(sdmax, __shfl_xor(sdmax, o, 64));
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const float u = swor_uniform(swor_philox(seed, hsh, (uint32_t)(k * 64 + lane), strm));
+        h[k] = ok[k] ? (h[k] - sdmax) - log(-log((double)u)) : -INFINITY;
+        s[k] = phi + ((s[k] - smax) - lt);                             // phi of the child
+        Zh = fmax(Zh, h[k]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) Zh = fmax(Zh, __shfl_xor(Zh, o, 64));
+    const double base = (double)phi - (double)lt;                      // g = base + h
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int i = k * 64 + lane;
+        if (i < V) {
+            const double a = (double)G - (base + h[k]) + log1p(-exp(h[k] - Zh));
+            const float gt = (float)((double)G - fmax(a, 0.0) - log1p(exp(-fabs(a))));
+            cr[i] = ok[k] ? gt : NEG, lr[i] = ok[k] ? z[k] - lse : NEG, pr[i] = ok[k] ? s[k] : NEG;
+        }
+    }
+}
+
+// ordered key of a float: a larger float is a larger unsigned key
+__device__ __forceinline__ uint32_t swor_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// singa_swor_select, first launch: one workgroup per pocket.
+//   * the k-th largest of the pocket's k V candidates by radix select on the 53-bit composite (ordered key << 21 | inverted
+//     flat index parent * V + token): digits of 11, 11, 10 bits of the key from the top, then 11 and 10 of the index, an LDS
+//     histogram per digit; a larger composite is a better candidate under the rule's order (g~ down, parent up, token up), and
+//     composites are unique.  The passes stop at the first digit whose bin holds exactly what is still needed - for distinct
+//     values no later than the key's last digit, so the index digits run only to split an exact tie at the threshold.
+//     -inf (no candidate) never enters a histogram.  The candidates are re-read from L2 per pass (k V <= 8 MiB).
+//   * the survivors are appended to LDS in any order and sorted there (bitonic, descending composites);
+//   * the new slots' scalars and column t + 1 go to `work` (w_*); swor_gather_kernel adds the parents' columns, and
+//     swor_commit_kernel overwrites the state once every parent has been read.
+__global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restrict__ cand, const float* __restrict__ cand_logp,
+                                                           const float* __restrict__ cand_phi, const unsigned char* __restrict__ cls,
+                                                           const long long* __restrict__ pos, int pos_offset, int kslots, int V, int T,
+                                                           int eos, int pad, const float* __restrict__ gumbel,
+                                                           const float* __restrict__ prop_logp, const float* __restrict__ sum_logp,
+                                                           const unsigned long long* __restrict__ hash,
+                                                           const unsigned char* __restrict__ finished, const int32_t* __restrict__ length,
+                                                           const int32_t* __restrict__ gstate, long long* __restrict__ next,
+                                                           long long* __restrict__ src, int32_t* __restrict__ live,
+                                                           float* __restrict__ w_gumbel, float* __restrict__ w_prop,
+                                                           float* __restrict__ w_sum, unsigned long long* __restrict__ w_hash,
+                                                           unsigned char* __restrict__ w_fin, int32_t* __restrict__ w_len,
+                                                           int32_t* __restrict__ w_gs, long long* __restrict__ w_tokens,
+                                                           float* __restrict__ w_toklogp) {
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned long long sel[2048];
+    __shared__ unsigned s_kk, s_bin, s_above, s_cnt, s_nsel;
+    __shared__ int s_live;
+    const int tid = threadIdx.x, lane = tid & 63, pocket = blockIdx.x;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;                                   // workgroup-uniform
+    const int n = kslots * V;
+    const float NEG = -INFINITY;
+    const float* base = cand + (long long)pocket * n;
+    const int SH[5] = {42, 31, 21, 10, 0}, NB[5] = {11, 11, 10, 11, 10};
+    unsigned long long prefix = 0;
+    unsigned need = 0, kk = 0;
+    int final_shift = 0;
+    for (int p = 0; p < 5; ++p) {
+        hist[tid] = 0, hist[tid + 1024] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 1024) {
+            const float f = base[i] + 0.f;                             // -0 -> +0: one key for equal floats
+            if (f > NEG) {
+                const unsigned long long comp = (unsigned long long)swor_key(f) << 21 | (unsigned)(0x1FFFFF - i);
+                if (p == 0 || (comp >> (SH[p] + NB[p])) == prefix) atomicAdd(&hist[(unsigned)(comp >> SH[p]) & ((1u << NB[p]) - 1)], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid < 64) {                                                // wave 0: lane l owns the 32 bins below 2047 - 32 l
+            const int top = 2047 - 32 * lane;
+            unsigned c = 0;
+            for (int j = 0; j < 32; ++j) c += hist[top - j];
+            unsigned P = c;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned y = __shfl_up(P, o, 64);
+                if (lane >= o) P += y;
+            }
+            const unsigned total = __shfl(P, 63, 64);
+            const unsigned nd = p == 0 ? min((unsigned)kslots, total) : need;
+            if (p == 0 && lane == 0) s_kk = nd, s_cnt = 0, s_above = 0, s_bin = 0;
+            const unsigned long long hit = __ballot(P >= nd);
+            if (nd > 0 && hit != 0 && lane == __ffsll((long long)hit) - 1) {
+                unsigned acc = P - c;
+                for (int j = 0; j < 32; ++j) {
+                    const unsigned hb = hist[top - j];
+                    if (acc + hb >= nd) {
+                        s_bin = top - j, s_above = acc, s_cnt = hb;
+                        break;
+                    }
+                    acc += hb;
+                }
+            }
+        }
+        __syncthreads();
+        if (p == 0) need = kk = s_kk;
+        if (kk == 0) break;                                            // no candidate at all: every slot dies
+        need -= s_above;
+        prefix = prefix << NB[p] | s_bin;
+        final_shift = SH[p];
+        if (s_cnt == need) break;                                      // the bin is taken whole (the last digit: one element)
+    }
+    sel[tid] = 0, sel[tid + 1024] = 0;
+    if (tid == 0) s_nsel = 0, s_live = 0;
+    __syncthreads();
+    if (kk > 0)
+        for (int i = tid; i < n; i += 1024) {
+            const float f = base[i] + 0.f;
+            if (f > NEG) {
+                const unsigned long long comp = (unsigned long long)swor_key(f) << 21 | (unsigned)(0x1FFFFF - i);
+                if ((comp >> final_shift) >= prefix) {
+                    const unsigned at = atomicAdd(&s_nsel, 1u);
+                    if (at < 2048) sel[at] = comp;
+                }
+            }
+        }
+    __syncthreads();
+    int N = 2;
+    while (N < (int)kk) N <<= 1;
+    for (int size = 2; size <= N; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            if (tid < N / 2) {
+                const int i = 2 * tid - (tid & (stride - 1)), j = i + stride;
+                const unsigned long long a = sel[i], b = sel[j];
+                if ((a < b) == ((i & size) == 0)) sel[i] = b, sel[j] = a;
+            }
+            __syncthreads();
+        }
+    // the new slots' scalars
+    for (int j = tid; j < kslots; j += 1024) {
+        const long long row = (long long)pocket * kslots + j;
+        long long from = row, tok = pad;
+        float lp = 0.f;
+        int alive = 0;
+        const int flat = 0x1FFFFF - (int)(sel[j] & 0x1FFFFF);          // (an empty entry of sel decodes to an index >= n)
+        if (j < (int)kk && flat < n) {
+            const int pi = flat / V, v = flat - pi * V;
+            from = (long long)pocket * kslots + pi;
+            const bool fin = finished[from] != 0;
+            w_gumbel[row] = base[flat];
+            w_prop[row] = fin ? prop_logp[from] : cand_phi[from * V + v];
+            lp = fin ? 0.f : cand_logp[from * V + v];
+            w_sum[row] = fin ? sum_logp[from] : sum_logp[from] + lp;
+            w_hash[row] = fin ? hash[from] : swor_child_hash(hash[from], v);
+            w_fin[row] = (fin || v == eos) ? 1 : 0;
+            w_len[row] = length[from] + (fin ? 0 : 1);
+            if (gstate) w_gs[row] = fin ? gstate[from] : smiles_next(gstate[from], cls[v]);
+            tok = fin ? pad : v;
+            alive = (fin || v == eos) ? 0 : 1;
+        } else {
+            w_gumbel[row] = NEG, w_prop[row] = NEG, w_sum[row] = 0.f, w_hash[row] = 0, w_fin[row] = 0, w_len[row] = 0;
+            if (gstate) w_gs[row] = gstate[row];
+        }
+        next[row] = tok, src[row] = from;
+        if (alive) atomicAdd(&s_live, 1);
+        w_tokens[row * T + t + 1] = tok, w_toklogp[row * T + t + 1] = lp;   // column t + 1; the parent's columns: swor_gather_kernel
+    }
+    __syncthreads();
+    if (tid == 0) live[pocket] = s_live;
+}
+
+// singa_swor_select, second launch: the parents' columns 0 .. t of the new slots' rows into `work`, one wave per row over the
+// whole grid.  src and w_gumbel are what swor_select_kernel has just written.  (Gathered by the 16 waves of the pocket's select
+// workgroup instead, select took 393 instead of 278 us at 1 x 2,048 slots: profiles/sampling/README.md.)
+__global__ void __launch_bounds__(256) swor_gather_kernel(const long long* __restrict__ pos, int pos_offset, int rows, int T, int pad,
+                                                          const long long* __restrict__ src, const float* __restrict__ w_gumbel,
+                                                          const long long* __restrict__ tokens, const float* __restrict__ tok_logp,
+                                                          long long* __restrict__ w_tokens, float* __restrict__ w_toklogp) {
+    const int lane = threadIdx.x & 63;
+    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    const bool has = w_gumbel[row] > -INFINITY;
+    const long long from = src[row];
+    for (int c = lane; c <= t; c += 64) {
+        w_tokens[row * T + c] = has ? tokens[from * T + c] : (c == 0 ? tokens[row * T] : pad);
+        w_toklogp[row * T + c] = has ? tok_logp[from * T + c] : 0.f;
+    }
+}
+
+// singa_swor_select, third launch: the new row state from `work` into the state arrays (one wave per row)
+__global__ void __launch_bounds__(256) swor_commit_kernel(const long long* __restrict__ pos, int pos_offset, int rows, int T,
+                                                          float* __restrict__ gumbel, float* __restrict__ prop_logp,
+                                                          float* __restrict__ sum_logp, unsigned long long* __restrict__ hash,
+                                                          unsigned char* __restrict__ finished, int32_t* __restrict__ length,
+                                                          int32_t* __restrict__ gstate, long long* __restrict__ tokens,
+                                                          float* __restrict__ tok_logp, const float* __restrict__ w_gumbel,
+                                                          const float* __restrict__ w_prop, const float* __restrict__ w_sum,
+                                                          const unsigned long long* __restrict__ w_hash,
+                                                          const unsigned char* __restrict__ w_fin, const int32_t* __restrict__ w_len,
+                                                          const int32_t* __restrict__ w_gs, const long long* __restrict__ w_tokens,
+                                                          const float* __restrict__ w_toklogp) {
+    const int lane = threadIdx.x & 63;
+    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    if (lane == 0) {
+        gumbel[row] = w_gumbel[row], prop_logp[row] = w_prop[row], sum_logp[row] = w_sum[row], hash[row] = w_hash[row];
+        finished[row] = w_fin[row], length[row] = w_len[row];
+        if (gstate) gstate[row] = w_gs[row];
+    }
+    for (int c = lane; c <= t + 1; c += 64) tokens[row * T + c] = w_tokens[row * T + c], tok_logp[row * T + c] = w_toklogp[row * T + c];
+}
+
+// singa_swor_follow: workgroup (row, layer); a head's positions [0, pos) are one contiguous run of pos * dk floats
+__global__ void __launch_bounds__(256) swor_follow_kernel(const float* __restrict__ k_src, const float* __restrict__ v_src,
+                                                          float* __restrict__ k_dst, float* __restrict__ v_dst,
+                                                          const long long* __restrict__ src, const float* __restrict__ gumbel,
+                                                          const unsigned char* __restrict__ finished, const long long* __restrict__ pos,
+                                                          int rows, int heads, int P, int dk, int dv, long long k_row_ld,
+                                                          long long k_layer_ld, long long v_row_ld, long long v_layer_ld) {
+    const int r = blockIdx.x, layer = blockIdx.y;
+    if (!(gumbel[r] > -INFINITY) || finished[r]) return;               // workgroup-uniform
+    const long long s = src[r];
+    if (s < 0 || s >= rows) return;
+    long long p = *pos;
+    p = p > P ? P : p;
+    if (p <= 0) return;
+    const float4* ks = reinterpret_cast<const float4*>(k_src + layer * k_layer_ld + s * k_row_ld);
+    float4* kd = reinterpret_cast<float4*>(k_dst + layer * k_layer_ld + r * k_row_ld);
+    const int kq = (int)(p * dk / 4), kh = P * (dk / 4);               // 16-byte words of a head: to copy, pitch
+    for (int e = threadIdx.x; e < heads * kq; e += 256) {
+        const int h = e / kq, o = e - h * kq;
+        kd[h * kh + o] = ks[h * kh + o];
+    }
+    const float4* vs = reinterpret_cast<const float4*>(v_src + layer * v_layer_ld + s * v_row_ld);
+    float4* vd = reinterpret_cast<float4*>(v_dst + layer * v_layer_ld + r * v_row_ld);
+    const int vq = (int)(p * dv / 4), vh = P * (dv / 4);
+    for (int e = threadIdx.x; e < heads * vq; e += 256) {
+        const int h = e / vq, o = e - h * vq;
+        vd[h * vh + o] = vs[h * vh + o];
     }
 }
 #endif
@@ -6842,6 +7210,135 @@ int singa_smiles_rule_host(const unsigned char* cls, const int32_t* state, const
         next_state[i] = ok[i] ? smiles_next(state[i], cls[i]) : state[i];
     }
     return SINGA_OK;
+}
+
+int singa_swor_noise_host(unsigned long long seed, const unsigned long long* hash, const int32_t* v, const uint32_t* streams,
+                          int n, uint32_t* x, float* u, unsigned long long* child) {
+    if (!hash || !v || !streams) return fail(SINGA_E_NULL, "swor_noise_host: null pointer");
+    if (n < 0) return fail(SINGA_E_SHAPE, "swor_noise_host: n must be >= 0");
+    for (int i = 0; i < n; ++i) {
+        const uint32_t w = swor_philox(seed, hash[i], (uint32_t)v[i], streams[i]);
+        if (x) x[i] = w;
+        if (u) u[i] = swor_uniform(w);
+        if (child) child[i] = swor_child_hash(hash[i], v[i]);
+    }
+    return SINGA_OK;
+}
+
+long long singa_swor_work(int rows, int T) {
+    if (rows < 0 || T < 2) return -1;
+    return SworWork(rows, T).bytes;
+}
+
+namespace {
+// the checks singa_swor_expand and singa_swor_select share; 0 = go on
+int swor_shape(const char* what, int rows, int k, int V, int T, bool grammar, int eos, int pad) {
+    static thread_local char msg[160];
+    const char* bad = nullptr;
+    if (V < 1 || V > 1024) bad = "vocabulary of 1..1024 tokens";
+    else if (k < 1 || k > 2048) bad = "1..2048 slots per pocket";
+    else if (rows < 0 || rows % k) bad = "rows must be pockets x slots";
+    else if (T < (grammar ? 3 : 2)) bad = "T >= 2 columns (3 under the grammar)";
+    else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
+    if (!bad) return SINGA_OK;
+    snprintf(msg, sizeof(msg), "%s: %s", what, bad);
+    return fail(SINGA_E_SHAPE, msg);
+}
+}  // namespace
+
+int singa_swor_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const long long* pos,
+                      int pos_offset, int rows, int k, int V, int T, float tau, unsigned long long seed,
+                      const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
+                      const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
+                      float* cand_logp, float* cand_phi, void* stream) {
+    if (!logits || !pos || !streams || !gumbel || !prop_logp || !hash || !finished || !cand || !cand_logp || !cand_phi)
+        return fail(SINGA_E_NULL, "swor_expand: null pointer");
+    if (!cls != !gstate) return fail(SINGA_E_NULL, "swor_expand: cls and gstate go together");
+    if (const int e = swor_shape("swor_expand", rows, k, V, T, cls != nullptr, 0, pad)) return e;
+    if (!(tau > 0.f)) return fail(SINGA_E_SHAPE, "swor_expand: temperature must be > 0");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "swor_expand: not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define SINGA_SWOR_LAUNCH(NPL)                                                                                                 \
+    do {                                                                                                                       \
+        if (cls)                                                                                                               \
+            hipLaunchKernelGGL((swor_expand_kernel<NPL, true>), grid, block, 0, st, logits, allowed, cls, pos, pos_offset, rows, \
+                               k, V, T, tau, seed, streams, pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp,   \
+                               cand_phi);                                                                                      \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((swor_expand_kernel<NPL, false>), grid, block, 0, st, logits, allowed, cls, pos, pos_offset, rows, \
+                               k, V, T, tau, seed, streams, pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp,   \
+                               cand_phi);                                                                                      \
+    } while (0)
+    if (V <= 128) SINGA_SWOR_LAUNCH(2);
+    else if (V <= 256) SINGA_SWOR_LAUNCH(4);
+    else if (V <= 512) SINGA_SWOR_LAUNCH(8);
+    else SINGA_SWOR_LAUNCH(16);
+#undef SINGA_SWOR_LAUNCH
+    return check_launch("swor_expand");
+#endif
+}
+
+int singa_swor_select(const float* cand, const float* cand_logp, const float* cand_phi, const unsigned char* cls,
+                      const long long* pos, int pos_offset, int rows, int k, int V, int T, int eos, int pad, float* gumbel,
+                      float* prop_logp, float* sum_logp, unsigned long long* hash, unsigned char* finished, int32_t* length,
+                      int32_t* gstate, long long* tokens, float* tok_logp, long long* next, long long* src, int32_t* live,
+                      void* work, void* stream) {
+    if (!cand || !cand_logp || !cand_phi || !pos || !gumbel || !prop_logp || !sum_logp || !hash || !finished || !length ||
+        !tokens || !tok_logp || !next || !src || !live || !work)
+        return fail(SINGA_E_NULL, "swor_select: null pointer");
+    if (!cls != !gstate) return fail(SINGA_E_NULL, "swor_select: cls and gstate go together");
+    if (const int e = swor_shape("swor_select", rows, k, V, T, cls != nullptr, eos, pad)) return e;
+    if ((uintptr_t)work % 16) return fail(SINGA_E_SHAPE, "swor_select: work must be 16-byte aligned");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "swor_select: not part of the emulation build");
+#else
+    const SworWork w(rows, T);
+    char* b = (char*)work;
+    float *wg = (float*)(b + w.gumbel), *wp = (float*)(b + w.prop), *ws = (float*)(b + w.sum), *wl = (float*)(b + w.toklogp);
+    unsigned long long* wh = (unsigned long long*)(b + w.hash);
+    long long* wt = (long long*)(b + w.tokens);
+    int32_t *wn = (int32_t*)(b + w.length), *wgs = (int32_t*)(b + w.gstate);
+    unsigned char* wf = (unsigned char*)(b + w.fin);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(swor_select_kernel, dim3(rows / k), dim3(1024), 0, st, cand, cand_logp, cand_phi, cls, pos, pos_offset, k, V, T,
+                       eos, pad, gumbel, prop_logp, sum_logp, hash, finished, length, gstate, next, src, live, wg, wp, ws, wh, wf, wn,
+                       wgs, wt, wl);
+    hipLaunchKernelGGL(swor_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, pos, pos_offset, rows, T, pad, src, wg, tokens,
+                       tok_logp, wt, wl);
+    hipLaunchKernelGGL(swor_commit_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, pos, pos_offset, rows, T, gumbel, prop_logp,
+                       sum_logp, hash, finished, length, gstate, tokens, tok_logp, wg, wp, ws, wh, wf, wn, wgs, wt, wl);
+    return check_launch("swor_select");
+#endif
+}
+
+int singa_swor_follow(const float* k_src, const float* v_src, float* k_dst, float* v_dst, const long long* src,
+                      const float* gumbel, const unsigned char* finished, const long long* pos, int layers, int rows,
+                      int heads, int P, int dk, int dv, long long k_row_ld, long long k_layer_ld, long long v_row_ld,
+                      long long v_layer_ld, void* stream) {
+    if (!k_src || !v_src || !k_dst || !v_dst || !src || !gumbel || !finished || !pos)
+        return fail(SINGA_E_NULL, "swor_follow: null pointer");
+    if (layers < 0 || rows < 0 || heads < 1 || P < 1 || dk < 4 || dv < 4 || dk % 4 || dv % 4 ||
+        (long long)heads * P * (dk > dv ? dk : dv) > INT32_MAX || layers > 65535)
+        return fail(SINGA_E_SHAPE, "swor_follow: dk and dv multiples of 4, at most 2^31 floats per cache row, 65535 layers");
+    if (k_row_ld % 4 || k_layer_ld % 4 || v_row_ld % 4 || v_layer_ld % 4 || k_row_ld < (long long)heads * P * dk ||
+        v_row_ld < (long long)heads * P * dv || k_layer_ld < rows * k_row_ld || v_layer_ld < rows * v_row_ld)
+        return fail(SINGA_E_SHAPE, "swor_follow: pitches are multiples of 4 floats and hold a row / a layer");
+    if ((uintptr_t)k_src % 16 || (uintptr_t)v_src % 16 || (uintptr_t)k_dst % 16 || (uintptr_t)v_dst % 16)
+        return fail(SINGA_E_SHAPE, "swor_follow: the caches must be 16-byte aligned");
+    if (k_src == k_dst || v_src == v_dst) return fail(SINGA_E_SHAPE, "swor_follow: source and destination must be two buffers");
+    if (rows == 0 || layers == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "swor_follow: not part of the emulation build");
+#else
+    hipLaunchKernelGGL(swor_follow_kernel, dim3(rows, layers), dim3(256), 0, (hipStream_t)stream, k_src, v_src, k_dst, v_dst, src,
+                       gumbel, finished, pos, rows, heads, P, dk, dv, k_row_ld, k_layer_ld, v_row_ld, v_layer_ld);
+    return check_launch("swor_follow");
+#endif
 }
 
 int singa_edge_mlp_fwd(const float* attr, const float* w1tk, const float* b1k, const float* w2tk, const float* b2k,

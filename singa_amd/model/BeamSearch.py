@@ -138,13 +138,16 @@ class KVDecoder:
         d = self.dec
         return d.prop_nn(prop) + d.type_emb.weight[0]
 
-    def advance(self, x):
-        """x [rows, hidden]: decoder input at position `pos` -> decoder output at that position; pos += 1."""
+    def advance(self, x, k=None, v=None):
+        """x [rows, hidden]: decoder input at position `pos` -> decoder output at that position; pos += 1.  `k`, `v`: the
+        caches to append to and attend over instead of the decoder's own (same shapes; `sample_distinct` alternates between
+        two pairs of buffers)."""
+        k, v = self.k if k is None else k, self.v if v is None else v
         if self.fused:
             # three hand-written launches per layer (singa_dec_*): q/k/v + cache append + attention + projection + LayerNorm,
             # encoder-decoder attention, feed-forward - instead of ~33 library / elementwise launches on 20-row operands
             for l in range(len(self.dec.layers)):
-                x = ops.dec_layer_step(x.contiguous(), self.w[l], self.k[l], self.v[l], self.pos, self.cross_k[l],
+                x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], self.pos, self.cross_k[l],
                                        self.cross_v[l], self.pad_u8, self.beams)
             self.pos += 1
             return x
@@ -152,11 +155,11 @@ class KVDecoder:
         unwritten = (self.slots > self.pos).view(1, 1, 1, self.P)
         for l, layer in enumerate(self.dec.layers):
             a = layer.dec_self_attn
-            self.k[l].index_copy_(2, self.pos, a.W_K(x).view(R, H, 1, self.dk))
-            self.v[l].index_copy_(2, self.pos, a.W_V(x).view(R, H, 1, self.dv))
+            k[l].index_copy_(2, self.pos, a.W_K(x).view(R, H, 1, self.dk))
+            v[l].index_copy_(2, self.pos, a.W_V(x).view(R, H, 1, self.dv))
             q = a.W_Q(x).view(R, H, 1, self.dk)
-            s = (torch.matmul(q, self.k[l].transpose(-1, -2)) / math.sqrt(self.dk)).masked_fill(unwritten, float("-inf"))
-            ctx = torch.matmul(torch.softmax(s, dim=-1), self.v[l]).reshape(R, H * self.dv)
+            s = (torch.matmul(q, k[l].transpose(-1, -2)) / math.sqrt(self.dk)).masked_fill(unwritten, float("-inf"))
+            ctx = torch.matmul(torch.softmax(s, dim=-1), v[l]).reshape(R, H * self.dv)
             y = a.layer_norm(a.linear(ctx) + x)
             c = layer.dec_enc_attn
             q = c.W_Q(y).view(B, self.beams, H, self.dk).transpose(1, 2)                   # beams = query rows

@@ -35,7 +35,16 @@ where that word is a token, takes it with the bookkeeping of a drawn one.  Forci
 scaffold; forcing every column up to '$' scores a given molecule (`score`): the log-likelihood then comes from the same
 kernels, in the same order, as the `sum_logp` of a drawn row, so the two are comparable bit for bit.  The host validates what
 it forces (`smiles.check_forced`, through the library's own rule) before any device work; the kernel does not.
+
+`sample_distinct` draws WITHOUT replacement: `num_samples` pairwise distinct sequences per pocket by stochastic beam search
+(Kool, van Hoof, Welling 2019; include/singa_hip_swor.h states the rule), an exact sample without replacement from the
+proposal in one pass of `num_samples` rows.  Here the rows of a pocket ARE coupled, and the coupled part runs on the device
+inside the captured step: `ops.swor_expand` (the perturbed score of every candidate), `ops.swor_select` (the best k per
+pocket, the row state gathered from the parents) and `ops.swor_follow` (one launch moves the surviving prefixes' key / value
+cache rows from one cache buffer to the other; the step is captured twice, for even and odd tokens, and the two graphs are
+replayed in turn).  `swor_weights` turns the run's `gumbel` / `prop_logp` into the importance weights of the paper's estimator.
 """
+import numpy as np
 import torch
 
 from .. import ops, smiles
@@ -264,3 +273,166 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
         for k in keys:
             out[k].append([host[k][r, 1:1 + lengths[r]].copy() for r in rows])
     return out
+
+
+SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
+
+
+@torch.no_grad()
+def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
+                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None):
+    """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
+    replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` (as in `sample`), by
+    stochastic beam search on the device (include/singa_hip_swor.h states the rule).  `model`, `smiVoc`, `example`, `prop`
+    and `device` as in `sample`; the rows of a pocket exchange prefixes, so they are expected to carry one property prompt.
+
+    All randomness is a function of (`seed`, the pocket's entry of `streams`, the prefix): `seed` is a 64-bit integer,
+    `streams` [batch_size] 32-bit integers (default 0, 1, ...), so a pocket's result does not depend on its neighbours in the
+    batch, and the k best of a run with more slots are the run with k slots.  `graph=False` launches the step's kernels one
+    by one (same result).  Only the k17 step kernels serve this mode.
+
+    Returns the int64 token matrix [batch_size * num_samples, max_length], pocket-major, a pocket's rows in descending order
+    of their perturbed log-probability G.  A pocket whose tree has fewer than `num_samples` leaves leaves trailing slots dead.
+    `trace`, if a dict, receives `gumbel` (G, -inf for dead slots), `prop_logp` (log-probability under the proposal),
+    `sum_logp` / `token_logp` (the unmodified model's, as `sample` and `score` report them), `lengths`, `valid` (uint8: 0 for
+    dead slots) and `steps`.  A list handed in as `trace["gumbel_history"]` receives a copy of G [rows] after every step:
+    G[k - 1] - G[k] of a run with one slot more bounds the margin by which the k-slot run's selections were decided.  ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
+    length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory."""
+    dev = torch.device(device)
+    if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
+        raise RuntimeError("sample_distinct runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
+    if num_samples < 1 or batch_size < 1 or max_length < 2:
+        raise ValueError(f"sample_distinct: num_samples >= 1, batch_size >= 1, max_length >= 2 (got {num_samples}, {batch_size}, "
+                         f"{max_length})")
+    if not temperature > 0:
+        raise ValueError(f"sample_distinct: temperature > 0 (got {temperature}): the perturbation needs a proper distribution")
+    if num_samples > SWOR_MAX_K:
+        raise ValueError(f"sample_distinct: at most {SWOR_MAX_K} samples per pocket (got {num_samples})")
+    cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
+    tf = model.model
+    voc = list(smiVoc)
+    V = len(voc)
+    sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
+    k, rows = num_samples, batch_size * num_samples
+    num = 1 if tf.decoder.num_props else 0
+    positions = max_length - 1 + num
+    a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
+    atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
+    if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
+            and positions <= 256 and atoms <= 1024 and V <= 1024):
+        raise ValueError("sample_distinct: the k17 step kernels are the only path: the shipped decoder geometry, at most 256 "
+                         "positions, 1024 pocket atoms and 1024 tokens")
+    if streams is None:
+        streams = np.arange(batch_size)
+    streams = np.asarray(streams.cpu() if torch.is_tensor(streams) else streams).astype(np.int64)
+    if streams.shape != (batch_size,) or (streams < 0).any() or (streams >= 2 ** 32).any():
+        raise ValueError(f"sample_distinct: streams holds one 32-bit integer per pocket, got shape {streams.shape}")
+    need = 2 * cache_bytes(tf.decoder, rows, positions) + 3 * rows * V * 4 + 2 * rows * max_length * 12
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
+        raise ValueError(f"sample_distinct: the two key / value cache buffers of {rows} rows x {positions} positions and the "
+                         f"candidates take {need} bytes, {free} bytes are free on {dev}: draw fewer samples per call")
+    streams = torch.as_tensor(streams.astype(np.uint32).view(np.int32)).to(dev)
+
+    enc_outputs, enc_pad_mask, _ = tf.encoder(example.protein_atom_feature.float(), example.protein_pos,
+                                              example.protein_element_batch, example.protein_atom_laplacian, batch_size,
+                                              getattr(example, "protein_knn", None))
+    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, k, positions, V, True, search_buffers=False)
+    bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
+    allowed = None
+    if suppress:
+        allowed = torch.ones(V, dtype=torch.uint8)
+        allowed[[voc.index(x) for x in suppress]] = 0
+        allowed = allowed.to(dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    state = {"gumbel": torch.empty(rows, **f32), "prop_logp": torch.empty(rows, **f32), "sum_logp": torch.empty(rows, **f32),
+             "hash": torch.empty(rows, dtype=torch.int64, device=dev), "finished": torch.empty(rows, dtype=torch.uint8, device=dev),
+             "length": torch.empty(rows, dtype=torch.int32, device=dev),
+             "tokens": torch.empty(rows, max_length, dtype=torch.int64, device=dev), "tok_logp": torch.empty(rows, max_length, **f32),
+             "next": torch.empty(rows, dtype=torch.int64, device=dev), "src": torch.empty(rows, dtype=torch.int64, device=dev),
+             "live": torch.empty(batch_size, dtype=torch.int32, device=dev), "cand": torch.empty(rows, V, **f32),
+             "cand_logp": torch.empty(rows, V, **f32), "cand_phi": torch.empty(rows, V, **f32)}
+    if grammar is not None:
+        cls = torch.as_tensor(cls).to(dev)
+        state["grammar"] = torch.empty(rows, dtype=torch.int32, device=dev)
+    work = ops.swor_work(rows, max_length, dev)
+
+    def start():
+        state["tokens"].fill_(pad)
+        state["tokens"][:, 0] = sos
+        state["next"].fill_(sos)
+        state["gumbel"].fill_(float("-inf")), state["prop_logp"].fill_(float("-inf"))
+        state["gumbel"].view(batch_size, k)[:, 0] = 0                  # slot 0 of every pocket is the root
+        state["prop_logp"].view(batch_size, k)[:, 0] = 0
+        state["sum_logp"].zero_(), state["hash"].zero_(), state["finished"].zero_(), state["length"].zero_()
+        state["tok_logp"].zero_(), state["src"].zero_()
+        state["live"].fill_(1)
+        if grammar is not None:
+            state["grammar"].fill_(smiles.FRESH)
+        kv.reset()
+
+    def step(parity):
+        (ck, cv), (ok, ov) = bufs[parity], bufs[1 - parity]
+        out = kv.advance(kv.token_input(state["next"]), ck, cv)
+        ops.swor_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, streams, float(temperature), int(seed), pad,
+                        allowed, cls if grammar is not None else None)
+        ops.swor_select(kv.pos, num + 1, state, k, work, eos, pad, cls if grammar is not None else None)
+        ops.swor_follow(ck, cv, ok, ov, state["src"], state["gumbel"], state["finished"], kv.pos)
+
+    replay = (lambda: step(0), lambda: step(1))
+    if graph:
+        # as in `sample`: warm up on a side stream, then capture - here twice, the step on each pair of cache buffers
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            start()
+            kv.pos += num
+            step(0), step(1)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graphs = []
+        for parity in (0, 1):
+            start()
+            kv.pos += num
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                step(parity)
+            graphs.append(g)
+        replay = (graphs[0].replay, graphs[1].replay)
+    start()
+    if num:
+        kv.advance(kv.prop_input(prop.to(dev).float()))                # position 0 is the property prompt, in the first buffer
+    steps = 0
+    history = trace.get("gumbel_history") if trace is not None else None
+    while steps < max_length - 1:
+        replay[steps % 2]()
+        steps += 1
+        if history is not None:
+            history.append(state["gumbel"].clone())
+        if steps % LIVE_POLL == 0 and int(state["live"].sum().item()) == 0:
+            break
+    if trace is not None:
+        trace.update(gumbel=state["gumbel"], prop_logp=state["prop_logp"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"],
+                     lengths=state["length"], valid=(state["gumbel"] > float("-inf")).to(torch.uint8), steps=steps)
+    return state["tokens"]
+
+
+def swor_weights(prop_logp, gumbel, valid):
+    """The importance weights of a `sample_distinct` run (Kool et al. 2019, section 4.2): per pocket (one row of the 2-D
+    arguments), kappa is the smallest G among the valid slots; the slot at kappa gets weight 0 and every other valid slot
+    1 / q with q = 1 - exp(-exp(phi - kappa)), the probability that its perturbed score exceeds kappa.  sum_i w_i f(s_i) is
+    then an unbiased estimate of E[f] under the proposal.  float64 arrays [pockets, k] in, float64 weights out (0 for dead
+    slots)."""
+    phi, g = np.asarray(prop_logp, np.float64), np.asarray(gumbel, np.float64)
+    ok = np.asarray(valid).astype(bool)
+    if phi.ndim != 2 or phi.shape != g.shape or ok.shape != g.shape:
+        raise ValueError(f"swor_weights: three arrays [pockets, k], got {phi.shape}, {g.shape}, {ok.shape}")
+    w = np.zeros_like(phi)
+    for b in range(phi.shape[0]):
+        idx = np.flatnonzero(ok[b])
+        if len(idx) == 0:
+            continue
+        at = idx[np.argmin(g[b, idx])]
+        rest = idx[idx != at]
+        w[b, rest] = 1.0 / -np.expm1(-np.exp(phi[b, rest] - g[b, at]))
+    return w

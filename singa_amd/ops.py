@@ -887,6 +887,94 @@ def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=No
                                               _stream()), "singa_sample_token_forced")
 
 
+def swor_work(rows, T, device):
+    """The scratch `swor_select` needs for `rows` rows of `T` columns: a uint8 tensor of `singa_swor_work` bytes."""
+    n = int(_lib.lib().singa_swor_work(rows, T))
+    if n < 0:
+        raise RuntimeError(f"swor_work: rows >= 0 and T >= 2, got {rows}, {T}")
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+
+
+def _swor_views(what, state, R, V, T, names, cls=None, allowed=None, extra=()):
+    """The argument checks of the swor ops: contiguous GPU tensors of the dtypes / shapes of include/singa_hip_swor.h."""
+    spec = {"gumbel": (torch.float32, (R,)), "prop_logp": (torch.float32, (R,)), "sum_logp": (torch.float32, (R,)),
+            "hash": (torch.int64, (R,)), "finished": (torch.uint8, (R,)), "length": (torch.int32, (R,)),
+            "grammar": (torch.int32, (R,)), "tokens": (torch.int64, (R, T)), "tok_logp": (torch.float32, (R, T)),
+            "next": (torch.int64, (R,)), "src": (torch.int64, (R,)), "cand": (torch.float32, (R, V)),
+            "cand_logp": (torch.float32, (R, V)), "cand_phi": (torch.float32, (R, V))}
+    items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (allowed, torch.uint8, (V,))] + list(extra)
+    for t, dt, shape in items:
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise RuntimeError(f"{what}: expected a contiguous {dt} GPU tensor of shape {shape}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}")
+    _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
+
+
+def swor_expand(logits, pos, pos_offset, state, k, streams, temperature=1.0, seed=0, pad=0, allowed=None, cls=None):
+    """Sub-steps 1 to 3 of stochastic beam search (`singa_swor_expand`, include/singa_hip_swor.h states the rule; inference
+    only): the perturbed, parent-conditioned score of every candidate of every row.  logits [R, V] f32, R = pockets * k; pos:
+    int64 device scalar (the step is pos - pos_offset); streams [pockets] int32 (read as 32-bit words); `state`: gumbel,
+    prop_logp [R] f32, hash [R] int64 (the 64 bits of the prefix hash), finished [R] uint8, tokens [R, T] (for T only), with
+    `cls` ([V] uint8 class bytes) also grammar [R] int32 - all read - and cand, cand_logp, cand_phi [R, V] f32, written."""
+    R, V = logits.shape
+    T = state["tokens"].shape[1]
+    names = ("gumbel", "prop_logp", "hash", "finished", "cand", "cand_logp", "cand_phi") + (("grammar",) if cls is not None else ())
+    _swor_views("swor_expand", state, R, V, T, names, cls, allowed,
+                ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (streams, torch.int32, (R // max(k, 1),))))
+    _chk(_lib.lib().singa_swor_expand(_p(logits), _p(allowed), _p(cls), _p(pos), pos_offset, R, k, V, T, temperature,
+                                      int(seed) & (2 ** 64 - 1), _p(streams), pad, _p(state["gumbel"]), _p(state["prop_logp"]),
+                                      _p(state["hash"]), _p(state["finished"]), _p(state["grammar"] if cls is not None else None),
+                                      _p(state["cand"]), _p(state["cand_logp"]), _p(state["cand_phi"]), _stream()),
+         "singa_swor_expand")
+
+
+def swor_select(pos, pos_offset, state, k, work, eos=0, pad=0, cls=None):
+    """Sub-steps 4 and 5 (`singa_swor_select`): per pocket the k best candidates of `state`'s cand in the rule's order become
+    the new slots; gumbel, prop_logp, sum_logp, hash, finished, length, (grammar,) tokens and tok_logp follow the parents,
+    next [R] int64 (the emitted token), src [R] int64 (the parent row) and live [pockets] int32 are written.  `work`:
+    `swor_work(R, T, device)`."""
+    R, V = state["cand"].shape
+    T = state["tokens"].shape[1]
+    names = ("gumbel", "prop_logp", "sum_logp", "hash", "finished", "length", "tokens", "tok_logp", "next", "src", "cand",
+             "cand_logp", "cand_phi") + (("grammar",) if cls is not None else ())
+    _swor_views("swor_select", state, R, V, T, names, cls, None,
+                ((pos, torch.int64, None), (state["live"], torch.int32, (R // max(k, 1),)), (work, torch.uint8, None)))
+    need = int(_lib.lib().singa_swor_work(R, T))
+    if work.numel() < need:
+        raise RuntimeError(f"swor_select: work holds {work.numel()} bytes, singa_swor_work({R}, {T}) = {need}")
+    _chk(_lib.lib().singa_swor_select(_p(state["cand"]), _p(state["cand_logp"]), _p(state["cand_phi"]), _p(cls), _p(pos),
+                                      pos_offset, R, k, V, T, eos, pad, _p(state["gumbel"]), _p(state["prop_logp"]),
+                                      _p(state["sum_logp"]), _p(state["hash"]), _p(state["finished"]), _p(state["length"]),
+                                      _p(state["grammar"] if cls is not None else None), _p(state["tokens"]),
+                                      _p(state["tok_logp"]), _p(state["next"]), _p(state["src"]), _p(state["live"]), _p(work),
+                                      _stream()), "singa_swor_select")
+
+
+def swor_follow(k_src, v_src, k_dst, v_dst, src, gumbel, finished, pos):
+    """The caches follow the surviving prefixes (`singa_swor_follow`): positions [0, pos) of every layer's and head's keys /
+    values move from row src[r] of (k_src, v_src) to row r of (k_dst, v_dst), skipping dead (gumbel = -inf) and finished rows;
+    one launch, 16-byte accesses.  Caches [layers, R, heads, P, dk] / [.., dv] f32, dense from the heads on (row and layer
+    strides are passed on); the two buffers are alike and distinct."""
+    n, R, H, P, dk = k_src.shape
+    dv = v_src.shape[4]
+    for a, b, d in ((k_src, k_dst, dk), (v_src, v_dst, dv)):
+        if not (a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float32 and tuple(a.shape) == tuple(b.shape) == (n, R, H, P, d)
+                and a.stride() == b.stride() and a.stride()[2:] == (P * d, d, 1)):
+            raise RuntimeError(f"swor_follow: two alike float32 GPU caches [layers, rows, heads, P, d], dense from the heads on; "
+                               f"got {tuple(a.shape)} {a.stride()} and {tuple(b.shape)} {b.stride()}")
+    for t, dt in ((src, torch.int64), (gumbel, torch.float32), (finished, torch.uint8)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (R,):
+            raise RuntimeError(f"swor_follow: expected a contiguous {dt} GPU tensor of shape {(R,)}, got {t.dtype} {tuple(t.shape)}")
+    if not pos.is_cuda or pos.dtype != torch.int64:
+        raise RuntimeError("swor_follow: pos is an int64 device scalar")
+    _lib.ensure_init(k_src.device.index if k_src.device.index is not None else torch.cuda.current_device())
+    _chk(_lib.lib().singa_swor_follow(_p(k_src), _p(v_src), _p(k_dst), _p(v_dst), _p(src), _p(gumbel), _p(finished), _p(pos), n, R,
+                                      H, P, dk, dv, k_src.stride(1), k_src.stride(0), v_src.stride(1), v_src.stride(0), _stream()),
+         "singa_swor_follow")
+
+
 class _MaskedSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, mask, scale, heads):

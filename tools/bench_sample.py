@@ -4,6 +4,7 @@ atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket w
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
     python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
+                                  [--distinct]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
@@ -14,7 +15,9 @@ needs it - but its logit keeps rows from ending before the budget forces them to
 the k17 step with a forced prefix of 5 tokens next to the plain one at rows = 20, 2048, interleaved (`forced_table`), and
 `score` on 2,048 molecules of 40 tokens for the pocket, timed as a whole call (`score_2048`: molecules / s).  A generation is timed
 as a whole - encoder, cache set-up, graph capture and
-every step - and divided by its steps, as bench_beam.py does.
+every step - and divided by its steps, as bench_beam.py does.  With `--distinct` also `sample_distinct` (sampling without
+replacement: expand, select and the cache move inside the step, two captured graphs) next to the plain k17 step at rows = 128,
+512, 2048 for the one pocket, interleaved (`distinct_table`).
 """
 import argparse
 import json
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--table", action="store_true")
     ap.add_argument("--grammar", action="store_true", help="also time the grammar-constrained step (grammar_table)")
     ap.add_argument("--forced", action="store_true", help="also time the step with a forced prefix, and score() (forced_table)")
+    ap.add_argument("--distinct", action="store_true", help="also time sample_distinct next to the plain step (distinct_table)")
+    ap.add_argument("--distinct-only", type=int, default=0, metavar="ROWS",
+                    help="nothing but two sample_distinct generations of ROWS slots: the run to take a kernel trace of")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -50,7 +56,7 @@ def main():
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
-    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample, score
+    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample, sample_distinct, score
     dev = torch.device("cuda", 0)
     cfg = load_config(lmax=2)
     torch.manual_seed(cfg.train.seed)
@@ -96,6 +102,16 @@ def main():
         return {"rows": rows, "ms_per_step": round(ms, 4), "new_tokens_per_s": round(rows / ms * 1e3, 1),
                 "sequences_per_s": round(rows / (ms * (T - 1)) * 1e3, 2)}
 
+    if args.distinct_only:
+        rows = args.distinct_only
+        ms = []
+        for _ in range(2):
+            tr = {}
+            ms.append(timed(lambda: sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev,
+                                                    temperature=args.temperature, suppress=("$",), seed=rows, trace=tr) is None
+                            or tr["steps"]))
+        print(json.dumps({"distinct_only_rows": rows, "ms_per_step": [round(x, 4) for x in ms]}))
+        return
     fused = {"auto": None, "k17": True, "library": False}[args.fused]
     run_beam(), run_sample(20, None), run_sample(args.rows, fused)           # warm-up: library initialisation, code objects
     beam_ms, samp_ms = [], []
@@ -153,6 +169,23 @@ def main():
         secs = [timed(do_score) / 1e3 for _ in range(3)]
         res["score_2048"] = {"molecules": 2048, "tokens_each": 40, "seconds": [round(x, 4) for x in secs],
                              "molecules_per_s": round(2048 / statistics.median(secs), 1)}
+    if args.distinct:
+        def run_distinct(rows):
+            tr = {}
+            sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev, temperature=args.temperature,
+                            suppress=("$",), seed=rows, trace=tr)
+            return tr["steps"]
+        dtable = []
+        for rows in (128, 512, 2048):
+            run_sample(rows, True), run_distinct(rows)
+            plain, dist = [], []
+            for _ in range(3 if rows >= 512 else args.reps):
+                plain.append(timed(lambda: run_sample(rows, True)))
+                dist.append(timed(lambda: run_distinct(rows)))
+            dtable.append({"rows": rows, "path": "k17", "plain_ms_per_step": round(statistics.median(plain), 4),
+                           "distinct_ms_per_step": round(statistics.median(dist), 4),
+                           "plain_runs_ms": [round(x, 4) for x in plain], "distinct_runs_ms": [round(x, 4) for x in dist]})
+        res["distinct_table"] = dtable
     print(json.dumps(res))
 
 
