@@ -5956,6 +5956,28 @@ bool pack_mut(const singa_seg_mut_t* s, int nseg, SegsMut* out) {
         }                                                                               \
     } while (0)
 
+// The vocabulary width of a row-in-registers kernel (sample_token_kernel, swor_expand_kernel: a lane holds NPL tokens) and a
+// run-time flag as template arguments: f is called once, with a std::integral_constant to read the value from.
+template <class F>
+void dispatch_npl(int V, F&& f) {
+    if (V <= 128) f(std::integral_constant<int, 2>{});
+    else if (V <= 256) f(std::integral_constant<int, 4>{});
+    else if (V <= 512) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
+template <class F>
+void dispatch_flag(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// "<entry>: <text>" as the last error: the checks that several entry points share spell their text once
+int fail_at(int code, const char* entry, const char* text) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, text);
+    return code;
+}
+
 // ------------------------------------------------------------------------------------------------ n1: kNN graph
 // torch_cluster.knn_graph(pos, k, batch, flow='target_to_source') (reference model/CProMG.py:293,330): for every atom its k
 // nearest other atoms of the same molecule.  One wavefront per centre atom; the molecule's atoms (a contiguous index range
@@ -7095,36 +7117,60 @@ int singa_dec_ffn(const float* z, const float* w1_t, const float* b1, const floa
     return check_launch("dec_ffn");
 }
 
+namespace {
+// Whether an entry point takes the grammar operands (cls, gstate, allowed_logp) of sample_token_kernel
+enum GrammarOperands { GRAMMAR_NONE, GRAMMAR_OPTIONAL, GRAMMAR_REQUIRED };
+
+// The one place where a token choice is validated and launched: singa_sample_token, _grammar and _forced are this function
+// with their name, the operands they do not have as null pointers, and the two facts in which they differ.  The grammar runs
+// where cls and gstate are given, forcing where `forced` is.
+int sample_choice(const char* name, GrammarOperands gram, bool need_forced, const float* logits, const float* uniforms,
+                  const unsigned char* allowed, const unsigned char* cls, const long long* pos, int pos_offset, int rows, int V,
+                  int T, float tau, int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
+                  float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp, int32_t* gstate,
+                  float* allowed_logp, const long long* forced, int32_t* rank, void* stream) {
+    static const char* const columns[] = {"T >= 2 columns, eos / pad inside the vocabulary",
+                                          "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary",
+                                          "T >= 3 columns, eos / pad inside the vocabulary"};
+    const bool grammar = cls && gstate;
+    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live ||
+        (gram == GRAMMAR_REQUIRED && !grammar) || (need_forced && !forced))
+        return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (!grammar && (cls || gstate || allowed_logp))
+        return fail_at(SINGA_E_NULL, name, "cls and gstate go together (allowed_logp only with them)");
+    if (V < 1 || V > 1024) return fail_at(SINGA_E_SHAPE, name, "vocabulary of 1..1024 tokens");
+    if (!(tau >= 0.f)) return fail_at(SINGA_E_SHAPE, name, "temperature must be >= 0");
+    if (top_k < 0) return fail_at(SINGA_E_SHAPE, name, "top_k must be >= 0 (0 = off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail_at(SINGA_E_SHAPE, name, "top_p must be in (0, 1]");
+    if (T < (grammar ? 3 : 2) || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
+        return fail_at(SINGA_E_SHAPE, name, columns[gram]);
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    dispatch_npl(V, [&](auto npl) {
+        dispatch_flag(grammar, [&](auto g) {
+            dispatch_flag(forced != nullptr, [&](auto f) {
+                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value>), grid,
+                                   block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau,
+                                   top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,
+                                   allowed_logp, forced, rank);
+            });
+        });
+    });
+    return check_launch(name);
+#endif
+}
+}  // namespace
+
 int singa_sample_token(const float* logits, const float* uniforms, const unsigned char* allowed, const long long* pos,
                        int pos_offset, int rows, int V, int T, float tau, int top_k, float top_p, int eos, int pad,
                        unsigned char* finished, int32_t* length, float* sum_logp, long long* tokens, long long* next,
                        int32_t* live, float* tok_logp, void* stream) {
-    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live)
-        return fail(SINGA_E_NULL, "sample_token: null pointer");
-    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token: vocabulary of 1..1024 tokens");
-    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token: temperature must be >= 0");
-    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token: top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token: top_p must be in (0, 1]");
-    if (T < 2 || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
-        return fail(SINGA_E_SHAPE, "sample_token: T >= 2 columns, eos / pad inside the vocabulary");
-    if (rows == 0) return SINGA_OK;
-#ifdef SINGA_EMUL
-    return fail(SINGA_E_SHAPE, "sample_token: not part of the emulation build");
-#else
-    const dim3 grid((rows + 3) / 4), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    hipLaunchKernelGGL((sample_token_kernel<NPL, false, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
-                       T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp,                  \
-                       (const unsigned char*)nullptr, (int32_t*)nullptr, (float*)nullptr, (const long long*)nullptr,                  \
-                       (int32_t*)nullptr)
-    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
-    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
-    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
-    else SINGA_SAMPLE_LAUNCH(16);
-#undef SINGA_SAMPLE_LAUNCH
-    return check_launch("sample_token");
-#endif
+    return sample_choice("sample_token", GRAMMAR_NONE, false, logits, uniforms, allowed, nullptr, pos, pos_offset, rows, V, T, tau,
+                         top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, nullptr, nullptr, nullptr,
+                         nullptr, stream);
 }
 
 int singa_sample_token_grammar(const float* logits, const float* uniforms, const unsigned char* allowed,
@@ -7132,31 +7178,9 @@ int singa_sample_token_grammar(const float* logits, const float* uniforms, const
                                int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
                                float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp,
                                int32_t* gstate, float* allowed_logp, void* stream) {
-    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live || !cls || !gstate)
-        return fail(SINGA_E_NULL, "sample_token_grammar: null pointer");
-    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token_grammar: vocabulary of 1..1024 tokens");
-    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token_grammar: temperature must be >= 0");
-    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token_grammar: top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token_grammar: top_p must be in (0, 1]");
-    if (T < 3 || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
-        return fail(SINGA_E_SHAPE, "sample_token_grammar: T >= 3 columns, eos / pad inside the vocabulary");
-    if (rows == 0) return SINGA_OK;
-#ifdef SINGA_EMUL
-    return fail(SINGA_E_SHAPE, "sample_token_grammar: not part of the emulation build");
-#else
-    const dim3 grid((rows + 3) / 4), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    hipLaunchKernelGGL((sample_token_kernel<NPL, true, false>), grid, block, 0, st, logits, uniforms, allowed, pos, pos_offset, rows, V, \
-                       T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,     \
-                       allowed_logp, (const long long*)nullptr, (int32_t*)nullptr)
-    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
-    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
-    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
-    else SINGA_SAMPLE_LAUNCH(16);
-#undef SINGA_SAMPLE_LAUNCH
-    return check_launch("sample_token_grammar");
-#endif
+    return sample_choice("sample_token_grammar", GRAMMAR_REQUIRED, false, logits, uniforms, allowed, cls, pos, pos_offset, rows, V,
+                         T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, gstate,
+                         allowed_logp, nullptr, nullptr, stream);
 }
 
 int singa_sample_token_forced(const float* logits, const float* uniforms, const unsigned char* allowed,
@@ -7164,41 +7188,9 @@ int singa_sample_token_forced(const float* logits, const float* uniforms, const 
                               int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
                               float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp,
                               int32_t* gstate, float* allowed_logp, const long long* forced, int32_t* rank, void* stream) {
-    const bool grammar = cls && gstate;
-    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live || !forced)
-        return fail(SINGA_E_NULL, "sample_token_forced: null pointer");
-    if (!grammar && (cls || gstate || allowed_logp))
-        return fail(SINGA_E_NULL, "sample_token_forced: cls and gstate go together (allowed_logp only with them)");
-    if (V < 1 || V > 1024) return fail(SINGA_E_SHAPE, "sample_token_forced: vocabulary of 1..1024 tokens");
-    if (!(tau >= 0.f)) return fail(SINGA_E_SHAPE, "sample_token_forced: temperature must be >= 0");
-    if (top_k < 0) return fail(SINGA_E_SHAPE, "sample_token_forced: top_k must be >= 0 (0 = off)");
-    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SINGA_E_SHAPE, "sample_token_forced: top_p must be in (0, 1]");
-    if (T < (grammar ? 3 : 2) || eos < 0 || eos >= V || pad < 0 || pad >= V || rows < 0)
-        return fail(SINGA_E_SHAPE, "sample_token_forced: T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary");
-    if (rows == 0) return SINGA_OK;
-#ifdef SINGA_EMUL
-    return fail(SINGA_E_SHAPE, "sample_token_forced: not part of the emulation build");
-#else
-    const dim3 grid((rows + 3) / 4), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define SINGA_SAMPLE_LAUNCH(NPL)                                                                                              \
-    do {                                                                                                                      \
-        if (grammar)                                                                                                          \
-            hipLaunchKernelGGL((sample_token_kernel<NPL, true, true>), grid, block, 0, st, logits, uniforms, allowed, pos,    \
-                               pos_offset, rows, V, T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, \
-                               live, tok_logp, cls, gstate, allowed_logp, forced, rank);                                      \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((sample_token_kernel<NPL, false, true>), grid, block, 0, st, logits, uniforms, allowed, pos,   \
-                               pos_offset, rows, V, T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, \
-                               live, tok_logp, cls, gstate, allowed_logp, forced, rank);                                      \
-    } while (0)
-    if (V <= 128) SINGA_SAMPLE_LAUNCH(2);
-    else if (V <= 256) SINGA_SAMPLE_LAUNCH(4);
-    else if (V <= 512) SINGA_SAMPLE_LAUNCH(8);
-    else SINGA_SAMPLE_LAUNCH(16);
-#undef SINGA_SAMPLE_LAUNCH
-    return check_launch("sample_token_forced");
-#endif
+    return sample_choice("sample_token_forced", GRAMMAR_OPTIONAL, true, logits, uniforms, allowed, cls, pos, pos_offset, rows, V,
+                         T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, gstate,
+                         allowed_logp, forced, rank, stream);
 }
 
 int singa_smiles_rule_host(const unsigned char* cls, const int32_t* state, const int32_t* rem, int n, unsigned char* ok,
@@ -7233,16 +7225,13 @@ long long singa_swor_work(int rows, int T) {
 namespace {
 // the checks singa_swor_expand and singa_swor_select share; 0 = go on
 int swor_shape(const char* what, int rows, int k, int V, int T, bool grammar, int eos, int pad) {
-    static thread_local char msg[160];
     const char* bad = nullptr;
     if (V < 1 || V > 1024) bad = "vocabulary of 1..1024 tokens";
     else if (k < 1 || k > 2048) bad = "1..2048 slots per pocket";
     else if (rows < 0 || rows % k) bad = "rows must be pockets x slots";
     else if (T < (grammar ? 3 : 2)) bad = "T >= 2 columns (3 under the grammar)";
     else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
-    if (!bad) return SINGA_OK;
-    snprintf(msg, sizeof(msg), "%s: %s", what, bad);
-    return fail(SINGA_E_SHAPE, msg);
+    return bad ? fail_at(SINGA_E_SHAPE, what, bad) : SINGA_OK;
 }
 }  // namespace
 
@@ -7251,34 +7240,25 @@ int singa_swor_expand(const float* logits, const unsigned char* allowed, const u
                       const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
                       const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
                       float* cand_logp, float* cand_phi, void* stream) {
+    const char* name = "swor_expand";
     if (!logits || !pos || !streams || !gumbel || !prop_logp || !hash || !finished || !cand || !cand_logp || !cand_phi)
-        return fail(SINGA_E_NULL, "swor_expand: null pointer");
-    if (!cls != !gstate) return fail(SINGA_E_NULL, "swor_expand: cls and gstate go together");
-    if (const int e = swor_shape("swor_expand", rows, k, V, T, cls != nullptr, 0, pad)) return e;
-    if (!(tau > 0.f)) return fail(SINGA_E_SHAPE, "swor_expand: temperature must be > 0");
+        return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (!cls != !gstate) return fail_at(SINGA_E_NULL, name, "cls and gstate go together");
+    if (const int e = swor_shape(name, rows, k, V, T, cls != nullptr, 0, pad)) return e;
+    if (!(tau > 0.f)) return fail_at(SINGA_E_SHAPE, name, "temperature must be > 0");
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
-    return fail(SINGA_E_SHAPE, "swor_expand: not part of the emulation build");
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
 #else
     const dim3 grid((rows + 3) / 4), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define SINGA_SWOR_LAUNCH(NPL)                                                                                                 \
-    do {                                                                                                                       \
-        if (cls)                                                                                                               \
-            hipLaunchKernelGGL((swor_expand_kernel<NPL, true>), grid, block, 0, st, logits, allowed, cls, pos, pos_offset, rows, \
-                               k, V, T, tau, seed, streams, pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp,   \
-                               cand_phi);                                                                                      \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((swor_expand_kernel<NPL, false>), grid, block, 0, st, logits, allowed, cls, pos, pos_offset, rows, \
-                               k, V, T, tau, seed, streams, pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp,   \
-                               cand_phi);                                                                                      \
-    } while (0)
-    if (V <= 128) SINGA_SWOR_LAUNCH(2);
-    else if (V <= 256) SINGA_SWOR_LAUNCH(4);
-    else if (V <= 512) SINGA_SWOR_LAUNCH(8);
-    else SINGA_SWOR_LAUNCH(16);
-#undef SINGA_SWOR_LAUNCH
-    return check_launch("swor_expand");
+    dispatch_npl(V, [&](auto npl) {
+        dispatch_flag(cls != nullptr, [&](auto g) {
+            hipLaunchKernelGGL((swor_expand_kernel<decltype(npl)::value, decltype(g)::value>), grid, block, 0, (hipStream_t)stream,
+                               logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams, pad, gumbel, prop_logp,
+                               hash, finished, gstate, cand, cand_logp, cand_phi);
+        });
+    });
+    return check_launch(name);
 #endif
 }
 
@@ -7289,13 +7269,13 @@ int singa_swor_select(const float* cand, const float* cand_logp, const float* ca
                       void* work, void* stream) {
     if (!cand || !cand_logp || !cand_phi || !pos || !gumbel || !prop_logp || !sum_logp || !hash || !finished || !length ||
         !tokens || !tok_logp || !next || !src || !live || !work)
-        return fail(SINGA_E_NULL, "swor_select: null pointer");
-    if (!cls != !gstate) return fail(SINGA_E_NULL, "swor_select: cls and gstate go together");
+        return fail_at(SINGA_E_NULL, "swor_select", "null pointer");
+    if (!cls != !gstate) return fail_at(SINGA_E_NULL, "swor_select", "cls and gstate go together");
     if (const int e = swor_shape("swor_select", rows, k, V, T, cls != nullptr, eos, pad)) return e;
     if ((uintptr_t)work % 16) return fail(SINGA_E_SHAPE, "swor_select: work must be 16-byte aligned");
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
-    return fail(SINGA_E_SHAPE, "swor_select: not part of the emulation build");
+    return fail_at(SINGA_E_SHAPE, "swor_select", "not part of the emulation build");
 #else
     const SworWork w(rows, T);
     char* b = (char*)work;

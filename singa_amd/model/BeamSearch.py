@@ -112,7 +112,7 @@ class KVDecoder:
         self.v = torch.zeros(n, self.R, self.heads, max_positions, self.dv, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)            # next position to be written
         self.slots = torch.arange(max_positions, device=dev)
-        self.graph = None
+        self.replay = None                                                 # the captured step's replay, once `capture` has run
         if not search_buffers:
             return
         # the step's inputs (scores, tokens, source rows - one row each, as doubles: exact for fp32 and for indices) and
@@ -184,20 +184,12 @@ class KVDecoder:
         the caller resets `pos` afterwards, and slots >= pos are never read."""
         self.step_in.zero_()
         self.step_in[2] = torch.arange(self.R, device=self.dev)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.reset()
-                self.pos += self.num
-                self._step_body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.reset()
-        self.pos += self.num
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self._step_body()
+
+        def prime():
+            self.reset()
+            self.pos += self.num
+
+        self.replay, = capture_steps(prime, [self._step_body], 2)
         self.reset()
 
     def step(self, scores, tokens, src_rows):
@@ -205,12 +197,43 @@ class KVDecoder:
         flat candidate indices int64 [B, 2*beams]) on the host.  One H2D copy, one graph replay, one D2H copy."""
         host = np.stack([scores.astype(np.float64), tokens.astype(np.float64), src_rows.astype(np.float64)])
         self.step_in.copy_(torch.from_numpy(host))
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._step_body()
+        (self.replay or self._step_body)()
         out = self.step_out.cpu().numpy()
         return out[0].astype(np.float32), out[1].astype(np.int64)
+
+
+def capture_steps(prime, bodies, warmups):
+    """The one place where decode steps become HIP graphs (`KVDecoder.capture`, `Sampling.sample`, `sample_distinct`).
+    `prime()` resets the caller's row state and advances `pos` past the property prompt; `bodies` are the steps, each captured
+    into a graph of its own.  `warmups` times on a side stream: prime, then every body in order; back on the current stream
+    and synchronised, per body: prime, capture.  Returns the graphs' replay callables, one per body.  Warm-up and capture write
+    cache slots and row state, which the caller resets afterwards; slots >= pos are never read."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmups):
+            prime()
+            for body in bodies:
+                body()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    replays = []
+    for body in bodies:
+        prime()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            body()
+        replays.append(g.replay)                                       # the bound method keeps its graph alive
+    return replays
+
+
+def encode_pockets(tf, example, batch_size):
+    """The encoder's (outputs, padding mask) for the `batch_size` pockets of `example` (its optional `protein_knn`: a
+    precomputed [2, E] kNN list; otherwise drawn on the GPU)."""
+    enc_outputs, enc_pad_mask, _ = tf.encoder(example.protein_atom_feature.float(), example.protein_pos,
+                                              example.protein_element_batch, example.protein_atom_laplacian, batch_size,
+                                              getattr(example, "protein_knn", None))
+    return enc_outputs, enc_pad_mask
 
 
 def _select(cand_score, cand_flat, prefixes, hyps, done, num_beams, vocab_size, eos, pad, cur_len):
@@ -262,10 +285,7 @@ def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example,
     voc = list(smiVoc)
     sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
     dev = torch.device(device)
-    feat = example.protein_atom_feature.float()
-    enc_outputs, enc_pad_mask, _ = tf.encoder(feat, example.protein_pos, example.protein_element_batch,
-                                              example.protein_atom_laplacian, batch_size,
-                                              getattr(example, "protein_knn", None))
+    enc_outputs, enc_pad_mask = encode_pockets(tf, example, batch_size)
     rows = batch_size * num_beams
     num = 1 if tf.decoder.num_props else 0
     kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_beams, max_length + num, vocab_size, fused)

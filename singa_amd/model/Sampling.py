@@ -21,15 +21,15 @@ by its uniforms, on any device and at any row count.
 A live row that draws '^' or '&' carries on: to the KV-cached decoder they are tokens like any other (as in beam search, the
 caches have no padding mask).  `suppress=("&", "^")` keeps them from being drawn.
 
-`grammar="smiles"` constrains the draw to syntactically complete SMILES: the token choice then runs as
-`ops.sample_token_grammar` (kernel `singa_sample_token_grammar`; include/singa_hip_gen.h states the rule), which keeps one
+`grammar="smiles"` constrains the draw to syntactically complete SMILES: `ops.sample_token`, given the class bytes, then
+runs `singa_sample_token_grammar` (include/singa_hip_gen.h states the rule), which keeps one
 more word of state per row on the device and masks, per row, what cannot follow the row's prefix or could not be finished in
 the columns left.  Every row then ends in '$' before `max_length` and the text in front of it has balanced branches, paired
 ring-closure digits and no dangling bond symbol.  Syntax only: valence, aromaticity, duplicate ring bonds (C1C1), %nn
 closures and beam search are outside the rule (singa_amd/smiles.py).  The step stays one captured graph.
 
-`forced=` gives tokens instead of drawing them: the token choice then runs as `ops.sample_token_forced` (kernel
-`singa_sample_token_forced`; include/singa_hip_force.h states the rule), which reads one more 8-byte word per row from a
+`forced=` gives tokens instead of drawing them: `ops.sample_token`, given the forced matrix, then runs
+`singa_sample_token_forced` (include/singa_hip_force.h states the rule), which reads one more 8-byte word per row from a
 fixed device matrix indexed by the device-resident position - like the uniforms, so the step stays one captured graph - and,
 where that word is a token, takes it with the bookkeeping of a drawn one.  Forcing the first columns of a row continues a
 scaffold; forcing every column up to '$' scores a given molecule (`score`): the log-likelihood then comes from the same
@@ -43,24 +43,60 @@ inside the captured step: `ops.swor_expand` (the perturbed score of every candid
 pocket, the row state gathered from the parents) and `ops.swor_follow` (one launch moves the surviving prefixes' key / value
 cache rows from one cache buffer to the other; the step is captured twice, for even and odd tokens, and the two graphs are
 replayed in turn).  `swor_weights` turns the run's `gumbel` / `prop_logp` into the importance weights of the paper's estimator.
+
+What the two loops share is written once: `_prologue` (the checks and figures both start from), `BeamSearch.encode_pockets`,
+`BeamSearch.capture_steps` (warm-up on a side stream, one HIP graph per step body) and `_decode` (replay, count, poll).
 """
 import numpy as np
 import torch
 
 from .. import ops, smiles
-from .BeamSearch import KVDecoder
+from .BeamSearch import KVDecoder, capture_steps, encode_pockets
 
-# Row count above which `fused=None` takes the library path (GEMMs that read a layer's weights once per step) instead of the
-# k17 step kernels (one workgroup per row, the weights re-read per workgroup).  Measured at 20 / 128 / 512 / 2,048 rows
-# (profiles/sampling/README.md): k17 is faster at every one of them (2.40 against 3.36 ms per step at 2,048 rows, and both
-# grow by about 1.1 us per row from 512 on), so there is no crossover to switch at: None = k17 wherever its limits allow.
-FUSED_MAX_ROWS = None
 LIVE_POLL = 16          # tokens between two reads of the live-row counter
 
 
 def cache_bytes(decoder, rows, positions):
     a = decoder.layers[0].dec_self_attn
     return len(decoder.layers) * rows * positions * (a.key_channels + a.hidden_channels) * 4
+
+
+def _prologue(fn, model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress):
+    """What `sample` and `sample_distinct` (`fn`: the caller's name, for the messages) check and work out alike before they
+    differ -> (device, transformer, vocabulary, (sos, eos, pad), rows, 1 with a property prompt else 0, cache positions, free
+    bytes on the device, the grammar's class bytes or None, the [V] uint8 mask of `suppress` on the device or None)."""
+    dev = torch.device(device)
+    if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
+        raise RuntimeError(f"{fn} runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
+    if num_samples < 1 or batch_size < 1 or max_length < 2:
+        raise ValueError(f"{fn}: num_samples >= 1, batch_size >= 1, max_length >= 2 (got {num_samples}, {batch_size}, {max_length})")
+    cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
+    tf = model.model
+    voc = list(smiVoc)
+    marks = voc.index("&"), voc.index("$"), voc.index("^")
+    rows = batch_size * num_samples
+    num = 1 if tf.decoder.num_props else 0
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    allowed = None
+    if suppress:
+        allowed = torch.ones(len(voc), dtype=torch.uint8)
+        allowed[[voc.index(s) for s in suppress]] = 0
+        allowed = allowed.to(dev)
+    return dev, tf, voc, marks, rows, num, max_length - 1 + num, free, cls, allowed
+
+
+def _decode(replays, max_steps, live, each=None):
+    """Replay the step - `replays` in turn - up to `max_steps` times; `each()`, if given, after every step; every `LIVE_POLL`
+    steps `live()` reads the device's count of live rows, and zero ends the loop.  Returns the steps taken."""
+    steps = 0
+    while steps < max_steps:
+        replays[steps % len(replays)]()
+        steps += 1
+        if each is not None:
+            each()
+        if steps % LIVE_POLL == 0 and live() == 0:
+            break
+    return steps
 
 
 @torch.no_grad()
@@ -73,7 +109,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     as in `beam_search`.  `suppress`: tokens never to be drawn.  `generator`: torch.Generator for the uniforms (CPU or device);
     `uniforms` [max_length, rows] f32 in [0, 1) replaces the draw (row t is read by the step that writes column t + 1).
     `graph=False` launches the step's kernels one by one (same tokens).  `fused`: True = k17 step kernels, False = library
-    GEMMs, None = the faster one for the row count (`FUSED_MAX_ROWS`: k17 wherever the k17 kernels' limits allow).
+    GEMMs, None = k17 wherever the k17 kernels' limits allow (it is the faster one at every row count measured).
 
     Returns the int64 token matrix [batch_size * num_samples, max_length], pocket-major: a row starts with '&', ends with
     '$' if the model ended it before `max_length`, and is padded with '^'.  `trace`, if a dict, receives `lengths` (int32:
@@ -95,14 +131,10 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     prefix the rule does not allow or that cannot be finished in `max_length`, with a ValueError before any device work.
     `trace` also receives `rank` [rows, max_length] int32: the rank of every emitted token among the row's raw logits (0 = the
     arg-max; 0 behind a row's end).  Free columns are drawn exactly as without `forced`, from the same uniforms."""
-    dev = torch.device(device)
-    if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
-        raise RuntimeError("sample runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
-    if num_samples < 1 or batch_size < 1 or max_length < 2:
-        raise ValueError(f"sample: num_samples >= 1, batch_size >= 1, max_length >= 2 (got {num_samples}, {batch_size}, {max_length})")
+    dev, tf, voc, (sos, eos, pad), rows, num, positions, free, cls, allowed = _prologue(
+        "sample", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError(f"sample: temperature >= 0, top_k >= 0, 0 < top_p <= 1 (got {temperature}, {top_k}, {top_p})")
-    cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
     if forced is not None:
         forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
         forced = smiles.check_forced(forced, smiVoc, max_length, grammar)
@@ -111,15 +143,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         if forced.shape[0] != batch_size * num_samples:
             raise ValueError(f"sample: forced has {forced.shape[0]} rows, expected {batch_size * num_samples} (or one per pocket: "
                              f"{batch_size})")
-    tf = model.model
-    voc = list(smiVoc)
-    V = len(voc)
-    sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
-    rows = batch_size * num_samples
-    num = 1 if tf.decoder.num_props else 0
-    positions = max_length - 1 + num
     need = cache_bytes(tf.decoder, rows, positions)
-    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
     if need + (64 << 10) * rows > free:                  # + the step's activations: a few [rows, 1024] f32 operands
         raise ValueError(f"sample: the key / value caches of {rows} rows x {positions} positions take {need} bytes, "
                          f"{free} bytes are free on {dev}: draw fewer samples per call and call again with the next "
@@ -132,19 +156,10 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
                          f"{uniforms.dtype} {tuple(uniforms.shape)}")
     uniforms = uniforms.to(dev).contiguous()
 
-    enc_outputs, enc_pad_mask, _ = tf.encoder(example.protein_atom_feature.float(), example.protein_pos,
-                                              example.protein_element_batch, example.protein_atom_laplacian, batch_size,
-                                              getattr(example, "protein_knn", None))
-    want_fused = (FUSED_MAX_ROWS is None or rows <= FUSED_MAX_ROWS) if fused is None else bool(fused)
-    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_samples, positions, V, want_fused,
-                   search_buffers=False)
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), num_samples, positions, len(voc),
+                   fused is None or bool(fused), search_buffers=False)
     if fused and not kv.fused:
         raise ValueError("sample: fused=True needs the shipped decoder geometry, at most 256 positions and 1024 pocket atoms")
-    allowed = None
-    if suppress:
-        allowed = torch.ones(V, dtype=torch.uint8)
-        allowed[[voc.index(s) for s in suppress]] = 0
-        allowed = allowed.to(dev)
     state = {"tokens": torch.empty(rows, max_length, dtype=torch.int64, device=dev),
              "next": torch.empty(rows, dtype=torch.int64, device=dev),
              "finished": torch.empty(rows, dtype=torch.uint8, device=dev),
@@ -172,47 +187,21 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
             state["rank"].zero_()
         kv.reset()
 
-    def step():
-        out = kv.advance(kv.token_input(state["next"]))
-        if forced is not None:
-            ops.sample_token_forced(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, forced,
-                                    cls if grammar is not None else None, float(temperature), int(top_k), float(top_p), eos, pad,
-                                    allowed)
-        elif grammar is None:
-            ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
-                             float(top_p), eos, pad, allowed)
-        else:
-            ops.sample_token_grammar(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, cls, float(temperature),
-                                     int(top_k), float(top_p), eos, pad, allowed)
-
-    replay = step
-    if graph:
-        # as KVDecoder.capture: two warm-up steps on a side stream, then the capture; both write cache slots and row state,
-        # which `start` resets, and slots >= pos are never read
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                start()
-                kv.pos += num
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+    def prime():
         start()
         kv.pos += num
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            step()
-        replay = g.replay
+
+    def step():
+        out = kv.advance(kv.token_input(state["next"]))
+        ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
+                         float(top_p), eos, pad, allowed, cls=cls, forced=forced)
+
+    replays = capture_steps(prime, [step], 2) if graph else [step]     # two warm-up steps, as KVDecoder.capture
     start()
     if num:
         kv.advance(kv.prop_input(prop.to(dev).float()))                # position 0 is the property prompt, CP:404-412
-    steps = 0
-    while steps < max_length - 1:
-        replay()
-        steps += 1
-        if steps % LIVE_POLL == 0 and int(state["live"].item()) == 0:  # one 4-byte copy: every row has drawn its '$'
-            break
+    # one 4-byte copy per poll: zero when every row has drawn its '$'
+    steps = _decode(replays, max_length - 1, lambda: int(state["live"].item()))
     if trace is not None:
         trace.update(lengths=state["length"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"], uniforms=uniforms,
                      path="k17" if kv.fused else "library", steps=steps)
@@ -298,24 +287,13 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     dead slots) and `steps`.  A list handed in as `trace["gumbel_history"]` receives a copy of G [rows] after every step:
     G[k - 1] - G[k] of a run with one slot more bounds the margin by which the k-slot run's selections were decided.  ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
     length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory."""
-    dev = torch.device(device)
-    if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
-        raise RuntimeError("sample_distinct runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
-    if num_samples < 1 or batch_size < 1 or max_length < 2:
-        raise ValueError(f"sample_distinct: num_samples >= 1, batch_size >= 1, max_length >= 2 (got {num_samples}, {batch_size}, "
-                         f"{max_length})")
+    dev, tf, voc, (sos, eos, pad), rows, num, positions, free, cls, allowed = _prologue(
+        "sample_distinct", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
+    k, V = num_samples, len(voc)
     if not temperature > 0:
         raise ValueError(f"sample_distinct: temperature > 0 (got {temperature}): the perturbation needs a proper distribution")
     if num_samples > SWOR_MAX_K:
         raise ValueError(f"sample_distinct: at most {SWOR_MAX_K} samples per pocket (got {num_samples})")
-    cls = smiles.check_arguments(grammar, smiVoc, max_length, suppress)
-    tf = model.model
-    voc = list(smiVoc)
-    V = len(voc)
-    sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
-    k, rows = num_samples, batch_size * num_samples
-    num = 1 if tf.decoder.num_props else 0
-    positions = max_length - 1 + num
     a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
     atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
     if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
@@ -328,22 +306,13 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     if streams.shape != (batch_size,) or (streams < 0).any() or (streams >= 2 ** 32).any():
         raise ValueError(f"sample_distinct: streams holds one 32-bit integer per pocket, got shape {streams.shape}")
     need = 2 * cache_bytes(tf.decoder, rows, positions) + 3 * rows * V * 4 + 2 * rows * max_length * 12
-    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
     if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
         raise ValueError(f"sample_distinct: the two key / value cache buffers of {rows} rows x {positions} positions and the "
                          f"candidates take {need} bytes, {free} bytes are free on {dev}: draw fewer samples per call")
     streams = torch.as_tensor(streams.astype(np.uint32).view(np.int32)).to(dev)
 
-    enc_outputs, enc_pad_mask, _ = tf.encoder(example.protein_atom_feature.float(), example.protein_pos,
-                                              example.protein_element_batch, example.protein_atom_laplacian, batch_size,
-                                              getattr(example, "protein_knn", None))
-    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, k, positions, V, True, search_buffers=False)
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
     bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
-    allowed = None
-    if suppress:
-        allowed = torch.ones(V, dtype=torch.uint8)
-        allowed[[voc.index(x) for x in suppress]] = 0
-        allowed = allowed.to(dev)
     f32 = dict(dtype=torch.float32, device=dev)
     state = {"gumbel": torch.empty(rows, **f32), "prop_logp": torch.empty(rows, **f32), "sum_logp": torch.empty(rows, **f32),
              "hash": torch.empty(rows, dtype=torch.int64, device=dev), "finished": torch.empty(rows, dtype=torch.uint8, device=dev),
@@ -375,42 +344,23 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         (ck, cv), (ok, ov) = bufs[parity], bufs[1 - parity]
         out = kv.advance(kv.token_input(state["next"]), ck, cv)
         ops.swor_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, streams, float(temperature), int(seed), pad,
-                        allowed, cls if grammar is not None else None)
-        ops.swor_select(kv.pos, num + 1, state, k, work, eos, pad, cls if grammar is not None else None)
+                        allowed, cls)
+        ops.swor_select(kv.pos, num + 1, state, k, work, eos, pad, cls)
         ops.swor_follow(ck, cv, ok, ov, state["src"], state["gumbel"], state["finished"], kv.pos)
 
-    replay = (lambda: step(0), lambda: step(1))
+    def prime():
+        start()
+        kv.pos += num
+
+    replays = [lambda: step(0), lambda: step(1)]                       # the step on each pair of cache buffers, taken in turn
     if graph:
-        # as in `sample`: warm up on a side stream, then capture - here twice, the step on each pair of cache buffers
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            start()
-            kv.pos += num
-            step(0), step(1)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graphs = []
-        for parity in (0, 1):
-            start()
-            kv.pos += num
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                step(parity)
-            graphs.append(g)
-        replay = (graphs[0].replay, graphs[1].replay)
+        replays = capture_steps(prime, replays, 1)
     start()
     if num:
         kv.advance(kv.prop_input(prop.to(dev).float()))                # position 0 is the property prompt, in the first buffer
-    steps = 0
     history = trace.get("gumbel_history") if trace is not None else None
-    while steps < max_length - 1:
-        replay[steps % 2]()
-        steps += 1
-        if history is not None:
-            history.append(state["gumbel"].clone())
-        if steps % LIVE_POLL == 0 and int(state["live"].sum().item()) == 0:
-            break
+    steps = _decode(replays, max_length - 1, lambda: int(state["live"].sum().item()),
+                    (lambda: history.append(state["gumbel"].clone())) if history is not None else None)
     if trace is not None:
         trace.update(gumbel=state["gumbel"], prop_logp=state["prop_logp"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"],
                      lengths=state["length"], valid=(state["gumbel"] > float("-inf")).to(torch.uint8), steps=steps)

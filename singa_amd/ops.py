@@ -810,21 +810,30 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams):
     return out
 
 
-def _sample_token_views(what, logits, uniforms, pos, state, allowed, extra=()):
-    """The argument checks `sample_token` and `sample_token_grammar` share; `extra`: further (tensor, dtype, shape) triples."""
-    _dev(logits, uniforms, state["sum_logp"], state["length"], state["live"], state.get("tok_logp"))
-    R, V = logits.shape
-    tokens, nxt, fin = state["tokens"], state["next"], state["finished"]
-    T = tokens.shape[1]
-    for t, dt, shape in ((tokens, torch.int64, (R, T)), (nxt, torch.int64, (R,)), (fin, torch.uint8, (R,)),
-                         (state["length"], torch.int32, (R,)), (state["sum_logp"], torch.float32, (R,)),
-                         (state["live"], torch.int32, (1,)), (pos, torch.int64, None), (allowed, torch.uint8, (V,)),
-                         (state.get("tok_logp"), torch.float32, (R, T))) + tuple(extra):
+def _check_views(what, items):
+    """Every (tensor, dtype, shape) triple of `items` whose tensor is given: a contiguous GPU tensor of that dtype and, unless
+    the shape is None, that shape."""
+    for t, dt, shape in items:
         if t is None:
             continue
         if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
             raise RuntimeError(f"{what}: expected a contiguous {dt} GPU tensor of shape {shape}, got {t.dtype} "
                                f"{tuple(t.shape)} on {t.device}")
+
+
+def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, gstate=None, alp=None, forced=None, rank=None):
+    """The argument checks of the token-choice ops; gstate, alp / rank: the state's grammar, allowed_logp / rank where `cls` /
+    `forced` is given."""
+    _dev(logits, uniforms, state["sum_logp"], state["length"], state["live"], state.get("tok_logp"))
+    R, V = logits.shape
+    tokens, nxt, fin = state["tokens"], state["next"], state["finished"]
+    T = tokens.shape[1]
+    _check_views(what, ((tokens, torch.int64, (R, T)), (nxt, torch.int64, (R,)), (fin, torch.uint8, (R,)),
+                        (state["length"], torch.int32, (R,)), (state["sum_logp"], torch.float32, (R,)),
+                        (state["live"], torch.int32, (1,)), (pos, torch.int64, None), (allowed, torch.uint8, (V,)),
+                        (state.get("tok_logp"), torch.float32, (R, T)), (forced, torch.int64, (R, T)),
+                        (rank, torch.int32, (R, T)), (cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)),
+                        (alp, torch.float32, (R, T))))
     if not (logits.is_contiguous() and uniforms.is_contiguous() and uniforms.dim() == 2 and uniforms.shape[1] == R
             and uniforms.shape[0] >= T - 1):
         raise RuntimeError(f"{what}: logits [R, V] and uniforms [>= T - 1, R] must be contiguous, got "
@@ -832,17 +841,31 @@ def _sample_token_views(what, logits, uniforms, pos, state, allowed, extra=()):
     return R, V, T
 
 
-def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0, allowed=None):
+def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0, allowed=None,
+                 cls=None, forced=None):
     """The next token of every row, drawn on the device (`singa_sample_token`, include/singa_hip.h states the rule; inference
     only, no autograd): one launch.  logits [R, V] f32 (raw projection outputs), uniforms [>= T - 1, R] f32 in [0, 1), pos: int64
     device scalar, the step is pos - pos_offset.  `state`: dict of the rows' device state, updated in place - tokens [R, T] int64,
     next [R] int64, finished [R] uint8, length [R] int32, sum_logp [R] f32, live [1] int32 and, optionally, tok_logp [R, T] f32.
-    allowed: [V] uint8, 0 = never drawn."""
-    R, V, T = _sample_token_views("sample_token", logits, uniforms, pos, state, allowed)
-    _chk(_lib.lib().singa_sample_token(_p(logits), _p(uniforms), _p(allowed), _p(pos), pos_offset, R, V, T, temperature, top_k, top_p,
-                                       eos, pad, _p(state["finished"]), _p(state["length"]), _p(state["sum_logp"]),
-                                       _p(state["tokens"]), _p(state["next"]), _p(state["live"]), _p(state.get("tok_logp")),
-                                       _stream()), "singa_sample_token")
+    allowed: [V] uint8, 0 = never drawn.  `cls` / `forced`: the op is `sample_token_grammar` / `sample_token_forced`, which
+    describe them; this is where all three assemble their arguments."""
+    entry = "sample_token_forced" if forced is not None else "sample_token_grammar" if cls is not None else "sample_token"
+    rank = state.get("rank") if forced is not None else None
+    gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
+    for t in (rank, gstate, alp):
+        if t is not None:
+            _dev(t)
+    R, V, T = _sample_token_views(entry, logits, uniforms, pos, state, allowed, cls, gstate, alp, forced, rank)
+    lib, head = _lib.lib(), (_p(logits), _p(uniforms), _p(allowed))
+    rest = (_p(pos), pos_offset, R, V, T, temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
+            _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]), _p(state.get("tok_logp")))
+    if forced is not None:
+        code = lib.singa_sample_token_forced(*head, _p(cls), *rest, _p(gstate), _p(alp), _p(forced), _p(rank), _stream())
+    elif cls is not None:
+        code = lib.singa_sample_token_grammar(*head, _p(cls), *rest, _p(gstate), _p(alp), _stream())
+    else:
+        code = lib.singa_sample_token(*head, *rest, _stream())
+    _chk(code, "singa_" + entry)
 
 
 def sample_token_grammar(logits, uniforms, pos, pos_offset, state, cls, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0,
@@ -851,16 +874,7 @@ def sample_token_grammar(logits, uniforms, pos, pos_offset, state, cls, temperat
     what the rule lets follow the row's state.  cls: [V] uint8 class bytes (`singa_amd.smiles.classify`); `state` as for
     `sample_token`, plus grammar [R] int32 (the rows' packed rule state, `smiles.FRESH` for a fresh row; updated in place) and,
     optionally, allowed_logp [R, T] f32 (log of the model's probability mass on the effective mask)."""
-    _dev(state["grammar"], state.get("allowed_logp"))
-    (R, V), T = logits.shape, state["tokens"].shape[1]
-    _sample_token_views("sample_token_grammar", logits, uniforms, pos, state, allowed,
-                                  ((cls, torch.uint8, (V,)), (state["grammar"], torch.int32, (R,)),
-                                   (state.get("allowed_logp"), torch.float32, (R, T))))
-    _chk(_lib.lib().singa_sample_token_grammar(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), pos_offset, R, V, T,
-                                               temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
-                                               _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]),
-                                               _p(state.get("tok_logp")), _p(state["grammar"]), _p(state.get("allowed_logp")),
-                                               _stream()), "singa_sample_token_grammar")
+    sample_token(logits, uniforms, pos, pos_offset, state, temperature, top_k, top_p, eos, pad, allowed, cls=cls)
 
 
 def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=None, temperature=1.0, top_k=0, top_p=1.0, eos=0,
@@ -870,21 +884,7 @@ def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=No
     step t a row whose forced[row, t + 1] lies in [0, V) takes that token with the bookkeeping of a drawn one, any other row
     chooses as the unforced op does, bit for bit.  `state` as for those ops (grammar [R] int32 and, optionally, allowed_logp
     under the grammar) and, optionally, rank [R, T] int32: the rank of every emitted token among the row's raw logits."""
-    if state.get("rank") is not None:
-        _dev(state["rank"])
-    (R, V), T = logits.shape, state["tokens"].shape[1]
-    extra = ((forced, torch.int64, (R, T)), (state.get("rank"), torch.int32, (R, T)))
-    gstate = alp = None
-    if cls is not None:
-        gstate, alp = state["grammar"], state.get("allowed_logp")
-        _dev(gstate, alp)
-        extra += ((cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)), (alp, torch.float32, (R, T)))
-    _sample_token_views("sample_token_forced", logits, uniforms, pos, state, allowed, extra)
-    _chk(_lib.lib().singa_sample_token_forced(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), pos_offset, R, V, T,
-                                              temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
-                                              _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]),
-                                              _p(state.get("tok_logp")), _p(gstate), _p(alp), _p(forced), _p(state.get("rank")),
-                                              _stream()), "singa_sample_token_forced")
+    sample_token(logits, uniforms, pos, pos_offset, state, temperature, top_k, top_p, eos, pad, allowed, cls=cls, forced=forced)
 
 
 def swor_work(rows, T, device):
@@ -903,12 +903,7 @@ def _swor_views(what, state, R, V, T, names, cls=None, allowed=None, extra=()):
             "next": (torch.int64, (R,)), "src": (torch.int64, (R,)), "cand": (torch.float32, (R, V)),
             "cand_logp": (torch.float32, (R, V)), "cand_phi": (torch.float32, (R, V))}
     items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (allowed, torch.uint8, (V,))] + list(extra)
-    for t, dt, shape in items:
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
-            raise RuntimeError(f"{what}: expected a contiguous {dt} GPU tensor of shape {shape}, got {t.dtype} "
-                               f"{tuple(t.shape)} on {t.device}")
+    _check_views(what, items)
     _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
 
 

@@ -40,6 +40,152 @@ def test_sample_token_argument_errors_without_gpu(lib):
     assert lib.singa_sample_token(p, p, None, p, 2, 0, 1024, 8, 0.0, 7, 1e-6, 3, 4, p, p, p, p, p, p, p, None) == 0
 
 
+NAN = float("nan")
+# (entry point, the arguments that differ from a valid call, return code, text of singa_last_error_string() behind "<entry>: "),
+# recorded from the library as it was when each entry point carried its own checks: one bad argument at a time, then pairs,
+# which pin the order of the checks.  Pointers: True = some address, None = null, "misaligned" = that address + 4.
+BAD_ARGUMENTS = [
+    ("sample_token", dict(logits=None), -1, "null pointer"),
+    ("sample_token", dict(live=None), -1, "null pointer"),
+    ("sample_token", dict(V=0), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token", dict(V=1025), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token", dict(tau=-0.5), -3, "temperature must be >= 0"),
+    ("sample_token", dict(tau=NAN), -3, "temperature must be >= 0"),
+    ("sample_token", dict(top_k=-1), -3, "top_k must be >= 0 (0 = off)"),
+    ("sample_token", dict(top_p=0.0), -3, "top_p must be in (0, 1]"),
+    ("sample_token", dict(top_p=1.5), -3, "top_p must be in (0, 1]"),
+    ("sample_token", dict(top_p=NAN), -3, "top_p must be in (0, 1]"),
+    ("sample_token", dict(T=1), -3, "T >= 2 columns, eos / pad inside the vocabulary"),
+    ("sample_token", dict(eos=116), -3, "T >= 2 columns, eos / pad inside the vocabulary"),
+    ("sample_token", dict(eos=-1), -3, "T >= 2 columns, eos / pad inside the vocabulary"),
+    ("sample_token", dict(pad=116), -3, "T >= 2 columns, eos / pad inside the vocabulary"),
+    ("sample_token", dict(pad=-1), -3, "T >= 2 columns, eos / pad inside the vocabulary"),
+    ("sample_token_grammar", dict(logits=None), -1, "null pointer"),
+    ("sample_token_grammar", dict(live=None), -1, "null pointer"),
+    ("sample_token_grammar", dict(cls=None), -1, "null pointer"),
+    ("sample_token_grammar", dict(gstate=None), -1, "null pointer"),
+    ("sample_token_grammar", dict(V=0), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token_grammar", dict(V=1025), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token_grammar", dict(tau=-0.5), -3, "temperature must be >= 0"),
+    ("sample_token_grammar", dict(tau=NAN), -3, "temperature must be >= 0"),
+    ("sample_token_grammar", dict(top_k=-1), -3, "top_k must be >= 0 (0 = off)"),
+    ("sample_token_grammar", dict(top_p=0.0), -3, "top_p must be in (0, 1]"),
+    ("sample_token_grammar", dict(top_p=1.5), -3, "top_p must be in (0, 1]"),
+    ("sample_token_grammar", dict(top_p=NAN), -3, "top_p must be in (0, 1]"),
+    ("sample_token_grammar", dict(T=2), -3, "T >= 3 columns, eos / pad inside the vocabulary"),
+    ("sample_token_grammar", dict(eos=116), -3, "T >= 3 columns, eos / pad inside the vocabulary"),
+    ("sample_token_grammar", dict(eos=-1), -3, "T >= 3 columns, eos / pad inside the vocabulary"),
+    ("sample_token_grammar", dict(pad=116), -3, "T >= 3 columns, eos / pad inside the vocabulary"),
+    ("sample_token_grammar", dict(pad=-1), -3, "T >= 3 columns, eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(logits=None), -1, "null pointer"),
+    ("sample_token_forced", dict(live=None), -1, "null pointer"),
+    ("sample_token_forced", dict(forced=None), -1, "null pointer"),
+    ("sample_token_forced", dict(cls=True), -1, "cls and gstate go together (allowed_logp only with them)"),
+    ("sample_token_forced", dict(gstate=True), -1, "cls and gstate go together (allowed_logp only with them)"),
+    ("sample_token_forced", dict(alp=True), -1, "cls and gstate go together (allowed_logp only with them)"),
+    ("sample_token_forced", dict(V=0), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token_forced", dict(V=1025), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token_forced", dict(tau=-0.5), -3, "temperature must be >= 0"),
+    ("sample_token_forced", dict(tau=NAN), -3, "temperature must be >= 0"),
+    ("sample_token_forced", dict(top_k=-1), -3, "top_k must be >= 0 (0 = off)"),
+    ("sample_token_forced", dict(top_p=0.0), -3, "top_p must be in (0, 1]"),
+    ("sample_token_forced", dict(top_p=1.5), -3, "top_p must be in (0, 1]"),
+    ("sample_token_forced", dict(top_p=NAN), -3, "top_p must be in (0, 1]"),
+    ("sample_token_forced", dict(T=1), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(eos=116), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(eos=-1), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(pad=116), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(pad=-1), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("sample_token_forced", dict(T=2, cls=True, gstate=True), -3, "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary"),
+    ("swor_expand", dict(cand=None), -1, "null pointer"),
+    ("swor_expand", dict(cls=True), -1, "cls and gstate go together"),
+    ("swor_expand", dict(gstate=True), -1, "cls and gstate go together"),
+    ("swor_expand", dict(V=0), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_expand", dict(V=1025), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_expand", dict(k=0), -3, "1..2048 slots per pocket"),
+    ("swor_expand", dict(k=2049, rows=2049), -3, "1..2048 slots per pocket"),
+    ("swor_expand", dict(rows=5), -3, "rows must be pockets x slots"),
+    ("swor_expand", dict(T=1), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_expand", dict(T=2, cls=True, gstate=True), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_expand", dict(pad=116), -3, "eos / pad inside the vocabulary"),
+    ("swor_expand", dict(pad=-1), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(cand=None), -1, "null pointer"),
+    ("swor_select", dict(cls=True), -1, "cls and gstate go together"),
+    ("swor_select", dict(gstate=True), -1, "cls and gstate go together"),
+    ("swor_select", dict(V=0), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_select", dict(V=1025), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_select", dict(k=0), -3, "1..2048 slots per pocket"),
+    ("swor_select", dict(k=2049, rows=2049), -3, "1..2048 slots per pocket"),
+    ("swor_select", dict(rows=5), -3, "rows must be pockets x slots"),
+    ("swor_select", dict(T=1), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_select", dict(T=2, cls=True, gstate=True), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_select", dict(pad=116), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(pad=-1), -3, "eos / pad inside the vocabulary"),
+    ("swor_expand", dict(logits=None), -1, "null pointer"),
+    ("swor_expand", dict(streams=None), -1, "null pointer"),
+    ("swor_expand", dict(tau=0.0), -3, "temperature must be > 0"),
+    ("swor_expand", dict(tau=-1.0), -3, "temperature must be > 0"),
+    ("swor_expand", dict(tau=NAN), -3, "temperature must be > 0"),
+    ("swor_select", dict(work=None), -1, "null pointer"),
+    ("swor_select", dict(live=None), -1, "null pointer"),
+    ("swor_select", dict(eos=116), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(eos=-1), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(work="misaligned"), -3, "work must be 16-byte aligned"),
+    ("sample_token", dict(logits=None, V=0), -1, "null pointer"),
+    ("sample_token", dict(V=0, tau=-1.0), -3, "vocabulary of 1..1024 tokens"),
+    ("sample_token", dict(tau=NAN, top_k=-1), -3, "temperature must be >= 0"),
+    ("sample_token", dict(top_k=-1, top_p=0.0), -3, "top_k must be >= 0 (0 = off)"),
+    ("sample_token", dict(top_p=1.5, T=1), -3, "top_p must be in (0, 1]"),
+    ("sample_token_grammar", dict(cls=None, V=1025), -1, "null pointer"),
+    ("sample_token_grammar", dict(top_p=1.5, T=2), -3, "top_p must be in (0, 1]"),
+    ("sample_token_forced", dict(forced=None, cls=True), -1, "null pointer"),
+    ("sample_token_forced", dict(cls=True, V=0), -1, "cls and gstate go together (allowed_logp only with them)"),
+    ("sample_token_forced", dict(V=0, T=1), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_expand", dict(logits=None, cls=True), -1, "null pointer"),
+    ("swor_expand", dict(cls=True, V=0), -1, "cls and gstate go together"),
+    ("swor_expand", dict(V=0, k=0), -3, "vocabulary of 1..1024 tokens"),
+    ("swor_expand", dict(k=0, rows=5), -3, "1..2048 slots per pocket"),
+    ("swor_expand", dict(rows=5, T=1), -3, "rows must be pockets x slots"),
+    ("swor_expand", dict(T=1, pad=-1), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_expand", dict(pad=-1, tau=0.0), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(cand=None, gstate=True), -1, "null pointer"),
+    ("swor_select", dict(gstate=True, k=0), -1, "cls and gstate go together"),
+    ("swor_select", dict(T=1, eos=-1), -3, "T >= 2 columns (3 under the grammar)"),
+    ("swor_select", dict(eos=-1, work="misaligned"), -3, "eos / pad inside the vocabulary"),
+    ("swor_select", dict(V=1025, work="misaligned"), -3, "vocabulary of 1..1024 tokens"),
+]
+
+
+@pytest.mark.parametrize("entry,bad,code,text", BAD_ARGUMENTS, ids=[f"{e}-{i}" for i, (e, *_) in enumerate(BAD_ARGUMENTS)])
+def test_generation_entry_points_report_bad_arguments_as_recorded(lib, entry, bad, code, text):
+    """The five entry points that validate a token choice or a selection step - `singa_sample_token`, `_grammar`, `_forced`,
+    `singa_swor_expand`, `singa_swor_select` - return the same code and leave the same text, byte for byte, for every tuple of
+    the table.  No pointer is dereferenced: every call fails its checks."""
+    buf = (ctypes.c_char * 80)()
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) // 16 * 16)
+    a = dict(V=116, tau=1.0, top_k=0, top_p=1.0, T=8, eos=3, pad=4, rows=4, k=2, logits=True, live=True, cand=True, streams=True,
+             work=True, cls=entry == "sample_token_grammar", gstate=entry == "sample_token_grammar", alp=None, forced=True, rank=None)
+    a.update(bad)
+    q = {n: p if a[n] is True else ctypes.c_void_p(p.value + 4) if a[n] == "misaligned" else None
+         for n in ("logits", "live", "cand", "streams", "work", "cls", "gstate", "alp", "forced", "rank")}
+    choice = (a["rows"], a["V"], a["T"], a["tau"], a["top_k"], a["top_p"], a["eos"], a["pad"], p, p, p, p, p, q["live"], None)
+    if entry == "sample_token":
+        got = lib.singa_sample_token(q["logits"], p, None, p, 2, *choice, None)
+    elif entry == "sample_token_grammar":
+        got = lib.singa_sample_token_grammar(q["logits"], p, None, q["cls"], p, 2, *choice, q["gstate"], q["alp"], None)
+    elif entry == "sample_token_forced":
+        got = lib.singa_sample_token_forced(q["logits"], p, None, q["cls"], p, 2, *choice, q["gstate"], q["alp"], q["forced"],
+                                            q["rank"], None)
+    elif entry == "swor_expand":
+        got = lib.singa_swor_expand(q["logits"], None, q["cls"], p, 1, a["rows"], a["k"], a["V"], a["T"], a["tau"], 7, q["streams"],
+                                    a["pad"], p, p, p, p, q["gstate"], q["cand"], p, p, None)
+    else:
+        assert entry == "swor_select"
+        got = lib.singa_swor_select(q["cand"], p, p, q["cls"], p, 1, a["rows"], a["k"], a["V"], a["T"], a["eos"], a["pad"], p, p, p, p,
+                                    p, p, q["gstate"], p, p, p, p, q["live"], q["work"], None)
+    assert (got, lib.singa_last_error_string()) == (code, f"{entry}: {text}".encode())
+
+
 def test_restatement_matches_brute_force_on_tiny_vocabularies():
     rs = np.random.RandomState(0)
     n = 0

@@ -56,7 +56,7 @@ def main():
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
-    from singa_amd.model.Sampling import FUSED_MAX_ROWS, sample, sample_distinct, score
+    from singa_amd.model.Sampling import sample, sample_distinct, score
     dev = torch.device("cuda", 0)
     cfg = load_config(lmax=2)
     torch.manual_seed(cfg.train.seed)
@@ -129,7 +129,7 @@ def main():
                          "sample_runs_ms": [round(x, 4) for x in samp_ms], "beam_runs_ms": [round(x, 4) for x in beam_ms]}
     res["config"] = {"workload": "gen.py: 1 pocket (200 atoms), property prompt", "max_length": T, "temperature": args.temperature,
                      "top_k": args.top_k, "top_p": args.top_p, "launch": "hipGraph replay per step",
-                     "fused_none_picks": "k17 at every row count" if FUSED_MAX_ROWS is None else f"k17 up to {FUSED_MAX_ROWS} rows, library above"}
+                     "fused_none_picks": "k17 at every row count"}
     if args.table:
         table = []
         for rows in (20, 128, 512, 2048):
