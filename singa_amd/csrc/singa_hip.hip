@@ -4368,14 +4368,170 @@ struct GemmBatch {
 // Epilogue: an accumulator holds 4 consecutive ROWS of one column per register quad, so a direct store is 64 dword stores
 // per lane; instead each wavefront passes its 32-row blocks through LDS (the K-loop buffers are free by then) and writes
 // float4 rows - 4x fewer store instructions, full 256-byte row segments.
-#ifndef SINGA_GEMM_PIPE
+#ifndef SINGA_GEMM_PIPE      // 0: the 128 x 128 tile takes the three fenced phases instead of the interleaved issue order
 #define SINGA_GEMM_PIPE 1
 #endif
-#if SINGA_GEMM_PIPE   // the 128 x 128 tile takes the interleaved issue order (`pipeline` below) instead of the three fenced phases
-#define SINGA_GEMM_FENCE() do { if constexpr (CFG != 0 || !decltype(all_c)::value) __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define SINGA_GEMM_FENCE() __builtin_amdgcn_sched_barrier(0)
+#ifndef SINGA_CGEMM_PIPE     // the same switch for k7c
+#define SINGA_CGEMM_PIPE 1
 #endif
+
+// ---- the pieces k7 and k7c share: the tile walk, the reduction-contiguous loads, the fragment reads and the K loop
+
+// The workgroup's tile.  XCD-aware numbering: block b runs on XCD b % 8; every XCD gets a contiguous range of tile ids.
+// Tiles are ordered row tile by row tile, and inside a row tile problem by problem: every XCD's contiguous range then
+// holds the same mix of problems (their reduction lengths differ: problem-by-problem ranges left some XCDs with only the
+// long ones and the launch waited for them).  That is the interleaved order, for problems with equal row counts only;
+// otherwise problem after problem (tj_total = 0).
+struct GemmTile {
+    int split, pi, i0, j0;                     // reduction split, problem, first row and column of the tile
+    long long r_begin, r_end;                  // the split's reduction rows
+};
+template <int BM, int BN, int MAXP, class Batch>
+__device__ __forceinline__ bool gemm_tile_walk(const Batch& gb, GemmTile& T) {
+    const int nblk = gb.tiles_total * gb.splits;
+    const int per = (nblk + 7) >> 3;
+    const int id = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (id >= nblk) return false;
+    const int split = id / gb.tiles_total;
+    const int tile = id - split * gb.tiles_total;
+    const int ti = gb.tj_total ? tile / gb.tj_total : 0, trem = gb.tj_total ? tile - ti * gb.tj_total : tile;
+    int pi = 0;
+#pragma unroll
+    for (int q = 1; q < MAXP; ++q)
+        if (q < gb.n && trem >= gb.p[q].tile_begin) pi = q;
+    const auto& P = gb.p[pi];
+    const int local = trem - P.tile_begin;
+    T.split = split;
+    T.pi = pi;
+    T.i0 = (gb.tj_total ? ti : local / P.tiles_j) * BM;
+    T.j0 = (gb.tj_total ? local : local % P.tiles_j) * BN;
+    T.r_begin = (long long)split * gb.r_chunk;
+    T.r_end = (T.r_begin + gb.r_chunk < P.R) ? T.r_begin + gb.r_chunk : P.R;
+    return true;
+}
+
+// Loads of a reduction-contiguous operand: float4 kq of the thread's n rows (nullptr = outside the matrix) at reduction index
+// r0.  all_c: the tile lies inside the matrices and every K step is complete - loads without predicates (8 exec-mask
+// round trips per step less, and the compiler batches them).
+// Ragged tiles / K steps and grouped rows: every load is still issued unconditionally - from a clamped, valid address -
+// and a per-register-set bit mask says which registers hold data; the zeros are selected when the registers are
+// written to LDS.  (Predicated loads put branches into the K loop, and the compiler then waits for ALL outstanding
+// loads - vmcnt(0) - before each LDS write: the two-step prefetch collapsed to none, 5.7 us per K step on the
+// grouped-row gradients of SO3_LinearV2.)
+// (kq and the split's bounds come by reference, as a lambda inside the kernel would capture them: taken by value the same
+// predicates compile to ~1 % more instructions in the reduction-contiguous kernels.)
+template <class AllC>
+__device__ __forceinline__ void gemm_load_rc(AllC, float4* reg, unsigned& mask, const float* const* rows, const float* dummy, int n,
+                                             const int& kq, long long r0, const long long& r_begin, const long long& r_end) {
+    if constexpr (AllC::value) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) reg[j] = *reinterpret_cast<const float4*>(rows[j] + r0);
+        mask = ~0u;
+    } else {
+        const bool in = r0 + 4 * kq < r_end;
+        mask = 0;
+#pragma unroll
+        for (int j = 0; j < n; ++j) {
+            const bool ok = in && rows[j] != nullptr;
+            const float* src = ok ? rows[j] + r0 : dummy + r_begin;      // dummy: the first row of the matrix
+            reg[j] = *reinterpret_cast<const float4*>(src);
+            mask |= (ok ? 1u : 0u) << j;
+        }
+    }
+}
+
+// Fragments of k-group t (8 reduction indices = 4 MFMA k-steps) of the 32-wide block whose lane-l31 row / column is `col`:
+// one ds_read_b128 from a reduction-contiguous image (pitch PR), four ds_read_b32 from an output-contiguous one.
+template <int PR>
+__device__ __forceinline__ void gemm_frag(const float* S, bool rc, int pitch, int col, int t, int half, float (&f)[4]) {
+    if (rc) {
+        const float4 v = *reinterpret_cast<const float4*>(S + col * PR + 8 * t + 4 * half);
+        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) f[q] = S[(8 * t + q + 4 * half) * pitch + col];
+    }
+}
+
+// The K loop.  Two LDS buffers and two register sets: the loads of K step s+2 are issued at the start of step s and written
+// to LDS at the end of step s+1, so every load has two steps (~8,000 MFMA cycles) to arrive - one step did not cover an HBM
+// miss under load.  Step st computes LDS buffer st & 1; register set (st + 1) & 1 holds step st + 1 (written to LDS at the end
+// of this step), the other set receives step st + 2.  The steady-state loop has NO branch around its loads and the scheduler
+// may not move anything across the marks: only then does the compiler wait with a COUNT (the older set's loads) before
+// the LDS writes instead of vmcnt(0), i.e. only then are two steps of loads really in flight.  (With `if (st + 2 <
+// nsteps) load` inside one loop it issued vmcnt(0) at every join and hoisted the LDS writes above the new loads.)
+// INTERLEAVED (full tiles only): no marks; the kernel's `pipeline` says where the step's global loads, LDS fragment reads and
+// LDS writes go BETWEEN the MFMAs instead of standing in front of and behind them.  An MFMA occupies the matrix core for 64
+// cycles while the wavefront goes on issuing: with the three phases fenced off (load | MFMAs | store) a wavefront issued no
+// MFMA during ~15 % of a step and the pipe only stayed busy when the CU's second workgroup happened to be in its MFMA phase
+// (MFMA-busy 0.75).
+// The kernel supplies load_ab(all_c, set, r0), store_ab(set, buf), compute(all_c, buf, nt8) and pipeline(); nt8 = the
+// k-groups of 8 reduction indices to compute: BK / 8, and last8 in the last step.
+template <int NA, int NB>
+struct GemmRegs {
+    float4 a[NA], b[NB];
+    unsigned ma = 0, mb = 0;                   // bit j: a[j] / b[j] holds data
+};
+template <int BK, int NA, int NB, bool INTERLEAVED, class AllC, class LoadAB, class StoreAB, class Compute, class Pipeline>
+__device__ __forceinline__ void gemm_k_loop(AllC all_c, long long r_begin, long long nsteps, int last8, LoadAB&& load_ab,
+                                            StoreAB&& store_ab, Compute&& compute, Pipeline&& pipeline) {
+    constexpr bool FENCED = !(INTERLEAVED && AllC::value);
+    GemmRegs<NA, NB> s0, s1;
+    if (nsteps > 0) {
+        load_ab(all_c, s0, r_begin);
+        if (nsteps > 1) load_ab(all_c, s1, r_begin + BK);
+        store_ab(s0, 0);
+    }
+    __syncthreads();
+    long long st = 0;
+#if !defined(SINGA_GEMM_LAB_NOLOAD) && !defined(SINGA_GEMM_LAB_NOSYNC)
+    // all prologue loads land before the loop: otherwise the compiler's wait insertion merges "a prologue load into
+    // register X may be pending" into the loop header and waits for vmcnt(0) there on EVERY iteration
+    if (nsteps > 3) __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0) only
+    for (; st + 3 < nsteps; st += 2) {
+        load_ab(all_c, s0, r_begin + (st + 2) * BK);
+        if constexpr (FENCED) __builtin_amdgcn_sched_barrier(0);
+        compute(all_c, 0, BK / 8);
+        if constexpr (FENCED) __builtin_amdgcn_sched_barrier(0);
+        store_ab(s1, 1);
+        if constexpr (!FENCED) pipeline();
+        __syncthreads();
+        load_ab(all_c, s1, r_begin + (st + 3) * BK);
+        if constexpr (FENCED) __builtin_amdgcn_sched_barrier(0);
+        compute(all_c, 1, BK / 8);
+        if constexpr (FENCED) __builtin_amdgcn_sched_barrier(0);
+        store_ab(s0, 0);
+        if constexpr (!FENCED) pipeline();
+        __syncthreads();
+    }
+#endif
+    for (; st < nsteps; st += 2) {         // the last (up to three) steps, and the tools/lab variants
+#if defined(SINGA_GEMM_LAB_NOLOAD) || defined(SINGA_GEMM_LAB_NOSYNC)   // tools/lab only: which part of a step costs what
+        compute(all_c, 0, BK / 8);
+#ifndef SINGA_GEMM_LAB_NOSYNC
+        if (st + 1 < nsteps) store_ab(s1, 1);
+        __syncthreads();
+#endif
+        if (st + 1 >= nsteps) break;
+        compute(all_c, 1, BK / 8);
+#ifndef SINGA_GEMM_LAB_NOSYNC
+        if (st + 2 < nsteps) store_ab(s0, 0);
+        __syncthreads();
+#endif
+#else
+        if (st + 2 < nsteps) load_ab(all_c, s0, r_begin + (st + 2) * BK);
+        compute(all_c, 0, st + 1 == nsteps ? last8 : BK / 8);
+        if (st + 1 < nsteps) store_ab(s1, 1);
+        __syncthreads();
+        if (st + 1 >= nsteps) break;
+        if (st + 3 < nsteps) load_ab(all_c, s1, r_begin + (st + 3) * BK);
+        compute(all_c, 1, st + 2 == nsteps ? last8 : BK / 8);
+        if (st + 2 < nsteps) store_ab(s0, 0);
+        __syncthreads();
+#endif
+    }
+}
+
 template <bool A_RC, bool B_RC, int CFG>
 __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
     constexpr int BM = CFG == 2 ? 32 : (CFG == 3 ? 64 : 128), BN = CFG == 1 ? 32 : (CFG == 3 ? 64 : 128), BK = 32, PR = BK + 4;
@@ -4388,27 +4544,11 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
     float* const As0 = smem;
     float* const Bs0 = smem + 2 * SZA;
-    // XCD-aware numbering: block b runs on XCD b % 8; give every XCD a contiguous range of tile ids
-    const int nblk = gb.tiles_total * gb.splits;
-    const int per = (nblk + 7) >> 3;
-    const int id = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if (id >= nblk) return;
-    const int split = id / gb.tiles_total;
-    const int tile = id - split * gb.tiles_total;
-    // tiles are ordered row tile by row tile, and inside a row tile problem by problem: every XCD's contiguous range then
-    // holds the same mix of problems (their reduction lengths differ: problem-by-problem ranges left some XCDs with only
-    // the long ones and the launch waited for them)
-    // (problems with equal row counts only; otherwise problem after problem: tj_total = 0)
-    const int ti = gb.tj_total ? tile / gb.tj_total : 0, trem = gb.tj_total ? tile - ti * gb.tj_total : tile;
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < SINGA_GEMM_MAX; ++q)
-        if (q < gb.n && trem >= gb.p[q].tile_begin) pi = q;
-    const GemmProb& P = gb.p[pi];
-    const int local = trem - P.tile_begin;
-    const int i0 = (gb.tj_total ? ti : local / P.tiles_j) * BM, j0 = (gb.tj_total ? local : local % P.tiles_j) * BN;
-    const long long r_begin = (long long)split * gb.r_chunk;
-    const long long r_end = (r_begin + gb.r_chunk < P.R) ? r_begin + gb.r_chunk : P.R;
+    GemmTile T;
+    if (!gemm_tile_walk<BM, BN, SINGA_GEMM_MAX>(gb, T)) return;
+    const GemmProb& P = gb.p[T.pi];
+    const int split = T.split, i0 = T.i0, j0 = T.j0;
+    const long long r_begin = T.r_begin, r_end = T.r_end;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wrow = CFG == 0 ? (wave >> 1) * 64 : (CFG == 1 ? wave * 32 : (CFG == 3 ? (wave >> 1) * 32 : 0));   // the wavefront's block
     const int wcol = CFG == 0 ? (wave & 1) * 64 : (CFG == 1 ? 0 : (CFG == 3 ? (wave & 1) * 32 : wave * 32));
@@ -4434,34 +4574,8 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
             brow[j] = jj < P.J ? P.B + (long long)jj * P.ldb + 4 * kq : nullptr;
         }
     }
-    // two register sets: the loads of K step s+2 are issued at the start of step s and written to LDS at the end of step
-    // s+1, so every load has two steps (~8,000 MFMA cycles) to arrive - one step did not cover an HBM miss under load
-    float4 ra0[NA], rb0[NB], ra1[NA], rb1[NB];
-    // `full`: the tile lies inside the matrices and every K step is complete - loads without predicates (8 exec-mask
-    // round trips per step less, and the compiler batches them)
+    // `full`: the tile lies inside the matrices and every K step is complete
     const bool full = i0 + BM <= P.I && j0 + BN <= P.J && r_end > r_begin && (r_end - r_begin) % BK == 0;
-    // Ragged tiles / K steps and grouped rows: every load is still issued unconditionally - from a clamped, valid address -
-    // and a per-register-set bit mask says which registers hold data; the zeros are selected when the registers are
-    // written to LDS.  (Predicated loads put branches into the K loop, and the compiler then waits for ALL outstanding
-    // loads - vmcnt(0) - before each LDS write: the two-step prefetch collapsed to none, 5.7 us per K step on the
-    // grouped-row gradients of SO3_LinearV2.)
-    auto load_rc = [&](auto all_c, float4* reg, unsigned& mask, const float* const* rows, const float* dummy, int n, long long r0) {
-        if constexpr (decltype(all_c)::value) {
-#pragma unroll
-            for (int j = 0; j < n; ++j) reg[j] = *reinterpret_cast<const float4*>(rows[j] + r0);
-            mask = ~0u;
-        } else {
-            const bool in = r0 + 4 * kq < r_end;
-            mask = 0;
-#pragma unroll
-            for (int j = 0; j < n; ++j) {
-                const bool ok = in && rows[j] != nullptr;
-                const float* src = ok ? rows[j] + r0 : dummy + r_begin;      // dummy: the first row of the matrix
-                reg[j] = *reinterpret_cast<const float4*>(src);
-                mask |= (ok ? 1u : 0u) << j;
-            }
-        }
-    };
     auto load_oc = [&](auto all_c, float4* reg, unsigned& mask, const float* base, long long ld, int grp, long long gld, int o0,
                        int lim, int n, int width4, long long r0) {
         const int c4 = tid % width4, rq = tid / width4, rows = 256 / width4;
@@ -4498,11 +4612,11 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
         for (int j = 0; j < n; ++j)
             *reinterpret_cast<float4*>(S + (rq + rows * j) * pitch + 4 * c4) = (mask >> j) & 1u ? reg[j] : make_float4(0.f, 0.f, 0.f, 0.f);
     };
-    auto load_ab = [&](auto all_c, float4* ra, float4* rb, unsigned& ma, unsigned& mb, long long r0) __attribute__((always_inline)) {
-        if (A_RC) load_rc(all_c, ra, ma, arow, P.A, NA, r0);
-        else load_oc(all_c, ra, ma, P.A, P.lda, P.a_group, P.a_gld, i0, P.I, NA, BM / 4, r0);
-        if (B_RC) load_rc(all_c, rb, mb, brow, P.B, NB, r0);
-        else load_oc(all_c, rb, mb, P.B, P.ldb, P.b_group, P.b_gld, j0, P.J, NB, BN / 4, r0);
+    auto load_ab = [&](auto all_c, GemmRegs<NA, NB>& s, long long r0) __attribute__((always_inline)) {
+        if (A_RC) gemm_load_rc(all_c, s.a, s.ma, arow, P.A, NA, kq, r0, r_begin, r_end);
+        else load_oc(all_c, s.a, s.ma, P.A, P.lda, P.a_group, P.a_gld, i0, P.I, NA, BM / 4, r0);
+        if (B_RC) gemm_load_rc(all_c, s.b, s.mb, brow, P.B, NB, kq, r0, r_begin, r_end);
+        else load_oc(all_c, s.b, s.mb, P.B, P.ldb, P.b_group, P.b_gld, j0, P.J, NB, BN / 4, r0);
     };
     // (0, 0) form with `asum`: the column sums of A over the reduction rows - the bias gradient sum_m g[m, n] next to the weight
     // gradient g^T x - are taken from the registers on their way to LDS by the workgroups of the problem's first column tile:
@@ -4511,31 +4625,22 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
     const bool do_asum = !A_RC && P.asum != nullptr && j0 == 0;
     const float asum_on = do_asum ? 1.f : 0.f;
     float4 asum4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto store_ab = [&](const float4* ra, const float4* rb, unsigned ma, unsigned mb, int buf) __attribute__((always_inline)) {
+    auto store_ab = [&](const GemmRegs<NA, NB>& s, int buf) __attribute__((always_inline)) {
         if constexpr (!A_RC) {           // branch-free (a branch here would split the scheduled K step): weight 0 when not wanted
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
-                const float wj = ((ma >> j) & 1u) ? asum_on : 0.f;
-                asum4.x = fmaf(wj, ra[j].x, asum4.x); asum4.y = fmaf(wj, ra[j].y, asum4.y);
-                asum4.z = fmaf(wj, ra[j].z, asum4.z); asum4.w = fmaf(wj, ra[j].w, asum4.w);
+                const float wj = ((s.ma >> j) & 1u) ? asum_on : 0.f;
+                asum4.x = fmaf(wj, s.a[j].x, asum4.x); asum4.y = fmaf(wj, s.a[j].y, asum4.y);
+                asum4.z = fmaf(wj, s.a[j].z, asum4.z); asum4.w = fmaf(wj, s.a[j].w, asum4.w);
             }
         }
-        if (A_RC) store_rc(As0 + buf * SZA, ra, ma, NA);
-        else store_oc(As0 + buf * SZA, ra, ma, LDA, NA, BM / 4);
-        if (B_RC) store_rc(Bs0 + buf * SZB, rb, mb, NB);
-        else store_oc(Bs0 + buf * SZB, rb, mb, LDB, NB, BN / 4);
+        if (A_RC) store_rc(As0 + buf * SZA, s.a, s.ma, NA);
+        else store_oc(As0 + buf * SZA, s.a, s.ma, LDA, NA, BM / 4);
+        if (B_RC) store_rc(Bs0 + buf * SZB, s.b, s.mb, NB);
+        else store_oc(Bs0 + buf * SZB, s.b, s.mb, LDB, NB, BN / 4);
     };
-    // fragments of k-group t (8 reduction indices = 4 MFMA k-steps) for the wavefront's MT / NT 32-wide blocks
+    // the wavefront's MT / NT 32-wide blocks
     const int ia = wrow + l31, jb = wcol + l31;
-    auto frag = [&](const float* S, bool rc, int pitch, int col, int t, float (&f)[4]) __attribute__((always_inline)) {
-        if (rc) {
-            const float4 v = *reinterpret_cast<const float4*>(S + col * PR + 8 * t + 4 * half);
-            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) f[q] = S[(8 * t + q + 4 * half) * pitch + col];
-        }
-    };
 
     floatx16 acc[MT][NT];
 #pragma unroll
@@ -4557,23 +4662,23 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
         for (int b = 0; b < NT; ++b)
             blkv |= ((i0 + wrow + 32 * a < P.I) && (j0 + wcol + 32 * b < P.J) ? 1u : 0u) << (a * NT + b);
     blkv = __builtin_amdgcn_readfirstlane(blkv);
-    auto compute = [&](auto edge_c, int buf, int nt8) __attribute__((always_inline)) {
+    auto compute = [&](auto all_c, int buf, int nt8) __attribute__((always_inline)) {
         const float* Sa = As0 + buf * SZA;
         const float* Sb = Bs0 + buf * SZB;
         float fa[2][MT][4], fb[2][NT][4];
 #pragma unroll
-        for (int a = 0; a < MT; ++a) frag(Sa, A_RC, LDA, ia + 32 * a, 0, fa[0][a]);
+        for (int a = 0; a < MT; ++a) gemm_frag<PR>(Sa, A_RC, LDA, ia + 32 * a, 0, half, fa[0][a]);
 #pragma unroll
-        for (int b = 0; b < NT; ++b) frag(Sb, B_RC, LDB, jb + 32 * b, 0, fb[0][b]);
+        for (int b = 0; b < NT; ++b) gemm_frag<PR>(Sb, B_RC, LDB, jb + 32 * b, 0, half, fb[0][b]);
 #pragma unroll
         for (int t = 0; t < BK / 8; ++t) {
             if (t >= nt8) break;
             const int cur = t & 1;
             if (t + 1 < BK / 8) {            // the next group's fragments travel behind this group's MFMAs
 #pragma unroll
-                for (int a = 0; a < MT; ++a) frag(Sa, A_RC, LDA, ia + 32 * a, t + 1, fa[cur ^ 1][a]);
+                for (int a = 0; a < MT; ++a) gemm_frag<PR>(Sa, A_RC, LDA, ia + 32 * a, t + 1, half, fa[cur ^ 1][a]);
 #pragma unroll
-                for (int b = 0; b < NT; ++b) frag(Sb, B_RC, LDB, jb + 32 * b, t + 1, fb[cur ^ 1][b]);
+                for (int b = 0; b < NT; ++b) gemm_frag<PR>(Sb, B_RC, LDB, jb + 32 * b, t + 1, half, fb[cur ^ 1][b]);
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -4581,7 +4686,7 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
                 for (int a = 0; a < MT; ++a)
 #pragma unroll
                     for (int b = 0; b < NT; ++b) {
-                        if constexpr (decltype(edge_c)::value) {
+                        if constexpr (!decltype(all_c)::value) {      // ragged tiles skip padding blocks
                             if ((blkv >> (a * NT + b)) & 1u)
                                 acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][a][q], fb[cur][b][q], acc[a][b], 0, 0, 0);
                         } else {
@@ -4593,101 +4698,35 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
 
     const long long nsteps = r_end > r_begin ? (r_end - r_begin + BK - 1) / BK : 0;
     const int last8 = nsteps > 0 ? (int)((r_end - r_begin - (nsteps - 1) * BK + 7) / 8) : 0;   // k-groups of the last step
-    // Step st computes LDS buffer st & 1; register set (st + 1) & 1 holds step st + 1 (written to LDS at the end of this
-    // step), the other set receives step st + 2.  The steady-state loop has NO branch around its loads and the scheduler
-    // may not move anything across the marks: only then does the compiler wait with a COUNT (the older set's loads) before
-    // the LDS writes instead of vmcnt(0), i.e. only then are two steps of loads really in flight.  (With `if (st + 2 <
-    // nsteps) load` inside one loop it issued vmcnt(0) at every join and hoisted the LDS writes above the new loads.)
-    // Issue order of one steady-state K step of the 128 x 128 tile (SINGA_GEMM_PIPE): the step's 8 global loads, its LDS
-    // fragment reads and its 8 LDS writes are spread BETWEEN the 64 MFMAs instead of standing in front of and behind them.
-    // An MFMA occupies the matrix core for 64 cycles while the wavefront goes on issuing: with the three phases fenced off
-    // (load | 64 MFMAs | store) a wavefront issued no MFMA during ~15 % of a step and the pipe only stayed busy when the
-    // CU's second workgroup happened to be in its MFMA phase (MFMA-busy 0.75).  Groups (llvm.amdgcn.sched.group.barrier):
-    // k-group 0: 2 MFMA + 1 load, 8 times, with the fragment reads of k-group 1 among them; k-groups 1, 2: 16 MFMAs with
-    // the next group's fragment reads; k-group 3: 2 MFMA + 1 LDS write, 8 times.
-    auto pipeline = [&](auto interior_c) __attribute__((always_inline)) {
-#if SINGA_GEMM_PIPE
-        if constexpr (CFG == 0 && decltype(interior_c)::value) {
-            constexpr int DSR = (A_RC ? MT : 4 * MT) + (B_RC ? NT : 4 * NT);      // fragment reads per k-group
-            constexpr int MF = 0x008, VM = 0x020, DR = 0x100, DW = 0x200;
-            __builtin_amdgcn_sched_group_barrier(DR, DSR, 0);                      // k-group 0's fragments first
+    // Issue order of one steady-state K step of the 128 x 128 tile: the step's 8 global loads, its LDS fragment reads and its
+    // 8 LDS writes between the 64 MFMAs.  Groups (llvm.amdgcn.sched.group.barrier): k-group 0: 2 MFMA + 1 load, 8 times, with
+    // the fragment reads of k-group 1 among them; k-groups 1, 2: 16 MFMAs with the next group's fragment reads; k-group 3:
+    // 2 MFMA + 1 LDS write, 8 times.
+    auto pipeline = [&]() __attribute__((always_inline)) {
+        constexpr int DSR = (A_RC ? MT : 4 * MT) + (B_RC ? NT : 4 * NT);      // fragment reads per k-group
+        constexpr int MF = 0x008, VM = 0x020, DR = 0x100, DW = 0x200;
+        __builtin_amdgcn_sched_group_barrier(DR, DSR, 0);                      // k-group 0's fragments first
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                __builtin_amdgcn_sched_group_barrier(MF, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(VM, 1, 0);
-                if (i % 2 == 1) __builtin_amdgcn_sched_group_barrier(DR, DSR / 4, 0);
-            }
-#pragma unroll
-            for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
-                    __builtin_amdgcn_sched_group_barrier(DR, DSR / 4, 0);
-                }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                __builtin_amdgcn_sched_group_barrier(MF, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(DW, 1, 0);
-            }
+        for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(MF, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(VM, 1, 0);
+            if (i % 2 == 1) __builtin_amdgcn_sched_group_barrier(DR, DSR / 4, 0);
         }
-#endif
+#pragma unroll
+        for (int g2 = 0; g2 < 2; ++g2)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(DR, DSR / 4, 0);
+            }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(MF, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(DW, 1, 0);
+        }
     };
     auto k_loop = [&](auto all_c) __attribute__((always_inline)) {
-        constexpr std::integral_constant<bool, !decltype(all_c)::value> edge_c{};      // ragged tiles skip padding blocks
-        unsigned ma0 = 0, mb0 = 0, ma1 = 0, mb1 = 0;
-        if (nsteps > 0) {
-            load_ab(all_c, ra0, rb0, ma0, mb0, r_begin);
-            if (nsteps > 1) load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + BK);
-            store_ab(ra0, rb0, ma0, mb0, 0);
-        }
-        __syncthreads();
-        long long st = 0;
-#if !defined(SINGA_GEMM_LAB_NOLOAD) && !defined(SINGA_GEMM_LAB_NOSYNC)
-        // all prologue loads land before the loop: otherwise the compiler's wait insertion merges "a prologue load into
-        // register X may be pending" into the loop header and waits for vmcnt(0) there on EVERY iteration
-        if (nsteps > 3) __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0) only
-        for (; st + 3 < nsteps; st += 2) {
-            load_ab(all_c, ra0, rb0, ma0, mb0, r_begin + (st + 2) * BK);
-            SINGA_GEMM_FENCE();
-            compute(edge_c, 0, 4);
-            SINGA_GEMM_FENCE();
-            store_ab(ra1, rb1, ma1, mb1, 1);
-            pipeline(all_c);
-            __syncthreads();
-            load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + (st + 3) * BK);
-            SINGA_GEMM_FENCE();
-            compute(edge_c, 1, 4);
-            SINGA_GEMM_FENCE();
-            store_ab(ra0, rb0, ma0, mb0, 0);
-            pipeline(all_c);
-            __syncthreads();
-        }
-#endif
-        for (; st < nsteps; st += 2) {         // the last (up to three) steps, and the tools/lab variants
-#if defined(SINGA_GEMM_LAB_NOLOAD) || defined(SINGA_GEMM_LAB_NOSYNC)   // tools/lab only: which part of a step costs what
-            compute(edge_c, 0, 4);
-#ifndef SINGA_GEMM_LAB_NOSYNC
-            if (st + 1 < nsteps) store_ab(ra1, rb1, ma1, mb1, 1);
-            __syncthreads();
-#endif
-            if (st + 1 >= nsteps) break;
-            compute(edge_c, 1, 4);
-#ifndef SINGA_GEMM_LAB_NOSYNC
-            if (st + 2 < nsteps) store_ab(ra0, rb0, ma0, mb0, 0);
-            __syncthreads();
-#endif
-#else
-            if (st + 2 < nsteps) load_ab(all_c, ra0, rb0, ma0, mb0, r_begin + (st + 2) * BK);
-            compute(edge_c, 0, st + 1 == nsteps ? last8 : 4);
-            if (st + 1 < nsteps) store_ab(ra1, rb1, ma1, mb1, 1);
-            __syncthreads();
-            if (st + 1 >= nsteps) break;
-            if (st + 3 < nsteps) load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + (st + 3) * BK);
-            compute(edge_c, 1, st + 2 == nsteps ? last8 : 4);
-            if (st + 2 < nsteps) store_ab(ra0, rb0, ma0, mb0, 0);
-            __syncthreads();
-#endif
-        }
+        gemm_k_loop<BK, NA, NB, SINGA_GEMM_PIPE && CFG == 0>(all_c, r_begin, nsteps, last8, load_ab, store_ab, compute, pipeline);
     };
     // `full` tiles of ungrouped operands take the unpredicated loads
     if (full && P.a_group == (1 << 30) && P.b_group == (1 << 30)) k_loop(std::true_type{});
@@ -4761,8 +4800,9 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
 // The imaginary part of every operand lies a fixed number of elements behind the real part (a_im, b_im, c_im).  Both parts of
 // both operands are staged in LDS as they are; the sums a + b, sigma d - c, c + sigma d are formed on the fragments in
 // registers (8 + 8 VALU operations per 24 MFMAs).  Workgroup = 256 threads = 2 x 2 wavefronts, tile 128 rows x 64 complex
-// columns, K step 16 (complex), three accumulator sets of 2 MFMA tiles (96 registers), LDS images / two-step register prefetch /
-// XCD-contiguous tile ranges / staged float4 epilogue as in k7.
+// columns, K step 16 (complex), three accumulator sets of 2 MFMA tiles (96 registers).  The tile walk, the reduction-contiguous
+// loads, the fragment reads and the K loop are the pieces in front of k7 (gemm_tile_walk, gemm_load_rc, gemm_frag, gemm_k_loop);
+// the LDS images and the staged float4 epilogue have k7's layout with two parts, real and imaginary, side by side.
 struct CGemmProb {
     const float* A;
     const float* B;
@@ -4777,14 +4817,6 @@ struct CGemmBatch {
     long long r_chunk;
 };
 
-#ifndef SINGA_CGEMM_PIPE
-#define SINGA_CGEMM_PIPE 1
-#endif
-#if SINGA_CGEMM_PIPE
-#define SINGA_CGEMM_FENCE() do { if constexpr (!decltype(all_c)::value) __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define SINGA_CGEMM_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 template <bool A_RC, bool B_RC>
 __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
     constexpr int BM = 128, BN = 64, BK = 16, PR = BK + 4, LDA = BM + 4, LDB = BN + 4;
@@ -4796,22 +4828,11 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
     float* const As0 = smem;
     float* const Bs0 = smem + 2 * SZA;
-    const int nblk = gb.tiles_total * gb.splits;
-    const int per = (nblk + 7) >> 3;
-    const int id = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if (id >= nblk) return;
-    const int split = id / gb.tiles_total;
-    const int tile = id - split * gb.tiles_total;
-    const int ti = gb.tj_total ? tile / gb.tj_total : 0, trem = gb.tj_total ? tile - ti * gb.tj_total : tile;
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < SINGA_CGEMM_MAX; ++q)
-        if (q < gb.n && trem >= gb.p[q].tile_begin) pi = q;
-    const CGemmProb& P = gb.p[pi];
-    const int local = trem - P.tile_begin;
-    const int i0 = (gb.tj_total ? ti : local / P.tiles_j) * BM, j0 = (gb.tj_total ? local : local % P.tiles_j) * BN;
-    const long long r_begin = (long long)split * gb.r_chunk;
-    const long long r_end = (r_begin + gb.r_chunk < P.R) ? r_begin + gb.r_chunk : P.R;
+    GemmTile T;
+    if (!gemm_tile_walk<BM, BN, SINGA_CGEMM_MAX>(gb, T)) return;
+    const CGemmProb& P = gb.p[T.pi];
+    const int split = T.split, i0 = T.i0, j0 = T.j0;
+    const long long r_begin = T.r_begin, r_end = T.r_end;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 32;
     const int l31 = lane & 31, half = lane >> 5;
@@ -4836,25 +4857,7 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
             brow[j] = jj < P.J ? P.B + (long long)jj * P.ldb + (long long)pt * P.b_im + 4 * kq : nullptr;
         }
     }
-    float4 ra0[NA], rb0[NB], ra1[NA], rb1[NB];
     const bool full = i0 + BM <= P.I && j0 + BN <= P.J && r_end > r_begin && (r_end - r_begin) % BK == 0;
-    auto load_rc = [&](auto all_c, float4* reg, unsigned& mask, const float* const* rows, const float* dummy, int n, long long r0) {
-        if constexpr (decltype(all_c)::value) {
-#pragma unroll
-            for (int j = 0; j < n; ++j) reg[j] = *reinterpret_cast<const float4*>(rows[j] + r0);
-            mask = ~0u;
-        } else {
-            const bool in = r0 + 4 * kq < r_end;
-            mask = 0;
-#pragma unroll
-            for (int j = 0; j < n; ++j) {
-                const bool ok = in && rows[j] != nullptr;
-                const float* src = ok ? rows[j] + r0 : dummy + r_begin;
-                reg[j] = *reinterpret_cast<const float4*>(src);
-                mask |= (ok ? 1u : 0u) << j;
-            }
-        }
-    };
     // output-contiguous: `width4` float4 per reduction row and part, 256 / width4 reduction rows per pass, n / 2 passes per part
     auto load_oc = [&](auto all_c, float4* reg, unsigned& mask, const float* base, long long ld, long long im, int o0, int lim, int n,
                        int width4, long long r0) {
@@ -4897,28 +4900,19 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
                 (mask >> j) & 1u ? reg[j] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    auto load_ab = [&](auto all_c, float4* ra, float4* rb, unsigned& ma, unsigned& mb, long long r0) __attribute__((always_inline)) {
-        if (A_RC) load_rc(all_c, ra, ma, arow, P.A, NA, r0);
-        else load_oc(all_c, ra, ma, P.A, P.lda, P.a_im, i0, P.I, NA, BM / 4, r0);
-        if (B_RC) load_rc(all_c, rb, mb, brow, P.B, NB, r0);
-        else load_oc(all_c, rb, mb, P.B, P.ldb, P.b_im, j0, P.J, NB, BN / 4, r0);
+    auto load_ab = [&](auto all_c, GemmRegs<NA, NB>& s, long long r0) __attribute__((always_inline)) {
+        if (A_RC) gemm_load_rc(all_c, s.a, s.ma, arow, P.A, NA, kq, r0, r_begin, r_end);
+        else load_oc(all_c, s.a, s.ma, P.A, P.lda, P.a_im, i0, P.I, NA, BM / 4, r0);
+        if (B_RC) gemm_load_rc(all_c, s.b, s.mb, brow, P.B, NB, kq, r0, r_begin, r_end);
+        else load_oc(all_c, s.b, s.mb, P.B, P.ldb, P.b_im, j0, P.J, NB, BN / 4, r0);
     };
-    auto store_ab = [&](const float4* ra, const float4* rb, unsigned ma, unsigned mb, int buf) __attribute__((always_inline)) {
-        if (A_RC) store_rc(As0 + buf * SZA, SZA1, ra, ma, NA);
-        else store_oc(As0 + buf * SZA, SZA1, ra, ma, LDA, NA, BM / 4);
-        if (B_RC) store_rc(Bs0 + buf * SZB, SZB1, rb, mb, NB);
-        else store_oc(Bs0 + buf * SZB, SZB1, rb, mb, LDB, NB, BN / 4);
+    auto store_ab = [&](const GemmRegs<NA, NB>& s, int buf) __attribute__((always_inline)) {
+        if (A_RC) store_rc(As0 + buf * SZA, SZA1, s.a, s.ma, NA);
+        else store_oc(As0 + buf * SZA, SZA1, s.a, s.ma, LDA, NA, BM / 4);
+        if (B_RC) store_rc(Bs0 + buf * SZB, SZB1, s.b, s.mb, NB);
+        else store_oc(Bs0 + buf * SZB, SZB1, s.b, s.mb, LDB, NB, BN / 4);
     };
     const int ia = wrow + l31, jb = wcol + l31;
-    auto frag = [&](const float* S, bool rc, int pitch, int col, int t, float (&f)[4]) __attribute__((always_inline)) {
-        if (rc) {
-            const float4 v = *reinterpret_cast<const float4*>(S + col * PR + 8 * t + 4 * half);
-            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) f[q] = S[(8 * t + q + 4 * half) * pitch + col];
-        }
-    };
     floatx16 acc1[2], acc2[2], acc3[2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -4926,7 +4920,7 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
         for (int r = 0; r < 16; ++r) acc1[a][r] = acc2[a][r] = acc3[a][r] = 0.f;
     const bool row1 = __builtin_amdgcn_readfirstlane((int)(i0 + wrow + 32 < P.I)) != 0;      // the wavefront's second 32-row block holds rows
     const bool colv = __builtin_amdgcn_readfirstlane((int)(j0 + wcol < P.J)) != 0;           // ... its 32-column block holds columns
-    auto compute = [&](auto all_c, int buf) __attribute__((always_inline)) {
+    auto compute = [&](auto all_c, int buf, int) __attribute__((always_inline)) {      // (every step computes both k-groups)
         if constexpr (!decltype(all_c)::value) {
             if (!colv) return;                   // (a 96-wide result: the last tile's second column block is padding only)
         }
@@ -4937,11 +4931,11 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
             float ar[2][4], ai[2][4], br[4], bi[4];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-                frag(Sa, A_RC, LDA, ia + 32 * a, t, ar[a]);
-                frag(Sa + SZA1, A_RC, LDA, ia + 32 * a, t, ai[a]);
+                gemm_frag<PR>(Sa, A_RC, LDA, ia + 32 * a, t, half, ar[a]);
+                gemm_frag<PR>(Sa + SZA1, A_RC, LDA, ia + 32 * a, t, half, ai[a]);
             }
-            frag(Sb, B_RC, LDB, jb, t, br);
-            frag(Sb + SZB1, B_RC, LDB, jb, t, bi);
+            gemm_frag<PR>(Sb, B_RC, LDB, jb, t, half, br);
+            gemm_frag<PR>(Sb + SZB1, B_RC, LDB, jb, t, half, bi);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float ds = sigma * bi[q];
@@ -4958,65 +4952,26 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
         }
     };
     const long long nsteps = r_end > r_begin ? (r_end - r_begin + BK - 1) / BK : 0;
-    // Issue order of one steady-state K step of a full tile (as k7's `pipeline`): the 6 global loads and the 6 LDS writes are
-    // spread between the 48 MFMAs, the second k-group's fragment reads travel behind the first group's MFMAs.
-    auto pipeline = [&](auto interior_c) __attribute__((always_inline)) {
-#if SINGA_CGEMM_PIPE
-        if constexpr (decltype(interior_c)::value) {
-            constexpr int DSR = (A_RC ? 4 : 16) + (B_RC ? 2 : 8);                  // fragment reads per k-group
-            constexpr int MF = 0x008, VM = 0x020, DR = 0x100, DW = 0x200;
-            __builtin_amdgcn_sched_group_barrier(DR, DSR, 0);
+    // Issue order of one steady-state K step of a full tile: the 6 global loads and the 6 LDS writes are spread between the
+    // 48 MFMAs, the second k-group's fragment reads travel behind the first group's MFMAs.
+    auto pipeline = [&]() __attribute__((always_inline)) {
+        constexpr int DSR = (A_RC ? 4 : 16) + (B_RC ? 2 : 8);                  // fragment reads per k-group
+        constexpr int MF = 0x008, VM = 0x020, DR = 0x100, DW = 0x200;
+        __builtin_amdgcn_sched_group_barrier(DR, DSR, 0);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(VM, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(DR, (DSR + 5) / 6, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(DW, 1, 0);
-            }
+        for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(VM, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(DR, (DSR + 5) / 6, 0);
         }
-#endif
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(MF, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(DW, 1, 0);
+        }
     };
     auto k_loop = [&](auto all_c) __attribute__((always_inline)) {
-        unsigned ma0 = 0, mb0 = 0, ma1 = 0, mb1 = 0;
-        if (nsteps > 0) {
-            load_ab(all_c, ra0, rb0, ma0, mb0, r_begin);
-            if (nsteps > 1) load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + BK);
-            store_ab(ra0, rb0, ma0, mb0, 0);
-        }
-        __syncthreads();
-        long long st = 0;
-        if (nsteps > 3) __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0) only (see k7)
-        for (; st + 3 < nsteps; st += 2) {
-            load_ab(all_c, ra0, rb0, ma0, mb0, r_begin + (st + 2) * BK);
-            SINGA_CGEMM_FENCE();
-            compute(all_c, 0);
-            SINGA_CGEMM_FENCE();
-            store_ab(ra1, rb1, ma1, mb1, 1);
-            pipeline(all_c);
-            __syncthreads();
-            load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + (st + 3) * BK);
-            SINGA_CGEMM_FENCE();
-            compute(all_c, 1);
-            SINGA_CGEMM_FENCE();
-            store_ab(ra0, rb0, ma0, mb0, 0);
-            pipeline(all_c);
-            __syncthreads();
-        }
-        for (; st < nsteps; st += 2) {
-            if (st + 2 < nsteps) load_ab(all_c, ra0, rb0, ma0, mb0, r_begin + (st + 2) * BK);
-            compute(all_c, 0);
-            if (st + 1 < nsteps) store_ab(ra1, rb1, ma1, mb1, 1);
-            __syncthreads();
-            if (st + 1 >= nsteps) break;
-            if (st + 3 < nsteps) load_ab(all_c, ra1, rb1, ma1, mb1, r_begin + (st + 3) * BK);
-            compute(all_c, 1);
-            if (st + 2 < nsteps) store_ab(ra0, rb0, ma0, mb0, 0);
-            __syncthreads();
-        }
+        gemm_k_loop<BK, NA, NB, SINGA_CGEMM_PIPE != 0>(all_c, r_begin, nsteps, BK / 8, load_ab, store_ab, compute, pipeline);
     };
     if (full) k_loop(std::true_type{});
     else k_loop(std::false_type{});
@@ -5978,6 +5933,68 @@ int fail_at(int code, const char* entry, const char* text) {
     return code;
 }
 
+// The GEMM kernels' template arguments from run-time values, in the same manner: the macro tile CFG of k7 (0, 1, 2, else 3),
+// and the operand forms that are built - (1, 1), (1, 0), else (0, 0).
+template <class F>
+void dispatch_gemm_cfg(int cfg, F&& f) {
+    if (cfg == 0) f(std::integral_constant<int, 0>{});
+    else if (cfg == 1) f(std::integral_constant<int, 1>{});
+    else if (cfg == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
+
+template <class F>
+void dispatch_gemm_form(bool a_rc, bool b_rc, F&& f) {
+    if (a_rc && b_rc) f(std::true_type{}, std::true_type{});
+    else if (a_rc) f(std::true_type{}, std::false_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+
+// The checks singa_gemm_f32 and singa_cgemm3m_f32 make in the same words, and their tile plan.
+int gemm_check_launch(const char* entry, int a_r_contig, int b_r_contig, int splits) {
+    if (splits < 1) return fail_at(SINGA_E_SHAPE, entry, "splits must be >= 1");
+    if (!a_r_contig && b_r_contig) return fail_at(SINGA_E_SHAPE, entry, "A output-contiguous with B reduction-contiguous is not built");
+    return SINGA_OK;
+}
+
+template <class Q>
+int gemm_check_operands(const char* entry, const Q& q) {
+    if (!q.a || !q.b || !q.c) return fail_at(SINGA_E_NULL, entry, "null operand");
+    if (q.I < 0 || q.J < 0 || q.R < 0) return fail_at(SINGA_E_SHAPE, entry, "negative size");
+    return SINGA_OK;
+}
+
+// Tiles of BM x BN over the problems of gb (I, J, R filled in): tiles_j and tile_begin per problem - in the interleaved order,
+// for problems with equal row counts, the first column tile of the problem inside a row tile's group; else the first tile of
+// the problem - then tiles_total, tj_total and r_chunk (a multiple of the kernel's K step when the reduction is split).
+// *grid = the workgroups to launch, a multiple of 8 (one range of tile ids per XCD), or 0: no tile, nothing to launch.
+template <class Batch>
+int gemm_plan(Batch& gb, int BM, int BN, int kstep, const char* entry, unsigned* grid) {
+    long long rmax = 0;
+    int tj_total = 0, ti_max = 0, tiles_seq = 0;
+    bool same_rows = true;
+    for (int k = 1; k < gb.n; ++k) same_rows = same_rows && gb.p[k].I == gb.p[0].I;
+    for (int k = 0; k < gb.n; ++k) {
+        auto& P = gb.p[k];
+        P.tiles_j = (P.J + BN - 1) / BN;
+        P.tile_begin = same_rows ? tj_total : tiles_seq;
+        tj_total += P.tiles_j;
+        const int ti = (P.I + BM - 1) / BM;
+        tiles_seq += ti * P.tiles_j;
+        if (ti > ti_max) ti_max = ti;
+        if (P.R > rmax) rmax = P.R;
+    }
+    *grid = 0;
+    gb.tiles_total = same_rows ? ti_max * tj_total : tiles_seq;
+    if (gb.tiles_total == 0) return SINGA_OK;
+    gb.tj_total = same_rows ? tj_total : 0;
+    gb.r_chunk = gb.splits > 1 ? ((rmax + gb.splits - 1) / gb.splits + kstep - 1) / kstep * kstep : (rmax > 0 ? rmax : 1);
+    const long long nblk = (long long)gb.tiles_total * gb.splits;
+    if (nblk > (1 << 30)) return fail_at(SINGA_E_SHAPE, entry, "too many tiles");
+    *grid = (unsigned)((nblk + 7) / 8 * 8);
+    return SINGA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ n1: kNN graph
 // torch_cluster.knn_graph(pos, k, batch, flow='target_to_source') (reference model/CProMG.py:293,330): for every atom its k
 // nearest other atoms of the same molecule.  One wavefront per centre atom; the molecule's atoms (a contiguous index range
@@ -6814,13 +6831,12 @@ int singa_grad_norm(const float* const* g, const long long* sizes, const int32_t
 int singa_gemm_occupancy(int a_r_contig, int b_r_contig, int cfg) {
     int n = -1;
     hipError_t e = hipErrorInvalidValue;
-#define SINGA_OCC(ARC, BRC, CFG) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_f32_kernel<ARC, BRC, CFG>, 256, 0)
-#define SINGA_OCC4(ARC, BRC) do { if (cfg == 0) SINGA_OCC(ARC, BRC, 0); else if (cfg == 1) SINGA_OCC(ARC, BRC, 1); else if (cfg == 2) SINGA_OCC(ARC, BRC, 2); else SINGA_OCC(ARC, BRC, 3); } while (0)
-    if (a_r_contig && b_r_contig) SINGA_OCC4(true, true);
-    else if (a_r_contig) SINGA_OCC4(true, false);
-    else SINGA_OCC4(false, false);
-#undef SINGA_OCC4
-#undef SINGA_OCC
+    dispatch_gemm_form(a_r_contig, b_r_contig, [&](auto a, auto b) {
+        constexpr bool A_RC = decltype(a)::value, B_RC = decltype(b)::value;
+        dispatch_gemm_cfg(cfg, [&](auto c) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_f32_kernel<A_RC, B_RC, decltype(c)::value>, 256, 0);
+        });
+    });
     return e == hipSuccess ? n : -(int)e;
 }
 
@@ -6833,13 +6849,11 @@ int singa_gemm_force_cfg(int cfg) {
 
 int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
     if (!probs || n < 1 || n > SINGA_GEMM_MAX) return fail(SINGA_E_SHAPE, "gemm_f32: 1..SINGA_GEMM_MAX problems per launch");
-    if (splits < 1) return fail(SINGA_E_SHAPE, "gemm_f32: splits must be >= 1");
-    if (!a_r_contig && b_r_contig) return fail(SINGA_E_SHAPE, "gemm_f32: A output-contiguous with B reduction-contiguous is not built");
+    if (int bad = gemm_check_launch("gemm_f32", a_r_contig, b_r_contig, splits)) return bad;
     GemmBatch gb;
     memset(&gb, 0, sizeof(gb));
     gb.n = n;
     gb.splits = splits;
-    long long rmax = 0;
     int jmax = 0;
     for (int k = 0; k < n; ++k) jmax = probs[k].J > jmax ? probs[k].J : jmax;
     int imax = 0;
@@ -6853,15 +6867,10 @@ int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_con
         if (t128 * splits < 384 || (imax <= 64 && jmax <= 64)) cfg = 3;      // (an output of at most 64 x 64 is one small tile)
         if (g_gemm_force_cfg == 0 || g_gemm_force_cfg == 3) cfg = g_gemm_force_cfg;      // tests: both tile shapes on every case
     }
-    const int BM = cfg == 2 ? 32 : (cfg == 3 ? 64 : 128), BN = cfg == 1 ? 32 : (cfg == 3 ? 64 : 128);
-    int tj_total = 0, ti_max = 0, tiles_seq = 0;
-    bool same_rows = true;
-    for (int k = 1; k < n; ++k) same_rows = same_rows && probs[k].I == probs[0].I;
     for (int k = 0; k < n; ++k) {
         const singa_gemm_t& q = probs[k];
         GemmProb& P = gb.p[k];
-        if (!q.a || !q.b || !q.c) return fail(SINGA_E_NULL, "gemm_f32: null operand");
-        if (q.I < 0 || q.J < 0 || q.R < 0) return fail(SINGA_E_SHAPE, "gemm_f32: negative size");
+        if (int bad = gemm_check_operands("gemm_f32", q)) return bad;
         // float4 accesses: the contiguous axis of each operand must be a multiple of 4 floats and 16-byte aligned
         const bool a_ok = a_r_contig ? (q.R % 4 == 0) : (q.I % 4 == 0);
         const bool b_ok = b_r_contig ? (q.R % 4 == 0) : (q.J % 4 == 0);
@@ -6891,56 +6900,34 @@ int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_con
         P.c_gld = q.c_group > 0 ? q.c_group_ld : 0;
         P.c_split = q.c_split_stride;
         P.I = q.I; P.J = q.J; P.R = q.R;
-        P.tiles_j = (q.J + BN - 1) / BN;
-        // interleaved order: first column tile of this problem inside a row tile's group; else: first tile of the problem
-        P.tile_begin = same_rows ? tj_total : tiles_seq;
-        tj_total += P.tiles_j;
-        const int ti = (q.I + BM - 1) / BM;
-        tiles_seq += ti * P.tiles_j;
-        if (ti > ti_max) ti_max = ti;
-        if (q.R > rmax) rmax = q.R;
     }
-    const int tiles = same_rows ? ti_max * tj_total : tiles_seq;
-    if (tiles == 0) return SINGA_OK;
-    gb.tiles_total = tiles;
-    gb.tj_total = same_rows ? tj_total : 0;
-    gb.r_chunk = splits > 1 ? ((rmax + splits - 1) / splits + 31) / 32 * 32 : (rmax > 0 ? rmax : 1);
-    const long long nblk = (long long)tiles * splits;
-    if (nblk > (1 << 30)) return fail(SINGA_E_SHAPE, "gemm_f32: too many tiles");
-    const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(256);
+    unsigned nwg = 0;
+    if (int bad = gemm_plan(gb, cfg == 2 ? 32 : (cfg == 3 ? 64 : 128), cfg == 1 ? 32 : (cfg == 3 ? 64 : 128), 32, "gemm_f32", &nwg))
+        return bad;
+    if (nwg == 0) return SINGA_OK;
+    const dim3 grid(nwg), block(256);
     hipStream_t st = (hipStream_t)stream;
-#define SINGA_GEMM_GO(tag, ARC, BRC)                                                                        \
-    do {                                                                                                    \
-        if (cfg == 1) SINGA_LAUNCH(tag, 0, tiles, (gemm_f32_kernel<ARC, BRC, 1>), grid, block, st, gb);     \
-        else if (cfg == 2) SINGA_LAUNCH(tag, 0, tiles, (gemm_f32_kernel<ARC, BRC, 2>), grid, block, st, gb); \
-        else if (cfg == 3) SINGA_LAUNCH(tag, 0, tiles, (gemm_f32_kernel<ARC, BRC, 3>), grid, block, st, gb); \
-        else SINGA_LAUNCH(tag, 0, tiles, (gemm_f32_kernel<ARC, BRC, 0>), grid, block, st, gb);              \
-    } while (0)
-    if (a_r_contig && b_r_contig) SINGA_GEMM_GO(SINGA_PROF_GEMM_NT, true, true);
-    else if (a_r_contig) SINGA_GEMM_GO(SINGA_PROF_GEMM_NN, true, false);
-    else SINGA_GEMM_GO(SINGA_PROF_GEMM_TN, false, false);
-#undef SINGA_GEMM_GO
+    dispatch_gemm_form(a_r_contig, b_r_contig, [&](auto a, auto b) {
+        constexpr bool A_RC = decltype(a)::value, B_RC = decltype(b)::value;
+        constexpr int tag = B_RC ? SINGA_PROF_GEMM_NT : (A_RC ? SINGA_PROF_GEMM_NN : SINGA_PROF_GEMM_TN);
+        dispatch_gemm_cfg(cfg, [&](auto c) {
+            SINGA_LAUNCH(tag, 0, gb.tiles_total, (gemm_f32_kernel<A_RC, B_RC, decltype(c)::value>), grid, block, st, gb);
+        });
+    });
     return check_launch("gemm_f32");
 }
 
 int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
     if (!probs || n < 1 || n > SINGA_CGEMM_MAX) return fail(SINGA_E_SHAPE, "cgemm3m_f32: 1..SINGA_CGEMM_MAX problems per launch");
-    if (splits < 1) return fail(SINGA_E_SHAPE, "cgemm3m_f32: splits must be >= 1");
-    if (!a_r_contig && b_r_contig) return fail(SINGA_E_SHAPE, "cgemm3m_f32: A output-contiguous with B reduction-contiguous is not built");
+    if (int bad = gemm_check_launch("cgemm3m_f32", a_r_contig, b_r_contig, splits)) return bad;
     CGemmBatch gb;
     memset(&gb, 0, sizeof(gb));
     gb.n = n;
     gb.splits = splits;
-    constexpr int BM = 128, BN = 64;
-    long long rmax = 0;
-    int tj_total = 0, ti_max = 0, tiles_seq = 0;
-    bool same_rows = true;
-    for (int k = 1; k < n; ++k) same_rows = same_rows && probs[k].I == probs[0].I;
     for (int k = 0; k < n; ++k) {
         const singa_cgemm_t& q = probs[k];
         CGemmProb& P = gb.p[k];
-        if (!q.a || !q.b || !q.c) return fail(SINGA_E_NULL, "cgemm3m_f32: null operand");
-        if (q.I < 0 || q.J < 0 || q.R < 0) return fail(SINGA_E_SHAPE, "cgemm3m_f32: negative size");
+        if (int bad = gemm_check_operands("cgemm3m_f32", q)) return bad;
         const bool a_ok = a_r_contig ? (q.R % 4 == 0) : (q.I % 4 == 0);
         const bool b_ok = b_r_contig ? (q.R % 4 == 0) : (q.J % 4 == 0);
         if (!a_ok || !b_ok || q.J % 4 || q.lda % 4 || q.ldb % 4 || q.ldc % 4 || q.a_im % 4 || q.b_im % 4 || q.c_im % 4 ||
@@ -6954,26 +6941,17 @@ int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r
         P.c_split = q.c_split_stride;
         P.I = q.I; P.J = q.J; P.R = q.R;
         P.sigma = q.sigma;
-        P.tiles_j = (q.J + BN - 1) / BN;
-        P.tile_begin = same_rows ? tj_total : tiles_seq;
-        tj_total += P.tiles_j;
-        const int ti = (q.I + BM - 1) / BM;
-        tiles_seq += ti * P.tiles_j;
-        if (ti > ti_max) ti_max = ti;
-        if (q.R > rmax) rmax = q.R;
     }
-    const int tiles = same_rows ? ti_max * tj_total : tiles_seq;
-    if (tiles == 0) return SINGA_OK;
-    gb.tiles_total = tiles;
-    gb.tj_total = same_rows ? tj_total : 0;
-    gb.r_chunk = splits > 1 ? ((rmax + splits - 1) / splits + 15) / 16 * 16 : (rmax > 0 ? rmax : 1);
-    const long long nblk = (long long)tiles * splits;
-    if (nblk > (1 << 30)) return fail(SINGA_E_SHAPE, "cgemm3m_f32: too many tiles");
-    const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(256);
+    unsigned nwg = 0;
+    if (int bad = gemm_plan(gb, 128, 64, 16, "cgemm3m_f32", &nwg)) return bad;
+    if (nwg == 0) return SINGA_OK;
+    const dim3 grid(nwg), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (a_r_contig && b_r_contig) SINGA_LAUNCH(SINGA_PROF_CGEMM_NT, 0, tiles, (cgemm3m_f32_kernel<true, true>), grid, block, st, gb);
-    else if (a_r_contig) SINGA_LAUNCH(SINGA_PROF_CGEMM_NN, 0, tiles, (cgemm3m_f32_kernel<true, false>), grid, block, st, gb);
-    else SINGA_LAUNCH(SINGA_PROF_CGEMM_TN, 0, tiles, (cgemm3m_f32_kernel<false, false>), grid, block, st, gb);
+    dispatch_gemm_form(a_r_contig, b_r_contig, [&](auto a, auto b) {
+        constexpr bool A_RC = decltype(a)::value, B_RC = decltype(b)::value;
+        SINGA_LAUNCH(B_RC ? SINGA_PROF_CGEMM_NT : (A_RC ? SINGA_PROF_CGEMM_NN : SINGA_PROF_CGEMM_TN), 0, gb.tiles_total,
+                     (cgemm3m_f32_kernel<A_RC, B_RC>), grid, block, st, gb);
+    });
     return check_launch("cgemm3m_f32");
 }
 

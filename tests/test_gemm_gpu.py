@@ -17,6 +17,10 @@ def _f64(t):
     return t.detach().cpu().double()
 
 
+def check(got, ref, tol, slack, extra=0.0):
+    assert float((_f64(got) - ref).abs().max()) <= tol * float(ref.abs().max()) + slack + extra
+
+
 @pytest.fixture
 def tile_shape(request):
     """Force the 128 x 128 (0) or the 64 x 64 (3) macro tile wherever the library would choose between the two."""
@@ -73,24 +77,147 @@ def test_complex_gemm_3m_all_forms_against_float64(M, N, K):
         xr, xi, wr, wi, gr, gi = _f64(x[:, :K]), _f64(x[:, K:]), _f64(w[:N]), _f64(w[N:]), _f64(dy[:, :N]), _f64(dy[:, N:])
         tol = 0 if kind == "int" else 3e-6
         slack = 0 if kind == "int" else 1e-6
-
-        def check(got, ref, extra=0.0):
-            assert float((_f64(got) - ref).abs().max()) <= tol * float(ref.abs().max()) + slack + extra
-
         y = torch.full((M, 2 * N), float("nan"), device=DEV)
         ops._cgemm([dict(a=xd.data_ptr(), lda=2 * K, a_im=K, b=wd.data_ptr(), ldb=K, b_im=N * K, c=y.data_ptr(), ldc=2 * N, c_im=N,
                          I=M, J=N, R=K, sigma=1.0)], True, True)
-        check(y, torch.cat([xr @ wr.t() - xi @ wi.t(), xr @ wi.t() + xi @ wr.t()], 1))
+        check(y, torch.cat([xr @ wr.t() - xi @ wi.t(), xr @ wi.t() + xi @ wr.t()], 1), tol, slack)
         dx = torch.full((M, 2 * K), float("nan"), device=DEV)
         ops._cgemm([dict(a=dyd.data_ptr(), lda=2 * N, a_im=N, b=wd.data_ptr(), ldb=K, b_im=N * K, c=dx.data_ptr(), ldc=2 * K, c_im=K,
                          I=M, J=K, R=N, sigma=-1.0)], True, False)
-        check(dx, torch.cat([gr @ wr + gi @ wi, gi @ wr - gr @ wi], 1))
+        check(dx, torch.cat([gr @ wr + gi @ wi, gi @ wr - gr @ wi], 1), tol, slack)
         ref = torch.cat([gr.t() @ xr + gi.t() @ xi, gi.t() @ xr - gr.t() @ xi], 0)
         for S in (1, 3):
             part = torch.full((S, 2 * N * K), float("nan"), device=DEV)
             ops._cgemm([dict(a=dyd.data_ptr(), lda=2 * N, a_im=N, b=xd.data_ptr(), ldb=2 * K, b_im=K, c=part.data_ptr(), ldc=K,
                              c_im=N * K, I=N, J=K, R=M, sigma=-1.0, c_split_stride=2 * N * K)], False, False, S)
-            check(part.sum(0).view(2 * N, K), ref, 0 if kind == "int" else 3e-6 * M ** 0.5)
+            check(part.sum(0).view(2 * N, K), ref, tol, slack, 0 if kind == "int" else 3e-6 * M ** 0.5)
+
+
+FORMS = [(True, True), (True, False), (False, False)]
+
+
+def _makers(seed):
+    """(kind, tensor maker) for exact small integers, then random floats."""
+    g = torch.Generator().manual_seed(seed)
+    return [("int", lambda *s: torch.randint(-3, 4, s, generator=g).float()), ("float", lambda *s: torch.randn(*s, generator=g))]
+
+
+def _tol(kind, form, R, cplx=False):
+    """(tol, slack, extra) of `check` as test_gemm_nt_nn_tn_against_float64 / test_complex_gemm_3m_all_forms_against_float64
+    set them: integers are exact; the (0, 0) form's allowance grows with the root of its reduction length."""
+    if kind == "int":
+        return 0, 0, 0
+    if cplx:
+        return 3e-6, 1e-6, 0 if form[0] else 3e-6 * R ** 0.5
+    return 2e-6, 1e-6 if form[0] else 0, 0 if form[0] else 2e-6 * R ** 0.5
+
+
+def _real_problem(mk, form, I, J, R, S=1):
+    """One problem of singa_gemm_f32 in the given operand form -> (record, the tensors it points to, [S, I, J] result,
+    float64 reference)."""
+    a_rc, b_rc = form
+    a, b = (mk(I, R) if a_rc else mk(R, I)), (mk(J, R) if b_rc else mk(R, J))
+    ad, bd = a.to(DEV), b.to(DEV)
+    out = torch.full((S, I, J), float("nan"), device=DEV)
+    ref = (_f64(a) if a_rc else _f64(a).t()) @ (_f64(b).t() if b_rc else _f64(b))
+    rec = dict(a=ad.data_ptr(), lda=ad.stride(0), b=bd.data_ptr(), ldb=bd.stride(0), c=out.data_ptr(), ldc=J, I=I, J=J, R=R,
+               c_split_stride=I * J)
+    return rec, (ad, bd), out, ref
+
+
+def _complex_problem(mk, form, I, J, R, S=1):
+    """The same for singa_cgemm3m_f32 (extents in complex units): forward (1, 1), d input (1, 0), d weight (0, 0) as in
+    test_complex_gemm_3m_all_forms_against_float64; the result is [S, I, re | im of J] or, (0, 0), [S, re | im of I, J]."""
+    a_rc, b_rc = form
+    a = mk(I, 2 * R) if a_rc else mk(R, 2 * I)
+    b = mk(2 * J, R) if b_rc else (mk(2 * R, J) if a_rc else mk(R, 2 * J))
+    ad, bd = a.to(DEV), b.to(DEV)
+    ar, ai = (_f64(a[:, :R]), _f64(a[:, R:])) if a_rc else (_f64(a[:, :I]).t(), _f64(a[:, I:]).t())
+    if b_rc:
+        br, bi, b_im = _f64(b[:J]).t(), _f64(b[J:]).t(), J * R
+    elif a_rc:
+        br, bi, b_im = _f64(b[:R]), _f64(b[R:]), R * J
+    else:
+        br, bi, b_im = _f64(b[:, :J]), _f64(b[:, J:]), J
+    sigma = 1.0 if b_rc else -1.0
+    re, im = ar @ br - sigma * (ai @ bi), sigma * (ar @ bi) + ai @ br
+    rec = dict(a=ad.data_ptr(), lda=ad.stride(0), a_im=R if a_rc else I, b=bd.data_ptr(), ldb=bd.stride(0), b_im=b_im,
+               I=I, J=J, R=R, sigma=sigma, c_split_stride=2 * I * J)
+    if a_rc:
+        out = torch.full((S, I, 2 * J), float("nan"), device=DEV)
+        rec.update(c=out.data_ptr(), ldc=2 * J, c_im=J)
+        return rec, (ad, bd), out, torch.cat([re, im], 1)
+    out = torch.full((S, 2 * I, J), float("nan"), device=DEV)
+    rec.update(c=out.data_ptr(), ldc=J, c_im=I * J)
+    return rec, (ad, bd), out, torch.cat([re, im], 0)
+
+
+@pytest.mark.parametrize("tile_shape", [0, 3], indirect=True)
+@pytest.mark.parametrize("form", FORMS)
+def test_gemm_k_step_counts(form, tile_shape):
+    """One ragged 36 x 40 tile over reductions of 1-6 K steps of 32, the last one full or ragged: the K loop's prologue
+    alone, its tail of one, two and three steps, the steady-state loop entered once and twice."""
+    from singa_amd import ops
+    for kind, mk in _makers(36 * 7 + 40):
+        for R in (4, 32, 36, 64, 96, 100, 128, 160, 164):
+            rec, keep, out, ref = _real_problem(mk, form, 36, 40, R)
+            ops._gemm([rec], *form)
+            check(out[0], ref, *_tol(kind, form, R))
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_complex_gemm_k_step_counts(form):
+    """k7c: one ragged tile of 36 rows x 20 complex columns over reductions of 1-5 K steps of 16 (complex)."""
+    from singa_amd import ops
+    for kind, mk in _makers(36 * 5 + 20):
+        for R in (4, 16, 20, 32, 48, 52, 64, 80):
+            rec, keep, out, ref = _complex_problem(mk, form, 36, 20, R)
+            ops._cgemm([rec], *form)
+            check(out[0], ref, *_tol(kind, form, R, cplx=True))
+
+
+def test_gemm_trailing_split_without_rows_writes_zeros():
+    """Split reductions whose chunk, rounded up to the K step, leaves the last split no rows (real: R = 40 in 3 splits of 32;
+    complex: R = 20 in 3 splits of 16): zero K steps, and the split's slab - and its asum row - must be zeros."""
+    from singa_amd import ops
+    for kind, mk in _makers(40):
+        rec, keep, out, ref = _real_problem(mk, (False, False), 36, 40, 40, S=3)
+        asum = torch.full((3, 36), float("nan"), device=DEV)
+        ops._gemm([dict(rec, asum=asum.data_ptr(), asum_stride=36)], False, False, 3)
+        assert not out[2].any() and not asum[2].any()
+        check(out.sum(0), ref, *_tol(kind, (False, False), 40))
+        refb = _f64(keep[0]).sum(0)
+        assert float((_f64(asum).sum(0) - refb).abs().max()) <= (0 if kind == "int" else 2e-6 * 40 ** 0.5 + 1e-6 * float(refb.abs().max()))
+        rec, keep, out, ref = _complex_problem(mk, (False, False), 36, 20, 20, S=3)
+        ops._cgemm([rec], False, False, 3)
+        assert not out[2].any()
+        check(out.sum(0), ref, *_tol(kind, (False, False), 20, cplx=True))
+
+
+@pytest.mark.parametrize("tile_shape", [0, 3], indirect=True)
+@pytest.mark.parametrize("rows", [(100, 100), (100, 36)], ids=["same_rows", "different_rows"])
+@pytest.mark.parametrize("form", FORMS)
+def test_gemm_two_problems_per_launch(form, rows, tile_shape):
+    """Two problems in one launch, at most two tiles wide each way: equal row counts take the interleaved tile order (row
+    tile by row tile, problem by problem), different ones the sequential order; the reductions differ."""
+    from singa_amd import ops
+    for kind, mk in _makers(rows[1]):
+        cases = [_real_problem(mk, form, I, J, R) for I, J, R in zip(rows, (72, 40), (36, 68))]
+        ops._gemm([c[0] for c in cases], *form)
+        for (rec, keep, out, ref), R in zip(cases, (36, 68)):
+            check(out[0], ref, *_tol(kind, form, R))
+
+
+@pytest.mark.parametrize("rows", [(132, 132), (132, 36)], ids=["same_rows", "different_rows"])
+@pytest.mark.parametrize("form", FORMS)
+def test_complex_gemm_two_problems_per_launch(form, rows):
+    """k7c (tile 128 rows x 64 complex columns): two problems per launch in the interleaved and in the sequential order."""
+    from singa_amd import ops
+    for kind, mk in _makers(rows[1] + 1):
+        cases = [_complex_problem(mk, form, I, J, R) for I, J, R in zip(rows, (68, 20), (20, 36))]
+        ops._cgemm([c[0] for c in cases], *form)
+        for (rec, keep, out, ref), R in zip(cases, (20, 36)):
+            check(out[0], ref, *_tol(kind, form, R, cplx=True))
 
 
 def test_complex_gemm_argument_errors():
