@@ -55,6 +55,9 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--grammar", choices=["none", "smiles"], default="none",
                     help="sample: draw only tokens that keep the sequence a completable SMILES string")
+    ap.add_argument("--rows-per-pocket", type=int, default=None, metavar="R",
+                    help="sample: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
+                         "(sample_stream: same sequences for the same uniforms, whatever R)")
     ap.add_argument("--prefix", type=str, default=None, help="sample: every sequence starts with this SMILES fragment")
     ap.add_argument("--molecules", type=str, default=None,
                     help="score: a file of lines `pocket name<TAB>SMILES` (further columns are ignored)")
@@ -68,6 +71,8 @@ def main():
         "--grammar constrains sampling only: beam search selects on the host"
     assert args.mode != "distinct" or (args.top_k == 0 and args.top_p == 1.0), "--mode distinct takes no --top-k / --top-p"
     assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
+    assert args.rows_per_pocket is None or (args.mode == "sample" and args.prefix is None), \
+        "--rows-per-pocket is continuous sampling: sample mode, without --prefix"
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
     dev = torch.device(args.device if ":" in args.device else "cuda:0")
     torch.cuda.set_device(dev)
@@ -80,7 +85,7 @@ def main():
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
-    from singa_amd.model.Sampling import sample, sample_distinct, score
+    from singa_amd.model.Sampling import sample, sample_distinct, sample_stream, score
 
     cfg = load_config(args.config, lmax=args.lmax)
     torch.manual_seed(args.seed)
@@ -135,9 +140,15 @@ def main():
     if args.mode == "sample":
         gen = torch.Generator(device=dev).manual_seed(args.seed)
         forced = None if args.prefix is None else smiles.encode([args.prefix] * B, voc, max_length)
-        tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
-                        top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
-                        grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
+        if args.rows_per_pocket is not None:
+            tokens = sample_stream(model, voc, per, B, max_length, ex, None if prop is None else prop[:B], args.rows_per_pocket,
+                                   device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                   suppress=("&", "^"), generator=gen, trace=tr,
+                                   grammar=None if args.grammar == "none" else args.grammar).cpu()
+        else:
+            tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
+                            top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
+                            grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
         lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
         print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
     elif args.mode == "distinct":

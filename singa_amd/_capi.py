@@ -158,12 +158,22 @@ _SWOR_SIGS = {
 }
 SWOR_EXPORTS = tuple(_SWOR_SIGS)
 
+# include/singa_hip_stream.h: continuous sampling (`sample_stream`: a finished row starts the pocket's next molecule); a table
+# of its own
+_STREAM_SIGS = {
+    "singa_dec_self_attn_rows": ([P] * 10 + [I32, I32, P, F32, P], I32),
+    "singa_sample_token_stream": ([P] * 6 + [I32, I32, I32, I32, I32, F32, I32, F32, I32, I32] + [P] * 7 + [P], I32),
+    "singa_stream_refill": ([I32] * 8 + [P] * 8 + [P], I32),
+    "singa_stream_refill_host": ([I32] * 8 + [P] * 8, I32),
+}
+STREAM_EXPORTS = tuple(_STREAM_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
-            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()):
+            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

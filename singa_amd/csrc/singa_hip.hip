@@ -24,6 +24,7 @@
 #include "../../include/singa_hip_gen.h"
 #include "../../include/singa_hip_force.h"
 #include "../../include/singa_hip_swor.h"
+#include "../../include/singa_hip_stream.h"
 #include "so3_index.h"
 
 namespace {
@@ -1362,6 +1363,9 @@ __device__ __forceinline__ float sum4(const float* partial, int N, int c) {
 
 // self-attention sub-block: q,k,v projections of the new position, k/v appended to the caches at `pos`, attention of
 // each head (wavefront h of the first four) over positions 0..pos, output projection + residual + LayerNorm.
+// ROWS (singa_dec_self_attn_rows, include/singa_hip_stream.h): one position per row instead of one for all; append, mask and
+// context sum depend on nothing but the row's own pos.  A row whose position lies outside the cache is left alone.
+template <bool ROWS>
 __global__ void __launch_bounds__(1024) dec_self_attn_kernel(const float* __restrict__ x, const float* __restrict__ wqkv_t,
                                                              const float* __restrict__ bqkv, const float* __restrict__ wo_t,
                                                              const float* __restrict__ bo, const float* __restrict__ gamma,
@@ -1370,7 +1374,10 @@ __global__ void __launch_bounds__(1024) dec_self_attn_kernel(const float* __rest
                                                              float* __restrict__ y, float eps) {
     __shared__ float xs[256], qkv[512], ps[4][256], ctx[256], partial[4 * 512], red[4];
     const int r = blockIdx.x, t = threadIdx.x, c = t & 255, part = t >> 8, h = c >> 6, lane = c & 63;
-    const int pos = (int)pos_ptr[0];
+    const int pos = (int)pos_ptr[ROWS ? r : 0];
+    if constexpr (ROWS) {
+        if (pos < 0 || pos >= P) return;                               // (uniform over the workgroup)
+    }
     if (t < 256) xs[t] = x[(long long)r * 256 + t];
     __syncthreads();
     gemv_quarter<2>(xs, 256, wqkv_t, partial);
@@ -1589,7 +1596,10 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
 // inside [0, V) replaces the choice (mask, filters and the uniform take no part) and the bookkeeping below runs unchanged;
 // the rank of the emitted token among the raw logits is one wave reduction over the registers the row already sits in.
 // <NPL, *, false> reads neither `forced` nor `rank`.
-template <int NPL, bool GRAMMAR, bool FORCED>
+// STREAM (singa_sample_token_stream, include/singa_hip_stream.h): `pos` holds one position per row, the uniform is column
+// mol[row] of `uniforms` and the bookkeeping goes to row mol[row] of the outputs, which are indexed by molecule; next and gstate
+// stay the row's.  A retired row (mol < 0) returns at once; `finished` and `live` are not read - the hand-over launch decides.
+template <int NPL, bool GRAMMAR, bool FORCED, bool STREAM>
 __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
                                                            const unsigned char* __restrict__ allowed,
                                                            const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
@@ -1599,22 +1609,31 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
                                                            long long* __restrict__ next, int32_t* __restrict__ live,
                                                            float* __restrict__ tok_logp, const unsigned char* __restrict__ cls,
                                                            int32_t* __restrict__ gstate, float* __restrict__ allowed_logp,
-                                                           const long long* __restrict__ forced, int32_t* __restrict__ rank) {
+                                                           const long long* __restrict__ forced, int32_t* __restrict__ rank,
+                                                           const int32_t* __restrict__ mol, int molecules) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                           // wave-uniform from here on
-    const long long t = *pos - pos_offset;                             // decoding step: reads uniforms[t], writes column t + 1
+    long long out = row;                                               // the row of the outputs, the column of the uniforms
+    if constexpr (STREAM) {
+        const int j = __builtin_amdgcn_readfirstlane(mol[row]);
+        if (j < 0 || j >= molecules) return;
+        out = j;
+    }
+    const long long t = pos[STREAM ? row : 0] - pos_offset;            // decoding step: reads uniforms[t], writes column t + 1
     if (t < 0 || t + 1 >= T) return;
-    const long long slot = (long long)row * T + t + 1;
-    if (finished[row]) {
-        if (lane == 0) {
-            tokens[slot] = pad;
-            next[row] = pad;
-            if (tok_logp) tok_logp[slot] = 0.f;
-            if (GRAMMAR && allowed_logp) allowed_logp[slot] = 0.f;
-            if (FORCED && rank) rank[slot] = 0;
+    const long long slot = out * T + t + 1;
+    if constexpr (!STREAM) {
+        if (finished[row]) {
+            if (lane == 0) {
+                tokens[slot] = pad;
+                next[row] = pad;
+                if (tok_logp) tok_logp[slot] = 0.f;
+                if (GRAMMAR && allowed_logp) allowed_logp[slot] = 0.f;
+                if (FORCED && rank) rank[slot] = 0;
+            }
+            return;
         }
-        return;
     }
     int given = -1;                                                    // FORCED: the token to take, -1 = this column is free
     if constexpr (FORCED) {
@@ -1721,7 +1740,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < NPL; ++k) part += keep[k] ? e[k] : 0.f;
         const float total = wave_sum64(part);
-        const float u = uniforms[t * rows + row];
+        const float u = uniforms[t * (STREAM ? molecules : rows) + out];
         float carry = 0.f;
         int hit = INT32_MAX, last = -1;
 #pragma unroll
@@ -1776,12 +1795,89 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
         tokens[slot] = tok;
         next[row] = tok;
         if (tok_logp) tok_logp[slot] = lp;
-        sum_logp[row] += lp;
-        length[row] += 1;
-        if (tok == eos) {
-            finished[row] = 1;
-            atomicSub(live, 1);
+        sum_logp[out] += lp;
+        length[out] += 1;
+        if constexpr (!STREAM) {
+            if (tok == eos) {
+                finished[row] = 1;
+                atomicSub(live, 1);
+            }
         }
+    }
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------ continuous sampling: the hand-over
+// include/singa_hip_stream.h states the rule.  What happens to one row is one source for the kernel and for
+// singa_stream_refill_host; the two differ in how `before` - the done rows of the pocket in front of this one - is counted.
+struct StreamRefill {
+    int R, num_samples, T, pos_offset, sos, eos, fresh;
+    long long* pos;
+    int32_t* mol;
+    long long* next;
+    int32_t *gstate, *row_of, *start_step;
+};
+
+__host__ __device__ inline bool stream_done(const StreamRefill& a, long long row) {
+    return a.mol[row] >= 0 && (a.next[row] == a.eos || a.pos[row] - a.pos_offset >= a.T - 2);
+}
+
+// row `row` of pocket b, live (mol >= 0); `issued` is the pocket's count before this step.  Returns true if the row retires.
+__host__ __device__ inline bool stream_hand_over(const StreamRefill& a, int b, long long row, bool done, int before, int issued) {
+    if (!done) {
+        a.pos[row] += 1;
+        return false;
+    }
+    const long long i = (long long)issued + before;
+    if (i >= a.num_samples) {
+        a.mol[row] = -1;
+        return true;
+    }
+    const long long j = (long long)b * a.num_samples + i;
+    a.start_step[j] = a.start_step[a.mol[row]] + (int32_t)(a.pos[row] - a.pos_offset) + 1;
+    a.row_of[j] = (int32_t)row;
+    a.mol[row] = (int32_t)j;
+    a.pos[row] = a.pos_offset;
+    a.next[row] = a.sos;
+    if (a.gstate) a.gstate[row] = a.fresh;
+    return false;
+}
+
+#ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
+// One workgroup of 1024 per pocket, rows in chunks of 1024 in ascending order: the done rows in front of a row are the carry of
+// the chunks before, the done rows of the waves before it in the chunk (LDS) and those of the lower lanes of its wave (ballot).
+__global__ void __launch_bounds__(1024) stream_refill_kernel(StreamRefill a, int32_t* __restrict__ issued_ptr,
+                                                             int32_t* __restrict__ live_ptr) {
+    __shared__ int wave_done[16], wave_live[16], wave_retired[16];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int issued = issued_ptr[b];
+    int carry = 0, live = 0, retired = 0;
+    for (int base = 0; base < a.R; base += 1024) {
+        const int i = base + t;
+        const long long row = (long long)b * a.R + i;
+        const bool alive = i < a.R && a.mol[row] >= 0;
+        const bool done = alive && stream_done(a, row);
+        const unsigned long long dmask = __ballot(done), amask = __ballot(alive);
+        if (lane == 0) wave_done[w] = __popcll(dmask), wave_live[w] = __popcll(amask);
+        __syncthreads();
+        int before = carry + __popcll(dmask & ((1ull << lane) - 1ull)), chunk = 0;
+        for (int k = 0; k < 16; ++k) {
+            before += k < w ? wave_done[k] : 0;
+            chunk += wave_done[k];
+            live += wave_live[k];
+        }
+        const bool gone = alive && stream_hand_over(a, b, row, done, before, issued);
+        const unsigned long long gmask = __ballot(gone);
+        if (lane == 0) wave_retired[w] = __popcll(gmask);
+        __syncthreads();
+        for (int k = 0; k < 16; ++k) retired += wave_retired[k];
+        carry += chunk;
+        __syncthreads();                                               // the counts are read before the next chunk overwrites them
+    }
+    if (t == 0 && live > 0) {                                          // a pocket without a live row writes nothing
+        const int left = a.num_samples - issued;
+        if (carry > 0) issued_ptr[b] = issued + (carry < left ? carry : left);
+        if (retired > 0) live_ptr[b] = live - retired;
     }
 }
 #endif
@@ -7069,9 +7165,21 @@ int singa_dec_self_attn(const float* x, const float* wqkv_t, const float* bqkv, 
         return fail(SINGA_E_NULL, "dec_self_attn: null pointer");
     if (P <= 0 || P > 256) return fail(SINGA_E_SHAPE, "dec_self_attn: built for at most 256 cached positions");
     if (R <= 0) return SINGA_OK;
-    hipLaunchKernelGGL(dec_self_attn_kernel, dim3(R), dim3(1024), 0, (hipStream_t)stream, x, wqkv_t, bqkv, wo_t, bo, gamma, beta,
-                       k_cache, v_cache, pos, P, y, eps);
+    hipLaunchKernelGGL(dec_self_attn_kernel<false>, dim3(R), dim3(1024), 0, (hipStream_t)stream, x, wqkv_t, bqkv, wo_t, bo, gamma,
+                       beta, k_cache, v_cache, pos, P, y, eps);
     return check_launch("dec_self_attn");
+}
+
+int singa_dec_self_attn_rows(const float* x, const float* wqkv_t, const float* bqkv, const float* wo_t, const float* bo,
+                             const float* gamma, const float* beta, float* k_cache, float* v_cache, const long long* pos, int R,
+                             int P, float* y, float eps, void* stream) {
+    if (!x || !wqkv_t || !bqkv || !wo_t || !bo || !gamma || !beta || !k_cache || !v_cache || !pos || !y)
+        return fail_at(SINGA_E_NULL, "dec_self_attn_rows", "null pointer");
+    if (P <= 0 || P > 256) return fail_at(SINGA_E_SHAPE, "dec_self_attn_rows", "built for at most 256 cached positions");
+    if (R <= 0) return SINGA_OK;
+    hipLaunchKernelGGL(dec_self_attn_kernel<true>, dim3(R), dim3(1024), 0, (hipStream_t)stream, x, wqkv_t, bqkv, wo_t, bo, gamma,
+                       beta, k_cache, v_cache, pos, P, y, eps);
+    return check_launch("dec_self_attn_rows");
 }
 
 int singa_dec_cross_attn(const float* y, const float* wq_t, const float* bq, const float* ck, const float* cv,
@@ -7101,17 +7209,19 @@ enum GrammarOperands { GRAMMAR_NONE, GRAMMAR_OPTIONAL, GRAMMAR_REQUIRED };
 
 // The one place where a token choice is validated and launched: singa_sample_token, _grammar and _forced are this function
 // with their name, the operands they do not have as null pointers, and the two facts in which they differ.  The grammar runs
-// where cls and gstate are given, forcing where `forced` is.
+// where cls and gstate are given, forcing where `forced` is, the stream form (singa_sample_token_stream: positions per row,
+// outputs per molecule, neither `finished` nor `live`) where `mol` is.
 int sample_choice(const char* name, GrammarOperands gram, bool need_forced, const float* logits, const float* uniforms,
                   const unsigned char* allowed, const unsigned char* cls, const long long* pos, int pos_offset, int rows, int V,
                   int T, float tau, int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
                   float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp, int32_t* gstate,
-                  float* allowed_logp, const long long* forced, int32_t* rank, void* stream) {
+                  float* allowed_logp, const long long* forced, int32_t* rank, void* stream, const int32_t* mol = nullptr,
+                  int molecules = 0) {
     static const char* const columns[] = {"T >= 2 columns, eos / pad inside the vocabulary",
                                           "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary",
                                           "T >= 3 columns, eos / pad inside the vocabulary"};
     const bool grammar = cls && gstate;
-    if (!logits || !uniforms || !pos || !finished || !length || !sum_logp || !tokens || !next || !live ||
+    if (!logits || !uniforms || !pos || (!mol && (!finished || !live)) || !length || !sum_logp || !tokens || !next ||
         (gram == GRAMMAR_REQUIRED && !grammar) || (need_forced && !forced))
         return fail_at(SINGA_E_NULL, name, "null pointer");
     if (!grammar && (cls || gstate || allowed_logp))
@@ -7129,11 +7239,18 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
     const dim3 grid((rows + 3) / 4), block(256);
     dispatch_npl(V, [&](auto npl) {
         dispatch_flag(grammar, [&](auto g) {
+            if (mol) {                                                 // (the stream form is not built with forced tokens)
+                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, false, true>), grid, block, 0,
+                                   (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, top_k, top_p,
+                                   eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate, allowed_logp,
+                                   forced, rank, mol, molecules);
+                return;
+            }
             dispatch_flag(forced != nullptr, [&](auto f) {
-                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value>), grid,
-                                   block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau,
-                                   top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,
-                                   allowed_logp, forced, rank);
+                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value, false>),
+                                   grid, block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T,
+                                   tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls,
+                                   gstate, allowed_logp, forced, rank, mol, molecules);
             });
         });
     });
@@ -7169,6 +7286,75 @@ int singa_sample_token_forced(const float* logits, const float* uniforms, const 
     return sample_choice("sample_token_forced", GRAMMAR_OPTIONAL, true, logits, uniforms, allowed, cls, pos, pos_offset, rows, V,
                          T, tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, gstate,
                          allowed_logp, forced, rank, stream);
+}
+
+int singa_sample_token_stream(const float* logits, const float* uniforms, const unsigned char* allowed,
+                              const unsigned char* cls, const long long* pos, const int32_t* mol, int pos_offset, int rows,
+                              int molecules, int V, int T, float tau, int top_k, float top_p, int eos, int pad,
+                              int32_t* length, float* sum_logp, long long* tokens, long long* next, float* tok_logp,
+                              int32_t* gstate, float* allowed_logp, void* stream) {
+    if (!mol) return fail_at(SINGA_E_NULL, "sample_token_stream", "null pointer");
+    if (molecules < 1) return fail_at(SINGA_E_SHAPE, "sample_token_stream", "molecules must be >= 1");
+    return sample_choice("sample_token_stream", GRAMMAR_OPTIONAL, false, logits, uniforms, allowed, cls, pos, pos_offset, rows, V,
+                         T, tau, top_k, top_p, eos, pad, nullptr, length, sum_logp, tokens, next, nullptr, tok_logp, gstate,
+                         allowed_logp, nullptr, nullptr, stream, mol, molecules);
+}
+
+namespace {
+// the checks singa_stream_refill and its host twin share; 0 = go on
+int stream_refill_check(const char* name, int pockets, int R, int num_samples, int T, const long long* pos, const int32_t* mol,
+                        const long long* next, const int32_t* gstate, const int32_t* issued, const int32_t* live,
+                        const int32_t* row_of, const int32_t* start_step) {
+    if (!pos || !mol || !next || !issued || !live || !row_of || !start_step) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (R < 1 || R > 2048) return fail_at(SINGA_E_SHAPE, name, "R: 1..2048 rows per pocket");
+    if (num_samples < 1) return fail_at(SINGA_E_SHAPE, name, "num_samples must be >= 1");
+    if (T < (gstate ? 3 : 2)) return fail_at(SINGA_E_SHAPE, name, "T >= 2 columns (3 under the grammar)");
+    if (pockets < 0 || (long long)pockets * num_samples > INT32_MAX || (long long)pockets * R > INT32_MAX)
+        return fail_at(SINGA_E_SHAPE, name, "pockets >= 0, and at most 2^31 rows and molecules");
+    return SINGA_OK;
+}
+}  // namespace
+
+int singa_stream_refill(int pockets, int R, int num_samples, int T, int pos_offset, int sos, int eos, int fresh, long long* pos,
+                        int32_t* mol, long long* next, int32_t* gstate, int32_t* issued, int32_t* live, int32_t* row_of,
+                        int32_t* start_step, void* stream) {
+    const char* name = "stream_refill";
+    if (const int e = stream_refill_check(name, pockets, R, num_samples, T, pos, mol, next, gstate, issued, live, row_of, start_step))
+        return e;
+    if (pockets == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const StreamRefill a{R, num_samples, T, pos_offset, sos, eos, fresh, pos, mol, next, gstate, row_of, start_step};
+    hipLaunchKernelGGL(stream_refill_kernel, dim3(pockets), dim3(1024), 0, (hipStream_t)stream, a, issued, live);
+    return check_launch(name);
+#endif
+}
+
+int singa_stream_refill_host(int pockets, int R, int num_samples, int T, int pos_offset, int sos, int eos, int fresh,
+                             long long* pos, int32_t* mol, long long* next, int32_t* gstate, int32_t* issued, int32_t* live,
+                             int32_t* row_of, int32_t* start_step) {
+    if (const int e = stream_refill_check("stream_refill_host", pockets, R, num_samples, T, pos, mol, next, gstate, issued, live,
+                                          row_of, start_step))
+        return e;
+    const StreamRefill a{R, num_samples, T, pos_offset, sos, eos, fresh, pos, mol, next, gstate, row_of, start_step};
+    for (int b = 0; b < pockets; ++b) {
+        int before = 0, alive = 0, retired = 0;
+        for (int i = 0; i < R; ++i) {
+            const long long row = (long long)b * R + i;
+            if (mol[row] < 0) continue;
+            const bool done = stream_done(a, row);
+            ++alive;
+            retired += stream_hand_over(a, b, row, done, before, issued[b]) ? 1 : 0;
+            before += done ? 1 : 0;
+        }
+        if (alive > 0) {
+            const int left = num_samples - issued[b];
+            if (before > 0) issued[b] += before < left ? before : left;
+            if (retired > 0) live[b] = alive - retired;
+        }
+    }
+    return SINGA_OK;
 }
 
 int singa_smiles_rule_host(const unsigned char* cls, const int32_t* state, const int32_t* rem, int n, unsigned char* ok,

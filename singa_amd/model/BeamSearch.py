@@ -129,20 +129,29 @@ class KVDecoder:
         self.k.copy_(self.k.index_select(1, src_rows))
         self.v.copy_(self.v.index_select(1, src_rows))
 
-    def token_input(self, tokens):
+    def token_input(self, tokens, row_pos=None):
+        """`row_pos` [rows] int64: one position per row instead of the decoder's own `pos` (`Sampling.sample_stream`)."""
         d = self.dec
-        x = d.mol_emb.weight.index_select(0, tokens) + d.pos_emb.pe[:, 0].index_select(0, self.pos - self.num)
+        x = d.mol_emb.weight.index_select(0, tokens) + d.pos_emb.pe[:, 0].index_select(0, (self.pos if row_pos is None else row_pos) - self.num)
         return x + d.type_emb.weight[1] if d.num_props else x
 
     def prop_input(self, prop):
         d = self.dec
         return d.prop_nn(prop) + d.type_emb.weight[0]
 
-    def advance(self, x, k=None, v=None):
+    def advance(self, x, k=None, v=None, row_pos=None):
         """x [rows, hidden]: decoder input at position `pos` -> decoder output at that position; pos += 1.  `k`, `v`: the
         caches to append to and attend over instead of the decoder's own (same shapes; `sample_distinct` alternates between
-        two pairs of buffers)."""
+        two pairs of buffers).  `row_pos` [rows] int64: row r is at position row_pos[r] instead, and nothing is advanced - the
+        positions are the caller's to move (`Sampling.sample_stream`; the k17 step kernels only)."""
         k, v = self.k if k is None else k, self.v if v is None else v
+        if row_pos is not None:
+            if not self.fused:
+                raise ValueError("KVDecoder.advance: one position per row needs the k17 step kernels (fused)")
+            for l in range(len(self.dec.layers)):
+                x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], row_pos, self.cross_k[l], self.cross_v[l],
+                                       self.pad_u8, self.beams, per_row=True)
+            return x
         if self.fused:
             # three hand-written launches per layer (singa_dec_*): q/k/v + cache append + attention + projection + LayerNorm,
             # encoder-decoder attention, feed-forward - instead of ~33 library / elementwise launches on 20-row operands

@@ -44,7 +44,15 @@ pocket, the row state gathered from the parents) and `ops.swor_follow` (one laun
 cache rows from one cache buffer to the other; the step is captured twice, for even and odd tokens, and the two graphs are
 replayed in turn).  `swor_weights` turns the run's `gumbel` / `prop_logp` into the importance weights of the paper's estimator.
 
-What the two loops share is written once: `_prologue` (the checks and figures both start from), `BeamSearch.encode_pockets`,
+`sample_stream` makes the number of ROWS a fixed budget and the number of molecules free: `rows_per_pocket` rows per pocket
+decode `num_samples` molecules per pocket, and a row that has ended its molecule starts the pocket's next one in the following
+step (include/singa_hip_stream.h states the rule).  Every row is at a position of its own, so the step is: the per-row token
+input, the decoder layers with `singa_dec_self_attn_rows`, the projection, `ops.sample_token_stream` (the choice of `sample`,
+with the uniform and the bookkeeping indexed by the row's molecule) and `ops.stream_refill` (the hand-over, which is also
+where positions move) - one captured graph.  A molecule is a function of its pocket, the pocket's property prompt, the
+settings and its own column of the uniforms, so the result is `sample`'s, bit for bit, whatever the row budget.
+
+What the loops share is written once: `_prologue` (the checks and figures both start from), `BeamSearch.encode_pockets`,
 `BeamSearch.capture_steps` (warm-up on a side stream, one HIP graph per step body) and `_decode` (replay, count, poll).
 """
 import numpy as np
@@ -262,6 +270,119 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
         for k in keys:
             out[k].append([host[k][r, 1:1 + lengths[r]].copy() for r in rows])
     return out
+
+
+STREAM_MAX_ROWS = 2048  # rows per pocket singa_stream_refill is built for
+
+
+@torch.no_grad()
+def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, rows_per_pocket=64, device="cuda",
+                  temperature=1.0, top_k=0, top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, trace=None,
+                  grammar=None):
+    """`sample` on a fixed budget of rows: `num_samples` molecules for each of the `batch_size` pockets of `example`, decoded on
+    batch_size * `rows_per_pocket` rows; a row that has ended its molecule ('$', or the last column) starts the pocket's next
+    one in the following step, until the pocket has none left (include/singa_hip_stream.h states the rule).  Rows that have
+    ended cost nothing but the tail of the run, and the key / value caches are those of the rows, not of the molecules.
+
+    `model`, `smiVoc`, `example`, `device`, `temperature`, `top_k`, `top_p`, `suppress`, `graph` and `grammar` as in `sample`.
+    `prop`: [batch_size, num_props], ONE property prompt per pocket (a row keeps cache position 0 across its molecules).
+    `uniforms`: [max_length, batch_size * num_samples] f32, column j belongs to MOLECULE j (row t is read by the step that
+    writes the molecule's column t + 1); drawn once per call from `generator` if not given.
+
+    Returns the int64 token matrix [batch_size * num_samples, max_length], pocket-major, with `sample`'s conventions.  Molecule
+    j is a function of its pocket, the pocket's prompt, the settings and uniforms[:, j] alone: the result does not depend on
+    `rows_per_pocket` and equals, bit for bit, what `sample` returns for `num_samples` rows per pocket given the same uniforms
+    and `prop` repeated per row - tokens and everything `trace` receives: `lengths`, `sum_logp`, `token_logp`, `uniforms`,
+    `path`, `steps` (steps of the run) and, under `grammar`, `allowed_logp`, all indexed by molecule, plus `row_of` (int32: the
+    row that decoded the molecule) and `start_step` (int32: the step of the run, from 0, that chose its first token).
+
+    ValueError before any device work for a `prop` of another shape, `rows_per_pocket` outside 1..2048, a decoder geometry,
+    length or pocket size the k17 step kernels are not built for (they are the only path), and a run whose caches and
+    per-molecule buffers do not fit the free memory.  Forced tokens are not part of this mode."""
+    dev, tf, voc, (sos, eos, pad), mols, num, positions, free, cls, allowed = _prologue(
+        "sample_stream", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
+    R, V = int(rows_per_pocket), len(voc)
+    if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
+        raise ValueError(f"sample_stream: temperature >= 0, top_k >= 0, 0 < top_p <= 1 (got {temperature}, {top_k}, {top_p})")
+    if not 1 <= R <= STREAM_MAX_ROWS:
+        raise ValueError(f"sample_stream: rows_per_pocket of 1..{STREAM_MAX_ROWS} is supported (got {rows_per_pocket})")
+    if num and (prop is None or tuple(prop.shape) != (batch_size, tf.decoder.num_props)):
+        raise ValueError(f"sample_stream: prop must be [batch_size, num_props] = [{batch_size}, {tf.decoder.num_props}], one prompt "
+                         f"per pocket; a prompt per row is unsupported (got {None if prop is None else tuple(prop.shape)})")
+    a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
+    atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
+    if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
+            and positions <= 256 and atoms <= 1024 and V <= 1024):
+        raise ValueError("sample_stream: unsupported decoder geometry - the k17 step kernels are the only path: the shipped "
+                         "decoder geometry, at most 256 positions, 1024 pocket atoms and 1024 tokens")
+    rows = batch_size * R
+    need = cache_bytes(tf.decoder, rows, positions) + mols * max_length * (8 + 4 + 4 + 4)
+    if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
+        raise ValueError(f"sample_stream: the key / value caches of {rows} rows x {positions} positions and the outputs and "
+                         f"uniforms of {mols} molecules take {need} bytes, {free} bytes are free on {dev}: unsupported - use "
+                         f"fewer rows per pocket or draw fewer molecules per call")
+    if uniforms is None:
+        gdev = generator.device if generator is not None else dev
+        uniforms = torch.rand((max_length, mols), generator=generator, device=gdev, dtype=torch.float32)
+    if tuple(uniforms.shape) != (max_length, mols) or uniforms.dtype != torch.float32:
+        raise ValueError(f"sample_stream: uniforms must be float32 [max_length, molecules] = [{max_length}, {mols}], got "
+                         f"{uniforms.dtype} {tuple(uniforms.shape)}")
+    uniforms = uniforms.to(dev).contiguous()
+
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), R, positions, V, True, search_buffers=False)
+    if not kv.fused:
+        raise ValueError("sample_stream: unsupported decoder geometry for the k17 step kernels")
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+    state = {"tokens": torch.empty(mols, max_length, dtype=torch.int64, device=dev), "tok_logp": torch.empty(mols, max_length, **f32),
+             "length": torch.empty(mols, **i32), "sum_logp": torch.empty(mols, **f32), "row_of": torch.empty(mols, **i32),
+             "start_step": torch.empty(mols, **i32), "next": torch.empty(rows, dtype=torch.int64, device=dev),
+             "pos": torch.empty(rows, dtype=torch.int64, device=dev), "mol": torch.empty(rows, **i32),
+             "issued": torch.empty(batch_size, **i32), "live": torch.empty(batch_size, **i32)}
+    if grammar is not None:
+        cls = torch.as_tensor(cls).to(dev)
+        state["grammar"] = torch.empty(rows, **i32)
+        state["allowed_logp"] = torch.empty(mols, max_length, **f32)
+    # the start of a run: the first min(R, num_samples) rows of pocket b hold its first molecules, the others are retired
+    first = min(R, num_samples)
+    mol0 = np.full((batch_size, R), -1, np.int32)
+    mol0[:, :first] = np.arange(batch_size)[:, None] * num_samples + np.arange(first)[None]
+    row0 = np.zeros((batch_size, num_samples), np.int32)
+    row0[:, :first] = np.arange(batch_size)[:, None] * R + np.arange(first)[None]
+    mol0, row0 = torch.as_tensor(mol0.reshape(-1)).to(dev), torch.as_tensor(row0.reshape(-1)).to(dev)
+
+    def start():
+        state["tokens"].fill_(pad)
+        state["tokens"][:, 0] = sos
+        state["next"].fill_(sos)
+        state["length"].zero_(), state["sum_logp"].zero_(), state["tok_logp"].zero_(), state["start_step"].zero_()
+        state["mol"].copy_(mol0), state["row_of"].copy_(row0)
+        state["pos"].fill_(num)
+        state["issued"].fill_(first), state["live"].fill_(first)
+        if grammar is not None:
+            state["grammar"].fill_(smiles.FRESH), state["allowed_logp"].zero_()
+        kv.reset()
+
+    def step():
+        out = kv.advance(kv.token_input(state["next"], state["pos"]), row_pos=state["pos"])
+        ops.sample_token_stream(tf.projection(out).contiguous(), uniforms, state["pos"], state["mol"], num, state, float(temperature),
+                                int(top_k), float(top_p), eos, pad, allowed, cls=cls)
+        ops.stream_refill(state["pos"], state["mol"], num, state, R, num_samples, max_length, sos, eos, smiles.FRESH,
+                          grammar is not None)
+
+    replays = capture_steps(start, [step], 2) if graph else [step]
+    start()
+    if num:                                                            # position 0 of every row is its pocket's property prompt
+        kv.advance(kv.prop_input(prop.to(dev).float().repeat_interleave(R, 0)))
+    live = lambda: int(state["live"].sum().item())
+    steps = _decode(replays, (-(-num_samples // R) + 1) * (max_length - 1), live)
+    if live() != 0:
+        raise RuntimeError(f"sample_stream: {live()} rows still hold a molecule after {steps} steps")
+    if trace is not None:
+        trace.update(lengths=state["length"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"], uniforms=uniforms,
+                     path="k17", steps=steps, row_of=state["row_of"], start_step=state["start_step"])
+        if grammar is not None:
+            trace.update(allowed_logp=state["allowed_logp"])
+    return state["tokens"]
 
 
 SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for

@@ -792,17 +792,23 @@ def ln_silu(x, gamma, beta, eps=1e-5):
     return _LnSilu.apply(x, gamma, beta, eps)
 
 
-def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams):
+def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, per_row=False):
     """One decoder layer for one new position of every beam-search row (k17; inference only, no autograd): three launches.
     `w`: dict of the layer's transposed weights as built by BeamSearch.KVDecoder; k_cache [R,4,P,32], v_cache [R,4,P,64];
-    pos: int64 device scalar; cross_k [B,4,32,S], cross_v [B,4,S,64], pad [B,S] uint8."""
+    pos: int64 device scalar; cross_k [B,4,32,S], cross_v [B,4,S,64], pad [B,S] uint8.  `pos` of shape [R] (more than one
+    dimension-0 entry, or `per_row=True`) is one position per row: the self-attention launch is `singa_dec_self_attn_rows` of
+    include/singa_hip_stream.h, the other two launches do not depend on the position."""
     _dev(x, k_cache, v_cache, cross_k, cross_v)
     lib, st = _lib.lib(), _stream()
     R, P, S = x.shape[0], k_cache.shape[2], cross_v.shape[2]
     y, z, out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     a, c, f = w["self"], w["cross"], w["ffn"]
-    _chk(lib.singa_dec_self_attn(_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]), _p(a["beta"]),
-                                 _p(k_cache), _p(v_cache), _p(pos), R, P, _p(y), a["eps"], st), "singa_dec_self_attn")
+    if per_row:
+        _check_views("dec_layer_step", ((pos, torch.int64, (R,)),))
+    self_attn, name = (lib.singa_dec_self_attn_rows, "singa_dec_self_attn_rows") if per_row else \
+        (lib.singa_dec_self_attn, "singa_dec_self_attn")
+    _chk(self_attn(_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]), _p(a["beta"]), _p(k_cache),
+                   _p(v_cache), _p(pos), R, P, _p(y), a["eps"], st), name)
     _chk(lib.singa_dec_cross_attn(_p(y), _p(c["wq_t"]), _p(c["bq"]), _p(cross_k), _p(cross_v), _p(pad), _p(c["wo_t"]), _p(c["bo"]),
                                   _p(c["gamma"]), _p(c["beta"]), R, beams, S, _p(z), c["eps"], st), "singa_dec_cross_attn")
     _chk(lib.singa_dec_ffn(_p(z), _p(f["w1_t"]), _p(f["b1"]), _p(f["w2_t"]), _p(f["b2"]), _p(f["gamma"]), _p(f["beta"]), R, _p(out),
@@ -885,6 +891,50 @@ def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=No
     chooses as the unforced op does, bit for bit.  `state` as for those ops (grammar [R] int32 and, optionally, allowed_logp
     under the grammar) and, optionally, rank [R, T] int32: the rank of every emitted token among the row's raw logits."""
     sample_token(logits, uniforms, pos, pos_offset, state, temperature, top_k, top_p, eos, pad, allowed, cls=cls, forced=forced)
+
+
+def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0,
+                        allowed=None, cls=None):
+    """`sample_token` (cls=None) or `sample_token_grammar` for rows that hold a molecule each (`singa_sample_token_stream`,
+    include/singa_hip_stream.h states the rule; inference only): logits [R, V] f32; pos [R] int64, the rows' own positions (a
+    row's step is pos - pos_offset); mol [R] int32, the molecule a row decodes (-1: retired, the row is skipped); uniforms
+    [>= T - 1, M] f32, one column per molecule.  `state`: tokens [M, T] int64, length [M] int32, sum_logp [M] f32 and,
+    optionally, tok_logp [M, T] f32 - indexed by molecule - and next [R] int64; with `cls` also grammar [R] int32 and, optionally,
+    allowed_logp [M, T] f32.  Updated in place, bit for bit as the per-row ops update a row that draws the same logits."""
+    R, V = logits.shape
+    M, T = state["tokens"].shape
+    gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
+    _check_views("sample_token_stream", (
+        (logits, torch.float32, (R, V)), (uniforms, torch.float32, None), (pos, torch.int64, (R,)), (mol, torch.int32, (R,)),
+        (state["tokens"], torch.int64, (M, T)), (state["length"], torch.int32, (M,)), (state["sum_logp"], torch.float32, (M,)),
+        (state.get("tok_logp"), torch.float32, (M, T)), (state["next"], torch.int64, (R,)), (allowed, torch.uint8, (V,)),
+        (cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)), (alp, torch.float32, (M, T))))
+    if uniforms.dim() != 2 or uniforms.shape[1] != M or uniforms.shape[0] < T - 1:
+        raise RuntimeError(f"sample_token_stream: uniforms [>= T - 1, molecules], got {tuple(uniforms.shape)} for T = {T}, {M} molecules")
+    _lib.ensure_init(logits.device.index if logits.device.index is not None else torch.cuda.current_device())
+    _chk(_lib.lib().singa_sample_token_stream(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), _p(mol), pos_offset, R, M, V,
+                                              T, temperature, top_k, top_p, eos, pad, _p(state["length"]), _p(state["sum_logp"]),
+                                              _p(state["tokens"]), _p(state["next"]), _p(state.get("tok_logp")), _p(gstate), _p(alp),
+                                              _stream()), "singa_sample_token_stream")
+
+
+def stream_refill(pos, mol, pos_offset, state, rows_per_pocket, num_samples, T, sos=0, eos=0, fresh=0, grammar=False):
+    """The hand-over of continuous sampling (`singa_stream_refill`, include/singa_hip_stream.h states the rule): per pocket the
+    rows that have ended their molecule take the pocket's next molecules in ascending row order, or retire; every other live
+    row moves on by one position.  pos [R] int64, mol [R] int32, `state`: next [R] int64, issued / live [pockets] int32, row_of /
+    start_step [pockets * num_samples] int32 and, with `grammar`, grammar [R] int32 (restarted at `fresh`).  One launch, one
+    workgroup per pocket."""
+    B = state["issued"].shape[0]
+    R, M = B * rows_per_pocket, B * num_samples
+    gstate = state["grammar"] if grammar else None
+    _check_views("stream_refill", ((pos, torch.int64, (R,)), (mol, torch.int32, (R,)), (state["next"], torch.int64, (R,)),
+                                   (gstate, torch.int32, (R,)), (state["issued"], torch.int32, (B,)),
+                                   (state["live"], torch.int32, (B,)), (state["row_of"], torch.int32, (M,)),
+                                   (state["start_step"], torch.int32, (M,))))
+    _lib.ensure_init(pos.device.index if pos.device.index is not None else torch.cuda.current_device())
+    _chk(_lib.lib().singa_stream_refill(B, rows_per_pocket, num_samples, T, pos_offset, sos, eos, fresh, _p(pos), _p(mol),
+                                        _p(state["next"]), _p(gstate), _p(state["issued"]), _p(state["live"]), _p(state["row_of"]),
+                                        _p(state["start_step"]), _stream()), "singa_stream_refill")
 
 
 def swor_work(rows, T, device):

@@ -4,7 +4,7 @@ atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket w
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
     python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
-                                  [--distinct]
+                                  [--distinct] [--rows-per-pocket R]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
@@ -17,7 +17,13 @@ the k17 step with a forced prefix of 5 tokens next to the plain one at rows = 20
 as a whole - encoder, cache set-up, graph capture and
 every step - and divided by its steps, as bench_beam.py does.  With `--distinct` also `sample_distinct` (sampling without
 replacement: expand, select and the cache move inside the step, two captured graphs) next to the plain k17 step at rows = 128,
-512, 2048 for the one pocket, interleaved (`distinct_table`).
+512, 2048 for the one pocket, interleaved (`distinct_table`).  With `--rows-per-pocket R` nothing but continuous sampling
+(`sample_stream`) is measured: `stream_table` - the streaming step (per-row positions, choice by molecule, hand-over) next to
+the plain k17 step at rows = 128, 512, 2048 on the synthetic pocket, one molecule per row so that both run max_length - 1 steps,
+interleaved - and `throughput` - on the `beam_b2_k6_eos` golden model (tests/golden; its rows end all over a 41-column
+window), 4,096 molecules per pocket through `sample_stream(rows_per_pocket=R)` against `sample` called 16 times with 256 rows
+per pocket, whole calls timed, with the length distribution of the run and the ratio it predicts: (steps until the longest
+of 256 rows has ended, as the polling loop sees it) / (mean length).
 """
 import argparse
 import json
@@ -47,6 +53,8 @@ def main():
     ap.add_argument("--distinct", action="store_true", help="also time sample_distinct next to the plain step (distinct_table)")
     ap.add_argument("--distinct-only", type=int, default=0, metavar="ROWS",
                     help="nothing but two sample_distinct generations of ROWS slots: the run to take a kernel trace of")
+    ap.add_argument("--rows-per-pocket", type=int, default=0, metavar="R",
+                    help="nothing but sample_stream: the streaming step next to the plain one, and molecules / s at R rows per pocket")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -56,7 +64,7 @@ def main():
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
-    from singa_amd.model.Sampling import sample, sample_distinct, score
+    from singa_amd.model.Sampling import LIVE_POLL, sample, sample_distinct, sample_stream, score
     dev = torch.device("cuda", 0)
     cfg = load_config(lmax=2)
     torch.manual_seed(cfg.train.seed)
@@ -111,6 +119,70 @@ def main():
                                                     temperature=args.temperature, suppress=("$",), seed=rows, trace=tr) is None
                             or tr["steps"]))
         print(json.dumps({"distinct_only_rows": rows, "ms_per_step": [round(x, 4) for x in ms]}))
+        return
+    if args.rows_per_pocket:
+        def run_stream(rows):
+            tr = {}
+            sample_stream(model, voc, rows, 1, T, ex, torch.ones(1, 3, device=dev), rows, device=dev, temperature=args.temperature,
+                          top_k=args.top_k, top_p=args.top_p, suppress=("$",), generator=gen, trace=tr)
+            return tr["steps"]
+        stable = []
+        for rows in (128, 512, 2048):
+            run_sample(rows, True), run_stream(rows)
+            plain, strm = [], []
+            for _ in range(3 if rows >= 512 else args.reps):
+                plain.append(timed(lambda: run_sample(rows, True)))
+                strm.append(timed(lambda: run_stream(rows)))
+            stable.append({"rows": rows, "path": "k17", "plain_ms_per_step": round(statistics.median(plain), 4),
+                           "stream_ms_per_step": round(statistics.median(strm), 4),
+                           "plain_runs_ms": [round(x, 4) for x in plain], "stream_runs_ms": [round(x, 4) for x in strm]})
+        # molecules / s on the golden model whose rows end early
+        import numpy as np
+        from tests.helpers import golden, smi_voc
+        from tests.test_beam_gpu import build_model
+        from tests.test_sampling_gpu import example_of
+        z = golden("beam_b2_k6_eos.npz")
+        gmodel, gex, gvoc, B, Tg, R = build_model(z)[0], example_of(z), smi_voc(), len(z["names"]), 41, args.rows_per_pocket
+        n, chunk = 4096, 256
+        u = torch.rand(Tg, B * n, generator=torch.Generator().manual_seed(1))
+        prop1 = torch.as_tensor(z["prop"][:1]).float()
+        lengths = []
+
+        def chunks():
+            lengths.clear()
+            for c in range(n // chunk):
+                cols = torch.cat([torch.arange(b * n + c * chunk, b * n + (c + 1) * chunk) for b in range(B)])
+                tr = {}
+                sample(gmodel, gvoc, chunk, B, Tg, gex, prop1.repeat(B * chunk, 1).to(dev), device=dev, uniforms=u[:, cols], fused=True,
+                       trace=tr)
+                lengths.append(tr["lengths"].cpu().numpy())
+            return 1
+
+        def streamed():
+            tr = {}
+            sample_stream(gmodel, gvoc, n, B, Tg, gex, prop1.repeat(B, 1).to(dev), R, device=dev, uniforms=u, trace=tr)
+            streamed.steps = tr["steps"]
+            return 1
+        chunks(), streamed()
+        t_chunks, t_stream = [], []
+        for _ in range(3):
+            t_chunks.append(timed(chunks) / 1e3)
+            t_stream.append(timed(streamed) / 1e3)
+        per_chunk = [int(-(-l.max() // LIVE_POLL) * LIVE_POLL) for l in lengths]
+        flat = np.concatenate(lengths)
+        mean = float(flat.mean())
+        sc, ss = statistics.median(t_chunks), statistics.median(t_stream)
+        res = {"metric": "stream_molecules_per_s", "unit": "molecules/s", "value": round(B * n / ss, 1), "stream_table": stable,
+               "throughput": {"model": "beam_b2_k6_eos", "pockets": B, "molecules_per_pocket": n, "max_length": Tg,
+                              "rows_per_pocket": R, "stream_seconds": [round(x, 4) for x in t_stream], "stream_steps": streamed.steps,
+                              "sample_16x256_seconds": [round(x, 4) for x in t_chunks],
+                              "stream_molecules_per_s": round(B * n / ss, 1), "sample_molecules_per_s": round(B * n / sc, 1),
+                              "observed_ratio": round(sc / ss, 3),
+                              "lengths": {"mean": round(mean, 2), "min": int(flat.min()), "max": int(flat.max()),
+                                          "deciles": [int(x) for x in np.percentile(flat, range(10, 100, 10))]},
+                              "steps_per_256_row_call": per_chunk,
+                              "predicted_ratio": round(statistics.mean(per_chunk) / mean, 3)}}
+        print(json.dumps(res))
         return
     fused = {"auto": None, "k17": True, "library": False}[args.fused]
     run_beam(), run_sample(20, None), run_sample(args.rows, fused)           # warm-up: library initialisation, code objects
