@@ -10,8 +10,10 @@ The reference's PDB / docking front end is out of scope, so pock
 example graphs the reference bundles) or `--data synthetic`.  No chemistry toolkit is required: the sequences are written as
 they were decoded, without a validity filter.  `--grammar smiles` (sample mode) removes the syntactic rejects where the token
 is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired ring-closure digits and no
-dangling bond symbol (include/singa_hip_gen.h states the rule).  Chemical validity - valence, aromaticity, duplicate ring
-bonds - is still not checked, and beam search is not constrained.  `--prefix TEXT` (sample mode) starts every sequence with
+dangling bond symbol (include/singa_hip_gen.h states the rule).  Under `--grammar smiles` chemical validity - valence,
+aromaticity, duplicate ring bonds - is still not checked, and beam search is not constrained.  `--grammar valence` (sample mode only) adds a
+bonding-capacity rule: no atom of a sequence carries more bond order than its token can (include/singa_hip_valence.h; a necessary
+condition for validity - aromaticity and duplicate ring bonds stay unchecked).  `--prefix TEXT` (sample mode) starts every sequence with
 that fragment - a scaffold to continue; under `--grammar smiles` a fragment the rule refuses is an error before anything runs.
 `--mode score --molecules FILE` draws nothing: FILE holds lines of `pocket name<TAB>SMILES`, and every molecule's
 log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input.
@@ -53,7 +55,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
-    ap.add_argument("--grammar", choices=["none", "smiles"], default="none",
+    ap.add_argument("--grammar", choices=["none", "smiles", "valence"], default="none",
                     help="sample: draw only tokens that keep the sequence a completable SMILES string")
     ap.add_argument("--rows-per-pocket", type=int, default=None, metavar="R",
                     help="sample: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
@@ -69,6 +71,7 @@ def main():
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
     assert args.grammar == "none" or args.mode in ("sample", "distinct"), \
         "--grammar constrains sampling only: beam search selects on the host"
+    assert args.grammar != "valence" or args.mode == "sample", "--grammar valence: sample mode only (distinct gathers one state word)"
     assert args.mode != "distinct" or (args.top_k == 0 and args.top_p == 1.0), "--mode distinct takes no --top-k / --top-p"
     assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
     assert args.rows_per_pocket is None or (args.mode == "sample" and args.prefix is None), \

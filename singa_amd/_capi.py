@@ -168,12 +168,19 @@ _STREAM_SIGS = {
 }
 STREAM_EXPORTS = tuple(_STREAM_SIGS)
 
+# include/singa_hip_valence.h: valence-aware token choice (`grammar="valence"`); a table of its own
+_VALENCE_SIGS = {
+    "singa_sample_token_valence": ([P] * 7 + [I32, I32, I32, I32, I32, F32, I32, F32, I32, I32] + [P] * 12 + [P], I32),
+    "singa_valence_rule_host": ([P] * 5 + [I32] + [P] * 3, I32),
+}
+VALENCE_EXPORTS = tuple(_VALENCE_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
-            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()):
+            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -25,6 +25,7 @@
 #include "../../include/singa_hip_force.h"
 #include "../../include/singa_hip_swor.h"
 #include "../../include/singa_hip_stream.h"
+#include "../../include/singa_hip_valence.h"
 #include "so3_index.h"
 
 namespace {
@@ -1574,6 +1575,103 @@ __host__ __device__ inline bool smiles_allows(int st, int c, int rem) {
     return end | (gram & (rem >= smiles_need(smiles_next(st, c))));
 }
 
+// The valence rule of singa_sample_token_valence (include/singa_hip_valence.h states it): the SMILES rule above plus a
+// bonding-capacity rule, one source for the kernel and for singa_valence_rule_host.  A row's state is the word of the SMILES
+// rule and two more: v0 = att (bits 0-2) | pend (3-4) | first (5) | rord (6-14), v1 = the stack, level l at bits 3l.  `c` is a
+// class byte whose high nibble holds order - 1 for a BOND token, `cap` the capacity of the token.  As above: no branch on
+// the class, which differs from lane to lane.
+struct ValenceState {
+    int gs, v0, v1;
+};
+
+__host__ __device__ inline ValenceState valence_load(int gs, int v0, int v1) {   // a START row reads both words as 0
+    const bool fresh = (gs & 15) == SMI_START;
+    return {gs, fresh ? 0 : v0, fresh ? 0 : v1};
+}
+
+__host__ __device__ inline int valence_stack_max(int stack, int depth) {         // over the live entries: levels < depth
+    int m = 0;
+    for (int l = 0; l < 10; ++l) {
+        const int e = l < depth ? (stack >> (3 * l)) & 7 : 0;
+        m = e > m ? e : m;
+    }
+    return m;
+}
+
+// the bond order that token `c` puts on the attach atom: an atom's or an opening digit's is the pending symbol's or 1 (0 for an
+// atom that starts a component), a closing digit's is the one its ring was opened with, a bond symbol's is its own
+__host__ __device__ inline int valence_order(const ValenceState& s, int c) {
+    const int cl = c & 15, d = c >> 4, prev = s.gs & 15, ring = (s.gs >> 10) & 511;
+    const int pend = (s.v0 >> 3) & 3, rord = (s.v0 >> 6) & 511, link = pend ? pend : 1;
+    const int atom = ((prev == SMI_START) | (prev == SMI_DOT)) ? 0 : link;
+    const int digit = !(ring >> d & 1) ? link : (rord >> d & 1) ? 2 : 1;
+    return cl == SMI_ATOM ? atom : cl == SMI_BOND ? (d < 2 ? d + 1 : 3) : cl == SMI_RING ? digit : 0;
+}
+
+__host__ __device__ inline ValenceState valence_next(const ValenceState& s, int c, int cap) {
+    const int cl = c & 15, bit = 1 << (c >> 4);
+    const int depth = (s.gs >> 4) & 63, ring = (s.gs >> 10) & 511;
+    int att = s.v0 & 7, pend = (s.v0 >> 3) & 3, first = (s.v0 >> 5) & 1, rord = (s.v0 >> 6) & 511, stack = s.v1;
+    const int o = valence_order(s, c);
+    const int top = 3 * (depth < 1 ? 0 : depth > 10 ? 9 : depth - 1), push = 3 * (depth > 9 ? 9 : depth);
+    const int held = depth > 0 ? (stack >> top) & 7 : 0;               // the branch point of the open level
+    const bool opening = (cl == SMI_RING) & !(ring & bit);
+    const int charged = held > o ? held - o : 0, fresh_att = cap > o ? cap - o : 0, less = att > o ? att - o : 0;
+    stack = ((cl == SMI_ATOM) & (first != 0) & (depth > 0)) ? (stack & ~(7 << top)) | charged << top : stack;
+    stack = cl == SMI_OPEN ? (stack & ~(7 << push)) | att << push : stack;
+    stack = ((cl == SMI_CLOSE) & (depth > 0)) ? stack & ~(7 << top) : stack;
+    att = cl == SMI_ATOM ? fresh_att : cl == SMI_CLOSE ? held : cl == SMI_RING ? less : cl == SMI_DOT ? 0 : att;
+    pend = cl == SMI_BOND ? o : ((cl == SMI_ATOM) | opening) ? 0 : pend;
+    first = cl == SMI_OPEN ? 1 : cl == SMI_ATOM ? 0 : first;
+    rord = opening ? (rord & ~bit) | (o == 2 ? bit : 0) : rord;
+    const bool stays = (cl == SMI_NONE) | (cl >= SMI_EOS);             // '$': the state stays
+    return {smiles_next(s.gs, c), stays ? s.v0 : att | pend << 3 | first << 5 | rord << 6, stays ? s.v1 : stack};
+}
+
+// E: the largest capacity at which the row can still be continued - the live stack entries and, with A, the attach atom
+__host__ __device__ inline int valence_reach(const ValenceState& s) {
+    const int prev = s.gs & 15, depth = (s.gs >> 4) & 63, att = s.v0 & 7;
+    const int m = valence_stack_max(s.v1, depth);
+    return (((prev == SMI_ATOM) | (prev == SMI_RING) | (prev == SMI_CLOSE)) & (att > m)) ? att : m;
+}
+
+// columns of the shortest completion, '$' included: [one atom], per open ring an atom of capacity >= 4 and its closing digit -
+// less one if a digit can close right here -, ')' x depth, '$'
+__host__ __device__ inline int valence_need(const ValenceState& s) {
+    const int prev = s.gs & 15, depth = (s.gs >> 4) & 63, ring = (s.gs >> 10) & 511, here = (s.gs >> 19) & 511;
+    const int att = s.v0 & 7, rord = (s.v0 >> 6) & 511, k = __builtin_popcount((unsigned)ring);
+    const bool a = (prev == SMI_START) | (prev == SMI_DOT) | (prev == SMI_BOND) | (prev == SMI_BONDX) | (prev == SMI_OPEN);
+    // a closing digit of order o passes if att >= o and, where another ring stays open, E >= 1 afterwards
+    const bool other = (k < 2) | (valence_stack_max(s.v1, depth) >= 1);
+    const int closable = ring & ~here;
+    const bool single = ((closable & ~rord) != 0) & (att >= 1) & (other | (att >= 2));
+    const bool twice = ((closable & rord) != 0) & (att >= 2) & (other | (att >= 3));
+    const bool b = ((prev == SMI_ATOM) | (prev == SMI_RING)) & (single | twice);
+    return depth + 1 + (a ? 1 : 0) + 2 * k - (b ? 1 : 0);
+}
+
+__host__ __device__ inline bool valence_allows(const ValenceState& s, int c, int cap, int rem) {
+    const int cl = c & 15, d = c >> 4;
+    const int prev = s.gs & 15, depth = (s.gs >> 4) & 63, ring = (s.gs >> 10) & 511, here = (s.gs >> 19) & 511, att = s.v0 & 7;
+    const bool after_atom = (prev == SMI_ATOM) | (prev == SMI_RING), A = after_atom | (prev == SMI_CLOSE);
+    const bool is_open = ring >> d & 1;
+    const bool opens = (after_atom | (prev == SMI_BOND)) & !is_open, closes = after_atom & is_open & !(here >> d & 1);
+    const bool gram = (cl == SMI_ATOM) | ((cl == SMI_BOND) & (A | (prev == SMI_OPEN))) | ((cl == SMI_OPEN) & A & (depth < 10)) |
+                      ((cl == SMI_CLOSE) & A & (depth > 0)) | ((cl == SMI_DOT) & A) |
+                      ((cl == SMI_RING) & (d < 9) & (opens | closes));
+    const bool end = (cl == SMI_EOS) & A & (depth == 0) & (ring == 0);
+    const int o = valence_order(s, c);
+    const bool bonds = cl == SMI_ATOM ? (o == 0) | ((att >= o) & (cap >= o))
+                     : cl == SMI_BOND ? att >= o
+                     : cl == SMI_OPEN ? att >= 1
+                     : cl == SMI_RING ? (att >= o) & (is_open | (o <= 2)) : true;
+    const ValenceState n = valence_next(s, c, cap);
+    // while a ring is open, an atom, a digit and ')' must leave somewhere to attach the atom that closes it
+    const bool settles = (cl == SMI_ATOM) | (cl == SMI_RING) | (cl == SMI_CLOSE);
+    const bool reach = !settles | (((n.gs >> 10) & 511) == 0) | (valence_reach(n) >= 1);
+    return end | (gram & bonds & reach & (rem >= valence_need(n)));
+}
+
 #ifndef SINGA_EMUL      // (cross-lane: not part of the sequential CPU emulation build of tests/emul)
 __device__ __forceinline__ int wave_min64i(int v) {
 #pragma unroll
@@ -1599,7 +1697,10 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
 // STREAM (singa_sample_token_stream, include/singa_hip_stream.h): `pos` holds one position per row, the uniform is column
 // mol[row] of `uniforms` and the bookkeeping goes to row mol[row] of the outputs, which are indexed by molecule; next and gstate
 // stay the row's.  A retired row (mol < 0) returns at once; `finished` and `live` are not read - the hand-over launch decides.
-template <int NPL, bool GRAMMAR, bool FORCED, bool STREAM>
+// VALENCE (singa_sample_token_valence, include/singa_hip_valence.h; only with GRAMMAR): the row's two valence words are read
+// wave-uniformly beside the state word, the capacity byte of a token rides in bits 8-10 of its class register, valence_allows
+// takes the place of smiles_allows and lane 0 stores all three words.  <NPL, *, *, *, false> reads neither `cap` nor `vstate`.
+template <int NPL, bool GRAMMAR, bool FORCED, bool STREAM, bool VALENCE>
 __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
                                                            const unsigned char* __restrict__ allowed,
                                                            const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
@@ -1610,7 +1711,9 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
                                                            float* __restrict__ tok_logp, const unsigned char* __restrict__ cls,
                                                            int32_t* __restrict__ gstate, float* __restrict__ allowed_logp,
                                                            const long long* __restrict__ forced, int32_t* __restrict__ rank,
-                                                           const int32_t* __restrict__ mol, int molecules) {
+                                                           const int32_t* __restrict__ mol, int molecules,
+                                                           const unsigned char* __restrict__ cap, int32_t* __restrict__ vstate) {
+    static_assert(GRAMMAR || !VALENCE, "the valence rule extends the SMILES rule");
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                           // wave-uniform from here on
@@ -1646,6 +1749,10 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
     bool ok[NPL];
     int gs = 0, c[NPL];
     if constexpr (GRAMMAR) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
+    ValenceState vs{0, 0, 0};
+    if constexpr (VALENCE)
+        vs = valence_load(gs, __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row]),
+                          __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row + 1]));
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const int i = k * 64 + lane;
@@ -1653,7 +1760,13 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
         ok[k] = i < V && (!allowed || allowed[i]);
         if constexpr (GRAMMAR) {
             c[k] = i < V ? cls[i] : 0;
-            ok[k] = ok[k] && smiles_allows(gs, c[k], (int)(T - 2 - t));
+            if constexpr (VALENCE) {
+                const int cp = i < V ? cap[i] & 7 : 0;
+                ok[k] = ok[k] && valence_allows(vs, c[k], cp, (int)(T - 2 - t));
+                c[k] |= cp << 8;
+            } else {
+                ok[k] = ok[k] && smiles_allows(gs, c[k], (int)(T - 2 - t));
+            }
         }
     }
     // the model's own log-sum-exp (tau = 1, nothing filtered)
@@ -1785,7 +1898,16 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
     }
     if (lane == 0) {
         if constexpr (GRAMMAR) {
-            if (drawn) gstate[row] = smiles_next(gs, ct);
+            if constexpr (VALENCE) {
+                if (drawn) {
+                    const ValenceState n = valence_next(vs, ct & 255, ct >> 8);
+                    gstate[row] = n.gs;
+                    vstate[2 * (long long)row] = n.v0;
+                    vstate[2 * (long long)row + 1] = n.v1;
+                }
+            } else {
+                if (drawn) gstate[row] = smiles_next(gs, ct);
+            }
             if (allowed_logp) allowed_logp[slot] = alp;
         }
         if constexpr (FORCED) {
@@ -7216,7 +7338,7 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
                   int T, float tau, int top_k, float top_p, int eos, int pad, unsigned char* finished, int32_t* length,
                   float* sum_logp, long long* tokens, long long* next, int32_t* live, float* tok_logp, int32_t* gstate,
                   float* allowed_logp, const long long* forced, int32_t* rank, void* stream, const int32_t* mol = nullptr,
-                  int molecules = 0) {
+                  int molecules = 0, const unsigned char* cap = nullptr, int32_t* vstate = nullptr) {
     static const char* const columns[] = {"T >= 2 columns, eos / pad inside the vocabulary",
                                           "T >= 2 columns (3 under the grammar), eos / pad inside the vocabulary",
                                           "T >= 3 columns, eos / pad inside the vocabulary"};
@@ -7226,6 +7348,8 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
         return fail_at(SINGA_E_NULL, name, "null pointer");
     if (!grammar && (cls || gstate || allowed_logp))
         return fail_at(SINGA_E_NULL, name, "cls and gstate go together (allowed_logp only with them)");
+    if ((cap != nullptr) != (vstate != nullptr) || (cap && !grammar))
+        return fail_at(SINGA_E_NULL, name, "cap and vstate go together, and only with cls and gstate");
     if (V < 1 || V > 1024) return fail_at(SINGA_E_SHAPE, name, "vocabulary of 1..1024 tokens");
     if (!(tau >= 0.f)) return fail_at(SINGA_E_SHAPE, name, "temperature must be >= 0");
     if (top_k < 0) return fail_at(SINGA_E_SHAPE, name, "top_k must be >= 0 (0 = off)");
@@ -7238,20 +7362,21 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
 #else
     const dim3 grid((rows + 3) / 4), block(256);
     dispatch_npl(V, [&](auto npl) {
+        auto launch = [&](auto g, auto f, auto s, auto v) {
+            hipLaunchKernelGGL(
+                (sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value, decltype(s)::value, decltype(v)::value>),
+                grid, block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, top_k, top_p, eos,
+                pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate, allowed_logp, forced, rank, mol,
+                molecules, cap, vstate);
+        };
+        if (cap) {                                                     // the valence rule: always with the grammar
+            if (mol) launch(std::true_type{}, std::false_type{}, std::true_type{}, std::true_type{});
+            else dispatch_flag(forced != nullptr, [&](auto f) { launch(std::true_type{}, f, std::false_type{}, std::true_type{}); });
+            return;
+        }
         dispatch_flag(grammar, [&](auto g) {
-            if (mol) {                                                 // (the stream form is not built with forced tokens)
-                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, false, true>), grid, block, 0,
-                                   (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, top_k, top_p,
-                                   eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate, allowed_logp,
-                                   forced, rank, mol, molecules);
-                return;
-            }
-            dispatch_flag(forced != nullptr, [&](auto f) {
-                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value, false>),
-                                   grid, block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T,
-                                   tau, top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls,
-                                   gstate, allowed_logp, forced, rank, mol, molecules);
-            });
+            if (mol) launch(g, std::false_type{}, std::true_type{}, std::false_type{});   // (no stream form with forced tokens)
+            else dispatch_flag(forced != nullptr, [&](auto f) { launch(g, f, std::false_type{}, std::false_type{}); });
         });
     });
     return check_launch(name);
@@ -7353,6 +7478,38 @@ int singa_stream_refill_host(int pockets, int R, int num_samples, int T, int pos
             if (before > 0) issued[b] += before < left ? before : left;
             if (retired > 0) live[b] = alive - retired;
         }
+    }
+    return SINGA_OK;
+}
+
+int singa_sample_token_valence(const float* logits, const float* uniforms, const unsigned char* allowed,
+                               const unsigned char* cls, const unsigned char* cap, const long long* pos, const int32_t* mol,
+                               int pos_offset, int rows, int molecules, int V, int T, float tau, int top_k, float top_p, int eos,
+                               int pad, unsigned char* finished, int32_t* length, float* sum_logp, long long* tokens,
+                               long long* next, int32_t* live, float* tok_logp, int32_t* gstate, int32_t* vstate,
+                               float* allowed_logp, const long long* forced, int32_t* rank, void* stream) {
+    const char* name = "sample_token_valence";
+    if (!cap || !vstate) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (!forced && rank) return fail_at(SINGA_E_NULL, name, "rank only with forced");
+    if (mol && molecules < 1) return fail_at(SINGA_E_SHAPE, name, "molecules must be >= 1");
+    if (mol && forced) return fail_at(SINGA_E_SHAPE, name, "no stream form with forced tokens: forced and mol exclude each other");
+    return sample_choice(name, GRAMMAR_REQUIRED, false, logits, uniforms, allowed, cls, pos, pos_offset, rows, V, T, tau, top_k,
+                         top_p, eos, pad, mol ? nullptr : finished, length, sum_logp, tokens, next, mol ? nullptr : live, tok_logp,
+                         gstate, allowed_logp, forced, rank, stream, mol, molecules, cap, vstate);
+}
+
+int singa_valence_rule_host(const unsigned char* cls, const unsigned char* cap, const int32_t* state, const int32_t* vstate,
+                            const int32_t* rem, int n, unsigned char* ok, int32_t* next_state, int32_t* next_vstate) {
+    if (!cls || !cap || !state || !vstate || !rem || !ok || !next_state || !next_vstate)
+        return fail(SINGA_E_NULL, "valence_rule_host: null pointer");
+    if (n < 0) return fail(SINGA_E_SHAPE, "valence_rule_host: n must be >= 0");
+    for (int i = 0; i < n; ++i) {
+        const ValenceState s = valence_load(state[i], vstate[2 * i], vstate[2 * i + 1]);
+        ok[i] = valence_allows(s, cls[i], cap[i] & 7, rem[i]) ? 1 : 0;
+        const ValenceState to = valence_next(s, cls[i], cap[i] & 7);
+        next_state[i] = ok[i] ? to.gs : state[i];
+        next_vstate[2 * i] = ok[i] ? to.v0 : vstate[2 * i];
+        next_vstate[2 * i + 1] = ok[i] ? to.v1 : vstate[2 * i + 1];
     }
     return SINGA_OK;
 }

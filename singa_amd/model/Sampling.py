@@ -25,8 +25,14 @@ caches have no padding mask).  `suppress=("&", "^")` keeps them from being drawn
 runs `singa_sample_token_grammar` (include/singa_hip_gen.h states the rule), which keeps one
 more word of state per row on the device and masks, per row, what cannot follow the row's prefix or could not be finished in
 the columns left.  Every row then ends in '$' before `max_length` and the text in front of it has balanced branches, paired
-ring-closure digits and no dangling bond symbol.  Syntax only: valence, aromaticity, duplicate ring bonds (C1C1), %nn
-closures and beam search are outside the rule (singa_amd/smiles.py).  The step stays one captured graph.
+ring-closure digits and no dangling bond symbol.  This grammar is syntax only: valence, aromaticity, duplicate ring bonds
+(C1C1), %nn closures and beam search are outside its rule (singa_amd/smiles.py).  The step stays one captured graph.
+
+`grammar="valence"` adds a bonding-capacity rule to that syntax (include/singa_hip_valence.h states it): `ops.sample_token`,
+given the capacity bytes as well, runs `singa_sample_token_valence`, which keeps two more words of state per row and also
+masks what would give an atom more bond order than its token can carry - `F(C)C`, `C1CF1`, `C(=O)(=O)(=O)C` are not drawn.
+A necessary condition for validity, not a sufficient one: aromaticity, kekulisation and duplicate ring bonds stay outside.
+`sample`, `score` and `sample_stream` take it; `sample_distinct` does not (its selection gathers one state word per row).
 
 `forced=` gives tokens instead of drawing them: `ops.sample_token`, given the forced matrix, then runs
 `singa_sample_token_forced` (include/singa_hip_force.h states the rule), which reads one more 8-byte word per row from a
@@ -93,6 +99,14 @@ def _prologue(fn, model, smiVoc, num_samples, batch_size, max_length, example, d
     return dev, tf, voc, marks, rows, num, max_length - 1 + num, free, cls, allowed
 
 
+def _valence_operands(grammar, smiVoc, rows, dev):
+    """-> (the [V] uint8 capacities, the rows' [rows, 2] int32 valence words) on the device under grammar="valence", else
+    (None, None).  The words are zeroed once and never reset: a row whose rule state is fresh reads them as 0."""
+    if grammar != "valence":
+        return None, None
+    return torch.as_tensor(smiles.capacity(smiVoc)).to(dev), torch.zeros(rows, 2, dtype=torch.int32, device=dev)
+
+
 def _decode(replays, max_steps, live, each=None):
     """Replay the step - `replays` in turn - up to `max_steps` times; `each()`, if given, after every step; every `LIVE_POLL`
     steps `live()` reads the device's count of live rows, and zero ends the loop.  Returns the steps taken."""
@@ -130,6 +144,8 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     `trace` also receives `allowed_logp` [rows, max_length]: log of the model's probability mass on the tokens the rule (and
     `suppress`) allowed at that step, so that token_logp - allowed_logp is the log-probability under the constrained proposal.
     ValueError for an unknown grammar, max_length < 3, or a `suppress` that removes every atom, '$', or ')' but not '('.
+    `grammar="valence"`: the same, and no atom of a row carries more bond order than `smiles.capacity` gives its token;
+    `allowed_logp` is then the mass on that stricter mask.  ValueError also for a `suppress` that leaves no atom of capacity >= 4.
 
     `forced`: int64 tensor or array [rows, max_length] or [batch_size, max_length] (one prefix per pocket, repeated for its
     `num_samples` rows), `smiles.encode` builds it: a value inside the vocabulary in column c is the token of column c, given
@@ -179,6 +195,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         cls = torch.as_tensor(cls).to(dev)
         state["grammar"] = torch.empty(rows, dtype=torch.int32, device=dev)
         state["allowed_logp"] = torch.empty(rows, max_length, dtype=torch.float32, device=dev)
+    cap, vstate = _valence_operands(grammar, smiVoc, rows, dev)
     if forced is not None:
         forced = torch.as_tensor(forced).to(dev).contiguous()          # uploaded once; the step indexes it with the device's position
         state["rank"] = torch.empty(rows, max_length, dtype=torch.int32, device=dev)
@@ -202,7 +219,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     def step():
         out = kv.advance(kv.token_input(state["next"]))
         ops.sample_token(tf.projection(out).contiguous(), uniforms, kv.pos, num + 1, state, float(temperature), int(top_k),
-                         float(top_p), eos, pad, allowed, cls=cls, forced=forced)
+                         float(top_p), eos, pad, allowed, cls=cls, forced=forced, cap=cap, vstate=vstate)
 
     replays = capture_steps(prime, [step], 2) if graph else [step]     # two warm-up steps, as KVDecoder.capture
     start()
@@ -342,6 +359,7 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
         cls = torch.as_tensor(cls).to(dev)
         state["grammar"] = torch.empty(rows, **i32)
         state["allowed_logp"] = torch.empty(mols, max_length, **f32)
+    cap, vstate = _valence_operands(grammar, smiVoc, rows, dev)
     # the start of a run: the first min(R, num_samples) rows of pocket b hold its first molecules, the others are retired
     first = min(R, num_samples)
     mol0 = np.full((batch_size, R), -1, np.int32)
@@ -365,7 +383,7 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
     def step():
         out = kv.advance(kv.token_input(state["next"], state["pos"]), row_pos=state["pos"])
         ops.sample_token_stream(tf.projection(out).contiguous(), uniforms, state["pos"], state["mol"], num, state, float(temperature),
-                                int(top_k), float(top_p), eos, pad, allowed, cls=cls)
+                                int(top_k), float(top_p), eos, pad, allowed, cls=cls, cap=cap, vstate=vstate)
         ops.stream_refill(state["pos"], state["mol"], num, state, R, num_samples, max_length, sos, eos, smiles.FRESH,
                           grammar is not None)
 
@@ -392,7 +410,8 @@ SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
 def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
                     suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None):
     """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
-    replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` (as in `sample`), by
+    replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` ("smiles", as in `sample`;
+    "valence" is a ValueError here), by
     stochastic beam search on the device (include/singa_hip_swor.h states the rule).  `model`, `smiVoc`, `example`, `prop`
     and `device` as in `sample`; the rows of a pocket exchange prefixes, so they are expected to carry one property prompt.
 
@@ -408,6 +427,9 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     dead slots) and `steps`.  A list handed in as `trace["gumbel_history"]` receives a copy of G [rows] after every step:
     G[k - 1] - G[k] of a run with one slot more bounds the margin by which the k-slot run's selections were decided.  ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
     length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory."""
+    if grammar == "valence":
+        raise ValueError("sample_distinct: grammar='valence' is unsupported (the selection gathers one state word per row); use "
+                         "grammar='smiles' here, or `sample` / `sample_stream` for the valence rule")
     dev, tf, voc, (sos, eos, pad), rows, num, positions, free, cls, allowed = _prologue(
         "sample_distinct", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
     k, V = num_samples, len(voc)

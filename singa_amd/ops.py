@@ -827,9 +827,10 @@ def _check_views(what, items):
                                f"{tuple(t.shape)} on {t.device}")
 
 
-def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, gstate=None, alp=None, forced=None, rank=None):
-    """The argument checks of the token-choice ops; gstate, alp / rank: the state's grammar, allowed_logp / rank where `cls` /
-    `forced` is given."""
+def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, gstate=None, alp=None, forced=None, rank=None,
+                        cap=None, vstate=None):
+    """The argument checks of the token-choice ops; gstate, alp / rank / vstate: the state's grammar, allowed_logp / rank /
+    valence where `cls` / `forced` / `cap` is given."""
     _dev(logits, uniforms, state["sum_logp"], state["length"], state["live"], state.get("tok_logp"))
     R, V = logits.shape
     tokens, nxt, fin = state["tokens"], state["next"], state["finished"]
@@ -839,7 +840,7 @@ def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, g
                         (state["live"], torch.int32, (1,)), (pos, torch.int64, None), (allowed, torch.uint8, (V,)),
                         (state.get("tok_logp"), torch.float32, (R, T)), (forced, torch.int64, (R, T)),
                         (rank, torch.int32, (R, T)), (cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)),
-                        (alp, torch.float32, (R, T))))
+                        (alp, torch.float32, (R, T)), (cap, torch.uint8, (V,)), (vstate, torch.int32, (R, 2))))
     if not (logits.is_contiguous() and uniforms.is_contiguous() and uniforms.dim() == 2 and uniforms.shape[1] == R
             and uniforms.shape[0] >= T - 1):
         raise RuntimeError(f"{what}: logits [R, V] and uniforms [>= T - 1, R] must be contiguous, got "
@@ -848,24 +849,33 @@ def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, g
 
 
 def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0, allowed=None,
-                 cls=None, forced=None):
+                 cls=None, forced=None, cap=None, vstate=None):
     """The next token of every row, drawn on the device (`singa_sample_token`, include/singa_hip.h states the rule; inference
     only, no autograd): one launch.  logits [R, V] f32 (raw projection outputs), uniforms [>= T - 1, R] f32 in [0, 1), pos: int64
     device scalar, the step is pos - pos_offset.  `state`: dict of the rows' device state, updated in place - tokens [R, T] int64,
     next [R] int64, finished [R] uint8, length [R] int32, sum_logp [R] f32, live [1] int32 and, optionally, tok_logp [R, T] f32.
     allowed: [V] uint8, 0 = never drawn.  `cls` / `forced`: the op is `sample_token_grammar` / `sample_token_forced`, which
-    describe them; this is where all three assemble their arguments."""
-    entry = "sample_token_forced" if forced is not None else "sample_token_grammar" if cls is not None else "sample_token"
+    describe them; this is where all three assemble their arguments.  `cap` ([V] uint8 capacities, `smiles.capacity`; with the
+    class bytes of `smiles.classify_orders`) and `vstate` ([R, 2] int32, updated in place; a row whose grammar word is
+    `smiles.FRESH` needs no reset of it): the valence rule of include/singa_hip_valence.h (`singa_sample_token_valence`) in
+    place of the SMILES rule, with or without `forced`."""
+    if (cap is None) != (vstate is None) or (cap is not None and cls is None):
+        raise RuntimeError("sample_token: cap and vstate go together, and only with cls")
+    entry = "sample_token_valence" if cap is not None else "sample_token_forced" if forced is not None else \
+        "sample_token_grammar" if cls is not None else "sample_token"
     rank = state.get("rank") if forced is not None else None
     gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
-    for t in (rank, gstate, alp):
+    for t in (rank, gstate, alp, vstate):
         if t is not None:
             _dev(t)
-    R, V, T = _sample_token_views(entry, logits, uniforms, pos, state, allowed, cls, gstate, alp, forced, rank)
+    R, V, T = _sample_token_views(entry, logits, uniforms, pos, state, allowed, cls, gstate, alp, forced, rank, cap, vstate)
     lib, head = _lib.lib(), (_p(logits), _p(uniforms), _p(allowed))
     rest = (_p(pos), pos_offset, R, V, T, temperature, top_k, top_p, eos, pad, _p(state["finished"]), _p(state["length"]),
             _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), _p(state["live"]), _p(state.get("tok_logp")))
-    if forced is not None:
+    if cap is not None:
+        code = lib.singa_sample_token_valence(*head, _p(cls), _p(cap), _p(pos), None, pos_offset, R, 0, *rest[3:], _p(gstate),
+                                              _p(vstate), _p(alp), _p(forced), _p(rank), _stream())
+    elif forced is not None:
         code = lib.singa_sample_token_forced(*head, _p(cls), *rest, _p(gstate), _p(alp), _p(forced), _p(rank), _stream())
     elif cls is not None:
         code = lib.singa_sample_token_grammar(*head, _p(cls), *rest, _p(gstate), _p(alp), _stream())
@@ -894,13 +904,16 @@ def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=No
 
 
 def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0,
-                        allowed=None, cls=None):
+                        allowed=None, cls=None, cap=None, vstate=None):
     """`sample_token` (cls=None) or `sample_token_grammar` for rows that hold a molecule each (`singa_sample_token_stream`,
     include/singa_hip_stream.h states the rule; inference only): logits [R, V] f32; pos [R] int64, the rows' own positions (a
     row's step is pos - pos_offset); mol [R] int32, the molecule a row decodes (-1: retired, the row is skipped); uniforms
     [>= T - 1, M] f32, one column per molecule.  `state`: tokens [M, T] int64, length [M] int32, sum_logp [M] f32 and,
     optionally, tok_logp [M, T] f32 - indexed by molecule - and next [R] int64; with `cls` also grammar [R] int32 and, optionally,
-    allowed_logp [M, T] f32.  Updated in place, bit for bit as the per-row ops update a row that draws the same logits."""
+    allowed_logp [M, T] f32.  Updated in place, bit for bit as the per-row ops update a row that draws the same logits.
+    `cap` [V] uint8 and `vstate` [R, 2] int32 (with `cls`): the valence rule, as in `sample_token`."""
+    if (cap is None) != (vstate is None) or (cap is not None and cls is None):
+        raise RuntimeError("sample_token_stream: cap and vstate go together, and only with cls")
     R, V = logits.shape
     M, T = state["tokens"].shape
     gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
@@ -908,10 +921,18 @@ def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperatu
         (logits, torch.float32, (R, V)), (uniforms, torch.float32, None), (pos, torch.int64, (R,)), (mol, torch.int32, (R,)),
         (state["tokens"], torch.int64, (M, T)), (state["length"], torch.int32, (M,)), (state["sum_logp"], torch.float32, (M,)),
         (state.get("tok_logp"), torch.float32, (M, T)), (state["next"], torch.int64, (R,)), (allowed, torch.uint8, (V,)),
-        (cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)), (alp, torch.float32, (M, T))))
+        (cls, torch.uint8, (V,)), (gstate, torch.int32, (R,)), (alp, torch.float32, (M, T)), (cap, torch.uint8, (V,)),
+        (vstate, torch.int32, (R, 2))))
     if uniforms.dim() != 2 or uniforms.shape[1] != M or uniforms.shape[0] < T - 1:
         raise RuntimeError(f"sample_token_stream: uniforms [>= T - 1, molecules], got {tuple(uniforms.shape)} for T = {T}, {M} molecules")
     _lib.ensure_init(logits.device.index if logits.device.index is not None else torch.cuda.current_device())
+    if cap is not None:
+        _chk(_lib.lib().singa_sample_token_valence(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(cap), _p(pos), _p(mol), pos_offset,
+                                                   R, M, V, T, temperature, top_k, top_p, eos, pad, None, _p(state["length"]),
+                                                   _p(state["sum_logp"]), _p(state["tokens"]), _p(state["next"]), None,
+                                                   _p(state.get("tok_logp")), _p(gstate), _p(vstate), _p(alp), None, None, _stream()),
+             "singa_sample_token_valence")
+        return
     _chk(_lib.lib().singa_sample_token_stream(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(pos), _p(mol), pos_offset, R, M, V,
                                               T, temperature, top_k, top_p, eos, pad, _p(state["length"]), _p(state["sum_logp"]),
                                               _p(state["tokens"]), _p(state["next"]), _p(state.get("tok_logp")), _p(gstate), _p(alp),

@@ -3,17 +3,24 @@ the packed per-row state of the rule that include/singa_hip_gen.h states and `si
 device.  The rule itself is not restated here - only what the host has to prepare: one class byte per vocabulary entry and
 the fresh state.
 
-Scope of the rule: syntax only - balanced branches, paired ring-closure digits, no dangling bond symbol, and a '$' before the
-columns run out.  Not covered: chemical validity (valence, aromaticity, duplicate ring bonds such as C1C1), %nn closures (the
-vocabulary has none), a bond symbol in front of a closing ring digit (never drawn), beam search."""
+Scope of the "smiles" rule: syntax only - balanced branches, paired ring-closure digits, no dangling bond symbol, and a '$'
+before the columns run out.  Not covered: chemical validity (valence, aromaticity, duplicate ring bonds such as C1C1), %nn
+closures (the vocabulary has none), a bond symbol in front of a closing ring digit (never drawn), beam search.
+
+`grammar="valence"` (include/singa_hip_valence.h states the rule, `singa_sample_token_valence` evaluates it) adds a
+bonding-capacity rule to the syntax: no atom of a drawn row carries more bond order than the capacity of its token
+(`capacity`).  The host prepares one more byte per vocabulary entry for it, and the class bytes of the bond tokens carry
+their order (`classify_orders`).  A necessary condition for validity, not a sufficient one: aromaticity, kekulisation and
+duplicate ring bonds stay uncovered."""
 import functools
+import re
 
 import numpy as np
 
 NONE, ATOM, BOND, OPEN, CLOSE, RING, DOT, EOS = range(8)        # token classes; prev codes 1-6 are the classes' own
 START, BONDX = 7, 8                                             # further prev codes: fresh row, bond symbol after '(' or ')'
 FRESH = START                                                   # state word of a fresh row: prev = START, everything else 0
-GRAMMARS = ("smiles",)
+GRAMMARS = ("smiles", "valence")
 
 _ORGANIC = {"B", "C", "N", "O", "P", "S", "F", "I", "Br", "Cl", "b", "c", "n", "o", "p", "s"}
 _FIXED = {"(": OPEN, ")": CLOSE, ".": DOT, "$": EOS}
@@ -35,6 +42,59 @@ def classify(voc):
     return out
 
 
+def classify_orders(voc):
+    """`classify` for the valence rule: the high nibble of a BOND token holds its order - 1 (1 for '=', 2 for '#', 0 for every
+    other bond symbol), which the SMILES rule does not read."""
+    out = classify(voc)
+    for i, tok in enumerate(voc):
+        if out[i] == BOND:
+            out[i] |= {"=": 1, "#": 2}.get(str(tok), 0) << 4
+    return out
+
+
+# Upper bounds of the bond order an element's atom carries, so that no valid string is excluded (include/singa_hip_valence.h)
+_CAPACITY = {"B": 3, "C": 4, "Si": 4, "N": 3, "O": 2, "P": 5, "As": 5, "S": 6, "Se": 6, "F": 1, "Cl": 1, "Br": 1, "I": 1}
+_CHARGE_ADDS = {"N", "P", "As", "O", "S", "Se", "F", "Cl", "Br", "I"}         # the N, O and halogen groups: + charge
+_BRACKET = re.compile(r"\[(\d+)?(se|as|[bcnops]|[A-Z][a-z]?)(@{0,2})(?:H(\d?))?(\+{1,3}|-{1,3}|[+-]\d)?\]")
+UNCONSTRAINED = 7
+
+
+def capacity(voc):
+    """uint8 [V]: the bonding capacity 0..7 of every ATOM token, 0 for every other token - the most bond order the valence
+    rule lets the token's atom carry.  UPPER bounds, so that no valid string is ever excluded:
+
+        B 3    C, Si 4    N 3    O 2    P, As 5    S, Se 6    F, Cl, Br, I 1
+
+    A lower-case (aromatic) symbol takes its element's value.  A bracket atom is read as
+    [isotope? element chirality? H-count? charge?]: its capacity is table[element] + the charge term - the H count, clamped
+    to 0..7, with the charge term + charge for the N, O and halogen groups ([N+] 4, [O-] 1, [Cl-] 0), - charge for B ([B-] 4)
+    and - |charge| for C and Si.  An element outside the table, or a bracket that does not read this way, gets 7 (no
+    constraint)."""
+    cls = classify(voc)
+    out = np.zeros(len(voc), np.uint8)
+    for i, tok in enumerate(voc):
+        if cls[i] != ATOM:
+            continue
+        tok = str(tok)
+        if tok[0] != "[":
+            out[i] = _CAPACITY[tok.capitalize()]
+            continue
+        m = _BRACKET.fullmatch(tok)
+        element = m.group(2).capitalize() if m else None
+        if element not in _CAPACITY:
+            out[i] = UNCONSTRAINED
+            continue
+        hydrogens = 0 if m.group(4) is None else int(m.group(4) or 1)
+        sign = m.group(5) or ""
+        charge = 0 if not sign else (int(sign[1:]) if sign[1:].isdigit() else len(sign)) * (1 if sign[0] == "+" else -1)
+        term = charge if element in _CHARGE_ADDS else -charge if element == "B" else -abs(charge)
+        out[i] = min(max(_CAPACITY[element] + term - hydrogens, 0), UNCONSTRAINED)
+    return out
+
+
+ANCHOR = 4              # the valence rule finishes every row with atoms of at least this capacity
+
+
 def pack(prev, depth=0, ring=0, here=0):
     return int(prev) | int(depth) << 4 | int(ring) << 10 | int(here) << 19
 
@@ -46,7 +106,8 @@ def unpack(state):
 
 def check_arguments(grammar, voc, max_length, suppress=()):
     """The argument check of `sample(..., grammar=...)`: raises ValueError for what the rule cannot work with; returns the class
-    bytes otherwise (None for grammar=None)."""
+    bytes otherwise (None for grammar=None; `classify_orders` for "valence", which also needs an atom token of capacity >= 4
+    that `suppress` leaves: the rule's shortest completion closes the open rings on such atoms)."""
     if grammar is None:
         return None
     if grammar not in GRAMMARS:
@@ -54,13 +115,16 @@ def check_arguments(grammar, voc, max_length, suppress=()):
     if max_length < 3:
         raise ValueError(f"sample: grammar={grammar!r} needs max_length >= 3 ('&', one atom, '$'), got {max_length}")
     voc = [str(v) for v in voc]
-    cls = classify(voc)
+    cls = classify_orders(voc) if grammar == "valence" else classify(voc)
     if "$" not in voc or cls[voc.index("$")] != EOS:
         raise ValueError("sample: the grammar ends a row with '$', which the vocabulary does not hold as its end token")
     gone = {str(s) for s in suppress}
     kept = lambda c: [v for v, k in zip(voc, cls & 15) if k == c and v not in gone]
     if not kept(ATOM):
         raise ValueError("sample: suppress removes every atom token; the grammar could draw nothing")
+    if grammar == "valence" and not any(c >= ANCHOR and k == ATOM and v not in gone for v, k, c in zip(voc, cls & 15, capacity(voc))):
+        raise ValueError(f"sample: grammar='valence' needs an atom token of capacity >= {ANCHOR} that suppress leaves (such as 'C'): "
+                         "its open rings could not be closed otherwise")
     if not kept(EOS):
         raise ValueError("sample: suppress removes '$'; under the grammar every row has to end")
     if kept(OPEN) and not kept(CLOSE):
@@ -139,7 +203,8 @@ def check_forced(forced, voc, max_length, grammar=None):
     """The argument check of `sample(..., forced=...)`, on the CPU: `forced` [rows, max_length] integers, a value outside the
     vocabulary (-1) = a free column.  Column 0 must be '&' or free, a row's forced columns must be one run that starts at column
     1 (no free column in front of a forced one), and nothing may be forced behind a forced '$'.  Under `grammar` every forced
-    token is walked through the library's rule (`singa_smiles_rule_host`: the functions the kernel evaluates), from the fresh
+    token is walked through the library's rule of that grammar (`singa_smiles_rule_host` / `singa_valence_rule_host`: the
+    functions the kernel evaluates), from the fresh
     state with rem = max_length - 2 - t at step t, so a prefix that leaves too few columns to finish is refused as well.  One
     exception: a row forced to '$' in column 1 is an empty row (what `score` pads ragged lists with) and passes under any
     grammar.  ValueError names row, column and token of the first refusal; returns the matrix as a contiguous int64 array."""
@@ -163,13 +228,15 @@ def check_forced(forced, voc, max_length, grammar=None):
                          f"run from column 1")
     ended = np.zeros(len(f), bool)
     state = np.full(len(f), FRESH, np.int32)
+    vstate = np.zeros((len(f), 2), np.int32)
     filler = (n >= 1) & (f[:, 1] == eos)
     rule = None
     if grammar is not None:
         import ctypes
 
         from . import _capi, _lib
-        rule = _lib.lib().singa_smiles_rule_host
+        rule = _lib.lib().singa_valence_rule_host if grammar == "valence" else _lib.lib().singa_smiles_rule_host
+        cap = capacity(voc) if grammar == "valence" else None
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     for t in range(int(n.max()) if len(n) else 0):
         on = np.flatnonzero(n > t)
@@ -183,7 +250,13 @@ def check_forced(forced, voc, max_length, grammar=None):
             st = np.ascontiguousarray(state[on])
             rem = np.full(len(on), max_length - 2 - t, np.int32)
             ok, nxt = np.zeros(len(on), np.uint8), np.zeros(len(on), np.int32)
-            _capi.check(_lib.lib(), rule(vp(c), vp(st), vp(rem), len(on), vp(ok), vp(nxt)), "singa_smiles_rule_host")
+            if grammar == "valence":
+                k, vs, vnxt = np.ascontiguousarray(cap[tok]), np.ascontiguousarray(vstate[on]), np.zeros((len(on), 2), np.int32)
+                _capi.check(_lib.lib(), rule(vp(c), vp(k), vp(st), vp(vs), vp(rem), len(on), vp(ok), vp(nxt), vp(vnxt)),
+                            "singa_valence_rule_host")
+                vstate[on] = vnxt
+            else:
+                _capi.check(_lib.lib(), rule(vp(c), vp(st), vp(rem), len(on), vp(ok), vp(nxt)), "singa_smiles_rule_host")
             refused = on[(ok == 0) & ~filler[on]]
             if len(refused):
                 r = int(refused[0])

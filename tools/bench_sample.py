@@ -4,7 +4,7 @@ atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket w
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
     python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
-                                  [--distinct] [--rows-per-pocket R]
+                                  [--distinct] [--rows-per-pocket R] [--valence]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
@@ -23,7 +23,8 @@ the plain k17 step at rows = 128, 512, 2048 on the synthetic pocket, one molecul
 interleaved - and `throughput` - on the `beam_b2_k6_eos` golden model (tests/golden; its rows end all over a 41-column
 window), 4,096 molecules per pocket through `sample_stream(rows_per_pocket=R)` against `sample` called 16 times with 256 rows
 per pocket, whole calls timed, with the length distribution of the run and the ratio it predicts: (steps until the longest
-of 256 rows has ended, as the polling loop sees it) / (mean length).
+of 256 rows has ended, as the polling loop sees it) / (mean length).  With `--valence` nothing but the k17 step under
+`grammar="valence"` next to the one under `grammar="smiles"` at rows = 128, 512, 2048, interleaved (`valence_table`).
 """
 import argparse
 import json
@@ -53,6 +54,8 @@ def main():
     ap.add_argument("--distinct", action="store_true", help="also time sample_distinct next to the plain step (distinct_table)")
     ap.add_argument("--distinct-only", type=int, default=0, metavar="ROWS",
                     help="nothing but two sample_distinct generations of ROWS slots: the run to take a kernel trace of")
+    ap.add_argument("--valence", action="store_true",
+                    help="nothing but the k17 step under grammar='valence' next to grammar='smiles' at rows = 128, 512, 2048 (valence_table)")
     ap.add_argument("--rows-per-pocket", type=int, default=0, metavar="R",
                     help="nothing but sample_stream: the streaming step next to the plain one, and molecules / s at R rows per pocket")
     args = ap.parse_args()
@@ -120,6 +123,20 @@ def main():
                             or tr["steps"]))
         print(json.dumps({"distinct_only_rows": rows, "ms_per_step": [round(x, 4) for x in ms]}))
         return
+    if args.valence:
+        vtable = []
+        for rows in (128, 512, 2048):
+            run_sample(rows, True, "smiles"), run_sample(rows, True, "valence")
+            gram, val, steps = [], [], {"smiles": [], "valence": []}
+            for _ in range(3 if rows >= 512 else args.reps):
+                for g, ms in (("smiles", gram), ("valence", val)):
+                    ms.append(timed(lambda: steps[g].append(run_sample(rows, True, g)) or steps[g][-1]))
+            vtable.append({"rows": rows, "path": "k17", "smiles_ms_per_step": round(statistics.median(gram), 4),
+                           "valence_ms_per_step": round(statistics.median(val), 4), "steps": steps,
+                           "smiles_runs_ms": [round(x, 4) for x in gram], "valence_runs_ms": [round(x, 4) for x in val]})
+        print(json.dumps({"max_length": T, "valence_table": vtable}))
+        return
+
     if args.rows_per_pocket:
         def run_stream(rows):
             tr = {}
