@@ -8,12 +8,15 @@ do not), best perturbed score first.
 
 The reference's PDB / docking front end is out of scope, so pockets come from `--data golden` (the three
 example graphs the reference bundles) or `--data synthetic`.  No chemistry toolkit is required: the sequences are written as
-they were decoded, without a validity filter.  `--grammar smiles` (sample mode) removes the syntactic rejects where the token
-is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired ring-closure digits and no
-dangling bond symbol (include/singa_hip_gen.h states the rule).  Under `--grammar smiles` chemical validity - valence,
-aromaticity, duplicate ring bonds - is still not checked, and beam search is not constrained.  `--grammar valence` (sample mode only) adds a
+they were decoded, without a validity filter.  `--grammar smiles` (sample, distinct and beam mode) removes the syntactic rejects
+where the token is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired
+ring-closure digits and no dangling bond symbol (include/singa_hip_gen.h states the rule).  Under `--grammar smiles` chemical
+validity - valence, aromaticity, duplicate ring bonds - is still not checked.  `--grammar valence` (sample and beam mode) adds a
 bonding-capacity rule: no atom of a sequence carries more bond order than its token can (include/singa_hip_valence.h; a necessary
-condition for validity - aromaticity and duplicate ring bonds stay unchecked).  `--prefix TEXT` (sample mode) starts every sequence with
+condition for validity - aromaticity and duplicate ring bonds stay unchecked).  Beam search selects on the host, as the
+reference does, unless `--beam-select device` or a `--grammar` is given: then the selection runs on the device
+(`beam_search_device`; include/singa_hip_beam.h states the rule), which is what lets a grammar constrain it; without a grammar
+the two select the same hypotheses up to the order of exactly tied candidates.  `--prefix TEXT` (sample mode) starts every sequence with
 that fragment - a scaffold to continue; under `--grammar smiles` a fragment the rule refuses is an error before anything runs.
 `--mode score --molecules FILE` draws nothing: FILE holds lines of `pocket name<TAB>SMILES`, and every molecule's
 log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input.
@@ -24,6 +27,7 @@ log-likelihood under the model for its pocket is written, in the same four colum
     python gen.py --data golden --mode sample --num-samples 100 --grammar smiles --prefix "c1ccc("
     python gen.py --data golden --mode score --molecules library.tsv
     python gen.py --data golden --mode distinct --num-samples 100 --grammar smiles --seed 3
+    python gen.py --data golden --mode beam --num-beams 20 --grammar valence
 
 One line per sequence on stdout (or in `--out`), tab-separated: pocket name, the SMILES string between '&' and '$', the
 number of tokens decoded ('$' included), the summed log-probability of the sequence under the model.  Everything else that
@@ -40,7 +44,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, parsed and checked: everything that can be refused before a device is touched."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=os.path.join(ROOT, "config", "train.yml"))
     ap.add_argument("--ckpt", type=str, default=None, help="a train.py checkpoint; without it the weights are random")
@@ -56,7 +61,9 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--grammar", choices=["none", "smiles", "valence"], default="none",
-                    help="sample: draw only tokens that keep the sequence a completable SMILES string")
+                    help="sample, distinct, beam: choose only tokens that keep the sequence a completable SMILES string")
+    ap.add_argument("--beam-select", choices=["host", "device"], default="host",
+                    help="beam: where the candidates are selected; a --grammar selects on the device whatever this says")
     ap.add_argument("--rows-per-pocket", type=int, default=None, metavar="R",
                     help="sample: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
                          "(sample_stream: same sequences for the same uniforms, whatever R)")
@@ -67,16 +74,22 @@ def main():
     ap.add_argument("--prop", type=float, nargs=3, default=[1.0, 1.0, 1.0], metavar=("V", "Q", "S"),
                     help="the property prompt: vina score below -7.5, QED above 0.6, SAS below 4 (1 = wanted)")
     ap.add_argument("--out", type=str, default=None, help="write the sequences here instead of stdout")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
-    assert args.grammar == "none" or args.mode in ("sample", "distinct"), \
-        "--grammar constrains sampling only: beam search selects on the host"
-    assert args.grammar != "valence" or args.mode == "sample", "--grammar valence: sample mode only (distinct gathers one state word)"
+    assert args.grammar == "none" or args.mode in ("sample", "distinct", "beam"), "--grammar constrains what is generated, not --mode score"
+    assert args.grammar != "valence" or args.mode in ("sample", "beam"), \
+        "--grammar valence: sample and beam mode only (distinct gathers one state word)"
+    assert args.beam_select == "host" or args.mode == "beam", "--beam-select is about beam search: beam mode only"
     assert args.mode != "distinct" or (args.top_k == 0 and args.top_p == 1.0), "--mode distinct takes no --top-k / --top-p"
     assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
     assert args.rows_per_pocket is None or (args.mode == "sample" and args.prefix is None), \
         "--rows-per-pocket is continuous sampling: sample mode, without --prefix"
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
+    return args
+
+
+def main():
+    args = parse_args()
     dev = torch.device(args.device if ":" in args.device else "cuda:0")
     torch.cuda.set_device(dev)
 
@@ -84,7 +97,7 @@ def main():
     __graft_entry__.build()
     from singa_amd import graph as G
     from singa_amd.config import Config, load_config
-    from singa_amd.model.BeamSearch import beam_search
+    from singa_amd.model.BeamSearch import beam_search, beam_search_device
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     from singa_amd import smiles
@@ -164,7 +177,12 @@ def main():
         tokens, names_of = tokens[keep], [names[r // per] for r in rows]
         lengths, logps = tr["lengths"].cpu()[keep].tolist(), tr["sum_logp"].cpu()[keep].tolist()
     else:
-        tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr).cpu()
+        if args.beam_select == "device" or args.grammar != "none":
+            tokens = beam_search_device(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr,
+                                        grammar=None if args.grammar == "none" else args.grammar).cpu()
+            print(f"# beam search selected on the device: {tr['steps']} steps")
+        else:
+            tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr).cpu()
         best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7
         lengths, logps = [len(h) for _, h in best], [s * len(h) ** 0.7 for s, h in best]
         per = 1

@@ -52,8 +52,8 @@
  * state with rem >= need and keeps rem >= need, so every row has drawn `eos` by column T - 1 (T >= 3).
  *
  * Out of scope of THIS rule: chemical validity (aromaticity, duplicate ring bonds such as C1C1 or C12CC12; valence is what the
- * rule of singa_hip_valence.h adds to this one), %nn closures, a bond symbol in front of a CLOSING ring digit (never drawn),
- * beam search.
+ * rule of singa_hip_valence.h adds to this one), %nn closures, a bond symbol in front of a CLOSING ring digit (never drawn).
+ * (Beam search takes this rule through singa_hip_beam.h.)
  *
  * singa_sample_token_grammar: singa_sample_token (same arguments, same state arrays, same rule 1-5) on the effective mask
  * allowed[i] (null: all) AND the grammar evaluated on gstate[row], cls[i] and rem.  The log-probability stays log-softmax of

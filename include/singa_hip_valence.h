@@ -5,8 +5,8 @@
  * THE RULE (kernel, singa_amd/smiles.py and tests/valence_rule.py restate this text).  The SMILES rule of singa_hip_gen.h plus
  * a bonding-capacity rule: every drawn row still ends with `eos` before its columns run out and still parses, and in the
  * molecule it spells no atom carries more bond order than the capacity of its token.  A NECESSARY condition for chemical
- * validity, not a sufficient one: aromaticity, kekulisation, duplicate ring bonds (C12CC12), %nn closures and beam search stay
- * out of scope.
+ * validity, not a sufficient one: aromaticity, kekulisation, duplicate ring bonds (C12CC12) and %nn closures stay out of
+ * scope.  (Beam search takes this rule through singa_hip_beam.h.)
  *
  * Capacity of a token.  cap[V] bytes, derived by the caller from the vocabulary's strings (singa_amd.smiles.capacity): 0..7
  * for an ATOM token, 0 for every other token.  UPPER bounds, so that no valid string is excluded:

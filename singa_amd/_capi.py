@@ -175,12 +175,21 @@ _VALENCE_SIGS = {
 }
 VALENCE_EXPORTS = tuple(_VALENCE_SIGS)
 
+# include/singa_hip_beam.h: beam search selected on the device (`beam_search_device`); a table of its own
+_BEAM_SIGS = {
+    "singa_beam_work": ([I32, I32], C.c_longlong),
+    "singa_beam_expand": ([P] * 5 + [I32] * 5 + [P] * 5 + [P], I32),
+    "singa_beam_select": ([P] * 4 + [I32] * 7 + [P] * 18 + [P], I32),
+}
+BEAM_EXPORTS = tuple(_BEAM_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
-            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()):
+            list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
+            list(_BEAM_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

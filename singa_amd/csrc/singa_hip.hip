@@ -26,6 +26,7 @@
 #include "../../include/singa_hip_swor.h"
 #include "../../include/singa_hip_stream.h"
 #include "../../include/singa_hip_valence.h"
+#include "../../include/singa_hip_beam.h"
 #include "so3_index.h"
 
 namespace {
@@ -2153,40 +2154,21 @@ __device__ __forceinline__ uint32_t swor_key(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// singa_swor_select, first launch: one workgroup per pocket.
-//   * the k-th largest of the pocket's k V candidates by radix select on the 53-bit composite (ordered key << 21 | inverted
-//     flat index parent * V + token): digits of 11, 11, 10 bits of the key from the top, then 11 and 10 of the index, an LDS
-//     histogram per digit; a larger composite is a better candidate under the rule's order (g~ down, parent up, token up), and
-//     composites are unique.  The passes stop at the first digit whose bin holds exactly what is still needed - for distinct
-//     values no later than the key's last digit, so the index digits run only to split an exact tie at the threshold.
-//     -inf (no candidate) never enters a histogram.  The candidates are re-read from L2 per pass (k V <= 8 MiB).
-//   * the survivors are appended to LDS in any order and sorted there (bitonic, descending composites);
-//   * the new slots' scalars and column t + 1 go to `work` (w_*); swor_gather_kernel adds the parents' columns, and
-//     swor_commit_kernel overwrites the state once every parent has been read.
-__global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restrict__ cand, const float* __restrict__ cand_logp,
-                                                           const float* __restrict__ cand_phi, const unsigned char* __restrict__ cls,
-                                                           const long long* __restrict__ pos, int pos_offset, int kslots, int V, int T,
-                                                           int eos, int pad, const float* __restrict__ gumbel,
-                                                           const float* __restrict__ prop_logp, const float* __restrict__ sum_logp,
-                                                           const unsigned long long* __restrict__ hash,
-                                                           const unsigned char* __restrict__ finished, const int32_t* __restrict__ length,
-                                                           const int32_t* __restrict__ gstate, long long* __restrict__ next,
-                                                           long long* __restrict__ src, int32_t* __restrict__ live,
-                                                           float* __restrict__ w_gumbel, float* __restrict__ w_prop,
-                                                           float* __restrict__ w_sum, unsigned long long* __restrict__ w_hash,
-                                                           unsigned char* __restrict__ w_fin, int32_t* __restrict__ w_len,
-                                                           int32_t* __restrict__ w_gs, long long* __restrict__ w_tokens,
-                                                           float* __restrict__ w_toklogp) {
-    __shared__ unsigned hist[2048];
-    __shared__ unsigned long long sel[2048];
-    __shared__ unsigned s_kk, s_bin, s_above, s_cnt, s_nsel;
-    __shared__ int s_live;
-    const int tid = threadIdx.x, lane = tid & 63, pocket = blockIdx.x;
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;                                   // workgroup-uniform
-    const int n = kslots * V;
+// The `want` best of a pocket's n candidates, in the rule's order, for a workgroup of 1024 threads (all of them call it):
+//   * the want-th largest by radix select on the 53-bit composite (ordered key << 21 | inverted flat index parent * V +
+//     token): digits of 11, 11, 10 bits of the key from the top, then 11 and 10 of the index, an LDS histogram per digit; a
+//     larger composite is a better candidate under the rule's order (value down, parent up, token up), and composites are
+//     unique.  The passes stop at the first digit whose bin holds exactly what is still needed - for distinct values no later
+//     than the key's last digit, so the index digits run only to split an exact tie at the threshold.  -inf (no candidate)
+//     never enters a histogram.  The candidates are re-read from L2 per pass (n <= 2^21 floats = 8 MiB).
+//   * the survivors are appended to LDS in any order and sorted there (bitonic, descending composites).
+// hist [2048], sel [2048] and s [5] are LDS; want <= 2048.  Returns how many there are - min(want, the finite candidates) - and
+// leaves their composites in sel[0 ..), zeros behind them (an empty entry decodes to a flat index >= n).
+__device__ __forceinline__ unsigned swor_topk(const float* __restrict__ base, int n, unsigned want, unsigned* hist,
+                                              unsigned long long* sel, unsigned* s) {
+    unsigned &s_kk = s[0], &s_bin = s[1], &s_above = s[2], &s_cnt = s[3], &s_nsel = s[4];
+    const int tid = threadIdx.x, lane = tid & 63;
     const float NEG = -INFINITY;
-    const float* base = cand + (long long)pocket * n;
     const int SH[5] = {42, 31, 21, 10, 0}, NB[5] = {11, 11, 10, 11, 10};
     unsigned long long prefix = 0;
     unsigned need = 0, kk = 0;
@@ -2213,7 +2195,7 @@ __global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restri
                 if (lane >= o) P += y;
             }
             const unsigned total = __shfl(P, 63, 64);
-            const unsigned nd = p == 0 ? min((unsigned)kslots, total) : need;
+            const unsigned nd = p == 0 ? min(want, total) : need;
             if (p == 0 && lane == 0) s_kk = nd, s_cnt = 0, s_above = 0, s_bin = 0;
             const unsigned long long hit = __ballot(P >= nd);
             if (nd > 0 && hit != 0 && lane == __ffsll((long long)hit) - 1) {
@@ -2230,14 +2212,14 @@ __global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restri
         }
         __syncthreads();
         if (p == 0) need = kk = s_kk;
-        if (kk == 0) break;                                            // no candidate at all: every slot dies
+        if (kk == 0) break;                                            // no candidate at all
         need -= s_above;
         prefix = prefix << NB[p] | s_bin;
         final_shift = SH[p];
         if (s_cnt == need) break;                                      // the bin is taken whole (the last digit: one element)
     }
     sel[tid] = 0, sel[tid + 1024] = 0;
-    if (tid == 0) s_nsel = 0, s_live = 0;
+    if (tid == 0) s_nsel = 0;
     __syncthreads();
     if (kk > 0)
         for (int i = tid; i < n; i += 1024) {
@@ -2262,6 +2244,39 @@ __global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restri
             }
             __syncthreads();
         }
+    return kk;
+}
+
+// singa_swor_select, first launch: one workgroup per pocket.
+//   * the k best of the pocket's k V candidates, sorted: swor_topk;
+//   * the new slots' scalars and column t + 1 go to `work` (w_*); swor_gather_kernel adds the parents' columns, and
+//     swor_commit_kernel overwrites the state once every parent has been read.
+__global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restrict__ cand, const float* __restrict__ cand_logp,
+                                                           const float* __restrict__ cand_phi, const unsigned char* __restrict__ cls,
+                                                           const long long* __restrict__ pos, int pos_offset, int kslots, int V, int T,
+                                                           int eos, int pad, const float* __restrict__ gumbel,
+                                                           const float* __restrict__ prop_logp, const float* __restrict__ sum_logp,
+                                                           const unsigned long long* __restrict__ hash,
+                                                           const unsigned char* __restrict__ finished, const int32_t* __restrict__ length,
+                                                           const int32_t* __restrict__ gstate, long long* __restrict__ next,
+                                                           long long* __restrict__ src, int32_t* __restrict__ live,
+                                                           float* __restrict__ w_gumbel, float* __restrict__ w_prop,
+                                                           float* __restrict__ w_sum, unsigned long long* __restrict__ w_hash,
+                                                           unsigned char* __restrict__ w_fin, int32_t* __restrict__ w_len,
+                                                           int32_t* __restrict__ w_gs, long long* __restrict__ w_tokens,
+                                                           float* __restrict__ w_toklogp) {
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned long long sel[2048];
+    __shared__ unsigned s_top[5];
+    __shared__ int s_live;
+    const int tid = threadIdx.x, pocket = blockIdx.x;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;                                   // workgroup-uniform
+    const int n = kslots * V;
+    const float NEG = -INFINITY;
+    const float* base = cand + (long long)pocket * n;
+    if (tid == 0) s_live = 0;
+    const unsigned kk = swor_topk(base, n, (unsigned)kslots, hist, sel, s_top);
     // the new slots' scalars
     for (int j = tid; j < kslots; j += 1024) {
         const long long row = (long long)pocket * kslots + j;
@@ -2368,6 +2383,250 @@ __global__ void __launch_bounds__(256) swor_follow_kernel(const float* __restric
         const int h = e / vq, o = e - h * vq;
         vd[h * vh + o] = vs[h * vh + o];
     }
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------ constrained beam search
+// include/singa_hip_beam.h states the rule.  Where singa_beam_select keeps the new slots until every parent has been read:
+// offsets into `work`, 16-byte aligned.  `active` holds one word per pocket (pockets <= rows).
+struct BeamWork {
+    long long tokens, score, parent, tok, len, gs, v0, v1, active, bytes;
+    BeamWork(long long rows, long long T) {
+        auto up = [](long long b) { return (b + 15) / 16 * 16; };
+        tokens = 0;
+        score = tokens + up(rows * T * 8);
+        parent = score + up(rows * 4);
+        tok = parent + up(rows * 4);
+        len = tok + up(rows * 4);
+        gs = len + up(rows * 4);
+        v0 = gs + up(rows * 4);
+        v1 = v0 + up(rows * 4);
+        active = v1 + up(rows * 4);
+        bytes = active + up(rows * 4);
+    }
+};
+
+#ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
+// singa_beam_expand: one wave per row, the row's logits in registers as sample_token_kernel holds them.  lse and z - lse are
+// that kernel's expressions, so score + (z - lse) accumulates the bits that kernel's sum_logp accumulates.
+// MODE 0: `allowed` only; 1: the SMILES rule (cls, gstate); 2: the valence rule (cls, cap, gstate, vstate).
+template <int NPL, int MODE>
+__global__ void __launch_bounds__(256) beam_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
+                                                          const unsigned char* __restrict__ cls, const unsigned char* __restrict__ cap,
+                                                          const long long* __restrict__ pos, int pos_offset, int rows, int kslots,
+                                                          int V, int T, const float* __restrict__ score,
+                                                          const int32_t* __restrict__ gstate, const int32_t* __restrict__ vstate,
+                                                          const unsigned char* __restrict__ done, float* __restrict__ cand) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                           // wave-uniform from here on
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    if (done[row / kslots]) return;                                    // a done pocket is frozen
+    const float NEG = -INFINITY;
+    const float sc = score[row];
+    float* cr = cand + (long long)row * V;
+    if (!(sc > NEG)) {                                                 // dead: no candidate
+        for (int i = lane; i < V; i += 64) cr[i] = NEG;
+        return;
+    }
+    float z[NPL];
+    bool ok[NPL];
+    int gs = 0;
+    if constexpr (MODE > 0) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
+    ValenceState vs{0, 0, 0};
+    if constexpr (MODE == 2)
+        vs = valence_load(gs, __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row]),
+                          __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row + 1]));
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int i = k * 64 + lane;
+        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
+        ok[k] = i < V && (!allowed || allowed[i]);
+        if constexpr (MODE == 1) ok[k] = ok[k] && smiles_allows(gs, i < V ? cls[i] : 0, (int)(T - 2 - t));
+        if constexpr (MODE == 2) ok[k] = ok[k] && valence_allows(vs, i < V ? cls[i] : 0, i < V ? cap[i] & 7 : 0, (int)(T - 2 - t));
+    }
+    // the model's own log-sum-exp (nothing filtered), as in sample_token_kernel
+    float zmax = NEG;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
+    zmax = wave_max64(zmax);
+    float zsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
+    const float lse = zmax + logf(wave_sum64(zsum));
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int i = k * 64 + lane;
+        if (i < V) {
+            const float lp = z[k] - lse;
+            cr[i] = ok[k] ? sc + lp : NEG;
+        }
+    }
+}
+
+// singa_beam_select, first launch: one workgroup per pocket that is not done.
+//   * the 2k best finite candidates of the pocket's k V, sorted: swor_topk;
+//   * thread 0 walks them with the reference's rules on LDS copies of the pocket's hypothesis scores and records its decisions:
+//     the flat index of every new slot, the parent whose prefix a hypothesis slot now holds (the last owner of a slot wins);
+//   * the workgroup then copies the hypotheses' token rows from the (still unchanged) slots and writes the new slots' scalars
+//     to `work`; beam_gather_kernel adds the parents' columns and beam_commit_kernel overwrites the slots.
+// The walk costs O(k) per stored hypothesis once the pocket holds k of them (the search for the one to drop).
+__global__ void __launch_bounds__(1024) beam_select_kernel(const float* __restrict__ cand, const unsigned char* __restrict__ cls,
+                                                           const unsigned char* __restrict__ cap, const long long* __restrict__ pos,
+                                                           int pos_offset, int kslots, int V, int T, int eos, int pad,
+                                                           const double* __restrict__ len_pow, const int32_t* __restrict__ length,
+                                                           const long long* __restrict__ tokens, const int32_t* __restrict__ gstate,
+                                                           const int32_t* __restrict__ vstate, long long* __restrict__ next,
+                                                           long long* __restrict__ src, double* __restrict__ hyp_score,
+                                                           float* __restrict__ hyp_sum, int32_t* __restrict__ hyp_len,
+                                                           int32_t* __restrict__ hyp_stamp, long long* __restrict__ hyp_tokens,
+                                                           int32_t* __restrict__ n_hyp, double* __restrict__ worst,
+                                                           unsigned char* __restrict__ done, int32_t* __restrict__ live,
+                                                           float* __restrict__ w_score, int32_t* __restrict__ w_parent,
+                                                           int32_t* __restrict__ w_tok, int32_t* __restrict__ w_len,
+                                                           int32_t* __restrict__ w_gs, int32_t* __restrict__ w_v0,
+                                                           int32_t* __restrict__ w_v1, int32_t* __restrict__ w_active) {
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned long long sel[2048];
+    __shared__ unsigned s_top[5];
+    __shared__ double h_score[1024];
+    __shared__ float h_sum[1024];
+    __shared__ int h_stamp[1024], h_owner[1024], n_flat[1024];
+    __shared__ int s_kept;
+    const int tid = threadIdx.x, pocket = blockIdx.x;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;                                   // workgroup-uniform
+    if (done[pocket]) {                                                // frozen: nothing of it is written
+        if (tid == 0) w_active[pocket] = 0;
+        return;
+    }
+    const int n = kslots * V;
+    const float* base = cand + (long long)pocket * n;
+    const long long row0 = (long long)pocket * kslots;
+    if (tid < kslots) {
+        h_score[tid] = hyp_score[row0 + tid], h_sum[tid] = hyp_sum[row0 + tid], h_stamp[tid] = hyp_stamp[row0 + tid];
+        h_owner[tid] = -1;
+    }
+    const unsigned kk = swor_topk(base, n, 2u * (unsigned)kslots, hist, sel, s_top);
+    if (tid == 0) {
+        int nh = n_hyp[pocket], kept = 0;
+        double w = worst[pocket];
+        bool dn = false;
+        const double denom = len_pow[t + 1];                           // a stored prefix holds t + 1 tokens, '&' included
+        const double best = kk > 0 ? (double)base[0x1FFFFF - (int)(sel[0] & 0x1FFFFF)] / denom : 0.0;
+        for (int rank = 0; rank < (int)kk; ++rank) {
+            const int flat = 0x1FFFFF - (int)(sel[rank] & 0x1FFFFF);
+            const int pi = flat / V, v = flat - pi * V;
+            if (v == eos) {
+                if (rank >= kslots) continue;
+                const float sum = base[flat];
+                const double sc = (double)sum / denom;
+                if (!(nh >= kslots && sc <= w)) {                      // BeamHypotheses.add
+                    const bool full = nh >= kslots;
+                    int at = nh;
+                    if (full) {                                        // drop the lowest score, the earliest stored among equals
+                        at = 0;
+                        for (int h = 1; h < kslots; ++h)
+                            if (h_score[h] < h_score[at] || (h_score[h] == h_score[at] && h_stamp[h] < h_stamp[at])) at = h;
+                    } else {
+                        ++nh;
+                    }
+                    h_score[at] = sc, h_sum[at] = sum, h_stamp[at] = (int)t * 2 * kslots + rank, h_owner[at] = pi;
+                    if (full) {                                        // the worst is the lowest score that is left
+                        w = h_score[0];
+                        for (int h = 1; h < kslots; ++h) w = h_score[h] < w ? h_score[h] : w;
+                    } else {
+                        w = sc < w ? sc : w;
+                    }
+                }
+            } else {
+                n_flat[kept++] = flat;
+            }
+            if (kept == kslots) break;
+            dn = dn || (nh >= kslots && w >= best);                    // BeamHypotheses.is_done
+        }
+        n_hyp[pocket] = nh, worst[pocket] = w;
+        if (dn) done[pocket] = 1;
+        live[pocket] = dn ? 0 : kept;
+        w_active[pocket] = 1;
+        s_kept = kept;
+    }
+    __syncthreads();
+    const int kept = s_kept;
+    if (tid < kslots) {
+        const long long row = row0 + tid;
+        if (tid < kept) {
+            const int flat = n_flat[tid], pi = flat / V, v = flat - pi * V;
+            const long long from = row0 + pi;
+            w_score[row] = base[flat], w_parent[row] = (int)from, w_tok[row] = v, w_len[row] = length[from] + 1;
+            if (gstate) {
+                if (vstate) {
+                    const ValenceState to = valence_next(valence_load(gstate[from], vstate[2 * from], vstate[2 * from + 1]), cls[v],
+                                                         cap[v] & 7);
+                    w_gs[row] = to.gs, w_v0[row] = to.v0, w_v1[row] = to.v1;
+                } else {
+                    w_gs[row] = smiles_next(gstate[from], cls[v]);
+                }
+            }
+            next[row] = v, src[row] = from;
+        } else {
+            w_parent[row] = -1;
+            next[row] = pad, src[row] = row;
+        }
+        if (h_owner[tid] >= 0) {
+            hyp_score[row] = h_score[tid], hyp_sum[row] = h_sum[tid], hyp_stamp[row] = h_stamp[tid];
+            hyp_len[row] = (int)t + 1;
+        }
+    }
+    for (int e = tid; e < kslots * T; e += 1024) {                     // the stored prefixes, without '$'
+        const int h = e / T, c = e - h * T;
+        if (h_owner[h] >= 0) hyp_tokens[(row0 + h) * T + c] = c <= t ? tokens[(row0 + h_owner[h]) * T + c] : (long long)pad;
+    }
+}
+
+// singa_beam_select, second launch: the parents' columns 0 .. t of the new slots into `work` (one wave per row)
+__global__ void __launch_bounds__(256) beam_gather_kernel(const long long* __restrict__ pos, int pos_offset, int rows, int kslots, int T,
+                                                          const int32_t* __restrict__ w_active, const int32_t* __restrict__ w_parent,
+                                                          const long long* __restrict__ tokens, long long* __restrict__ w_tokens) {
+    const int lane = threadIdx.x & 63;
+    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    if (!w_active[row / kslots]) return;
+    const long long from = w_parent[row];
+    if (from < 0) return;
+    for (int c = lane; c <= t; c += 64) w_tokens[row * T + c] = tokens[from * T + c];
+}
+
+// singa_beam_select, third launch: the new slots from `work` into the state arrays (one wave per row).  A dead slot keeps its
+// tokens, its length and its state words.
+__global__ void __launch_bounds__(256) beam_commit_kernel(const long long* __restrict__ pos, int pos_offset, int rows, int kslots, int T,
+                                                          float* __restrict__ score, int32_t* __restrict__ length,
+                                                          long long* __restrict__ tokens, int32_t* __restrict__ gstate,
+                                                          int32_t* __restrict__ vstate, const int32_t* __restrict__ w_active,
+                                                          const float* __restrict__ w_score, const int32_t* __restrict__ w_parent,
+                                                          const int32_t* __restrict__ w_tok, const int32_t* __restrict__ w_len,
+                                                          const int32_t* __restrict__ w_gs, const int32_t* __restrict__ w_v0,
+                                                          const int32_t* __restrict__ w_v1, const long long* __restrict__ w_tokens) {
+    const int lane = threadIdx.x & 63;
+    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const long long t = *pos - pos_offset;
+    if (t < 0 || t + 1 >= T) return;
+    if (!w_active[row / kslots]) return;
+    if (w_parent[row] < 0) {
+        if (lane == 0) score[row] = -INFINITY;
+        return;
+    }
+    if (lane == 0) {
+        score[row] = w_score[row], length[row] = w_len[row];
+        if (gstate) gstate[row] = w_gs[row];
+        if (vstate) vstate[2 * row] = w_v0[row], vstate[2 * row + 1] = w_v1[row];
+        tokens[row * T + t + 1] = w_tok[row];
+    }
+    for (int c = lane; c <= t; c += 64) tokens[row * T + c] = w_tokens[row * T + c];
 }
 #endif
 
@@ -7639,6 +7898,84 @@ int singa_swor_follow(const float* k_src, const float* v_src, float* k_dst, floa
     hipLaunchKernelGGL(swor_follow_kernel, dim3(rows, layers), dim3(256), 0, (hipStream_t)stream, k_src, v_src, k_dst, v_dst, src,
                        gumbel, finished, pos, rows, heads, P, dk, dv, k_row_ld, k_layer_ld, v_row_ld, v_layer_ld);
     return check_launch("swor_follow");
+#endif
+}
+
+long long singa_beam_work(int rows, int T) {
+    if (rows < 0 || T < 2) return -1;
+    return BeamWork(rows, T).bytes;
+}
+
+namespace {
+// the checks singa_beam_expand and singa_beam_select share; 0 = go on
+int beam_args(const char* what, const void* cls, const void* cap, const void* gstate, const void* vstate, int rows, int k, int V,
+              int T, int eos, int pad) {
+    if (!cls != !gstate) return fail_at(SINGA_E_NULL, what, "cls and gstate go together");
+    if (!cap != !vstate || (cap && !cls)) return fail_at(SINGA_E_NULL, what, "cap and vstate go together, and only with cls");
+    const char* bad = nullptr;
+    if (V < 1 || V > 1024) bad = "vocabulary of 1..1024 tokens";
+    else if (k < 1 || k > 1024) bad = "1..1024 slots per pocket";
+    else if (rows < 0 || rows % k) bad = "rows must be pockets x slots";
+    else if (T < (cls ? 3 : 2)) bad = "T >= 2 columns (3 under a grammar)";
+    else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
+    return bad ? fail_at(SINGA_E_SHAPE, what, bad) : SINGA_OK;
+}
+}  // namespace
+
+int singa_beam_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const unsigned char* cap,
+                      const long long* pos, int pos_offset, int rows, int k, int V, int T, const float* score,
+                      const int32_t* gstate, const int32_t* vstate, const unsigned char* done, float* cand, void* stream) {
+    const char* name = "beam_expand";
+    if (!logits || !pos || !score || !done || !cand) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (const int e = beam_args(name, cls, cap, gstate, vstate, rows, k, V, T, 0, 0)) return e;
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const dim3 grid((rows + 3) / 4), block(256);
+    const int mode = cap ? 2 : cls ? 1 : 0;
+    dispatch_npl(V, [&](auto npl) {
+        auto launch = [&](auto m) {
+            hipLaunchKernelGGL((beam_expand_kernel<decltype(npl)::value, decltype(m)::value>), grid, block, 0, (hipStream_t)stream,
+                               logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate, vstate, done, cand);
+        };
+        if (mode == 2) launch(std::integral_constant<int, 2>{});
+        else if (mode == 1) launch(std::integral_constant<int, 1>{});
+        else launch(std::integral_constant<int, 0>{});
+    });
+    return check_launch(name);
+#endif
+}
+
+int singa_beam_select(const float* cand, const unsigned char* cls, const unsigned char* cap, const long long* pos, int pos_offset,
+                      int rows, int k, int V, int T, int eos, int pad, const double* len_pow, float* score, int32_t* length,
+                      long long* tokens, long long* next, long long* src, int32_t* gstate, int32_t* vstate, double* hyp_score,
+                      float* hyp_sum, int32_t* hyp_len, int32_t* hyp_stamp, long long* hyp_tokens, int32_t* n_hyp, double* worst,
+                      unsigned char* done, int32_t* live, void* work, void* stream) {
+    const char* name = "beam_select";
+    if (!cand || !pos || !len_pow || !score || !length || !tokens || !next || !src || !hyp_score || !hyp_sum || !hyp_len ||
+        !hyp_stamp || !hyp_tokens || !n_hyp || !worst || !done || !live || !work)
+        return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (const int e = beam_args(name, cls, cap, gstate, vstate, rows, k, V, T, eos, pad)) return e;
+    if ((uintptr_t)work % 16) return fail_at(SINGA_E_SHAPE, name, "work must be 16-byte aligned");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const BeamWork w(rows, T);
+    char* b = (char*)work;
+    long long* wt = (long long*)(b + w.tokens);
+    float* ws = (float*)(b + w.score);
+    int32_t *wp = (int32_t*)(b + w.parent), *wk = (int32_t*)(b + w.tok), *wl = (int32_t*)(b + w.len), *wg = (int32_t*)(b + w.gs),
+            *w0 = (int32_t*)(b + w.v0), *w1 = (int32_t*)(b + w.v1), *wa = (int32_t*)(b + w.active);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(rows / k), dim3(1024), 0, st, cand, cls, cap, pos, pos_offset, k, V, T, eos, pad,
+                       len_pow, length, tokens, gstate, vstate, next, src, hyp_score, hyp_sum, hyp_len, hyp_stamp, hyp_tokens, n_hyp,
+                       worst, done, live, ws, wp, wk, wl, wg, w0, w1, wa);
+    hipLaunchKernelGGL(beam_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, pos, pos_offset, rows, k, T, wa, wp, tokens, wt);
+    hipLaunchKernelGGL(beam_commit_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, pos, pos_offset, rows, k, T, score, length, tokens,
+                       gstate, vstate, wa, ws, wp, wk, wl, wg, w0, w1, wt);
+    return check_launch(name);
 #endif
 }
 

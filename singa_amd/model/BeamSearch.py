@@ -15,6 +15,11 @@ survive (see `_select` for the rules that are easy to get subtly different).  Wh
 
 The device work of a step is GEMMs (library calls through ops.linear), softmax / layer norm / top-k (library ops) on
 [rows, 256] operands; hypothesis bookkeeping stays on the host, as in the reference.
+
+`beam_search_device` is a second search beside it: the same selection rules as kernels inside the captured step
+(`ops.beam_expand`, `ops.beam_select`; include/singa_hip_beam.h states the rule), the hypotheses kept on the device, nothing
+copied per token - and therefore able to take the SMILES and the valence rule of the samplers (`grammar=`).  `beam_search`,
+its defaults and its host path are the ones pinned to the reference's goldens and stay as they are.
 """
 import math
 
@@ -344,4 +349,141 @@ def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example,
             decoded[i, :lens[i]] = x
             if lens[i] < max_length:
                 decoded[i, lens[i]] = eos
+    return torch.from_numpy(decoded).to(dev)
+
+
+BEAM_MAX_K = 1024       # slots per pocket singa_beam_select is built for
+
+
+@torch.no_grad()
+def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", grammar=None,
+                       suppress=(), length_penalty=0.7, graph=True, trace=None):
+    """`beam_search` with the selection on the device (include/singa_hip_beam.h states the rule: `_select` and `BeamHypotheses`
+    as kernels, ties ranked by slot, then token), which can therefore be constrained: `grammar` None, "smiles" or "valence"
+    and `suppress` as in `Sampling.sample`.  Under a grammar every stored hypothesis is a string the rule accepts, ended by its
+    own '$'.  The scores are the unmodified model's: the mask removes candidates, it does not renormalise.
+
+    `model`, `smiVoc`, `num_beams`, `batch_size`, `max_length`, `topk`, `example`, `prop` and `device` as in `beam_search`, and the
+    same return value: the int64 token matrix [batch_size * topk, T'] on `device`, padded and '$'-terminated as BS:164-173
+    does - except that under a grammar, where every hypothesis was ended by its own '$', the '$' is written back also when all
+    returned rows are equally long (BS:164-166 returns such rows bare).  `length_penalty`: the exponent of
+    `BeamHypotheses`.  `graph=False` launches the step's kernels one by one (same result).  The loop is `sample_distinct`'s:
+    two cache buffers taken in turn, the step captured once per parity, one read of the pockets' live counters every
+    `Sampling.LIVE_POLL` tokens and nothing else per token.  Only the k17 step kernels serve this mode.  The end of the search
+    stays on the host: a pocket that is not done adds its live beams as hypotheses (BS:141-149), the `topk` best are returned.
+
+    `trace`, if a dict, receives `hyps` (one `BeamHypotheses` per pocket, as `beam_search` leaves them), `hyp_sum_logp` and
+    `hyp_tokens` (per pocket, one entry per stored hypothesis in the order of `hyps[b].beams`: the f32 summed log-probability,
+    '$' included where the search ended the string, and the tokens without '$'), `steps` and `valid` (uint8 per returned row: 0
+    where the pocket stored fewer than `topk` hypotheses - such rows are all '^').  ValueError before any launch unless
+    1 <= topk <= num_beams <= 1024, for what `smiles.check_arguments` refuses, for a decoder geometry, length or pocket size
+    the k17 kernels are not built for, and for caches (two buffers) that do not fit the free memory."""
+    from . import Sampling as S
+    from .. import smiles
+    if not 1 <= topk <= num_beams <= BEAM_MAX_K:
+        raise ValueError(f"beam_search_device: 1 <= topk <= num_beams <= {BEAM_MAX_K} (got topk {topk}, num_beams {num_beams})")
+    dev, tf, voc, (sos, eos, pad), rows, num, positions, free, cls, allowed = S._prologue(
+        "beam_search_device", model, smiVoc, num_beams, batch_size, max_length, example, device, grammar, suppress)
+    k, V, T = num_beams, len(voc), max_length
+    a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
+    atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
+    if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
+            and positions <= 256 and atoms <= 1024 and V <= 1024):
+        raise ValueError("beam_search_device: the k17 step kernels are the only path: the shipped decoder geometry, at most 256 "
+                         "positions, 1024 pocket atoms and 1024 tokens")
+    need = 2 * S.cache_bytes(tf.decoder, rows, positions) + rows * V * 4 + 3 * rows * T * 8
+    if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
+        raise ValueError(f"beam_search_device: the two key / value cache buffers of {rows} rows x {positions} positions and the "
+                         f"candidates take {need} bytes, {free} bytes are free on {dev}: use fewer beams or pockets per call")
+
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
+    bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    state = {"score": new(rows, torch.float32), "length": new(rows, torch.int32), "tokens": new((rows, T), torch.int64),
+             "next": new(rows, torch.int64), "src": new(rows, torch.int64), "cand": new((rows, V), torch.float32),
+             "hyp_score": new(rows, torch.float64), "hyp_sum": new(rows, torch.float32), "hyp_len": new(rows, torch.int32),
+             "hyp_stamp": new(rows, torch.int32), "hyp_tokens": new((rows, T), torch.int64), "n_hyp": new(batch_size, torch.int32),
+             "worst": new(batch_size, torch.float64), "done": new(batch_size, torch.uint8), "live": new(batch_size, torch.int32)}
+    never = torch.zeros(rows, dtype=torch.uint8, device=dev)           # `finished` of the cache mover: a beam slot is live or dead
+    if grammar is not None:
+        cls = torch.as_tensor(cls).to(dev)
+        state["grammar"] = new(rows, torch.int32)
+    cap, vstate = S._valence_operands(grammar, smiVoc, rows, dev)
+    if vstate is not None:
+        state["vstate"] = vstate
+    # n ** length_penalty by Python's own `**`, as BeamHypotheses.add evaluates it (entry 0 is never read)
+    len_pow = torch.tensor([1.0] + [float(n ** length_penalty) for n in range(1, T)], dtype=torch.float64).to(dev)
+    work = ops.beam_work(rows, T, dev)
+
+    def start():
+        state["tokens"].fill_(pad)
+        state["tokens"][:, 0] = sos
+        state["next"].fill_(sos)
+        state["score"].fill_(float("-inf"))
+        state["score"].view(batch_size, k)[:, 0] = 0                   # slot 0 of every pocket is the root
+        state["length"].zero_(), state["src"].zero_(), state["cand"].fill_(float("-inf"))
+        state["hyp_score"].zero_(), state["hyp_sum"].zero_(), state["hyp_len"].zero_(), state["hyp_stamp"].zero_()
+        state["hyp_tokens"].fill_(pad)
+        state["n_hyp"].zero_(), state["worst"].fill_(1e9), state["done"].zero_(), state["live"].fill_(1)
+        if grammar is not None:
+            state["grammar"].fill_(smiles.FRESH)
+        kv.reset()
+
+    def step(parity):
+        (ck, cv), (ok, ov) = bufs[parity], bufs[1 - parity]
+        out = kv.advance(kv.token_input(state["next"]), ck, cv)
+        ops.beam_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, allowed, cls, cap)
+        ops.beam_select(kv.pos, num + 1, state, k, work, len_pow, eos, pad, cls, cap)
+        ops.swor_follow(ck, cv, ok, ov, state["src"], state["score"], never, kv.pos)
+
+    def prime():
+        start()
+        kv.pos += num
+
+    replays = [lambda: step(0), lambda: step(1)]                       # the step on each pair of cache buffers, taken in turn
+    if graph:
+        replays = capture_steps(prime, replays, 1)
+    start()
+    if num:
+        kv.advance(kv.prop_input(prop.to(dev).float()))                # position 0 is the property prompt, in the first buffer
+    steps = S._decode(replays, T - 1, lambda: int(state["live"].sum().item()))
+
+    # the end of the search on the host: a few hundred numbers, once
+    host = {n: state[n].cpu().numpy() for n in ("score", "length", "tokens", "hyp_score", "hyp_sum", "hyp_len", "hyp_stamp",
+                                                "hyp_tokens", "n_hyp", "worst", "done")}
+    per = lambda name: host[name].reshape(batch_size, k, *host[name].shape[1:])
+    hyps, sums = [], {}
+    for b in range(batch_size):
+        h = BeamHypotheses(k, T, length_penalty)
+        n = int(host["n_hyp"][b])
+        for i in np.argsort(per("hyp_stamp")[b, :n], kind="stable"):   # ascending stamps: the order `add` would have left
+            hyp = per("hyp_tokens")[b, i, :per("hyp_len")[b, i]].copy()
+            h.beams.append((float(per("hyp_score")[b, i]), hyp))
+            sums[id(hyp)] = per("hyp_sum")[b, i]
+        h.worst_score = float(host["worst"][b])
+        if not host["done"][b]:                                        # BS:141-149
+            for j in range(k):
+                if per("score")[b, j] > float("-inf"):
+                    hyp = per("tokens")[b, j, :per("length")[b, j] + 1].copy()
+                    sums[id(hyp)] = per("score")[b, j]
+                    h.add(hyp, float(per("score")[b, j]))
+        hyps.append(h)
+    best = []
+    for h in hyps:
+        ranked = sorted(h.beams, key=lambda x: x[0])
+        best += [ranked.pop()[1] if ranked else None for _ in range(topk)]
+    valid = np.array([x is not None for x in best], dtype=np.uint8)
+    lens = [len(x) for x in best if x is not None]
+    if grammar is None and valid.all() and min(lens) == max(lens):     # BS:164-173; under a grammar every row gets its '$' back
+        decoded = np.stack(best)
+    else:
+        decoded = np.full((len(best), min(max(lens, default=0) + 1, T)), pad, dtype=np.int64)
+        for i, x in enumerate(best):
+            if x is not None:
+                decoded[i, :len(x)] = x
+                if len(x) < T:
+                    decoded[i, len(x)] = eos
+    if trace is not None:
+        trace.update(hyps=hyps, hyp_sum_logp=[[sums[id(x)] for _, x in h.beams] for h in hyps],
+                     hyp_tokens=[[x for _, x in h.beams] for h in hyps], steps=steps, valid=torch.from_numpy(valid))
     return torch.from_numpy(decoded).to(dev)

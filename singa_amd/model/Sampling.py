@@ -26,7 +26,8 @@ runs `singa_sample_token_grammar` (include/singa_hip_gen.h states the rule), whi
 more word of state per row on the device and masks, per row, what cannot follow the row's prefix or could not be finished in
 the columns left.  Every row then ends in '$' before `max_length` and the text in front of it has balanced branches, paired
 ring-closure digits and no dangling bond symbol.  This grammar is syntax only: valence, aromaticity, duplicate ring bonds
-(C1C1), %nn closures and beam search are outside its rule (singa_amd/smiles.py).  The step stays one captured graph.
+(C1C1) and %nn closures are outside its rule (singa_amd/smiles.py); beam search takes it through `beam_search_device`.  The step
+stays one captured graph.
 
 `grammar="valence"` adds a bonding-capacity rule to that syntax (include/singa_hip_valence.h states it): `ops.sample_token`,
 given the capacity bytes as well, runs `singa_sample_token_valence`, which keeps two more words of state per row and also

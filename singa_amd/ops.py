@@ -1041,6 +1041,72 @@ def swor_follow(k_src, v_src, k_dst, v_dst, src, gumbel, finished, pos):
          "singa_swor_follow")
 
 
+def beam_work(rows, T, device):
+    """The scratch `beam_select` needs for `rows` rows of `T` columns: a uint8 tensor of `singa_beam_work` bytes."""
+    n = int(_lib.lib().singa_beam_work(rows, T))
+    if n < 0:
+        raise RuntimeError(f"beam_work: rows >= 0 and T >= 2, got {rows}, {T}")
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+
+
+def _beam_views(what, state, R, B, V, T, names, cls, cap, extra=()):
+    """The argument checks of the beam ops: contiguous GPU tensors of the dtypes / shapes of include/singa_hip_beam.h."""
+    spec = {"score": (torch.float32, (R,)), "length": (torch.int32, (R,)), "tokens": (torch.int64, (R, T)),
+            "next": (torch.int64, (R,)), "src": (torch.int64, (R,)), "grammar": (torch.int32, (R,)),
+            "vstate": (torch.int32, (R, 2)), "cand": (torch.float32, (R, V)), "hyp_score": (torch.float64, (R,)),
+            "hyp_sum": (torch.float32, (R,)), "hyp_len": (torch.int32, (R,)), "hyp_stamp": (torch.int32, (R,)),
+            "hyp_tokens": (torch.int64, (R, T)), "n_hyp": (torch.int32, (B,)), "worst": (torch.float64, (B,)),
+            "done": (torch.uint8, (B,)), "live": (torch.int32, (B,))}
+    if cap is not None and cls is None:
+        raise RuntimeError(f"{what}: cap goes only with cls")
+    names = names + (("grammar",) if cls is not None else ()) + (("vstate",) if cap is not None else ())
+    items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (cap, torch.uint8, (V,))] + list(extra)
+    _check_views(what, items)
+    _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
+
+
+def beam_expand(logits, pos, pos_offset, state, k, allowed=None, cls=None, cap=None):
+    """Sub-step 1 of the device beam search (`singa_beam_expand`, include/singa_hip_beam.h states the rule; inference only):
+    the summed log-probability of every candidate of every live row, -inf where `allowed`, the SMILES rule (`cls`: [V] uint8
+    class bytes) or the valence rule (`cls` of `smiles.classify_orders` and `cap`: [V] uint8 capacities) refuses the token.
+    logits [R, V] f32, R = pockets * k; pos: int64 device scalar (the step is pos - pos_offset); `state`: score [R] f32, tokens
+    [R, T] (for T only), done [pockets] uint8, with `cls` grammar [R] int32, with `cap` vstate [R, 2] int32 - all read - and
+    cand [R, V] f32, written."""
+    R, V = logits.shape
+    T = state["tokens"].shape[1]
+    _beam_views("beam_expand", state, R, R // max(k, 1), V, T, ("score", "done", "cand"), cls, cap,
+                ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (allowed, torch.uint8, (V,))))
+    _chk(_lib.lib().singa_beam_expand(_p(logits), _p(allowed), _p(cls), _p(cap), _p(pos), pos_offset, R, k, V, T, _p(state["score"]),
+                                      _p(state["grammar"] if cls is not None else None),
+                                      _p(state["vstate"] if cap is not None else None), _p(state["done"]), _p(state["cand"]),
+                                      _stream()), "singa_beam_expand")
+
+
+def beam_select(pos, pos_offset, state, k, work, len_pow, eos=0, pad=0, cls=None, cap=None):
+    """Sub-steps 2 and 3 (`singa_beam_select`): per pocket that is not done the 2k best candidates of `state`'s cand are walked
+    with the reference's rules - '$' candidates inside the first k are stored among the pocket's hypotheses (hyp_score f64,
+    hyp_sum f32, hyp_len, hyp_stamp int32 [R], hyp_tokens [R, T] int64, n_hyp int32, worst f64, done uint8 [pockets]), the others
+    become the new slots (score, length, tokens, next, src, grammar, vstate follow the parents) - and live [pockets] int32 is
+    written.  len_pow: [>= T] f64 on the device, n ** length_penalty.  `work`: `beam_work(R, T, device)`."""
+    R, V = state["cand"].shape
+    T = state["tokens"].shape[1]
+    names = ("score", "length", "tokens", "next", "src", "cand", "hyp_score", "hyp_sum", "hyp_len", "hyp_stamp", "hyp_tokens",
+             "n_hyp", "worst", "done", "live")
+    _beam_views("beam_select", state, R, R // max(k, 1), V, T, names, cls, cap,
+                ((pos, torch.int64, None), (work, torch.uint8, None), (len_pow, torch.float64, None)))
+    need = int(_lib.lib().singa_beam_work(R, T))
+    if work.numel() < need or len_pow.numel() < T:
+        raise RuntimeError(f"beam_select: work holds {work.numel()} bytes, singa_beam_work({R}, {T}) = {need}; len_pow holds "
+                           f"{len_pow.numel()} entries for T = {T}")
+    s = state
+    _chk(_lib.lib().singa_beam_select(_p(s["cand"]), _p(cls), _p(cap), _p(pos), pos_offset, R, k, V, T, eos, pad, _p(len_pow),
+                                      _p(s["score"]), _p(s["length"]), _p(s["tokens"]), _p(s["next"]), _p(s["src"]),
+                                      _p(s["grammar"] if cls is not None else None), _p(s["vstate"] if cap is not None else None),
+                                      _p(s["hyp_score"]), _p(s["hyp_sum"]), _p(s["hyp_len"]), _p(s["hyp_stamp"]), _p(s["hyp_tokens"]),
+                                      _p(s["n_hyp"]), _p(s["worst"]), _p(s["done"]), _p(s["live"]), _p(work), _stream()),
+         "singa_beam_select")
+
+
 class _MaskedSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, mask, scale, heads):

@@ -5,7 +5,8 @@ the fresh state.
 
 Scope of the "smiles" rule: syntax only - balanced branches, paired ring-closure digits, no dangling bond symbol, and a '$'
 before the columns run out.  Not covered: chemical validity (valence, aromaticity, duplicate ring bonds such as C1C1), %nn
-closures (the vocabulary has none), a bond symbol in front of a closing ring digit (never drawn), beam search.
+closures (the vocabulary has none), a bond symbol in front of a closing ring digit (never drawn).  Beam search takes both
+rules through `BeamSearch.beam_search_device` (include/singa_hip_beam.h).
 
 `grammar="valence"` (include/singa_hip_valence.h states the rule, `singa_sample_token_valence` evaluates it) adds a
 bonding-capacity rule to the syntax: no atom of a drawn row carries more bond order than the capacity of its token

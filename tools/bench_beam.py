@@ -3,8 +3,12 @@
 num_beams=20, topk=1, max_length = tgt_len + 1 = 201, property prompt - on synthetic pockets with random-init weights.
 
     python tools/bench_beam.py [--proteins 4] [--max-length 201] [--beams 20] [--no-graph] [--prefix-baseline]
+                               [--select host|device] [--batch 1]
 
 Prints one JSON line: new tokens per second (beams x steps / time), pockets per second, and the per-step time.
+`--select device` times `beam_search_device` (the selection as kernels inside the captured step, nothing copied per token)
+instead of `beam_search` (2 x beams candidates per pocket to the host and the choice back, per token); `--batch N` searches N
+pockets per call, so that the two can be compared at 1 and at several pockets, back to back on one device.
 `--prefix-baseline` also times the reference's schedule (the whole decoder re-run on the growing prefix for every
 token, BeamSearch.py:82) built from the same product modules on the same GPU, so the two differ by the algorithm only.
 """
@@ -53,12 +57,15 @@ def main():
     ap.add_argument("--max-length", type=int, default=201)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--prefix-baseline", action="store_true")
+    ap.add_argument("--select", choices=["host", "device"], default="host")
+    ap.add_argument("--batch", type=int, default=1, help="pockets per call")
     args = ap.parse_args()
+    assert not args.prefix_baseline or args.batch == 1, "--prefix-baseline re-runs one pocket: --batch 1"
     import __graft_entry__
     __graft_entry__.build()
     from singa_amd import graph as G
     from singa_amd.config import Config, load_config
-    from singa_amd.model.BeamSearch import beam_search
+    from singa_amd.model.BeamSearch import beam_search, beam_search_device
     from singa_amd.model.CProMG import DenseMap, knn_graph
     from singa_amd.model.GAN import SINGA
     dev = torch.device("cuda", 0)
@@ -72,10 +79,10 @@ def main():
         model.model.decoder.layers[-1].pos_ffn.layer_norm.bias[0] = 10.0
         model.model.projection.weight[voc.index("$")] = 0.0
         model.model.projection.weight[voc.index("$"), 0] = -3.0
-    prop = torch.ones(args.beams, 3, device=dev)
+    prop = torch.ones(args.batch * args.beams, 3, device=dev)
 
     def pocket(i):
-        b = G.collate([G.synthetic_graph(500 + i)]).to(dev)
+        b = G.collate([G.synthetic_graph(500 + args.batch * i + j) for j in range(args.batch)]).to(dev)
         model.prepare(b)
         with torch.no_grad():
             feat = model.embedding(b, gen_mode=True)[G.PA].embedding.reshape(b[G.PA]["x"].shape[0], -1)
@@ -83,12 +90,13 @@ def main():
         batch = b[G.PA]["batch"]
         ex.protein_element_batch, ex.protein_atom_feature, ex.protein_pos = batch, feat, b[G.PA]["pos"]
         ex.protein_atom_laplacian = b[G.PA]["lap_pe"]
-        knn = knn_graph(b[G.PA]["pos"], cfg.model.encoder.knn, batch, 1, DenseMap(batch, 1))
+        knn = knn_graph(b[G.PA]["pos"], cfg.model.encoder.knn, batch, args.batch, DenseMap(batch, args.batch))
         ex.protein_knn = knn[:, knn[0] >= 0]
         return ex
 
     pockets = [pocket(i) for i in range(args.proteins)]
-    run = lambda ex: beam_search(model, voc, args.beams, 1, args.max_length, 1, ex, prop, device=dev, graph=not args.no_graph)
+    search = beam_search_device if args.select == "device" else beam_search
+    run = lambda ex: search(model, voc, args.beams, args.batch, args.max_length, 1, ex, prop, device=dev, graph=not args.no_graph)
     out = run(pockets[0])                                               # warm-up (library initialisation)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -98,10 +106,10 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     steps = sum(n - 1 for n in lens)
-    res = {"metric": "beam_search_new_tokens_per_s", "value": round(steps * args.beams / dt, 1), "unit": "tokens/s",
-           "pockets_per_s": round(args.proteins / dt, 3), "ms_per_step": round(dt / steps * 1e3, 4),
-           "config": {"workload": "gen.py: 1 pocket (200 atoms), property prompt", "num_beams": args.beams,
-                      "max_length": args.max_length, "decoded_lengths": lens,
+    res = {"metric": "beam_search_new_tokens_per_s", "value": round(steps * args.beams * args.batch / dt, 1), "unit": "tokens/s",
+           "pockets_per_s": round(args.proteins * args.batch / dt, 3), "ms_per_step": round(dt / steps * 1e3, 4),
+           "config": {"workload": f"gen.py: {args.batch} pocket(s) (200 atoms) per call, property prompt", "num_beams": args.beams,
+                      "select": args.select, "max_length": args.max_length, "decoded_lengths": lens,
                       "launch": "eager" if args.no_graph else "hipGraph replay per step"}}
     if args.prefix_baseline:
         prefix_rerun_search(model, voc, args.beams, min(args.max_length, 20), pockets[0], prop)
