@@ -183,13 +183,20 @@ _BEAM_SIGS = {
 }
 BEAM_EXPORTS = tuple(_BEAM_SIGS)
 
+# include/singa_hip_units.h: the kNN edge MLPs once per undirected edge (`ops.edge_mlp_pair(..., units=...)`); a table of its own
+_UNITS_SIGS = {
+    "singa_edge_mlp_units_fwd": ([P] * 13 + [I32, I32, I32, I32, P], I32),
+    "singa_edge_mlp_units_bwd": ([P] * 8 + [I32, I32, I32, P], I32),
+}
+UNITS_EXPORTS = tuple(_UNITS_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
-            list(_BEAM_SIGS.items()):
+            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

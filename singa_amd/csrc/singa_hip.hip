@@ -27,6 +27,7 @@
 #include "../../include/singa_hip_stream.h"
 #include "../../include/singa_hip_valence.h"
 #include "../../include/singa_hip_beam.h"
+#include "../../include/singa_hip_units.h"
 #include "so3_index.h"
 
 namespace {
@@ -2750,12 +2751,34 @@ __device__ __forceinline__ void emlp_stage_store(float* __restrict__ img, const 
     }
 }
 
+// UNITS (include/singa_hip_units.h).  `KnnEdges` symmetrises the kNN list: a real edge (i -> j) has its mate (j -> i) and both
+// carry the same attribute row, so both nets give the same rows for the two.  In the unit form of the kernels below a lane
+// owns one UNDIRECTED edge, a pair of rows (a, b) taken from unit_a / unit_b [E] (b == a: a row without a mate; a < 0: no
+// unit, and only at the tail of the list): the attribute row comes from a, the forward kernel stores its registers at both
+// rows, the backward kernel adds the two gradient rows before the recompute chain.  Half the tiles, the same tile code.
+// The row numbers of tile t + 2 strides are loaded while the rows of tile t + stride travel and tile t is computed.
+#ifndef SINGA_EMUL
+__device__ __forceinline__ bool emlp_wave_any(bool p) { return __ballot(p) != 0ull; }
+#else
+__device__ __forceinline__ bool emlp_wave_any(bool p) { return p; }
+#endif
+// the unit of lane i of tile tl; anything that is no row of [0, E) counts as "no unit" / "no mate": no address leaves the arrays
+__device__ __forceinline__ void emlp_unit_of(const int32_t* __restrict__ unit_a, const int32_t* __restrict__ unit_b, long long tl,
+                                             int i, int E, int& a, int& b) {
+    const long long u = tl * 32 + i, uc = u < E ? u : (long long)E - 1;
+    const int ra = unit_a[uc], rb = unit_b[uc];
+    a = u < E && ra >= 0 && ra < E ? ra : -1;
+    b = rb >= 0 && rb < E ? rb : a;
+}
+
+template <bool UNITS>
 __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_fwd_kernel(const float* __restrict__ attr, const float* __restrict__ w1tk,
                                                                 const float* __restrict__ b1k, const float* __restrict__ w2tk,
                                                                 const float* __restrict__ b2k, const float* __restrict__ w1tv,
                                                                 const float* __restrict__ b1v, const float* __restrict__ w2tv,
                                                                 const float* __restrict__ b2v, float* __restrict__ wk,
-                                                                float* __restrict__ wv, int E) {
+                                                                float* __restrict__ wv, int E, const int32_t* __restrict__ unit_a,
+                                                                const int32_t* __restrict__ unit_b) {
     __shared__ __attribute__((aligned(16))) float lw1k[32 * EMLP_P1], lw2k[32 * 36], lw1v[64 * EMLP_P1], lw2v[64 * 68];
     __shared__ float lb[32 + 32 + 64 + 64];
     {                                                      // the parameters arrive in nn.Linear's own [out][in] layout
@@ -2777,24 +2800,40 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_fwd_kernel(const float* 
     const long long tiles = ((long long)E + 31) / 32, stride = (long long)gridDim.x * 4;
     long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     float4 nxt[8];
+    int ca = -1, cb = -1, na = -1, nb = -1;     // UNITS: the rows of the tile whose attr rows `nxt` holds, of the tile behind it
     auto fetch = [&](long long tl) __attribute__((always_inline)) {      // this lane's half row of its edge of tile tl
         long long ee = tl * 32 + i;
-        const float* row = attr + (ee < E ? ee : (long long)E - 1) * 64 + 32 * half;
+        if constexpr (UNITS) ee = na > 0 ? na : 0;                       // (na, nb) is the unit of tile tl here
+        else ee = ee < E ? ee : (long long)E - 1;
+        const float* row = attr + ee * 64 + 32 * half;
 #pragma unroll
         for (int m = 0; m < 8; ++m) nxt[m] = *reinterpret_cast<const float4*>(row + 4 * m);
     };
-    if (tile < tiles) fetch(tile);
+    auto advance = [&](long long tl) __attribute__((always_inline)) {    // UNITS: fetched (na, nb); now the unit of tile tl
+        ca = na, cb = nb, na = nb = -1;
+        if (tl < tiles) emlp_unit_of(unit_a, unit_b, tl, i, E, na, nb);
+    };
+    if (tile < tiles) {
+        if constexpr (UNITS) emlp_unit_of(unit_a, unit_b, tile, i, E, na, nb);
+        fetch(tile);
+        if constexpr (UNITS) advance(tile + stride);
+    }
     for (; tile < tiles; tile += stride) {
-        const long long e = tile * 32 + i;
-        const bool ok = e < E;
+        const long long e0 = UNITS ? ca : tile * 32 + i, e1 = UNITS ? cb : e0;
+        const bool ok = UNITS ? ca >= 0 : e0 < E;
+        if constexpr (UNITS)
+            if (!emlp_wave_any(ok)) break;                 // the units come first: nothing but the null tail from here on
+        const int rows = !ok ? 0 : e1 != e0 ? 2 : 1;       // the rows this lane's registers go to
         float asel[32];
 #pragma unroll
         for (int m = 0; m < 8; ++m) asel[4 * m] = nxt[m].x, asel[4 * m + 1] = nxt[m].y, asel[4 * m + 2] = nxt[m].z, asel[4 * m + 3] = nxt[m].w;
         if (tile + stride < tiles) fetch(tile + stride);   // the next tile's rows travel while this tile's 176 MFMAs run
+        if constexpr (UNITS) advance(tile + 2 * stride);
         {
             floatx16 out[1];
             edge_mlp_tile<32>(asel, lw1k, lb, lw2k, lb + 32, lane, out);
-            if (ok) {
+            for (int d = 0; d < rows; ++d) {
+                const long long e = d ? e1 : e0;
 #pragma unroll
                 for (int blk = 0; blk < 4; ++blk)
                     *reinterpret_cast<float4*>(wk + e * 32 + 8 * blk + 4 * half) =
@@ -2804,7 +2843,8 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_fwd_kernel(const float* 
         {
             floatx16 out[2];
             edge_mlp_tile<64>(asel, lw1v, lb + 64, lw2v, lb + 128, lane, out);
-            if (ok) {
+            for (int d = 0; d < rows; ++d) {
+                const long long e = d ? e1 : e0;
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -2842,10 +2882,18 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_fwd_kernel(const float* 
 // through LDS and every workgroup writes one partial row part[block][slice][32*64 | 32 | H*32 | H] =
 // [dW1 rows of the slice | db1 of the slice | dW2 columns of the slice, [out][32] | db2], reduced afterwards with
 // singa_colsum.  No gradient w.r.t. attr (it carries none, CP:295-298).
-template <int H>
+// UNITS: the lane's gradient row is g_out[a] + g_out[b] (b != a), added in f32 between the pre chain and the gh chain.  The
+// two half rows are loaded where the previous tile's gradient registers die (behind their LDS image), not with the attr
+// rows: held from there on they would cost H / 2 registers more at the kernel's peak, which the 64-unit net does not have
+// (it spilled).
+// Tiles are not moved back (a lane without a unit is clamped to row 0 and masked), and a wavefront leaves the loop at its
+// first tile without a unit.  The partial rows are those of the directed form: all of them are written.
+template <int H, bool UNITS>
 __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel(const float* __restrict__ attr, const float* __restrict__ g_out,
                                                                    const float* __restrict__ w1t, const float* __restrict__ b1,
-                                                                   const float* __restrict__ w2, float* __restrict__ part, int E) {
+                                                                   const float* __restrict__ w2, float* __restrict__ part, int E,
+                                                                   const int32_t* __restrict__ unit_a,
+                                                                   const int32_t* __restrict__ unit_b) {
     constexpr int TO = H / 32, LD = 36, HH = H / 2, P2 = H + 4;
     constexpr int PSZ = 32 * 64 + 32 + H * 32 + H;
     constexpr int REG = 32 * LD + 32 * EMLP_P1;         // a wavefront's region: [32][LD] transposed tile + [32][68] row image
@@ -2886,23 +2934,53 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel(const float* 
     for (int a = 0; a < TO; ++a) db2p[a] = 0.f;
     const long long tilesN = ((long long)E + 31) / 32, stride = (long long)gridDim.x * 4;
     long long tile = (long long)blockIdx.x * 4 + wave;
-    float4 asel4[8], grow4[HH / 4], nasel4[8], ngrow4[HH / 4];
+    float4 asel4[8], grow4[HH / 4], nasel4[8], ngrow4[HH / 4], nmate4[UNITS ? HH / 4 : 1];
+    int ca = -1, cb = -1, na = -1, nb = -1;             // UNITS: the rows of the tile that is fetched, of the tile behind it
     auto first_row = [&](long long tl) __attribute__((always_inline)) { return tl * 32 + 32 <= E ? tl * 32 : (long long)E - 32; };
     auto fetch = [&](long long tl) __attribute__((always_inline)) {      // this lane's half rows of its edge of tile tl
-        const long long ee = first_row(tl) + i, er = ee > 0 ? ee : 0;
+        const long long ee = UNITS ? na : first_row(tl) + i, er = ee > 0 ? ee : 0;     // UNITS: (na, nb) is the unit of tile tl
 #pragma unroll
         for (int m = 0; m < 8; ++m) nasel4[m] = *reinterpret_cast<const float4*>(attr + er * 64 + 32 * half + 4 * m);
+        if constexpr (!UNITS) {
+#pragma unroll
+            for (int m = 0; m < HH / 4; ++m) ngrow4[m] = *reinterpret_cast<const float4*>(g_out + er * H + HH * half + 4 * m);
+        }
+    };
+    auto advance = [&](long long tl) __attribute__((always_inline)) {    // UNITS: fetched (na, nb); now the unit of tile tl
+        ca = na, cb = nb;
+        emlp_unit_of(unit_a, unit_b, tl, i, E, na, nb);                  // (a tile behind the last one: no unit)
+    };
+    auto fetch_g = [&]() __attribute__((always_inline)) {                // UNITS: the gradient half rows of the unit (ca, cb)
+        const long long er = ca > 0 ? ca : 0, em = ca >= 0 ? cb : 0;     // (a row without a mate: its own row, read and not added)
 #pragma unroll
         for (int m = 0; m < HH / 4; ++m) ngrow4[m] = *reinterpret_cast<const float4*>(g_out + er * H + HH * half + 4 * m);
+#pragma unroll
+        for (int m = 0; m < HH / 4; ++m) nmate4[m] = *reinterpret_cast<const float4*>(g_out + em * H + HH * half + 4 * m);
     };
-    if (tile < tilesN) fetch(tile);
+    if (tile < tilesN) {
+        if constexpr (UNITS) emlp_unit_of(unit_a, unit_b, tile, i, E, na, nb);
+        fetch(tile);
+        if constexpr (UNITS) advance(tile + stride), fetch_g();
+    }
     for (; tile < tilesN; tile += stride) {
         const long long e0 = tile * 32;
-        const bool ok = first_row(tile) + i >= e0;          // false: a row the previous tile has taken (or a row before row 0)
+        // false: a row the previous tile has taken (or a row before row 0); UNITS: a lane without a unit
+        const bool ok = UNITS ? ca >= 0 : first_row(tile) + i >= e0;
+        if constexpr (UNITS)
+            if (!emlp_wave_any(ok)) break;                  // the units come first: nothing but the null tail from here on
 #pragma unroll
         for (int m = 0; m < 8; ++m) asel4[m] = nasel4[m];
+        if constexpr (UNITS) {      // a lane without a unit computes on zero rows: every product it adds is 0 (no mask behind the math)
 #pragma unroll
-        for (int m = 0; m < HH / 4; ++m) grow4[m] = ok ? ngrow4[m] : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int m = 0; m < 8; ++m)
+                asel4[m] = make_float4(ok ? asel4[m].x : 0.f, ok ? asel4[m].y : 0.f, ok ? asel4[m].z : 0.f, ok ? asel4[m].w : 0.f);
+        }
+        const bool live = UNITS || ok;
+        if constexpr (!UNITS) {
+#pragma unroll
+            for (int m = 0; m < HH / 4; ++m) grow4[m] = ok ? ngrow4[m] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const bool mated = UNITS && ok && cb != ca;
         // region = {g_pre^T (after the activation), attr rows (now)}
 #pragma unroll
         for (int m = 0; m < 8; ++m) *reinterpret_cast<float4*>(rimg + i * EMLP_P1 + 32 * half + 4 * m) = asel4[m];
@@ -2931,8 +3009,21 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel(const float* 
                 __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             }
         }
+        if constexpr (UNITS) {                              // the two rows have had the dW2 products and the pre chain to arrive
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < HH / 4; ++m) {
+                const float4 ga = ngrow4[m], gb = nmate4[m];             // (scalar selects: no branch per register)
+                const float ax = ok ? ga.x : 0.f, ay = ok ? ga.y : 0.f, az = ok ? ga.z : 0.f, aw = ok ? ga.w : 0.f;
+                const float bx = mated ? gb.x : 0.f, by = mated ? gb.y : 0.f, bz = mated ? gb.z : 0.f, bw = mated ? gb.w : 0.f;
+                grow4[m] = make_float4(ax + bx, ay + by, az + bz, aw + bw);
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
-        if (tile + stride < tilesN) fetch(tile + stride);   // the attr registers are free now; 96 MFMAs of cover
+        // the attr registers are free now; 96 MFMAs of cover.  (UNITS: a tile behind the last one has no units and fetches row 0 -
+        // without the condition the prefetch registers are no phi of two values, which cost the 64-unit net 16 spilled registers)
+        if (UNITS || tile + stride < tilesN) fetch(tile + stride);
+        if constexpr (UNITS) advance(tile + 2 * stride);
         __builtin_amdgcn_sched_barrier(0);
         {
             const float* a2 = lw2 + i * P2 + HH * half;     // k-step s: output unit s (lower lanes) / HH + s (upper lanes)
@@ -2961,8 +3052,8 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel(const float* 
             const float p = pacc[r];
             const float tq = __expf(-fabsf(p)), u = 1.f + tq;
             const float sg = (p >= 0.f ? 1.f : tq) * SINGA_RCP(u);
-            tt[j * LD + i] = ok ? gacc[r] * sg : 0.f;
-            pacc[r] = ok ? fmaxf(p, 0.f) + __logf(u) - 0.69314718055994530942f : 0.f;
+            tt[j * LD + i] = live ? gacc[r] * sg : 0.f;
+            pacc[r] = live ? fmaxf(p, 0.f) + __logf(u) - 0.69314718055994530942f : 0.f;
         }
         if (lane < 32) {
             float c = 0.f;
@@ -2993,6 +3084,11 @@ __global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel(const float* 
         for (int r = 0; r < 16; ++r) tt[(8 * (r >> 2) + 4 * half + (r & 3)) * LD + i] = pacc[r];
 #pragma unroll
         for (int m = 0; m < HH / 4; ++m) *reinterpret_cast<float4*>(rimg + i * P2 + HH * half + 4 * m) = grow4[m];
+        if constexpr (UNITS) {          // the gradient registers are free now: they take the two rows of the next tile, (ca, cb)
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_g();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         {
             const float* hrow = tt + i * LD + 16 * half;
             const float* grows = rimg + 16 * half * P2 + i;
@@ -7989,8 +8085,8 @@ int singa_edge_mlp_fwd(const float* attr, const float* w1tk, const float* b1k, c
     if (E <= 0) return SINGA_OK;
     const long long tiles = ((long long)E + 31) / 32;
     const long long blocks = (tiles + 3) / 4;
-    hipLaunchKernelGGL(edge_mlp_mfma_fwd_kernel, dim3((unsigned)(blocks < 768 ? blocks : 768)), dim3(256), 0, (hipStream_t)stream,
-                       attr, w1tk, b1k, w2tk, b2k, w1tv, b1v, w2tv, b2v, wk, wv, E);
+    hipLaunchKernelGGL(edge_mlp_mfma_fwd_kernel<false>, dim3((unsigned)(blocks < 768 ? blocks : 768)), dim3(256), 0,
+                       (hipStream_t)stream, attr, w1tk, b1k, w2tk, b2k, w1tv, b1v, w2tv, b2v, wk, wv, E, nullptr, nullptr);
     return check_launch("edge_mlp_fwd");
 }
 
@@ -8008,12 +8104,58 @@ int singa_edge_mlp_bwd(const float* attr, const float* g_out, const float* w1t, 
     if (E <= 0) return SINGA_OK;
     const int blocks = singa_edge_mlp_bwd_nparts(E, H);
     if (H == 32)
-        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<32>), dim3(blocks, 1), dim3(256), 0, (hipStream_t)stream, attr, g_out, w1t,
-                           b1, w2, part, E);
+        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<32, false>), dim3(blocks, 1), dim3(256), 0, (hipStream_t)stream, attr, g_out,
+                           w1t, b1, w2, part, E, nullptr, nullptr);
     else
-        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<64>), dim3(blocks, 2), dim3(256), 0, (hipStream_t)stream, attr, g_out, w1t,
-                           b1, w2, part, E);
+        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<64, false>), dim3(blocks, 2), dim3(256), 0, (hipStream_t)stream, attr, g_out,
+                           w1t, b1, w2, part, E, nullptr, nullptr);
     return check_launch("edge_mlp_bwd");
+}
+
+// the unit forms (include/singa_hip_units.h): the same kernels, the same grids - E is the length of the unit list
+int singa_edge_mlp_units_fwd(const float* attr, const int32_t* unit_a, const int32_t* unit_b, const float* w1tk, const float* b1k,
+                             const float* w2tk, const float* b2k, const float* w1tv, const float* b1v, const float* w2tv,
+                             const float* b2v, float* wk, float* wv, int E, int CIN, int HK, int HV, void* stream) {
+    const char* name = "edge_mlp_units_fwd";
+    if (!attr || !unit_a || !unit_b || !w1tk || !b1k || !w2tk || !b2k || !w1tv || !b1v || !w2tv || !b2v || !wk || !wv)
+        return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (CIN != 64 || HK != 32 || HV != 64)
+        return fail_at(SINGA_E_SHAPE, name, "built for 64 edge channels, 32 key / 64 value channels per head");
+    if (E < 0) return fail_at(SINGA_E_SHAPE, name, "E >= 0 rows");
+    if ((uintptr_t)attr % 16 || (uintptr_t)wk % 16 || (uintptr_t)wv % 16)
+        return fail_at(SINGA_E_SHAPE, name, "attr, wk and wv must be 16-byte aligned");
+    if (E == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const long long blocks = (((long long)E + 31) / 32 + 3) / 4;
+    hipLaunchKernelGGL(edge_mlp_mfma_fwd_kernel<true>, dim3((unsigned)(blocks < 768 ? blocks : 768)), dim3(256), 0,
+                       (hipStream_t)stream, attr, w1tk, b1k, w2tk, b2k, w1tv, b1v, w2tv, b2v, wk, wv, E, unit_a, unit_b);
+    return check_launch(name);
+#endif
+}
+
+int singa_edge_mlp_units_bwd(const float* attr, const int32_t* unit_a, const int32_t* unit_b, const float* g_out, const float* w1t,
+                             const float* b1, const float* w2, float* part, int E, int CIN, int H, void* stream) {
+    const char* name = "edge_mlp_units_bwd";
+    if (!attr || !unit_a || !unit_b || !g_out || !w1t || !b1 || !w2 || !part) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (CIN != 64 || (H != 32 && H != 64))
+        return fail_at(SINGA_E_SHAPE, name, "built for 64 edge channels, 32 key / 64 value channels per head");
+    if (E < 0) return fail_at(SINGA_E_SHAPE, name, "E >= 0 rows");
+    if ((uintptr_t)attr % 16 || (uintptr_t)g_out % 16) return fail_at(SINGA_E_SHAPE, name, "attr and g_out must be 16-byte aligned");
+    if (E == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    const int blocks = singa_edge_mlp_bwd_nparts(E, H);
+    if (H == 32)
+        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<32, true>), dim3(blocks, 1), dim3(256), 0, (hipStream_t)stream, attr, g_out,
+                           w1t, b1, w2, part, E, unit_a, unit_b);
+    else
+        hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<64, true>), dim3(blocks, 2), dim3(256), 0, (hipStream_t)stream, attr, g_out,
+                           w1t, b1, w2, part, E, unit_a, unit_b);
+    return check_launch(name);
+#endif
 }
 
 int singa_masked_softmax_fwd(const float* s, const unsigned char* mask, long long mask_stride_b, long long mask_stride_t, float* p,

@@ -191,9 +191,35 @@ class KnnEdges:
         self.eperm = eperm.to(torch.int32)
         self.col_ptr = torch.searchsorted(self.col[eperm], bounds).to(torch.int32)
         self.N = N
+        self.unit_a, self.unit_b = self._units(ukey, n_real, bool(triple))
+
+    def _units(self, ukey, n_real, repeats):
+        """The rows of `attr` as UNITS, one per undirected edge (k15c evaluates the edge MLPs once per unit): unit u is the row
+        unit_a[u] and its mate unit_b[u], the row of the opposite direction, which the symmetrisation above always creates and
+        whose length - the mean over the same one or two kNN slots - and hence attribute row are the same bits.  A real edge
+        is the first of its unit iff row < col; its mate is found in the coalesced keys and sits where every edge e of row r
+        sits, at e + r.  Self loops and the inert padding edges are units of their own (unit_b == unit_a), and so is every row
+        of a caller-supplied list with repeats, whose means are sums of atomics.  Both arrays have the length of the edge
+        list, units first in row order, -1 behind them: no shape depends on the data and nothing is read back."""
+        row, col = self.row, self.col
+        E, N = row.shape[0], self.N
+        idx = torch.arange(E, device=row.device)
+        if repeats or ukey.numel() == 0:
+            single = torch.ones_like(row, dtype=torch.bool)
+        else:
+            single = row == col
+            if n_real is not None:
+                single |= torch.maximum(row, col) >= n_real
+        mate = torch.where(single, idx, torch.searchsorted(ukey, col * N + row) + col)
+        first = single | (row < col)
+        slot = torch.where(first, torch.cumsum(first, 0) - 1, E)              # the others go to a slot behind the end
+        both = torch.stack([idx, mate], 1).to(torch.int32)
+        units = torch.full((E + 1, 2), -1, dtype=torch.int32, device=row.device).index_copy_(0, slot, both)
+        return units[:E, 0].contiguous(), units[:E, 1].contiguous()
 
     def tensors(self):
-        return [self.row, self.col, self.attr, self.row_ptr, self.row32, self.col32, self.eperm, self.col_ptr]
+        return [self.row, self.col, self.attr, self.row_ptr, self.row32, self.col32, self.eperm, self.col_ptr, self.unit_a,
+                self.unit_b]
 
 
 # ----------------------------------------------------------------------------------------------- attention modules
@@ -232,7 +258,8 @@ class MultiHeadAttention(nn.Module):
         scale = 1.0 / math.sqrt(h_keys.size(-1))
         if edges.attr.shape[1] == 64 and self.weight_k_net[0].out_features == 32 and self.weight_v_net[0].out_features == 64:
             W_k, W_v = ops.edge_mlp_pair(edges.attr, (self.weight_k_net[0], self.weight_k_net[2]),
-                                         (self.weight_v_net[0], self.weight_v_net[2]))        # [E, 32], [E, 64]: k15c
+                                         (self.weight_v_net[0], self.weight_v_net[2]),
+                                         units=(edges.unit_a, edges.unit_b))                  # [E, 32], [E, 64]: k15c
         else:                                    # other widths: the same two MLPs as library GEMMs + the k15d kernel
             W_k = self._edge_mlp(self.weight_k_net, edges.attr)
             W_v = self._edge_mlp(self.weight_v_net, edges.attr)

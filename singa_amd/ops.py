@@ -1317,7 +1317,7 @@ class _EdgeMLPPair(torch.autograd.Function):
     backward pass, which recomputes the hidden units and reduces all four parameter gradients itself."""
 
     @staticmethod
-    def forward(ctx, attr, w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v):
+    def forward(ctx, attr, unit_a, unit_b, w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v):
         ctx.params = (w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v)
         attr = attr.contiguous()
         fw = [t.contiguous() for t in (w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v)]      # nn.Linear's own layouts, no copies
@@ -1326,6 +1326,15 @@ class _EdgeMLPPair(torch.autograd.Function):
         HK, HV = w1k.shape[0], w1v.shape[0]
         wk = torch.empty(E, HK, device=attr.device, dtype=torch.float32)
         wv = torch.empty(E, HV, device=attr.device, dtype=torch.float32)
+        ctx.units = unit_a is not None
+        if ctx.units:           # once per undirected edge (include/singa_hip_units.h): every row is some unit's a or b
+            unit_a, unit_b = unit_a.contiguous(), unit_b.contiguous()
+            _dev(unit_a, unit_b)
+            assert unit_a.dtype == unit_b.dtype == torch.int32 and unit_a.shape == unit_b.shape == (E,)
+            _chk(_lib.lib().singa_edge_mlp_units_fwd(_p(attr), _p(unit_a), _p(unit_b), *[_p(t) for t in fw], _p(wk), _p(wv), E, CIN,
+                                                     HK, HV, _stream()), "singa_edge_mlp_units_fwd")
+            ctx.save_for_backward(attr, fw[0], fw[1], fw[2], fw[4], fw[5], fw[6], unit_a, unit_b)
+            return wk, wv
         _chk(_lib.lib().singa_edge_mlp_fwd(_p(attr), *[_p(t) for t in fw], _p(wk), _p(wv), E, CIN, HK, HV, _stream()),
              "singa_edge_mlp_fwd")
         ctx.save_for_backward(attr, fw[0], fw[1], fw[2], fw[4], fw[5], fw[6])
@@ -1333,26 +1342,35 @@ class _EdgeMLPPair(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gk, gv):
-        attr, w1tk, b1k, w2k, w1tv, b1v, w2v = ctx.saved_tensors
+        attr, w1tk, b1k, w2k, w1tv, b1v, w2v = ctx.saved_tensors[:7]
+        units = [_p(t) for t in ctx.saved_tensors[7:]]
         E, CIN = attr.shape
         lib = _lib.lib()
+        bwd, what = (lib.singa_edge_mlp_units_bwd, "singa_edge_mlp_units_bwd") if ctx.units else \
+            (lib.singa_edge_mlp_bwd, "singa_edge_mlp_bwd")
         grads = []
         for g, w1t, b1, w2, params in ((gk, w1tk, b1k, w2k, ctx.params[:4]), (gv, w1tv, b1v, w2v, ctx.params[4:])):
             g = g.contiguous()
             H = w2.shape[0]
             row = H * CIN + H + H * H + H                 # [dW1 | db1 | dW2 | db2] in the parameters' layouts (include/singa_hip.h)
             part = torch.empty(lib.singa_edge_mlp_bwd_nparts(E, H), row, device=attr.device, dtype=torch.float32)
-            _chk(lib.singa_edge_mlp_bwd(_p(attr), _p(g), _p(w1t), _p(b1), _p(w2), _p(part), E, CIN, H, _stream()),
-                 "singa_edge_mlp_bwd")
+            _chk(bwd(_p(attr), *units, _p(g), _p(w1t), _p(b1), _p(w2), _p(part), E, CIN, H, _stream()), what)
             o1, o2, o3 = H * CIN, H * CIN + H, H * CIN + H + H * H
             gs = param_colsum(part, [(0, o1, params[0]), (o1, H, params[1]), (o2, H * H, params[2]), (o3, H, params[3])])
             grads += [gs[0].view(H, CIN) if gs[0] is not None else None, gs[1], gs[2].view(H, H) if gs[2] is not None else None, gs[3]]
-        return (None, *grads)
+        return (None, None, None, *grads)
 
 
-def edge_mlp_pair(attr, k_net, v_net):
-    """k_net / v_net: (first Linear, second Linear) of `weight_k_net` / `weight_v_net`."""
-    return _EdgeMLPPair.apply(attr, k_net[0].weight, k_net[0].bias, k_net[1].weight, k_net[1].bias,
+# k15c once per undirected edge when the caller names the units (`KnnEdges.unit_a / unit_b`); False: every directed row, as
+# without units (A/B runs and the tests' comparison of the two)
+USE_EDGE_UNITS = True
+
+
+def edge_mlp_pair(attr, k_net, v_net, units=None):
+    """k_net / v_net: (first Linear, second Linear) of `weight_k_net` / `weight_v_net`.  units: (unit_a, unit_b) int32 [E] of
+    include/singa_hip_units.h - every row of attr is named once, and a unit's two rows hold the same attributes."""
+    unit_a, unit_b = units if units is not None and USE_EDGE_UNITS else (None, None)
+    return _EdgeMLPPair.apply(attr, unit_a, unit_b, k_net[0].weight, k_net[0].bias, k_net[1].weight, k_net[1].bias,
                               v_net[0].weight, v_net[0].bias, v_net[1].weight, v_net[1].bias)
 
 

@@ -12,6 +12,7 @@ HDR = r'''#include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <cstdlib>
+#include <cstdint>
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 #define SINGA_RCP(x) __builtin_amdgcn_rcpf(x)
 __device__ __forceinline__ float ssp_fast(float x) { return fmaxf(x, 0.f) + __logf(1.f + __expf(-fabsf(x))) - 0.69314718055994530942f; }
@@ -33,9 +34,9 @@ int main(int argc, char** argv) {
         float ms = 0;
         for (int it = 0; it < 23; ++it) {
             if (it == 3) hipEventRecord(e0, 0);
-            if (which == 0) hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<64>), dim3(256, 2), dim3(256), 0, 0, attr, g, w1, b1, w2, part, E);
-            if (which == 1) hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<32>), dim3(512, 1), dim3(256), 0, 0, attr, g, w1, b1, w2, part, E);
-            if (which == 2) hipLaunchKernelGGL(edge_mlp_mfma_fwd_kernel, dim3(768), dim3(256), 0, 0, attr, w1, b1, w2, b1, w1, b1, w2, b1, wk, wv, E);
+            if (which == 0) hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<64, false>), dim3(256, 2), dim3(256), 0, 0, attr, g, w1, b1, w2, part, E, nullptr, nullptr);
+            if (which == 1) hipLaunchKernelGGL((edge_mlp_mfma_bwd_kernel<32, false>), dim3(512, 1), dim3(256), 0, 0, attr, g, w1, b1, w2, part, E, nullptr, nullptr);
+            if (which == 2) hipLaunchKernelGGL(edge_mlp_mfma_fwd_kernel<false>, dim3(768), dim3(256), 0, 0, attr, w1, b1, w2, b1, w1, b1, w2, b1, wk, wv, E, nullptr, nullptr);
         }
         hipEventRecord(e1, 0); hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1);
         printf(" %s %8.1f us", which == 0 ? "bwd64" : which == 1 ? "bwd32" : "fwd", ms / 20 * 1e3);
@@ -54,15 +55,15 @@ def sub(text, old, new, count=1):
 def no_act(t):
     t = sub(t, "const float tq = __expf(-fabsf(p)), u = 1.f + tq;", "const float tq = p, u = p;")
     t = sub(t, "const float sg = (p >= 0.f ? 1.f : tq) * SINGA_RCP(u);", "const float sg = tq;")
-    return sub(t, "pacc[r] = ok ? fmaxf(p, 0.f) + __logf(u) - 0.69314718055994530942f : 0.f;", "pacc[r] = p + u;")
+    return sub(t, "pacc[r] = live ? fmaxf(p, 0.f) + __logf(u) - 0.69314718055994530942f : 0.f;", "pacc[r] = p + u;")
 
 
 def no_prefetch(t):       # bwd only: the in-loop fetch of the next tile (the first tile's rows are reused)
-    return sub(t, "if (tile + stride < tilesN) fetch(tile + stride);   // the attr registers are free now; 96 MFMAs of cover", "")
+    return sub(t, "if (UNITS || tile + stride < tilesN) fetch(tile + stride);", "")
 
 
 def no_fences(t):
-    i0 = t.index("template <int H>\n__global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel")
+    i0 = t.index("template <int H, bool UNITS>\n__global__ void __launch_bounds__(256, 2) edge_mlp_mfma_bwd_kernel")
     return t[:i0] + t[i0:].replace("__builtin_amdgcn_sched_barrier(0);", "")
 
 
