@@ -1674,6 +1674,17 @@ __host__ __device__ inline bool valence_allows(const ValenceState& s, int c, int
     return end | (gram & bonds & reach & (rem >= valence_need(n)));
 }
 
+// The rule in force on a row, the template argument of the three row kernels below: `allowed` only, the SMILES rule (cls,
+// gstate), the valence rule (cls, cap, gstate, vstate).
+enum Rule { RULE_NONE, RULE_SMILES, RULE_VALENCE };
+
+// The row's state after token `c` of capacity `cap`: one source for the kernels that store a new state (sample_token_kernel,
+// swor_select_kernel, beam_select_kernel) and for the two *_rule_host twins.  The SMILES rule leaves the valence words alone.
+__host__ __device__ inline ValenceState rule_next(Rule rule, const ValenceState& s, int c, int cap) {
+    if (rule == RULE_VALENCE) return valence_next(s, c, cap);
+    return {rule == RULE_SMILES ? smiles_next(s.gs, c) : s.gs, s.v0, s.v1};
+}
+
 #ifndef SINGA_EMUL      // (cross-lane: not part of the sequential CPU emulation build of tests/emul)
 __device__ __forceinline__ int wave_min64i(int v) {
 #pragma unroll
@@ -1689,9 +1700,73 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }
 
-// GRAMMAR (singa_sample_token_grammar): the row's state word is read once (wave-uniform), the rule is ANDed into ok[] from the
-// class bytes of the lane's tokens, the choice below runs unchanged, and lane 0 stores the new state with the bookkeeping.
-// <NPL, false, *> is singa_sample_token: cls, gstate and allowed_logp are not read.
+// The opening of a row-per-wave kernel of a decode step whose grid covers the rows four to a workgroup: the wave's row and the
+// step t = *pos - pos_offset, which reads column t and writes column t + 1.  `live` is wave-uniform.
+struct RowStep {
+    int lane, row;
+    long long t;
+    bool live;                                                         // a row of the grid at a step that has a column to write
+};
+__device__ __forceinline__ RowStep row_step(const long long* __restrict__ pos, int pos_offset, int rows, int T) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return {lane, row, 0, false};
+    const long long t = *pos - pos_offset;
+    return {lane, row, t, t >= 0 && t + 1 < T};
+}
+
+// The front end of sample_token_kernel, swor_expand_kernel and beam_expand_kernel: the row of raw logits in registers (lane l:
+// tokens l, l + 64, ...; -inf past V), the effective mask ok[] = `allowed` AND the rule in force, whose state words are read
+// once (wave-uniform), and the model's own log-sum-exp (tau = 1, nothing filtered).  This is the one place where lse is formed:
+// z[k] - lse carries the same bits in every consumer, which is what lets a beam hypothesis' sum, a sample_distinct row's sum
+// and the sampler's sum_logp all equal what score(...) reports for the string.  c[k] is the token's class byte with its
+// capacity in bits 8-10; a kernel that does not read it afterwards does not hold it.
+template <int NPL, Rule RULE>
+struct RowFront {
+    float z[NPL], zmax, lse;
+    bool ok[NPL];
+    int c[NPL];
+    ValenceState vs;                                                   // RULE_SMILES: gs only
+
+    __device__ __forceinline__ RowFront(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
+                                        const unsigned char* __restrict__ cls, const unsigned char* __restrict__ cap,
+                                        const int32_t* __restrict__ gstate, const int32_t* __restrict__ vstate, int row, int lane,
+                                        int V, int rem) {
+        ValenceState s{0, 0, 0};                                       // (locals, so that they are scalars from the start)
+        if constexpr (RULE != RULE_NONE) s.gs = __builtin_amdgcn_readfirstlane(gstate[row]);
+        if constexpr (RULE == RULE_VALENCE)
+            s = valence_load(s.gs, __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row]),
+                             __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row + 1]));
+        vs = s;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const int i = k * 64 + lane;
+            z[k] = i < V ? logits[(long long)row * V + i] : -INFINITY;
+            ok[k] = i < V && (!allowed || allowed[i]);
+            c[k] = 0;
+            if constexpr (RULE == RULE_SMILES) {
+                c[k] = i < V ? cls[i] : 0;
+                ok[k] = ok[k] && smiles_allows(s.gs, c[k], rem);
+            }
+            if constexpr (RULE == RULE_VALENCE) {
+                const int cl = i < V ? cls[i] : 0, cp = i < V ? cap[i] & 7 : 0;
+                ok[k] = ok[k] && valence_allows(s, cl, cp, rem);
+                c[k] = cl | cp << 8;
+            }
+        }
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) m = fmaxf(m, z[k]);
+        m = wave_max64(m);
+        float zsum = 0.f;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - m) : 0.f;
+        zmax = m, lse = m + logf(wave_sum64(zsum));
+    }
+};
+
+// RULE_SMILES (singa_sample_token_grammar): the rule is ANDed into ok[] from the class bytes of the lane's tokens, the choice
+// below runs unchanged, and lane 0 stores the new state with the bookkeeping.
+// <NPL, RULE_NONE, *> is singa_sample_token: cls, gstate and allowed_logp are not read.
 // FORCED (singa_sample_token_forced, include/singa_hip_force.h): one wave-uniform 8-byte read of forced[row][t + 1]; a value
 // inside [0, V) replaces the choice (mask, filters and the uniform take no part) and the bookkeeping below runs unchanged;
 // the rank of the emitted token among the raw logits is one wave reduction over the registers the row already sits in.
@@ -1699,10 +1774,9 @@ __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
 // STREAM (singa_sample_token_stream, include/singa_hip_stream.h): `pos` holds one position per row, the uniform is column
 // mol[row] of `uniforms` and the bookkeeping goes to row mol[row] of the outputs, which are indexed by molecule; next and gstate
 // stay the row's.  A retired row (mol < 0) returns at once; `finished` and `live` are not read - the hand-over launch decides.
-// VALENCE (singa_sample_token_valence, include/singa_hip_valence.h; only with GRAMMAR): the row's two valence words are read
-// wave-uniformly beside the state word, the capacity byte of a token rides in bits 8-10 of its class register, valence_allows
-// takes the place of smiles_allows and lane 0 stores all three words.  <NPL, *, *, *, false> reads neither `cap` nor `vstate`.
-template <int NPL, bool GRAMMAR, bool FORCED, bool STREAM, bool VALENCE>
+// RULE_VALENCE (singa_sample_token_valence, include/singa_hip_valence.h): valence_allows takes the place of smiles_allows and
+// lane 0 stores all three words.  No other rule reads `cap` or `vstate`.
+template <int NPL, Rule RULE, bool FORCED, bool STREAM>
 __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restrict__ logits, const float* __restrict__ uniforms,
                                                            const unsigned char* __restrict__ allowed,
                                                            const long long* __restrict__ pos, int pos_offset, int rows, int V, int T,
@@ -1715,7 +1789,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
                                                            const long long* __restrict__ forced, int32_t* __restrict__ rank,
                                                            const int32_t* __restrict__ mol, int molecules,
                                                            const unsigned char* __restrict__ cap, int32_t* __restrict__ vstate) {
-    static_assert(GRAMMAR || !VALENCE, "the valence rule extends the SMILES rule");
+    constexpr bool GRAMMAR = RULE != RULE_NONE;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;                                           // wave-uniform from here on
@@ -1747,45 +1821,16 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
         given = (hi == 0 && lo >= 0 && lo < V) ? lo : -1;
     }
     const float NEG = -INFINITY;
-    float z[NPL];
-    bool ok[NPL];
-    int gs = 0, c[NPL];
-    if constexpr (GRAMMAR) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
-    ValenceState vs{0, 0, 0};
-    if constexpr (VALENCE)
-        vs = valence_load(gs, __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row]),
-                          __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row + 1]));
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-        const int i = k * 64 + lane;
-        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
-        ok[k] = i < V && (!allowed || allowed[i]);
-        if constexpr (GRAMMAR) {
-            c[k] = i < V ? cls[i] : 0;
-            if constexpr (VALENCE) {
-                const int cp = i < V ? cap[i] & 7 : 0;
-                ok[k] = ok[k] && valence_allows(vs, c[k], cp, (int)(T - 2 - t));
-                c[k] |= cp << 8;
-            } else {
-                ok[k] = ok[k] && smiles_allows(gs, c[k], (int)(T - 2 - t));
-            }
-        }
-    }
-    // the model's own log-sum-exp (tau = 1, nothing filtered)
-    float zmax = NEG;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
-    zmax = wave_max64(zmax);
-    float zsum = 0.f;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
-    const float lse = zmax + logf(wave_sum64(zsum));
+    const RowFront<NPL, RULE> front(logits, allowed, cls, cap, gstate, vstate, row, lane, V, (int)(T - 2 - t));
+    const float (&z)[NPL] = front.z;
+    const bool (&ok)[NPL] = front.ok;
+    const float lse = front.lse;
     float alp = 0.f;                                                   // log of the model's mass on the effective mask
     if (GRAMMAR && allowed_logp) {
         float asum = 0.f;
 #pragma unroll
-        for (int k = 0; k < NPL; ++k) asum += ok[k] ? expf(z[k] - zmax) : 0.f;
-        alp = zmax + logf(wave_sum64(asum)) - lse;
+        for (int k = 0; k < NPL; ++k) asum += ok[k] ? expf(z[k] - front.zmax) : 0.f;
+        alp = front.zmax + logf(wave_sum64(asum)) - lse;
     }
 
     int tok;
@@ -1884,7 +1929,7 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
     for (int k = 0; k < NPL; ++k)
         if (tok >> 6 == k) {
             zt = lane_bcast_f(z[k], tok & 63);
-            if constexpr (GRAMMAR) ct = __builtin_amdgcn_readlane(c[k], tok & 63);
+            if constexpr (GRAMMAR) ct = __builtin_amdgcn_readlane(front.c[k], tok & 63);
         }
     int above = 0;                                                     // FORCED: tokens ranked before the emitted one
     if constexpr (FORCED) {
@@ -1900,15 +1945,10 @@ __global__ void __launch_bounds__(256) sample_token_kernel(const float* __restri
     }
     if (lane == 0) {
         if constexpr (GRAMMAR) {
-            if constexpr (VALENCE) {
-                if (drawn) {
-                    const ValenceState n = valence_next(vs, ct & 255, ct >> 8);
-                    gstate[row] = n.gs;
-                    vstate[2 * (long long)row] = n.v0;
-                    vstate[2 * (long long)row + 1] = n.v1;
-                }
-            } else {
-                if (drawn) gstate[row] = smiles_next(gs, ct);
+            if (drawn) {
+                const ValenceState n = rule_next(RULE, front.vs, ct & 255, ct >> 8);
+                gstate[row] = n.gs;
+                if constexpr (RULE == RULE_VALENCE) vstate[2 * (long long)row] = n.v0, vstate[2 * (long long)row + 1] = n.v1;
             }
             if (allowed_logp) allowed_logp[slot] = alp;
         }
@@ -2052,9 +2092,9 @@ struct SworWork {
 };
 
 #ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
-// singa_swor_expand: one wave per row, the row's logits in registers as sample_token_kernel holds them (lane l: tokens l,
-// l + 64, ...).  lse and the model's log-probability are that kernel's expressions, so they carry the same bits.
-template <int NPL, bool GRAMMAR>
+// singa_swor_expand: one wave per row; RowFront, then the Gumbel perturbation.  (No valence form in the ABI: RULE_NONE and
+// RULE_SMILES only.)
+template <int NPL, Rule RULE>
 __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
                                                           const unsigned char* __restrict__ cls, const long long* __restrict__ pos,
                                                           int pos_offset, int rows, int kslots, int V, int T, float tau,
@@ -2064,11 +2104,9 @@ __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restric
                                                           const unsigned char* __restrict__ finished,
                                                           const int32_t* __restrict__ gstate, float* __restrict__ cand,
                                                           float* __restrict__ cand_logp, float* __restrict__ cand_phi) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;                                           // wave-uniform from here on
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;                                               // wave-uniform from here on
+    const int lane = w.lane, row = w.row;
     const float NEG = -INFINITY;
     const float G = gumbel[row], phi = prop_logp[row];
     float* cr = cand + (long long)row * V;
@@ -2084,26 +2122,9 @@ __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restric
     }
     const unsigned long long hsh = hash[row];
     const uint32_t strm = streams[row / kslots];
-    float z[NPL];
-    bool ok[NPL];
-    int gs = 0;
-    if constexpr (GRAMMAR) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-        const int i = k * 64 + lane;
-        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
-        ok[k] = i < V && (!allowed || allowed[i]);
-        if constexpr (GRAMMAR) ok[k] = ok[k] && smiles_allows(gs, i < V ? cls[i] : 0, (int)(T - 2 - t));
-    }
-    // the model's own log-sum-exp (tau = 1, nothing filtered), as in sample_token_kernel
-    float zmax = NEG;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
-    zmax = wave_max64(zmax);
-    float zsum = 0.f;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
-    const float lse = zmax + logf(wave_sum64(zsum));
+    const RowFront<NPL, RULE> front(logits, allowed, cls, nullptr, gstate, nullptr, row, lane, V, (int)(T - 2 - w.t));
+    const float (&z)[NPL] = front.z;
+    const bool (&ok)[NPL] = front.ok;
     // the proposal: log-softmax of z / tau over the mask
     float s[NPL], smax = NEG;
 #pragma unroll
@@ -2144,7 +2165,7 @@ __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restric
         if (i < V) {
             const double a = (double)G - (base + h[k]) + log1p(-exp(h[k] - Zh));
             const float gt = (float)((double)G - fmax(a, 0.0) - log1p(exp(-fabs(a))));
-            cr[i] = ok[k] ? gt : NEG, lr[i] = ok[k] ? z[k] - lse : NEG, pr[i] = ok[k] ? s[k] : NEG;
+            cr[i] = ok[k] ? gt : NEG, lr[i] = ok[k] ? z[k] - front.lse : NEG, pr[i] = ok[k] ? s[k] : NEG;
         }
     }
 }
@@ -2296,7 +2317,7 @@ __global__ void __launch_bounds__(1024) swor_select_kernel(const float* __restri
             w_hash[row] = fin ? hash[from] : swor_child_hash(hash[from], v);
             w_fin[row] = (fin || v == eos) ? 1 : 0;
             w_len[row] = length[from] + (fin ? 0 : 1);
-            if (gstate) w_gs[row] = fin ? gstate[from] : smiles_next(gstate[from], cls[v]);
+            if (gstate) w_gs[row] = fin ? gstate[from] : rule_next(RULE_SMILES, {gstate[from], 0, 0}, cls[v], 0).gs;
             tok = fin ? pad : v;
             alive = (fin || v == eos) ? 0 : 1;
         } else {
@@ -2318,11 +2339,10 @@ __global__ void __launch_bounds__(256) swor_gather_kernel(const long long* __res
                                                           const long long* __restrict__ src, const float* __restrict__ w_gumbel,
                                                           const long long* __restrict__ tokens, const float* __restrict__ tok_logp,
                                                           long long* __restrict__ w_tokens, float* __restrict__ w_toklogp) {
-    const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;
+    const int lane = w.lane;
+    const long long row = w.row, t = w.t;
     const bool has = w_gumbel[row] > -INFINITY;
     const long long from = src[row];
     for (int c = lane; c <= t; c += 64) {
@@ -2343,11 +2363,10 @@ __global__ void __launch_bounds__(256) swor_commit_kernel(const long long* __res
                                                           const unsigned char* __restrict__ w_fin, const int32_t* __restrict__ w_len,
                                                           const int32_t* __restrict__ w_gs, const long long* __restrict__ w_tokens,
                                                           const float* __restrict__ w_toklogp) {
-    const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;
+    const int lane = w.lane;
+    const long long row = w.row, t = w.t;
     if (lane == 0) {
         gumbel[row] = w_gumbel[row], prop_logp[row] = w_prop[row], sum_logp[row] = w_sum[row], hash[row] = w_hash[row];
         finished[row] = w_fin[row], length[row] = w_len[row];
@@ -2408,21 +2427,18 @@ struct BeamWork {
 };
 
 #ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
-// singa_beam_expand: one wave per row, the row's logits in registers as sample_token_kernel holds them.  lse and z - lse are
-// that kernel's expressions, so score + (z - lse) accumulates the bits that kernel's sum_logp accumulates.
-// MODE 0: `allowed` only; 1: the SMILES rule (cls, gstate); 2: the valence rule (cls, cap, gstate, vstate).
-template <int NPL, int MODE>
+// singa_beam_expand: one wave per row; RowFront, then score + (z - lse), which accumulates the bits sample_token_kernel's
+// sum_logp accumulates.
+template <int NPL, Rule RULE>
 __global__ void __launch_bounds__(256) beam_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
                                                           const unsigned char* __restrict__ cls, const unsigned char* __restrict__ cap,
                                                           const long long* __restrict__ pos, int pos_offset, int rows, int kslots,
                                                           int V, int T, const float* __restrict__ score,
                                                           const int32_t* __restrict__ gstate, const int32_t* __restrict__ vstate,
                                                           const unsigned char* __restrict__ done, float* __restrict__ cand) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;                                           // wave-uniform from here on
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;                                               // wave-uniform from here on
+    const int lane = w.lane, row = w.row;
     if (done[row / kslots]) return;                                    // a done pocket is frozen
     const float NEG = -INFINITY;
     const float sc = score[row];
@@ -2431,37 +2447,13 @@ __global__ void __launch_bounds__(256) beam_expand_kernel(const float* __restric
         for (int i = lane; i < V; i += 64) cr[i] = NEG;
         return;
     }
-    float z[NPL];
-    bool ok[NPL];
-    int gs = 0;
-    if constexpr (MODE > 0) gs = __builtin_amdgcn_readfirstlane(gstate[row]);
-    ValenceState vs{0, 0, 0};
-    if constexpr (MODE == 2)
-        vs = valence_load(gs, __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row]),
-                          __builtin_amdgcn_readfirstlane(vstate[2 * (long long)row + 1]));
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-        const int i = k * 64 + lane;
-        z[k] = i < V ? logits[(long long)row * V + i] : NEG;
-        ok[k] = i < V && (!allowed || allowed[i]);
-        if constexpr (MODE == 1) ok[k] = ok[k] && smiles_allows(gs, i < V ? cls[i] : 0, (int)(T - 2 - t));
-        if constexpr (MODE == 2) ok[k] = ok[k] && valence_allows(vs, i < V ? cls[i] : 0, i < V ? cap[i] & 7 : 0, (int)(T - 2 - t));
-    }
-    // the model's own log-sum-exp (nothing filtered), as in sample_token_kernel
-    float zmax = NEG;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zmax = fmaxf(zmax, z[k]);
-    zmax = wave_max64(zmax);
-    float zsum = 0.f;
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) zsum += k * 64 + lane < V ? expf(z[k] - zmax) : 0.f;
-    const float lse = zmax + logf(wave_sum64(zsum));
+    const RowFront<NPL, RULE> front(logits, allowed, cls, cap, gstate, vstate, row, lane, V, (int)(T - 2 - w.t));
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const int i = k * 64 + lane;
         if (i < V) {
-            const float lp = z[k] - lse;
-            cr[i] = ok[k] ? sc + lp : NEG;
+            const float lp = front.z[k] - front.lse;
+            cr[i] = front.ok[k] ? sc + lp : NEG;
         }
     }
 }
@@ -2561,14 +2553,12 @@ __global__ void __launch_bounds__(1024) beam_select_kernel(const float* __restri
             const int flat = n_flat[tid], pi = flat / V, v = flat - pi * V;
             const long long from = row0 + pi;
             w_score[row] = base[flat], w_parent[row] = (int)from, w_tok[row] = v, w_len[row] = length[from] + 1;
-            if (gstate) {
-                if (vstate) {
-                    const ValenceState to = valence_next(valence_load(gstate[from], vstate[2 * from], vstate[2 * from + 1]), cls[v],
-                                                         cap[v] & 7);
-                    w_gs[row] = to.gs, w_v0[row] = to.v0, w_v1[row] = to.v1;
-                } else {
-                    w_gs[row] = smiles_next(gstate[from], cls[v]);
-                }
+            if (gstate) {                                              // the rule is the one whose operands are given
+                ValenceState s{gstate[from], 0, 0};
+                if (vstate) s = valence_load(s.gs, vstate[2 * from], vstate[2 * from + 1]);
+                const ValenceState to = rule_next(vstate ? RULE_VALENCE : RULE_SMILES, s, cls[v], vstate ? cap[v] & 7 : 0);
+                w_gs[row] = to.gs;
+                if (vstate) w_v0[row] = to.v0, w_v1[row] = to.v1;
             }
             next[row] = v, src[row] = from;
         } else {
@@ -2590,11 +2580,10 @@ __global__ void __launch_bounds__(1024) beam_select_kernel(const float* __restri
 __global__ void __launch_bounds__(256) beam_gather_kernel(const long long* __restrict__ pos, int pos_offset, int rows, int kslots, int T,
                                                           const int32_t* __restrict__ w_active, const int32_t* __restrict__ w_parent,
                                                           const long long* __restrict__ tokens, long long* __restrict__ w_tokens) {
-    const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;
+    const int lane = w.lane;
+    const long long row = w.row, t = w.t;
     if (!w_active[row / kslots]) return;
     const long long from = w_parent[row];
     if (from < 0) return;
@@ -2611,11 +2600,10 @@ __global__ void __launch_bounds__(256) beam_commit_kernel(const long long* __res
                                                           const int32_t* __restrict__ w_tok, const int32_t* __restrict__ w_len,
                                                           const int32_t* __restrict__ w_gs, const int32_t* __restrict__ w_v0,
                                                           const int32_t* __restrict__ w_v1, const long long* __restrict__ w_tokens) {
-    const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const long long t = *pos - pos_offset;
-    if (t < 0 || t + 1 >= T) return;
+    const RowStep w = row_step(pos, pos_offset, rows, T);
+    if (!w.live) return;
+    const int lane = w.lane;
+    const long long row = w.row, t = w.t;
     if (!w_active[row / kslots]) return;
     if (w_parent[row] < 0) {
         if (lane == 0) score[row] = -INFINITY;
@@ -6500,6 +6488,14 @@ void dispatch_flag(bool on, F&& f) {
     else f(std::false_type{});
 }
 
+// the rule in force from the operands that are given: cap -> the valence rule, cls alone -> the SMILES rule
+template <class F>
+void dispatch_rule(const void* cls, const void* cap, F&& f) {
+    if (cap) f(std::integral_constant<Rule, RULE_VALENCE>{});
+    else if (cls) f(std::integral_constant<Rule, RULE_SMILES>{});
+    else f(std::integral_constant<Rule, RULE_NONE>{});
+}
+
 // "<entry>: <text>" as the last error: the checks that several entry points share spell their text once
 int fail_at(int code, const char* entry, const char* text) {
     snprintf(g_err, sizeof(g_err), "%s: %s", entry, text);
@@ -7717,21 +7713,15 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
 #else
     const dim3 grid((rows + 3) / 4), block(256);
     dispatch_npl(V, [&](auto npl) {
-        auto launch = [&](auto g, auto f, auto s, auto v) {
-            hipLaunchKernelGGL(
-                (sample_token_kernel<decltype(npl)::value, decltype(g)::value, decltype(f)::value, decltype(s)::value, decltype(v)::value>),
-                grid, block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau, top_k, top_p, eos,
-                pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate, allowed_logp, forced, rank, mol,
-                molecules, cap, vstate);
-        };
-        if (cap) {                                                     // the valence rule: always with the grammar
-            if (mol) launch(std::true_type{}, std::false_type{}, std::true_type{}, std::true_type{});
-            else dispatch_flag(forced != nullptr, [&](auto f) { launch(std::true_type{}, f, std::false_type{}, std::true_type{}); });
-            return;
-        }
-        dispatch_flag(grammar, [&](auto g) {
-            if (mol) launch(g, std::false_type{}, std::true_type{}, std::false_type{});   // (no stream form with forced tokens)
-            else dispatch_flag(forced != nullptr, [&](auto f) { launch(g, f, std::false_type{}, std::false_type{}); });
+        dispatch_rule(cls, cap, [&](auto r) {
+            auto launch = [&](auto f, auto s) {
+                hipLaunchKernelGGL((sample_token_kernel<decltype(npl)::value, decltype(r)::value, decltype(f)::value, decltype(s)::value>),
+                                   grid, block, 0, (hipStream_t)stream, logits, uniforms, allowed, pos, pos_offset, rows, V, T, tau,
+                                   top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,
+                                   allowed_logp, forced, rank, mol, molecules, cap, vstate);
+            };
+            if (mol) launch(std::false_type{}, std::true_type{});      // (no stream form with forced tokens)
+            else dispatch_flag(forced != nullptr, [&](auto f) { launch(f, std::false_type{}); });
         });
     });
     return check_launch(name);
@@ -7861,7 +7851,7 @@ int singa_valence_rule_host(const unsigned char* cls, const unsigned char* cap, 
     for (int i = 0; i < n; ++i) {
         const ValenceState s = valence_load(state[i], vstate[2 * i], vstate[2 * i + 1]);
         ok[i] = valence_allows(s, cls[i], cap[i] & 7, rem[i]) ? 1 : 0;
-        const ValenceState to = valence_next(s, cls[i], cap[i] & 7);
+        const ValenceState to = rule_next(RULE_VALENCE, s, cls[i], cap[i] & 7);
         next_state[i] = ok[i] ? to.gs : state[i];
         next_vstate[2 * i] = ok[i] ? to.v0 : vstate[2 * i];
         next_vstate[2 * i + 1] = ok[i] ? to.v1 : vstate[2 * i + 1];
@@ -7875,7 +7865,7 @@ int singa_smiles_rule_host(const unsigned char* cls, const int32_t* state, const
     if (n < 0) return fail(SINGA_E_SHAPE, "smiles_rule_host: n must be >= 0");
     for (int i = 0; i < n; ++i) {
         ok[i] = smiles_allows(state[i], cls[i], rem[i]) ? 1 : 0;
-        next_state[i] = ok[i] ? smiles_next(state[i], cls[i]) : state[i];
+        next_state[i] = ok[i] ? rule_next(RULE_SMILES, {state[i], 0, 0}, cls[i], 0).gs : state[i];
     }
     return SINGA_OK;
 }
@@ -7899,13 +7889,25 @@ long long singa_swor_work(int rows, int T) {
 }
 
 namespace {
-// the checks singa_swor_expand and singa_swor_select share; 0 = go on
-int swor_shape(const char* what, int rows, int k, int V, int T, bool grammar, int eos, int pad) {
+// The checks the expand and select entry points of a slot search (k slots per pocket: singa_swor_*, singa_beam_*) share, in
+// the order their callers rely on; 0 = go on.  The slot cap and two wordings are what the searches differ in (the swor entry
+// points have no cap / vstate: null).
+struct SlotSearch {
+    int kmax;
+    const char *slots, *columns;
+};
+const SlotSearch SWOR_SLOTS{2048, "1..2048 slots per pocket", "T >= 2 columns (3 under the grammar)"},
+    BEAM_SLOTS{1024, "1..1024 slots per pocket", "T >= 2 columns (3 under a grammar)"};
+
+int slot_shape(const char* what, const SlotSearch& s, const void* cls, const void* cap, const void* gstate, const void* vstate,
+               int rows, int k, int V, int T, int eos, int pad) {
+    if (!cls != !gstate) return fail_at(SINGA_E_NULL, what, "cls and gstate go together");
+    if (!cap != !vstate || (cap && !cls)) return fail_at(SINGA_E_NULL, what, "cap and vstate go together, and only with cls");
     const char* bad = nullptr;
     if (V < 1 || V > 1024) bad = "vocabulary of 1..1024 tokens";
-    else if (k < 1 || k > 2048) bad = "1..2048 slots per pocket";
+    else if (k < 1 || k > s.kmax) bad = s.slots;
     else if (rows < 0 || rows % k) bad = "rows must be pockets x slots";
-    else if (T < (grammar ? 3 : 2)) bad = "T >= 2 columns (3 under the grammar)";
+    else if (T < (cls ? 3 : 2)) bad = s.columns;
     else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
     return bad ? fail_at(SINGA_E_SHAPE, what, bad) : SINGA_OK;
 }
@@ -7919,8 +7921,7 @@ int singa_swor_expand(const float* logits, const unsigned char* allowed, const u
     const char* name = "swor_expand";
     if (!logits || !pos || !streams || !gumbel || !prop_logp || !hash || !finished || !cand || !cand_logp || !cand_phi)
         return fail_at(SINGA_E_NULL, name, "null pointer");
-    if (!cls != !gstate) return fail_at(SINGA_E_NULL, name, "cls and gstate go together");
-    if (const int e = swor_shape(name, rows, k, V, T, cls != nullptr, 0, pad)) return e;
+    if (const int e = slot_shape(name, SWOR_SLOTS, cls, nullptr, gstate, nullptr, rows, k, V, T, 0, pad)) return e;
     if (!(tau > 0.f)) return fail_at(SINGA_E_SHAPE, name, "temperature must be > 0");
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
@@ -7928,10 +7929,11 @@ int singa_swor_expand(const float* logits, const unsigned char* allowed, const u
 #else
     const dim3 grid((rows + 3) / 4), block(256);
     dispatch_npl(V, [&](auto npl) {
-        dispatch_flag(cls != nullptr, [&](auto g) {
-            hipLaunchKernelGGL((swor_expand_kernel<decltype(npl)::value, decltype(g)::value>), grid, block, 0, (hipStream_t)stream,
-                               logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams, pad, gumbel, prop_logp,
-                               hash, finished, gstate, cand, cand_logp, cand_phi);
+        dispatch_rule(cls, nullptr, [&](auto r) {
+            if constexpr (decltype(r)::value != RULE_VALENCE)          // (never chosen without cap: not built)
+                hipLaunchKernelGGL((swor_expand_kernel<decltype(npl)::value, decltype(r)::value>), grid, block, 0, (hipStream_t)stream,
+                                   logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams, pad, gumbel, prop_logp,
+                                   hash, finished, gstate, cand, cand_logp, cand_phi);
         });
     });
     return check_launch(name);
@@ -7946,8 +7948,7 @@ int singa_swor_select(const float* cand, const float* cand_logp, const float* ca
     if (!cand || !cand_logp || !cand_phi || !pos || !gumbel || !prop_logp || !sum_logp || !hash || !finished || !length ||
         !tokens || !tok_logp || !next || !src || !live || !work)
         return fail_at(SINGA_E_NULL, "swor_select", "null pointer");
-    if (!cls != !gstate) return fail_at(SINGA_E_NULL, "swor_select", "cls and gstate go together");
-    if (const int e = swor_shape("swor_select", rows, k, V, T, cls != nullptr, eos, pad)) return e;
+    if (const int e = slot_shape("swor_select", SWOR_SLOTS, cls, nullptr, gstate, nullptr, rows, k, V, T, eos, pad)) return e;
     if ((uintptr_t)work % 16) return fail(SINGA_E_SHAPE, "swor_select: work must be 16-byte aligned");
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
@@ -8002,42 +8003,22 @@ long long singa_beam_work(int rows, int T) {
     return BeamWork(rows, T).bytes;
 }
 
-namespace {
-// the checks singa_beam_expand and singa_beam_select share; 0 = go on
-int beam_args(const char* what, const void* cls, const void* cap, const void* gstate, const void* vstate, int rows, int k, int V,
-              int T, int eos, int pad) {
-    if (!cls != !gstate) return fail_at(SINGA_E_NULL, what, "cls and gstate go together");
-    if (!cap != !vstate || (cap && !cls)) return fail_at(SINGA_E_NULL, what, "cap and vstate go together, and only with cls");
-    const char* bad = nullptr;
-    if (V < 1 || V > 1024) bad = "vocabulary of 1..1024 tokens";
-    else if (k < 1 || k > 1024) bad = "1..1024 slots per pocket";
-    else if (rows < 0 || rows % k) bad = "rows must be pockets x slots";
-    else if (T < (cls ? 3 : 2)) bad = "T >= 2 columns (3 under a grammar)";
-    else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
-    return bad ? fail_at(SINGA_E_SHAPE, what, bad) : SINGA_OK;
-}
-}  // namespace
-
 int singa_beam_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const unsigned char* cap,
                       const long long* pos, int pos_offset, int rows, int k, int V, int T, const float* score,
                       const int32_t* gstate, const int32_t* vstate, const unsigned char* done, float* cand, void* stream) {
     const char* name = "beam_expand";
     if (!logits || !pos || !score || !done || !cand) return fail_at(SINGA_E_NULL, name, "null pointer");
-    if (const int e = beam_args(name, cls, cap, gstate, vstate, rows, k, V, T, 0, 0)) return e;
+    if (const int e = slot_shape(name, BEAM_SLOTS, cls, cap, gstate, vstate, rows, k, V, T, 0, 0)) return e;
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
     return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
 #else
     const dim3 grid((rows + 3) / 4), block(256);
-    const int mode = cap ? 2 : cls ? 1 : 0;
     dispatch_npl(V, [&](auto npl) {
-        auto launch = [&](auto m) {
-            hipLaunchKernelGGL((beam_expand_kernel<decltype(npl)::value, decltype(m)::value>), grid, block, 0, (hipStream_t)stream,
+        dispatch_rule(cls, cap, [&](auto r) {
+            hipLaunchKernelGGL((beam_expand_kernel<decltype(npl)::value, decltype(r)::value>), grid, block, 0, (hipStream_t)stream,
                                logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate, vstate, done, cand);
-        };
-        if (mode == 2) launch(std::integral_constant<int, 2>{});
-        else if (mode == 1) launch(std::integral_constant<int, 1>{});
-        else launch(std::integral_constant<int, 0>{});
+        });
     });
     return check_launch(name);
 #endif
@@ -8052,7 +8033,7 @@ int singa_beam_select(const float* cand, const unsigned char* cls, const unsigne
     if (!cand || !pos || !len_pow || !score || !length || !tokens || !next || !src || !hyp_score || !hyp_sum || !hyp_len ||
         !hyp_stamp || !hyp_tokens || !n_hyp || !worst || !done || !live || !work)
         return fail_at(SINGA_E_NULL, name, "null pointer");
-    if (const int e = beam_args(name, cls, cap, gstate, vstate, rows, k, V, T, eos, pad)) return e;
+    if (const int e = slot_shape(name, BEAM_SLOTS, cls, cap, gstate, vstate, rows, k, V, T, eos, pad)) return e;
     if ((uintptr_t)work % 16) return fail_at(SINGA_E_SHAPE, name, "work must be 16-byte aligned");
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL

@@ -827,6 +827,12 @@ def _check_views(what, items):
                                f"{tuple(t.shape)} on {t.device}")
 
 
+def _cap_with_cls(what, cls, cap, vstate):
+    """The operands of the valence rule: cap and vstate go together, and only with cls."""
+    if (cap is None) != (vstate is None) or (cap is not None and cls is None):
+        raise RuntimeError(f"{what}: cap and vstate go together, and only with cls")
+
+
 def _sample_token_views(what, logits, uniforms, pos, state, allowed, cls=None, gstate=None, alp=None, forced=None, rank=None,
                         cap=None, vstate=None):
     """The argument checks of the token-choice ops; gstate, alp / rank / vstate: the state's grammar, allowed_logp / rank /
@@ -859,8 +865,7 @@ def sample_token(logits, uniforms, pos, pos_offset, state, temperature=1.0, top_
     class bytes of `smiles.classify_orders`) and `vstate` ([R, 2] int32, updated in place; a row whose grammar word is
     `smiles.FRESH` needs no reset of it): the valence rule of include/singa_hip_valence.h (`singa_sample_token_valence`) in
     place of the SMILES rule, with or without `forced`."""
-    if (cap is None) != (vstate is None) or (cap is not None and cls is None):
-        raise RuntimeError("sample_token: cap and vstate go together, and only with cls")
+    _cap_with_cls("sample_token", cls, cap, vstate)
     entry = "sample_token_valence" if cap is not None else "sample_token_forced" if forced is not None else \
         "sample_token_grammar" if cls is not None else "sample_token"
     rank = state.get("rank") if forced is not None else None
@@ -912,8 +917,7 @@ def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperatu
     optionally, tok_logp [M, T] f32 - indexed by molecule - and next [R] int64; with `cls` also grammar [R] int32 and, optionally,
     allowed_logp [M, T] f32.  Updated in place, bit for bit as the per-row ops update a row that draws the same logits.
     `cap` [V] uint8 and `vstate` [R, 2] int32 (with `cls`): the valence rule, as in `sample_token`."""
-    if (cap is None) != (vstate is None) or (cap is not None and cls is None):
-        raise RuntimeError("sample_token_stream: cap and vstate go together, and only with cls")
+    _cap_with_cls("sample_token_stream", cls, cap, vstate)
     R, V = logits.shape
     M, T = state["tokens"].shape
     gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
@@ -958,22 +962,33 @@ def stream_refill(pos, mol, pos_offset, state, rows_per_pocket, num_samples, T, 
                                         _p(state["start_step"]), _stream()), "singa_stream_refill")
 
 
-def swor_work(rows, T, device):
-    """The scratch `swor_select` needs for `rows` rows of `T` columns: a uint8 tensor of `singa_swor_work` bytes."""
-    n = int(_lib.lib().singa_swor_work(rows, T))
+def _slot_work(what, rows, T, device):
+    """The scratch of a slot search's select op: a uint8 tensor of `singa_<what>(rows, T)` bytes."""
+    n = int(getattr(_lib.lib(), "singa_" + what)(rows, T))
     if n < 0:
-        raise RuntimeError(f"swor_work: rows >= 0 and T >= 2, got {rows}, {T}")
+        raise RuntimeError(f"{what}: rows >= 0 and T >= 2, got {rows}, {T}")
     return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
 
 
-def _swor_views(what, state, R, V, T, names, cls=None, allowed=None, extra=()):
-    """The argument checks of the swor ops: contiguous GPU tensors of the dtypes / shapes of include/singa_hip_swor.h."""
-    spec = {"gumbel": (torch.float32, (R,)), "prop_logp": (torch.float32, (R,)), "sum_logp": (torch.float32, (R,)),
-            "hash": (torch.int64, (R,)), "finished": (torch.uint8, (R,)), "length": (torch.int32, (R,)),
-            "grammar": (torch.int32, (R,)), "tokens": (torch.int64, (R, T)), "tok_logp": (torch.float32, (R, T)),
-            "next": (torch.int64, (R,)), "src": (torch.int64, (R,)), "cand": (torch.float32, (R, V)),
-            "cand_logp": (torch.float32, (R, V)), "cand_phi": (torch.float32, (R, V))}
-    items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (allowed, torch.uint8, (V,))] + list(extra)
+def swor_work(rows, T, device):
+    """The scratch `swor_select` needs for `rows` rows of `T` columns: a uint8 tensor of `singa_swor_work` bytes."""
+    return _slot_work("swor_work", rows, T, device)
+
+
+def _slot_views(what, state, R, k, V, T, names, cls=None, cap=None, extra=()):
+    """The argument checks of the swor and beam ops (R = pockets x k slots): `names` of `state` - and grammar with `cls`,
+    vstate with `cap` - are contiguous GPU tensors of the dtypes / shapes of include/singa_hip_swor.h and singa_hip_beam.h."""
+    B, f32, i32, i64 = R // max(k, 1), torch.float32, torch.int32, torch.int64
+    spec = {"gumbel": (f32, (R,)), "prop_logp": (f32, (R,)), "sum_logp": (f32, (R,)), "hash": (i64, (R,)),
+            "finished": (torch.uint8, (R,)), "tok_logp": (f32, (R, T)), "cand_logp": (f32, (R, V)), "cand_phi": (f32, (R, V)),
+            "score": (f32, (R,)), "length": (i32, (R,)), "tokens": (i64, (R, T)), "next": (i64, (R,)), "src": (i64, (R,)),
+            "grammar": (i32, (R,)), "vstate": (i32, (R, 2)), "cand": (f32, (R, V)), "hyp_score": (torch.float64, (R,)),
+            "hyp_sum": (f32, (R,)), "hyp_len": (i32, (R,)), "hyp_stamp": (i32, (R,)), "hyp_tokens": (i64, (R, T)),
+            "n_hyp": (i32, (B,)), "worst": (torch.float64, (B,)), "done": (torch.uint8, (B,)), "live": (i32, (B,))}
+    if cap is not None and cls is None:
+        raise RuntimeError(f"{what}: cap goes only with cls")
+    names = names + (("grammar",) if cls is not None else ()) + (("vstate",) if cap is not None else ())
+    items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (cap, torch.uint8, (V,))] + list(extra)
     _check_views(what, items)
     _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
 
@@ -986,9 +1001,9 @@ def swor_expand(logits, pos, pos_offset, state, k, streams, temperature=1.0, see
     `cls` ([V] uint8 class bytes) also grammar [R] int32 - all read - and cand, cand_logp, cand_phi [R, V] f32, written."""
     R, V = logits.shape
     T = state["tokens"].shape[1]
-    names = ("gumbel", "prop_logp", "hash", "finished", "cand", "cand_logp", "cand_phi") + (("grammar",) if cls is not None else ())
-    _swor_views("swor_expand", state, R, V, T, names, cls, allowed,
-                ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (streams, torch.int32, (R // max(k, 1),))))
+    _slot_views("swor_expand", state, R, k, V, T, ("gumbel", "prop_logp", "hash", "finished", "cand", "cand_logp", "cand_phi"), cls,
+                None, ((allowed, torch.uint8, (V,)), (logits, torch.float32, (R, V)), (pos, torch.int64, None),
+                       (streams, torch.int32, (R // max(k, 1),))))
     _chk(_lib.lib().singa_swor_expand(_p(logits), _p(allowed), _p(cls), _p(pos), pos_offset, R, k, V, T, temperature,
                                       int(seed) & (2 ** 64 - 1), _p(streams), pad, _p(state["gumbel"]), _p(state["prop_logp"]),
                                       _p(state["hash"]), _p(state["finished"]), _p(state["grammar"] if cls is not None else None),
@@ -1004,8 +1019,8 @@ def swor_select(pos, pos_offset, state, k, work, eos=0, pad=0, cls=None):
     R, V = state["cand"].shape
     T = state["tokens"].shape[1]
     names = ("gumbel", "prop_logp", "sum_logp", "hash", "finished", "length", "tokens", "tok_logp", "next", "src", "cand",
-             "cand_logp", "cand_phi") + (("grammar",) if cls is not None else ())
-    _swor_views("swor_select", state, R, V, T, names, cls, None,
+             "cand_logp", "cand_phi")
+    _slot_views("swor_select", state, R, k, V, T, names, cls, None,
                 ((pos, torch.int64, None), (state["live"], torch.int32, (R // max(k, 1),)), (work, torch.uint8, None)))
     need = int(_lib.lib().singa_swor_work(R, T))
     if work.numel() < need:
@@ -1043,26 +1058,7 @@ def swor_follow(k_src, v_src, k_dst, v_dst, src, gumbel, finished, pos):
 
 def beam_work(rows, T, device):
     """The scratch `beam_select` needs for `rows` rows of `T` columns: a uint8 tensor of `singa_beam_work` bytes."""
-    n = int(_lib.lib().singa_beam_work(rows, T))
-    if n < 0:
-        raise RuntimeError(f"beam_work: rows >= 0 and T >= 2, got {rows}, {T}")
-    return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
-
-
-def _beam_views(what, state, R, B, V, T, names, cls, cap, extra=()):
-    """The argument checks of the beam ops: contiguous GPU tensors of the dtypes / shapes of include/singa_hip_beam.h."""
-    spec = {"score": (torch.float32, (R,)), "length": (torch.int32, (R,)), "tokens": (torch.int64, (R, T)),
-            "next": (torch.int64, (R,)), "src": (torch.int64, (R,)), "grammar": (torch.int32, (R,)),
-            "vstate": (torch.int32, (R, 2)), "cand": (torch.float32, (R, V)), "hyp_score": (torch.float64, (R,)),
-            "hyp_sum": (torch.float32, (R,)), "hyp_len": (torch.int32, (R,)), "hyp_stamp": (torch.int32, (R,)),
-            "hyp_tokens": (torch.int64, (R, T)), "n_hyp": (torch.int32, (B,)), "worst": (torch.float64, (B,)),
-            "done": (torch.uint8, (B,)), "live": (torch.int32, (B,))}
-    if cap is not None and cls is None:
-        raise RuntimeError(f"{what}: cap goes only with cls")
-    names = names + (("grammar",) if cls is not None else ()) + (("vstate",) if cap is not None else ())
-    items = [(state[n],) + spec[n] for n in names] + [(cls, torch.uint8, (V,)), (cap, torch.uint8, (V,))] + list(extra)
-    _check_views(what, items)
-    _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
+    return _slot_work("beam_work", rows, T, device)
 
 
 def beam_expand(logits, pos, pos_offset, state, k, allowed=None, cls=None, cap=None):
@@ -1074,7 +1070,7 @@ def beam_expand(logits, pos, pos_offset, state, k, allowed=None, cls=None, cap=N
     cand [R, V] f32, written."""
     R, V = logits.shape
     T = state["tokens"].shape[1]
-    _beam_views("beam_expand", state, R, R // max(k, 1), V, T, ("score", "done", "cand"), cls, cap,
+    _slot_views("beam_expand", state, R, k, V, T, ("score", "done", "cand"), cls, cap,
                 ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (allowed, torch.uint8, (V,))))
     _chk(_lib.lib().singa_beam_expand(_p(logits), _p(allowed), _p(cls), _p(cap), _p(pos), pos_offset, R, k, V, T, _p(state["score"]),
                                       _p(state["grammar"] if cls is not None else None),
@@ -1092,7 +1088,7 @@ def beam_select(pos, pos_offset, state, k, work, len_pow, eos=0, pad=0, cls=None
     T = state["tokens"].shape[1]
     names = ("score", "length", "tokens", "next", "src", "cand", "hyp_score", "hyp_sum", "hyp_len", "hyp_stamp", "hyp_tokens",
              "n_hyp", "worst", "done", "live")
-    _beam_views("beam_select", state, R, R // max(k, 1), V, T, names, cls, cap,
+    _slot_views("beam_select", state, R, k, V, T, names, cls, cap,
                 ((pos, torch.int64, None), (work, torch.uint8, None), (len_pow, torch.float64, None)))
     need = int(_lib.lib().singa_beam_work(R, T))
     if work.numel() < need or len_pow.numel() < T:
