@@ -16,10 +16,13 @@ bonding-capacity rule: no atom of a sequence carries more bond order than its to
 condition for validity - aromaticity and duplicate ring bonds stay unchecked).  Beam search selects on the host, as the
 reference does, unless `--beam-select device` or a `--grammar` is given: then the selection runs on the device
 (`beam_search_device`; include/singa_hip_beam.h states the rule), which is what lets a grammar constrain it; without a grammar
-the two select the same hypotheses up to the order of exactly tied candidates.  `--prefix TEXT` (sample mode) starts every sequence with
-that fragment - a scaffold to continue; under `--grammar smiles` a fragment the rule refuses is an error before anything runs.
+the two select the same hypotheses up to the order of exactly tied candidates.  `--prefix TEXT` starts every sequence with
+that fragment - a scaffold to continue - in sample mode (with or without `--rows-per-pocket`), in distinct mode and in beam
+mode with the selection on the device (include/singa_hip_prefix.h states the rule; host-selected beam search refuses it); under
+a `--grammar` a fragment the rule refuses is an error before anything runs.
 `--mode score --molecules FILE` draws nothing: FILE holds lines of `pocket name<TAB>SMILES`, and every molecule's
-log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input.
+log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input;
+`--rows-per-pocket R` scores them on R rows per pocket (same numbers, the caches of R rows whatever the length of FILE).
 
     python gen.py --config ./config/train.yml --ckpt logs/.../checkpoints/100.pt --data golden --mode sample \\
                   --num-samples 100 --temperature 0.9 --top-p 0.95 --seed 1
@@ -27,6 +30,8 @@ log-likelihood under the model for its pocket is written, in the same four colum
     python gen.py --data golden --mode sample --num-samples 100 --grammar smiles --prefix "c1ccc("
     python gen.py --data golden --mode score --molecules library.tsv
     python gen.py --data golden --mode distinct --num-samples 100 --grammar smiles --seed 3
+    python gen.py --data golden --mode distinct --num-samples 100 --grammar smiles --prefix "c1ccc("
+    python gen.py --data golden --mode score --molecules library.tsv --rows-per-pocket 256
     python gen.py --data golden --mode beam --num-beams 20 --grammar valence
 
 One line per sequence on stdout (or in `--out`), tab-separated: pocket name, the SMILES string between '&' and '$', the
@@ -65,9 +70,10 @@ def parse_args(argv=None):
     ap.add_argument("--beam-select", choices=["host", "device"], default="host",
                     help="beam: where the candidates are selected; a --grammar selects on the device whatever this says")
     ap.add_argument("--rows-per-pocket", type=int, default=None, metavar="R",
-                    help="sample: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
-                         "(sample_stream: same sequences for the same uniforms, whatever R)")
-    ap.add_argument("--prefix", type=str, default=None, help="sample: every sequence starts with this SMILES fragment")
+                    help="sample, score: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
+                         "(sample_stream: same sequences and scores for the same uniforms, whatever R)")
+    ap.add_argument("--prefix", type=str, default=None,
+                    help="sample, distinct, beam (selected on the device): every sequence starts with this SMILES fragment")
     ap.add_argument("--molecules", type=str, default=None,
                     help="score: a file of lines `pocket name<TAB>SMILES` (further columns are ignored)")
     ap.add_argument("--seed", type=int, default=0)
@@ -81,9 +87,13 @@ def parse_args(argv=None):
         "--grammar valence: sample and beam mode only (distinct gathers one state word)"
     assert args.beam_select == "host" or args.mode == "beam", "--beam-select is about beam search: beam mode only"
     assert args.mode != "distinct" or (args.top_k == 0 and args.top_p == 1.0), "--mode distinct takes no --top-k / --top-p"
-    assert args.prefix is None or args.mode == "sample", "--prefix gives sampled sequences their start: sample mode only"
-    assert args.rows_per_pocket is None or (args.mode == "sample" and args.prefix is None), \
-        "--rows-per-pocket is continuous sampling: sample mode, without --prefix"
+    if args.prefix is not None and args.mode == "score":
+        ap.error("--prefix gives generated sequences their start: sample, distinct and beam mode, not --mode score")
+    if args.prefix is not None and args.mode == "beam" and args.beam_select == "host" and args.grammar == "none":
+        ap.error("--prefix in beam mode needs the selection on the device: add --beam-select device (or a --grammar); the "
+                 "host-selected beam search takes no forced tokens")
+    if args.rows_per_pocket is not None and args.mode not in ("sample", "score"):
+        ap.error("--rows-per-pocket is continuous sampling: sample and score mode only")
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
     return args
 
@@ -139,7 +149,7 @@ def main():
         mols = [[smi for name, smi in wanted if name == n] for n in names]
         grammar = None if args.grammar == "none" else args.grammar
         res = score(model, voc, mols, B, ex, torch.tensor([args.prop], dtype=torch.float32) if cfg.train.num_props else None,
-                    device=dev, max_length=args.max_length, grammar=grammar)
+                    device=dev, max_length=args.max_length, grammar=grammar, rows_per_pocket=args.rows_per_pocket)
         print(f"# scored {len(wanted)} molecules for {B} pockets")
         seen = {n: 0 for n in names}
         lines = []
@@ -153,14 +163,14 @@ def main():
     per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
     prop = torch.tensor([args.prop] * (B * per), dtype=torch.float32, device=dev) if cfg.train.num_props else None
     tr = {}
+    forced = None if args.prefix is None else smiles.encode([args.prefix] * B, voc, max_length)
     if args.mode == "sample":
         gen = torch.Generator(device=dev).manual_seed(args.seed)
-        forced = None if args.prefix is None else smiles.encode([args.prefix] * B, voc, max_length)
         if args.rows_per_pocket is not None:
             tokens = sample_stream(model, voc, per, B, max_length, ex, None if prop is None else prop[:B], args.rows_per_pocket,
                                    device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                    suppress=("&", "^"), generator=gen, trace=tr,
-                                   grammar=None if args.grammar == "none" else args.grammar).cpu()
+                                   grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
         else:
             tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
                             top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
@@ -170,7 +180,7 @@ def main():
     elif args.mode == "distinct":
         tokens = sample_distinct(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature,
                                  suppress=("&", "^"), grammar=None if args.grammar == "none" else args.grammar, seed=args.seed,
-                                 trace=tr).cpu()
+                                 trace=tr, forced=forced).cpu()
         keep = tr["valid"].cpu().bool()                                       # a small tree leaves trailing slots empty
         print(f"# {int(keep.sum())} distinct sequences for {B} pockets ({per} asked for each): {tr['steps']} steps")
         rows = [r for r in range(B * per) if keep[r]]
@@ -179,7 +189,7 @@ def main():
     else:
         if args.beam_select == "device" or args.grammar != "none":
             tokens = beam_search_device(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr,
-                                        grammar=None if args.grammar == "none" else args.grammar).cpu()
+                                        grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
             print(f"# beam search selected on the device: {tr['steps']} steps")
         else:
             tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr).cpu()

@@ -190,13 +190,21 @@ _UNITS_SIGS = {
 }
 UNITS_EXPORTS = tuple(_UNITS_SIGS)
 
+# include/singa_hip_prefix.h: forced tokens in `sample_stream`, `sample_distinct` and `beam_search_device`; a table of its own
+_PREFIX_SIGS = {
+    "singa_sample_token_stream_forced": ([P] * 7 + [I32, I32, I32, I32, I32, F32, I32, F32, I32, I32] + [P] * 10 + [P], I32),
+    "singa_swor_expand_forced": ([P, P, P, P, I32, I32, I32, I32, I32, F32, U64, P, I32] + [P] * 9 + [P], I32),
+    "singa_forced_beam_expand": ([P] * 5 + [I32] * 5 + [P] * 6 + [P], I32),
+}
+PREFIX_EXPORTS = tuple(_PREFIX_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
-            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()):
+            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -28,6 +28,7 @@
 #include "../../include/singa_hip_valence.h"
 #include "../../include/singa_hip_beam.h"
 #include "../../include/singa_hip_units.h"
+#include "../../include/singa_hip_prefix.h"
 #include "so3_index.h"
 
 namespace {
@@ -1699,6 +1700,13 @@ __device__ __forceinline__ int wave_max64i(int v) {
 __device__ __forceinline__ float lane_bcast_f(float v, int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }
+// The token a slot search is given at forced[at] (include/singa_hip_prefix.h): one wave-uniform 8-byte read; -1 = the value
+// lies outside [0, V), the column is free.
+__device__ __forceinline__ int forced_token(const long long* __restrict__ forced, long long at, int V) {
+    const long long f = forced[at];
+    const int lo = __builtin_amdgcn_readfirstlane((int)(f & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(f >> 32));
+    return (hi == 0 && lo >= 0 && lo < V) ? lo : -1;
+}
 
 // The opening of a row-per-wave kernel of a decode step whose grid covers the rows four to a workgroup: the wave's row and the
 // step t = *pos - pos_offset, which reads column t and writes column t + 1.  `live` is wave-uniform.
@@ -1774,6 +1782,7 @@ struct RowFront {
 // STREAM (singa_sample_token_stream, include/singa_hip_stream.h): `pos` holds one position per row, the uniform is column
 // mol[row] of `uniforms` and the bookkeeping goes to row mol[row] of the outputs, which are indexed by molecule; next and gstate
 // stay the row's.  A retired row (mol < 0) returns at once; `finished` and `live` are not read - the hand-over launch decides.
+// With FORCED (singa_sample_token_stream_forced, include/singa_hip_prefix.h) `forced` and `rank` are indexed by molecule too.
 // RULE_VALENCE (singa_sample_token_valence, include/singa_hip_valence.h): valence_allows takes the place of smiles_allows and
 // lane 0 stores all three words.  No other rule reads `cap` or `vstate`.
 template <int NPL, Rule RULE, bool FORCED, bool STREAM>
@@ -2094,7 +2103,10 @@ struct SworWork {
 #ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
 // singa_swor_expand: one wave per row; RowFront, then the Gumbel perturbation.  (No valence form in the ABI: RULE_NONE and
 // RULE_SMILES only.)
-template <int NPL, Rule RULE>
+// FORCED (singa_swor_expand_forced, include/singa_hip_prefix.h): one wave-uniform 8-byte read of forced[pocket][t + 1] per live
+// row; a value inside [0, V) leaves that token as the row's only candidate, with the row's own G and phi (what the expansion
+// below gives under a one-hot mask) - mask, rule and noise take no part.  <NPL, RULE, false> does not read `forced`.
+template <int NPL, Rule RULE, bool FORCED>
 __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
                                                           const unsigned char* __restrict__ cls, const long long* __restrict__ pos,
                                                           int pos_offset, int rows, int kslots, int V, int T, float tau,
@@ -2103,7 +2115,8 @@ __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restric
                                                           const unsigned long long* __restrict__ hash,
                                                           const unsigned char* __restrict__ finished,
                                                           const int32_t* __restrict__ gstate, float* __restrict__ cand,
-                                                          float* __restrict__ cand_logp, float* __restrict__ cand_phi) {
+                                                          float* __restrict__ cand_logp, float* __restrict__ cand_phi,
+                                                          const long long* __restrict__ forced) {
     const RowStep w = row_step(pos, pos_offset, rows, T);
     if (!w.live) return;                                               // wave-uniform from here on
     const int lane = w.lane, row = w.row;
@@ -2125,6 +2138,20 @@ __global__ void __launch_bounds__(256) swor_expand_kernel(const float* __restric
     const RowFront<NPL, RULE> front(logits, allowed, cls, nullptr, gstate, nullptr, row, lane, V, (int)(T - 2 - w.t));
     const float (&z)[NPL] = front.z;
     const bool (&ok)[NPL] = front.ok;
+    if constexpr (FORCED) {
+        const int given = forced_token(forced, (long long)(row / kslots) * T + w.t + 1, V);
+        if (given >= 0) {                                              // (wave-uniform)
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                const int i = k * 64 + lane;
+                if (i < V) {
+                    const bool c = i == given;
+                    cr[i] = c ? G : NEG, lr[i] = c ? z[k] - front.lse : NEG, pr[i] = c ? phi : NEG;
+                }
+            }
+            return;
+        }
+    }
     // the proposal: log-softmax of z / tau over the mask
     float s[NPL], smax = NEG;
 #pragma unroll
@@ -2429,13 +2456,16 @@ struct BeamWork {
 #ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
 // singa_beam_expand: one wave per row; RowFront, then score + (z - lse), which accumulates the bits sample_token_kernel's
 // sum_logp accumulates.
-template <int NPL, Rule RULE>
+// FORCED (singa_forced_beam_expand, include/singa_hip_prefix.h): as in swor_expand_kernel - a forced column's only candidate is
+// the given token, at score + (z - lse); mask and rule take no part.  <NPL, RULE, false> does not read `forced`.
+template <int NPL, Rule RULE, bool FORCED>
 __global__ void __launch_bounds__(256) beam_expand_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ allowed,
                                                           const unsigned char* __restrict__ cls, const unsigned char* __restrict__ cap,
                                                           const long long* __restrict__ pos, int pos_offset, int rows, int kslots,
                                                           int V, int T, const float* __restrict__ score,
                                                           const int32_t* __restrict__ gstate, const int32_t* __restrict__ vstate,
-                                                          const unsigned char* __restrict__ done, float* __restrict__ cand) {
+                                                          const unsigned char* __restrict__ done, float* __restrict__ cand,
+                                                          const long long* __restrict__ forced) {
     const RowStep w = row_step(pos, pos_offset, rows, T);
     if (!w.live) return;                                               // wave-uniform from here on
     const int lane = w.lane, row = w.row;
@@ -2448,12 +2478,14 @@ __global__ void __launch_bounds__(256) beam_expand_kernel(const float* __restric
         return;
     }
     const RowFront<NPL, RULE> front(logits, allowed, cls, cap, gstate, vstate, row, lane, V, (int)(T - 2 - w.t));
+    int given = -1;                                                    // FORCED: the token to take, -1 = this column is free
+    if constexpr (FORCED) given = forced_token(forced, (long long)(row / kslots) * T + w.t + 1, V);
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const int i = k * 64 + lane;
         if (i < V) {
             const float lp = front.z[k] - front.lse;
-            cr[i] = front.ok[k] ? sc + lp : NEG;
+            cr[i] = (FORCED && given >= 0 ? i == given : front.ok[k]) ? sc + lp : NEG;
         }
     }
 }
@@ -7720,8 +7752,10 @@ int sample_choice(const char* name, GrammarOperands gram, bool need_forced, cons
                                    top_k, top_p, eos, pad, finished, length, sum_logp, tokens, next, live, tok_logp, cls, gstate,
                                    allowed_logp, forced, rank, mol, molecules, cap, vstate);
             };
-            if (mol) launch(std::false_type{}, std::true_type{});      // (no stream form with forced tokens)
-            else dispatch_flag(forced != nullptr, [&](auto f) { launch(f, std::false_type{}); });
+            dispatch_flag(forced != nullptr, [&](auto f) {
+                if (mol) launch(f, std::true_type{});                  // (forced there: singa_sample_token_stream_forced alone)
+                else launch(f, std::false_type{});
+            });
         });
     });
     return check_launch(name);
@@ -7768,6 +7802,20 @@ int singa_sample_token_stream(const float* logits, const float* uniforms, const 
     return sample_choice("sample_token_stream", GRAMMAR_OPTIONAL, false, logits, uniforms, allowed, cls, pos, pos_offset, rows, V,
                          T, tau, top_k, top_p, eos, pad, nullptr, length, sum_logp, tokens, next, nullptr, tok_logp, gstate,
                          allowed_logp, nullptr, nullptr, stream, mol, molecules);
+}
+
+int singa_sample_token_stream_forced(const float* logits, const float* uniforms, const unsigned char* allowed,
+                                     const unsigned char* cls, const unsigned char* cap, const long long* pos, const int32_t* mol,
+                                     int pos_offset, int rows, int molecules, int V, int T, float tau, int top_k, float top_p,
+                                     int eos, int pad, int32_t* length, float* sum_logp, long long* tokens, long long* next,
+                                     float* tok_logp, int32_t* gstate, int32_t* vstate, float* allowed_logp,
+                                     const long long* forced, int32_t* rank, void* stream) {
+    const char* name = "sample_token_stream_forced";
+    if (!mol || !forced) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (molecules < 1) return fail_at(SINGA_E_SHAPE, name, "molecules must be >= 1");
+    return sample_choice(name, GRAMMAR_OPTIONAL, true, logits, uniforms, allowed, cls, pos, pos_offset, rows, V, T, tau, top_k, top_p,
+                         eos, pad, nullptr, length, sum_logp, tokens, next, nullptr, tok_logp, gstate, allowed_logp, forced, rank,
+                         stream, mol, molecules, cap, vstate);
 }
 
 namespace {
@@ -7911,15 +7959,15 @@ int slot_shape(const char* what, const SlotSearch& s, const void* cls, const voi
     else if (eos < 0 || eos >= V || pad < 0 || pad >= V) bad = "eos / pad inside the vocabulary";
     return bad ? fail_at(SINGA_E_SHAPE, what, bad) : SINGA_OK;
 }
-}  // namespace
 
-int singa_swor_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const long long* pos,
-                      int pos_offset, int rows, int k, int V, int T, float tau, unsigned long long seed,
-                      const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
-                      const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
-                      float* cand_logp, float* cand_phi, void* stream) {
-    const char* name = "swor_expand";
-    if (!logits || !pos || !streams || !gumbel || !prop_logp || !hash || !finished || !cand || !cand_logp || !cand_phi)
+// singa_swor_expand and singa_swor_expand_forced: the latter is the former with its name, `forced` and the demand for it
+int swor_expand_launch(const char* name, bool need_forced, const float* logits, const unsigned char* allowed,
+                       const unsigned char* cls, const long long* pos, int pos_offset, int rows, int k, int V, int T, float tau,
+                       unsigned long long seed, const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
+                       const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
+                       float* cand_logp, float* cand_phi, const long long* forced, void* stream) {
+    if (!logits || !pos || !streams || !gumbel || !prop_logp || !hash || !finished || !cand || !cand_logp || !cand_phi ||
+        (need_forced && !forced))
         return fail_at(SINGA_E_NULL, name, "null pointer");
     if (const int e = slot_shape(name, SWOR_SLOTS, cls, nullptr, gstate, nullptr, rows, k, V, T, 0, pad)) return e;
     if (!(tau > 0.f)) return fail_at(SINGA_E_SHAPE, name, "temperature must be > 0");
@@ -7931,13 +7979,34 @@ int singa_swor_expand(const float* logits, const unsigned char* allowed, const u
     dispatch_npl(V, [&](auto npl) {
         dispatch_rule(cls, nullptr, [&](auto r) {
             if constexpr (decltype(r)::value != RULE_VALENCE)          // (never chosen without cap: not built)
-                hipLaunchKernelGGL((swor_expand_kernel<decltype(npl)::value, decltype(r)::value>), grid, block, 0, (hipStream_t)stream,
-                                   logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams, pad, gumbel, prop_logp,
-                                   hash, finished, gstate, cand, cand_logp, cand_phi);
+                dispatch_flag(forced != nullptr, [&](auto f) {
+                    hipLaunchKernelGGL((swor_expand_kernel<decltype(npl)::value, decltype(r)::value, decltype(f)::value>), grid, block,
+                                       0, (hipStream_t)stream, logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed,
+                                       streams, pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp, cand_phi, forced);
+                });
         });
     });
     return check_launch(name);
 #endif
+}
+}  // namespace
+
+int singa_swor_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const long long* pos,
+                      int pos_offset, int rows, int k, int V, int T, float tau, unsigned long long seed,
+                      const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
+                      const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
+                      float* cand_logp, float* cand_phi, void* stream) {
+    return swor_expand_launch("swor_expand", false, logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams, pad,
+                              gumbel, prop_logp, hash, finished, gstate, cand, cand_logp, cand_phi, nullptr, stream);
+}
+
+int singa_swor_expand_forced(const float* logits, const unsigned char* allowed, const unsigned char* cls, const long long* pos,
+                             int pos_offset, int rows, int k, int V, int T, float tau, unsigned long long seed,
+                             const uint32_t* streams, int pad, const float* gumbel, const float* prop_logp,
+                             const unsigned long long* hash, const unsigned char* finished, const int32_t* gstate, float* cand,
+                             float* cand_logp, float* cand_phi, const long long* forced, void* stream) {
+    return swor_expand_launch("swor_expand_forced", true, logits, allowed, cls, pos, pos_offset, rows, k, V, T, tau, seed, streams,
+                              pad, gumbel, prop_logp, hash, finished, gstate, cand, cand_logp, cand_phi, forced, stream);
 }
 
 int singa_swor_select(const float* cand, const float* cand_logp, const float* cand_phi, const unsigned char* cls,
@@ -8003,11 +8072,13 @@ long long singa_beam_work(int rows, int T) {
     return BeamWork(rows, T).bytes;
 }
 
-int singa_beam_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const unsigned char* cap,
-                      const long long* pos, int pos_offset, int rows, int k, int V, int T, const float* score,
-                      const int32_t* gstate, const int32_t* vstate, const unsigned char* done, float* cand, void* stream) {
-    const char* name = "beam_expand";
-    if (!logits || !pos || !score || !done || !cand) return fail_at(SINGA_E_NULL, name, "null pointer");
+namespace {
+// singa_beam_expand and singa_forced_beam_expand, as swor_expand_launch
+int beam_expand_launch(const char* name, bool need_forced, const float* logits, const unsigned char* allowed,
+                       const unsigned char* cls, const unsigned char* cap, const long long* pos, int pos_offset, int rows, int k,
+                       int V, int T, const float* score, const int32_t* gstate, const int32_t* vstate, const unsigned char* done,
+                       float* cand, const long long* forced, void* stream) {
+    if (!logits || !pos || !score || !done || !cand || (need_forced && !forced)) return fail_at(SINGA_E_NULL, name, "null pointer");
     if (const int e = slot_shape(name, BEAM_SLOTS, cls, cap, gstate, vstate, rows, k, V, T, 0, 0)) return e;
     if (rows == 0) return SINGA_OK;
 #ifdef SINGA_EMUL
@@ -8016,12 +8087,31 @@ int singa_beam_expand(const float* logits, const unsigned char* allowed, const u
     const dim3 grid((rows + 3) / 4), block(256);
     dispatch_npl(V, [&](auto npl) {
         dispatch_rule(cls, cap, [&](auto r) {
-            hipLaunchKernelGGL((beam_expand_kernel<decltype(npl)::value, decltype(r)::value>), grid, block, 0, (hipStream_t)stream,
-                               logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate, vstate, done, cand);
+            dispatch_flag(forced != nullptr, [&](auto f) {
+                hipLaunchKernelGGL((beam_expand_kernel<decltype(npl)::value, decltype(r)::value, decltype(f)::value>), grid, block, 0,
+                                   (hipStream_t)stream, logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate,
+                                   vstate, done, cand, forced);
+            });
         });
     });
     return check_launch(name);
 #endif
+}
+}  // namespace
+
+int singa_beam_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const unsigned char* cap,
+                      const long long* pos, int pos_offset, int rows, int k, int V, int T, const float* score,
+                      const int32_t* gstate, const int32_t* vstate, const unsigned char* done, float* cand, void* stream) {
+    return beam_expand_launch("beam_expand", false, logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate, vstate,
+                              done, cand, nullptr, stream);
+}
+
+int singa_forced_beam_expand(const float* logits, const unsigned char* allowed, const unsigned char* cls, const unsigned char* cap,
+                             const long long* pos, int pos_offset, int rows, int k, int V, int T, const float* score,
+                             const int32_t* gstate, const int32_t* vstate, const unsigned char* done, float* cand,
+                             const long long* forced, void* stream) {
+    return beam_expand_launch("forced_beam_expand", true, logits, allowed, cls, cap, pos, pos_offset, rows, k, V, T, score, gstate,
+                              vstate, done, cand, forced, stream);
 }
 
 int singa_beam_select(const float* cand, const unsigned char* cls, const unsigned char* cap, const long long* pos, int pos_offset,

@@ -357,7 +357,7 @@ BEAM_MAX_K = 1024       # slots per pocket singa_beam_select is built for
 
 @torch.no_grad()
 def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", grammar=None,
-                       suppress=(), length_penalty=0.7, graph=True, trace=None):
+                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None):
     """`beam_search` with the selection on the device (include/singa_hip_beam.h states the rule: `_select` and `BeamHypotheses`
     as kernels, ties ranked by slot, then token), which can therefore be constrained: `grammar` None, "smiles" or "valence"
     and `suppress` as in `Sampling.sample`.  Under a grammar every stored hypothesis is a string the rule accepts, ended by its
@@ -371,6 +371,11 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     two cache buffers taken in turn, the step captured once per parity, one read of the pockets' live counters every
     `Sampling.LIVE_POLL` tokens and nothing else per token.  Only the k17 step kernels serve this mode.  The end of the search
     stays on the host: a pocket that is not done adds its live beams as hypotheses (BS:141-149), the `topk` best are returned.
+
+    `forced`: int64 [batch_size, max_length], ONE prefix per pocket (`smiles.encode` builds it, `smiles.check_prefix` validates
+    it before any device work): every hypothesis of the pocket starts with it.  `ops.beam_expand`, given the matrix, runs
+    `singa_forced_beam_expand` (include/singa_hip_prefix.h states the rule): through the prefix a pocket keeps one live slot,
+    and the sums include the prefix.  The host-selected `beam_search` has no such argument.
 
     `trace`, if a dict, receives `hyps` (one `BeamHypotheses` per pocket, as `beam_search` leaves them), `hyp_sum_logp` and
     `hyp_tokens` (per pocket, one entry per stored hypothesis in the order of `hyps[b].beams`: the f32 summed log-probability,
@@ -395,6 +400,10 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
         raise ValueError(f"beam_search_device: the two key / value cache buffers of {rows} rows x {positions} positions and the "
                          f"candidates take {need} bytes, {free} bytes are free on {dev}: use fewer beams or pockets per call")
+
+    if forced is not None:
+        forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
+        forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
     bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
@@ -432,7 +441,7 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     def step(parity):
         (ck, cv), (ok, ov) = bufs[parity], bufs[1 - parity]
         out = kv.advance(kv.token_input(state["next"]), ck, cv)
-        ops.beam_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, allowed, cls, cap)
+        ops.beam_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, allowed, cls, cap, forced=forced)
         ops.beam_select(kv.pos, num + 1, state, k, work, len_pow, eos, pad, cls, cap)
         ops.swor_follow(ck, cv, ok, ov, state["src"], state["score"], never, kv.pos)
 

@@ -35,6 +35,10 @@ masks what would give an atom more bond order than its token can carry - `F(C)C`
 A necessary condition for validity, not a sufficient one: aromaticity, kekulisation and duplicate ring bonds stay outside.
 `sample`, `score` and `sample_stream` take it; `sample_distinct` does not (its selection gathers one state word per row).
 
+`sample_stream`, `sample_distinct` and `BeamSearch.beam_search_device` take `forced=` as well (include/singa_hip_prefix.h
+states the rule: a forced column's effective mask is the single given token, and everything behind the choice is the code a
+chosen token runs), and `score(..., rows_per_pocket=R)` scores a library on a fixed budget of rows through `sample_stream`.
+
 `forced=` gives tokens instead of drawing them: `ops.sample_token`, given the forced matrix, then runs
 `singa_sample_token_forced` (include/singa_hip_force.h states the rule), which reads one more 8-byte word per row from a
 fixed device matrix indexed by the device-resident position - like the uniforms, so the step stays one captured graph - and,
@@ -238,7 +242,8 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     return state["tokens"]
 
 
-def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda", max_length=None, grammar=None, fused=None):
+def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda", max_length=None, grammar=None, fused=None,
+          rows_per_pocket=None):
     """The model's own log-likelihood of given molecules: `molecules[b]` is the list of SMILES strings (or token lists, as
     `smiles.encode` takes them) to score for pocket b of `example`; the lists may differ in length.  Every molecule is one row
     of `sample` with all its columns forced up to and including '$', so a score comes from the same kernels, in the same
@@ -250,7 +255,13 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     Returns a dict of per-pocket lists, one entry per molecule in the order given: `sum_logp` (float), `length` (tokens, the
     '$' included), `token_logp` and `rank` (arrays of `length` entries: per token, '$' last; rank 0 = the model's arg-max,
     so the mean of rank == 0 is the top-1 accuracy) and, under `grammar`, `allowed_logp`.  ValueError before any launch for a
-    molecule the vocabulary cannot spell, one that does not fit `max_length`, or, under `grammar`, one the rule refuses."""
+    molecule the vocabulary cannot spell, one that does not fit `max_length`, or, under `grammar`, one the rule refuses.
+
+    `rows_per_pocket`: the molecules go through `sample_stream` on that many rows per pocket instead - the caches are those of
+    the rows, not of the library, and a row that has ended a short molecule starts the pocket's next one.  The same dict comes
+    back, bit for bit.  `prop` is then one prompt per pocket ([num_props] or [batch_size, num_props]); a prompt per molecule is
+    a ValueError (a row keeps its cache position 0 across molecules), and `fused` is not consulted (the k17 step kernels are
+    that mode's only path)."""
     dev = torch.device(device)
     if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
         raise RuntimeError("score runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
@@ -268,13 +279,23 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     forced = smiles.encode(items, voc, max_length, end=True)
     if prop is not None:
         prop = torch.as_tensor(prop).float().reshape(-1, torch.as_tensor(prop).shape[-1])
-        if prop.shape[0] == 1:
+        if rows_per_pocket is not None:
+            if prop.shape[0] not in (1, batch_size):
+                raise ValueError(f"score: with rows_per_pocket, prop is one prompt per pocket ([num_props] or [{batch_size}, num_props]); "
+                                 f"a prompt per molecule is unsupported there (got {prop.shape[0]} rows)")
+            prop = prop.repeat(batch_size, 1) if prop.shape[0] == 1 and batch_size > 1 else prop
+        elif prop.shape[0] == 1:
             prop = prop.repeat(batch_size * per, 1)
         elif prop.shape[0] == batch_size and per > 1:
             prop = prop.repeat_interleave(per, 0)
     tr = {}
-    sample(model, smiVoc, per, batch_size, max_length, example, prop, device=device, uniforms=torch.zeros(max_length, batch_size * per),
-           fused=fused, trace=tr, grammar=grammar, forced=forced)
+    uniforms = torch.zeros(max_length, batch_size * per)
+    if rows_per_pocket is not None:
+        sample_stream(model, smiVoc, per, batch_size, max_length, example, prop, rows_per_pocket, device=device, uniforms=uniforms,
+                      trace=tr, grammar=grammar, forced=forced)
+    else:
+        sample(model, smiVoc, per, batch_size, max_length, example, prop, device=device, uniforms=uniforms, fused=fused, trace=tr,
+               grammar=grammar, forced=forced)
     keys = {"token_logp": "token_logp", "rank": "rank"}
     if grammar is not None:
         keys["allowed_logp"] = "allowed_logp"
@@ -296,7 +317,7 @@ STREAM_MAX_ROWS = 2048  # rows per pocket singa_stream_refill is built for
 @torch.no_grad()
 def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, rows_per_pocket=64, device="cuda",
                   temperature=1.0, top_k=0, top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, trace=None,
-                  grammar=None):
+                  grammar=None, forced=None):
     """`sample` on a fixed budget of rows: `num_samples` molecules for each of the `batch_size` pockets of `example`, decoded on
     batch_size * `rows_per_pocket` rows; a row that has ended its molecule ('$', or the last column) starts the pocket's next
     one in the following step, until the pocket has none left (include/singa_hip_stream.h states the rule).  Rows that have
@@ -314,9 +335,16 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
     `path`, `steps` (steps of the run) and, under `grammar`, `allowed_logp`, all indexed by molecule, plus `row_of` (int32: the
     row that decoded the molecule) and `start_step` (int32: the step of the run, from 0, that chose its first token).
 
+    `forced`: as in `sample`, int64 [batch_size * num_samples, max_length], one row per MOLECULE, or [batch_size, max_length]
+    (one prefix per pocket, repeated for its molecules); `smiles.check_forced` validates it (a matrix that is not of an integer
+    type is a TypeError here).  `ops.sample_token_stream`, given
+    the matrix, runs `singa_sample_token_stream_forced` (include/singa_hip_prefix.h states the rule): the row that decodes
+    molecule j reads row j of the matrix at its own position.  `trace` then also receives `rank`, per molecule, and the result
+    still equals `sample(forced=...)`'s bit for bit.
+
     ValueError before any device work for a `prop` of another shape, `rows_per_pocket` outside 1..2048, a decoder geometry,
     length or pocket size the k17 step kernels are not built for (they are the only path), and a run whose caches and
-    per-molecule buffers do not fit the free memory.  Forced tokens are not part of this mode."""
+    per-molecule buffers (`forced` and `rank` included) do not fit the free memory."""
     dev, tf, voc, (sos, eos, pad), mols, num, positions, free, cls, allowed = _prologue(
         "sample_stream", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
     R, V = int(rows_per_pocket), len(voc)
@@ -333,8 +361,18 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
             and positions <= 256 and atoms <= 1024 and V <= 1024):
         raise ValueError("sample_stream: unsupported decoder geometry - the k17 step kernels are the only path: the shipped "
                          "decoder geometry, at most 256 positions, 1024 pocket atoms and 1024 tokens")
+    if forced is not None:
+        forced = forced.cpu().numpy() if torch.is_tensor(forced) else np.asarray(forced)
+        if forced.dtype.kind not in "iu":
+            raise TypeError(f"sample_stream: forced holds token ids, an integer matrix is expected (got {forced.dtype})")
+        forced = smiles.check_forced(forced, smiVoc, max_length, grammar)
+        if forced.shape[0] == batch_size and num_samples > 1:
+            forced = forced.repeat(num_samples, 0)
+        if forced.shape[0] != mols:
+            raise ValueError(f"sample_stream: forced has {forced.shape[0]} rows, expected one per molecule: {mols} (or one per "
+                             f"pocket: {batch_size})")
     rows = batch_size * R
-    need = cache_bytes(tf.decoder, rows, positions) + mols * max_length * (8 + 4 + 4 + 4)
+    need = cache_bytes(tf.decoder, rows, positions) + mols * max_length * (8 + 4 + 4 + 4 + (8 + 4 if forced is not None else 0))
     if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
         raise ValueError(f"sample_stream: the key / value caches of {rows} rows x {positions} positions and the outputs and "
                          f"uniforms of {mols} molecules take {need} bytes, {free} bytes are free on {dev}: unsupported - use "
@@ -361,6 +399,9 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
         state["grammar"] = torch.empty(rows, **i32)
         state["allowed_logp"] = torch.empty(mols, max_length, **f32)
     cap, vstate = _valence_operands(grammar, smiVoc, rows, dev)
+    if forced is not None:
+        forced = torch.as_tensor(forced).to(dev).contiguous()          # uploaded once, indexed by molecule and position
+        state["rank"] = torch.empty(mols, max_length, **i32)
     # the start of a run: the first min(R, num_samples) rows of pocket b hold its first molecules, the others are retired
     first = min(R, num_samples)
     mol0 = np.full((batch_size, R), -1, np.int32)
@@ -379,12 +420,14 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
         state["issued"].fill_(first), state["live"].fill_(first)
         if grammar is not None:
             state["grammar"].fill_(smiles.FRESH), state["allowed_logp"].zero_()
+        if forced is not None:
+            state["rank"].zero_()
         kv.reset()
 
     def step():
         out = kv.advance(kv.token_input(state["next"], state["pos"]), row_pos=state["pos"])
         ops.sample_token_stream(tf.projection(out).contiguous(), uniforms, state["pos"], state["mol"], num, state, float(temperature),
-                                int(top_k), float(top_p), eos, pad, allowed, cls=cls, cap=cap, vstate=vstate)
+                                int(top_k), float(top_p), eos, pad, allowed, cls=cls, cap=cap, vstate=vstate, forced=forced)
         ops.stream_refill(state["pos"], state["mol"], num, state, R, num_samples, max_length, sos, eos, smiles.FRESH,
                           grammar is not None)
 
@@ -401,6 +444,8 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
                      path="k17", steps=steps, row_of=state["row_of"], start_step=state["start_step"])
         if grammar is not None:
             trace.update(allowed_logp=state["allowed_logp"])
+        if forced is not None:
+            trace.update(rank=state["rank"])
     return state["tokens"]
 
 
@@ -409,7 +454,7 @@ SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
 
 @torch.no_grad()
 def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
-                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None):
+                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None):
     """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
     replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` ("smiles", as in `sample`;
     "valence" is a ValueError here), by
@@ -426,7 +471,17 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     `trace`, if a dict, receives `gumbel` (G, -inf for dead slots), `prop_logp` (log-probability under the proposal),
     `sum_logp` / `token_logp` (the unmodified model's, as `sample` and `score` report them), `lengths`, `valid` (uint8: 0 for
     dead slots) and `steps`.  A list handed in as `trace["gumbel_history"]` receives a copy of G [rows] after every step:
-    G[k - 1] - G[k] of a run with one slot more bounds the margin by which the k-slot run's selections were decided.  ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
+    G[k - 1] - G[k] of a run with one slot more bounds the margin by which the k-slot run's selections were decided.
+
+    `forced`: int64 [batch_size, max_length], ONE prefix per pocket (`smiles.encode` builds it, `smiles.check_prefix` validates
+    it: one run of tokens from column 1 without '$', at least one free column, under `grammar` a prefix the rule accepts and
+    can finish): every sequence of the pocket starts with it - distinct completions of a scaffold.  `ops.swor_expand`, given
+    the matrix, runs `singa_swor_expand_forced` (include/singa_hip_prefix.h states the rule): through the prefix a pocket
+    keeps one slot with G = 0.  `sum_logp` / `token_logp` include the prefix and stay `score`'s bit for bit; `prop_logp` is the
+    log-probability under the proposal CONDITIONAL on the prefix, so `swor_weights` of such a run estimates expectations over
+    the completions of the prefix, not over all sequences.  A matrix without a forced column gives the bits of `forced=None`.
+
+    ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
     length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory."""
     if grammar == "valence":
         raise ValueError("sample_distinct: grammar='valence' is unsupported (the selection gathers one state word per row); use "
@@ -454,6 +509,9 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         raise ValueError(f"sample_distinct: the two key / value cache buffers of {rows} rows x {positions} positions and the "
                          f"candidates take {need} bytes, {free} bytes are free on {dev}: draw fewer samples per call")
     streams = torch.as_tensor(streams.astype(np.uint32).view(np.int32)).to(dev)
+    if forced is not None:
+        forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
+        forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
     bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
@@ -488,7 +546,7 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         (ck, cv), (ok, ov) = bufs[parity], bufs[1 - parity]
         out = kv.advance(kv.token_input(state["next"]), ck, cv)
         ops.swor_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, streams, float(temperature), int(seed), pad,
-                        allowed, cls)
+                        allowed, cls, forced=forced)
         ops.swor_select(kv.pos, num + 1, state, k, work, eos, pad, cls)
         ops.swor_follow(ck, cv, ok, ov, state["src"], state["gumbel"], state["finished"], kv.pos)
 

@@ -909,19 +909,24 @@ def sample_token_forced(logits, uniforms, pos, pos_offset, state, forced, cls=No
 
 
 def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperature=1.0, top_k=0, top_p=1.0, eos=0, pad=0,
-                        allowed=None, cls=None, cap=None, vstate=None):
+                        allowed=None, cls=None, cap=None, vstate=None, forced=None):
     """`sample_token` (cls=None) or `sample_token_grammar` for rows that hold a molecule each (`singa_sample_token_stream`,
     include/singa_hip_stream.h states the rule; inference only): logits [R, V] f32; pos [R] int64, the rows' own positions (a
     row's step is pos - pos_offset); mol [R] int32, the molecule a row decodes (-1: retired, the row is skipped); uniforms
     [>= T - 1, M] f32, one column per molecule.  `state`: tokens [M, T] int64, length [M] int32, sum_logp [M] f32 and,
     optionally, tok_logp [M, T] f32 - indexed by molecule - and next [R] int64; with `cls` also grammar [R] int32 and, optionally,
     allowed_logp [M, T] f32.  Updated in place, bit for bit as the per-row ops update a row that draws the same logits.
-    `cap` [V] uint8 and `vstate` [R, 2] int32 (with `cls`): the valence rule, as in `sample_token`."""
+    `cap` [V] uint8 and `vstate` [R, 2] int32 (with `cls`): the valence rule, as in `sample_token`.
+    `forced` [M, T] int64, one row per molecule: the op is `singa_sample_token_stream_forced` (include/singa_hip_prefix.h), under
+    any of the three rules; a molecule whose forced[j, t + 1] lies in [0, V) takes that token at its step t, as in
+    `sample_token_forced`, and `state` may then hold rank [M, T] int32."""
     _cap_with_cls("sample_token_stream", cls, cap, vstate)
     R, V = logits.shape
     M, T = state["tokens"].shape
     gstate, alp = (state["grammar"], state.get("allowed_logp")) if cls is not None else (None, None)
+    rank = state.get("rank") if forced is not None else None
     _check_views("sample_token_stream", (
+        (forced, torch.int64, (M, T)), (rank, torch.int32, (M, T)),
         (logits, torch.float32, (R, V)), (uniforms, torch.float32, None), (pos, torch.int64, (R,)), (mol, torch.int32, (R,)),
         (state["tokens"], torch.int64, (M, T)), (state["length"], torch.int32, (M,)), (state["sum_logp"], torch.float32, (M,)),
         (state.get("tok_logp"), torch.float32, (M, T)), (state["next"], torch.int64, (R,)), (allowed, torch.uint8, (V,)),
@@ -930,6 +935,13 @@ def sample_token_stream(logits, uniforms, pos, mol, pos_offset, state, temperatu
     if uniforms.dim() != 2 or uniforms.shape[1] != M or uniforms.shape[0] < T - 1:
         raise RuntimeError(f"sample_token_stream: uniforms [>= T - 1, molecules], got {tuple(uniforms.shape)} for T = {T}, {M} molecules")
     _lib.ensure_init(logits.device.index if logits.device.index is not None else torch.cuda.current_device())
+    if forced is not None:
+        _chk(_lib.lib().singa_sample_token_stream_forced(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(cap), _p(pos), _p(mol),
+                                                         pos_offset, R, M, V, T, temperature, top_k, top_p, eos, pad,
+                                                         _p(state["length"]), _p(state["sum_logp"]), _p(state["tokens"]),
+                                                         _p(state["next"]), _p(state.get("tok_logp")), _p(gstate), _p(vstate), _p(alp),
+                                                         _p(forced), _p(rank), _stream()), "singa_sample_token_stream_forced")
+        return
     if cap is not None:
         _chk(_lib.lib().singa_sample_token_valence(_p(logits), _p(uniforms), _p(allowed), _p(cls), _p(cap), _p(pos), _p(mol), pos_offset,
                                                    R, M, V, T, temperature, top_k, top_p, eos, pad, None, _p(state["length"]),
@@ -993,22 +1005,26 @@ def _slot_views(what, state, R, k, V, T, names, cls=None, cap=None, extra=()):
     _lib.ensure_init(items[0][0].device.index if items[0][0].device.index is not None else torch.cuda.current_device())
 
 
-def swor_expand(logits, pos, pos_offset, state, k, streams, temperature=1.0, seed=0, pad=0, allowed=None, cls=None):
+def swor_expand(logits, pos, pos_offset, state, k, streams, temperature=1.0, seed=0, pad=0, allowed=None, cls=None, forced=None):
     """Sub-steps 1 to 3 of stochastic beam search (`singa_swor_expand`, include/singa_hip_swor.h states the rule; inference
     only): the perturbed, parent-conditioned score of every candidate of every row.  logits [R, V] f32, R = pockets * k; pos:
     int64 device scalar (the step is pos - pos_offset); streams [pockets] int32 (read as 32-bit words); `state`: gumbel,
     prop_logp [R] f32, hash [R] int64 (the 64 bits of the prefix hash), finished [R] uint8, tokens [R, T] (for T only), with
-    `cls` ([V] uint8 class bytes) also grammar [R] int32 - all read - and cand, cand_logp, cand_phi [R, V] f32, written."""
+    `cls` ([V] uint8 class bytes) also grammar [R] int32 - all read - and cand, cand_logp, cand_phi [R, V] f32, written.
+    `forced` [pockets, T] int64, one prefix per pocket: the op is `singa_swor_expand_forced` (include/singa_hip_prefix.h) - where
+    forced[p, t + 1] lies in [0, V) that token is the only candidate of pocket p's live rows, with the row's own G and phi."""
     R, V = logits.shape
     T = state["tokens"].shape[1]
     _slot_views("swor_expand", state, R, k, V, T, ("gumbel", "prop_logp", "hash", "finished", "cand", "cand_logp", "cand_phi"), cls,
                 None, ((allowed, torch.uint8, (V,)), (logits, torch.float32, (R, V)), (pos, torch.int64, None),
-                       (streams, torch.int32, (R // max(k, 1),))))
-    _chk(_lib.lib().singa_swor_expand(_p(logits), _p(allowed), _p(cls), _p(pos), pos_offset, R, k, V, T, temperature,
-                                      int(seed) & (2 ** 64 - 1), _p(streams), pad, _p(state["gumbel"]), _p(state["prop_logp"]),
-                                      _p(state["hash"]), _p(state["finished"]), _p(state["grammar"] if cls is not None else None),
-                                      _p(state["cand"]), _p(state["cand_logp"]), _p(state["cand_phi"]), _stream()),
-         "singa_swor_expand")
+                       (streams, torch.int32, (R // max(k, 1),)), (forced, torch.int64, (R // max(k, 1), T))))
+    args = (_p(logits), _p(allowed), _p(cls), _p(pos), pos_offset, R, k, V, T, temperature, int(seed) & (2 ** 64 - 1), _p(streams), pad,
+            _p(state["gumbel"]), _p(state["prop_logp"]), _p(state["hash"]), _p(state["finished"]),
+            _p(state["grammar"] if cls is not None else None), _p(state["cand"]), _p(state["cand_logp"]), _p(state["cand_phi"]))
+    if forced is not None:
+        _chk(_lib.lib().singa_swor_expand_forced(*args, _p(forced), _stream()), "singa_swor_expand_forced")
+    else:
+        _chk(_lib.lib().singa_swor_expand(*args, _stream()), "singa_swor_expand")
 
 
 def swor_select(pos, pos_offset, state, k, work, eos=0, pad=0, cls=None):
@@ -1061,21 +1077,26 @@ def beam_work(rows, T, device):
     return _slot_work("beam_work", rows, T, device)
 
 
-def beam_expand(logits, pos, pos_offset, state, k, allowed=None, cls=None, cap=None):
+def beam_expand(logits, pos, pos_offset, state, k, allowed=None, cls=None, cap=None, forced=None):
     """Sub-step 1 of the device beam search (`singa_beam_expand`, include/singa_hip_beam.h states the rule; inference only):
     the summed log-probability of every candidate of every live row, -inf where `allowed`, the SMILES rule (`cls`: [V] uint8
     class bytes) or the valence rule (`cls` of `smiles.classify_orders` and `cap`: [V] uint8 capacities) refuses the token.
     logits [R, V] f32, R = pockets * k; pos: int64 device scalar (the step is pos - pos_offset); `state`: score [R] f32, tokens
     [R, T] (for T only), done [pockets] uint8, with `cls` grammar [R] int32, with `cap` vstate [R, 2] int32 - all read - and
-    cand [R, V] f32, written."""
+    cand [R, V] f32, written.  `forced` [pockets, T] int64, one prefix per pocket: the op is `singa_forced_beam_expand`
+    (include/singa_hip_prefix.h) - where forced[p, t + 1] lies in [0, V) that token is the only candidate of pocket p's live rows."""
     R, V = logits.shape
     T = state["tokens"].shape[1]
     _slot_views("beam_expand", state, R, k, V, T, ("score", "done", "cand"), cls, cap,
-                ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (allowed, torch.uint8, (V,))))
-    _chk(_lib.lib().singa_beam_expand(_p(logits), _p(allowed), _p(cls), _p(cap), _p(pos), pos_offset, R, k, V, T, _p(state["score"]),
-                                      _p(state["grammar"] if cls is not None else None),
-                                      _p(state["vstate"] if cap is not None else None), _p(state["done"]), _p(state["cand"]),
-                                      _stream()), "singa_beam_expand")
+                ((logits, torch.float32, (R, V)), (pos, torch.int64, None), (allowed, torch.uint8, (V,)),
+                 (forced, torch.int64, (R // max(k, 1), T))))
+    args = (_p(logits), _p(allowed), _p(cls), _p(cap), _p(pos), pos_offset, R, k, V, T, _p(state["score"]),
+            _p(state["grammar"] if cls is not None else None), _p(state["vstate"] if cap is not None else None), _p(state["done"]),
+            _p(state["cand"]))
+    if forced is not None:
+        _chk(_lib.lib().singa_forced_beam_expand(*args, _p(forced), _stream()), "singa_forced_beam_expand")
+    else:
+        _chk(_lib.lib().singa_beam_expand(*args, _stream()), "singa_beam_expand")
 
 
 def beam_select(pos, pos_offset, state, k, work, len_pow, eos=0, pad=0, cls=None, cap=None):

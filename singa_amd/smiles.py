@@ -266,3 +266,35 @@ def check_forced(forced, voc, max_length, grammar=None):
             state[on] = nxt
         ended[on] |= tok == eos
     return f
+
+
+def check_prefix(forced, voc, batch_size, max_length, grammar=None):
+    """`check_forced` for the modes whose rows exchange prefixes (`sample_distinct(..., forced=...)`,
+    `beam_search_device(..., forced=...)`; include/singa_hip_prefix.h): `forced` is [batch_size, max_length], ONE prefix per
+    pocket.  On top of what `check_forced` demands - one run of forced columns from column 1, and under `grammar` a prefix the
+    rule accepts and can still finish - a prefix holds no '$' (a finished string leaves nothing to search for) and leaves at
+    least one free column.  ValueError names pocket, column and token of the first refusal; returns the contiguous int64 matrix."""
+    voc = [str(v) for v in voc]
+    f = np.asarray(forced)
+    if f.ndim != 2 or f.shape != (batch_size, max_length) or f.dtype.kind not in "iu":
+        raise ValueError(f"forced: one prefix per pocket, an integer matrix [batch_size = {batch_size}, max_length = {max_length}], "
+                         f"is expected, got {f.dtype} {f.shape}")
+    try:
+        f = check_forced(f, voc, max_length, None)
+    except ValueError as e:
+        raise ValueError(str(e).replace("forced: row", "forced: pocket", 1)) from None
+    is_f = (f >= 0) & (f < len(voc))
+    name = lambda p, c: f"pocket {p}, column {c}, token {voc[f[p, c]]!r}"
+    if "$" in voc:
+        for p, c in zip(*np.nonzero(is_f[:, 1:] & (f[:, 1:] == voc.index("$")))):
+            raise ValueError(f"forced: {name(int(p), int(c) + 1)}: a prefix holds no '$' - a whole molecule is scored (`score`), not "
+                             f"searched")
+    full = np.flatnonzero(is_f[:, 1:].all(1))
+    if len(full):
+        raise ValueError(f"forced: {name(int(full[0]), max_length - 1)}: the prefix leaves no free column of max_length = {max_length}")
+    if grammar is not None:
+        try:
+            check_forced(f, voc, max_length, grammar)
+        except ValueError as e:
+            raise ValueError(str(e).replace("forced: row", "forced: pocket", 1)) from None
+    return f

@@ -4,7 +4,7 @@ atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket w
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
     python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
-                                  [--distinct] [--rows-per-pocket R] [--valence]
+                                  [--distinct] [--rows-per-pocket R] [--valence] [--score-stream]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
@@ -25,6 +25,11 @@ window), 4,096 molecules per pocket through `sample_stream(rows_per_pocket=R)` a
 per pocket, whole calls timed, with the length distribution of the run and the ratio it predicts: (steps until the longest
 of 256 rows has ended, as the polling loop sees it) / (mean length).  With `--valence` nothing but the k17 step under
 `grammar="valence"` next to the one under `grammar="smiles"` at rows = 128, 512, 2048, interleaved (`valence_table`).
+With `--score-stream` nothing but forced tokens outside the lockstep sampler (include/singa_hip_prefix.h): `score_stream` - 2,048
+molecules per pocket of ragged length, drawn once by `sample` from the `beam_b2_k6_eos` golden model, scored by `score` in chunks
+of 256 molecules per pocket against `score(rows_per_pocket=256)`, whole calls timed, alternately, twice each, with the ratio of
+step counts that predicts the gain - and `prefix_table`: `sample_distinct` and `beam_search_device` on the synthetic pocket with
+a forced prefix of 5 tokens next to the same run without one, ms per step of whole generations, interleaved.
 """
 import argparse
 import json
@@ -58,6 +63,8 @@ def main():
                     help="nothing but the k17 step under grammar='valence' next to grammar='smiles' at rows = 128, 512, 2048 (valence_table)")
     ap.add_argument("--rows-per-pocket", type=int, default=0, metavar="R",
                     help="nothing but sample_stream: the streaming step next to the plain one, and molecules / s at R rows per pocket")
+    ap.add_argument("--score-stream", action="store_true",
+                    help="nothing but score on a row budget against score in chunks, and the forced step of the two slot searches")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -113,6 +120,84 @@ def main():
         return {"rows": rows, "ms_per_step": round(ms, 4), "new_tokens_per_s": round(rows / ms * 1e3, 1),
                 "sequences_per_s": round(rows / (ms * (T - 1)) * 1e3, 2)}
 
+    if args.score_stream:
+        import numpy as np
+        from singa_amd.model.BeamSearch import beam_search_device
+        from tests.helpers import golden, smi_voc
+        from tests.test_beam_gpu import build_model
+        from tests.test_sampling_gpu import example_of
+        z = golden("beam_b2_k6_eos.npz")
+        gmodel, gex, gvoc, B, Tg = build_model(z)[0], example_of(z), smi_voc(), len(z["names"]), 41
+        n, chunk, eos = 2048, 256, smi_voc().index("$")
+        prop1 = torch.as_tensor(z["prop"][:1]).float()
+        library = [[] for _ in range(B)]
+        for c in range(n // chunk):                                            # the library: what the model itself draws
+            tr = {}
+            u = torch.rand(Tg, B * chunk, generator=torch.Generator().manual_seed(c))
+            tok = sample(gmodel, gvoc, chunk, B, Tg, gex, prop1.repeat(B * chunk, 1).to(dev), device=dev, uniforms=u, fused=True,
+                         trace=tr).cpu().numpy()
+            ln = tr["lengths"].cpu().numpy()
+            for r in range(B * chunk):
+                body = tok[r, 1:1 + ln[r]]
+                library[r // chunk].append([int(t) for t in body[body != eos]])
+        tokens = np.array([len(m) + 1 for ms in library for m in ms]).reshape(B, n)       # scored columns, the '$' included
+        got = {}
+
+        def chunks():
+            out = []
+            for c in range(n // chunk):
+                out.append(score(gmodel, gvoc, [ms[c * chunk:(c + 1) * chunk] for ms in library], B, gex, prop1, device=dev,
+                                 max_length=Tg + 1, fused=True)["sum_logp"])
+            got["chunks"] = [sum((o[b] for o in out), []) for b in range(B)]
+            return 1
+
+        def streamed():
+            got["stream"] = score(gmodel, gvoc, library, B, gex, prop1, device=dev, max_length=Tg + 1, rows_per_pocket=chunk)["sum_logp"]
+            return 1
+        chunks(), streamed()
+        assert got["chunks"] == got["stream"]                                  # the same floats, whatever the row budget
+        t_chunks, t_stream = [], []
+        for _ in range(2):
+            t_chunks.append(timed(chunks) / 1e3)
+            t_stream.append(timed(streamed) / 1e3)
+        per_chunk = [int(-(-tokens[:, c * chunk:(c + 1) * chunk].max() // LIVE_POLL) * LIVE_POLL) for c in range(n // chunk)]
+        sc, ss = statistics.median(t_chunks), statistics.median(t_stream)
+        res = {"metric": "score_stream_molecules_per_s", "unit": "molecules/s", "value": round(B * n / ss, 1),
+               "score_stream": {"model": "beam_b2_k6_eos", "pockets": B, "molecules_per_pocket": n, "max_length": Tg + 1,
+                                "rows_per_pocket": chunk, "stream_seconds": [round(x, 4) for x in t_stream],
+                                "score_8x256_seconds": [round(x, 4) for x in t_chunks],
+                                "stream_molecules_per_s": round(B * n / ss, 1), "score_molecules_per_s": round(B * n / sc, 1),
+                                "observed_ratio": round(sc / ss, 3),
+                                "tokens": {"mean": round(float(tokens.mean()), 2), "min": int(tokens.min()), "max": int(tokens.max())},
+                                "steps_per_256_row_call": per_chunk,
+                                "predicted_ratio": round(statistics.mean(per_chunk) / float(tokens.mean()), 3)}}
+        prefix = smiles.encode(["CCOCN"], voc, T)                               # 5 forced columns, then the free search
+
+        def run_distinct(rows, forced):
+            tr = {}
+            sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev, temperature=args.temperature,
+                            suppress=("$",), seed=rows, trace=tr, forced=forced)
+            return tr["steps"]
+
+        def run_beam_device(rows, forced):
+            tr = {}
+            beam_search_device(model, voc, rows, 1, T, 1, ex, torch.ones(rows, 3, device=dev), device=dev, suppress=("$",), trace=tr,
+                               forced=forced)
+            return tr["steps"]
+        ptable = []
+        for name, fn, sizes in (("sample_distinct", run_distinct, (128, 2048)), ("beam_search_device", run_beam_device, (128, 1024))):
+            for rows in sizes:
+                fn(rows, None), fn(rows, prefix)
+                plain, forc = [], []
+                for _ in range(3):
+                    plain.append(timed(lambda: fn(rows, None)))
+                    forc.append(timed(lambda: fn(rows, prefix)))
+                ptable.append({"mode": name, "rows": rows, "plain_ms_per_step": round(statistics.median(plain), 4),
+                               "prefix_ms_per_step": round(statistics.median(forc), 4),
+                               "plain_runs_ms": [round(x, 4) for x in plain], "prefix_runs_ms": [round(x, 4) for x in forc]})
+        res["prefix_table"] = ptable
+        print(json.dumps(res))
+        return
     if args.distinct_only:
         rows = args.distinct_only
         ms = []
