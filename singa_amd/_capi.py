@@ -199,12 +199,24 @@ _PREFIX_SIGS = {
 PREFIX_EXPORTS = tuple(_PREFIX_SIGS)
 
 
+class CollateField(C.Structure):
+    """singa_collate_field_t of include/singa_hip_data.h"""
+    _fields_ = [("src", P), ("dst", P), ("axis", C.c_int32), ("width", C.c_int32), ("kind", C.c_int32), ("base_axis", C.c_int32)]
+
+
+# include/singa_hip_data.h: batches from the device-resident packed dataset (singa_amd/dataset.py); a table of its own
+_DATA_SIGS = {
+    "singa_collate_batch": ([P, I32, I32, P, P, P, C.POINTER(CollateField), I32, C.POINTER(I64), P], I32),
+}
+DATA_EXPORTS = tuple(_DATA_SIGS)
+
+
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
-            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()):
+            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

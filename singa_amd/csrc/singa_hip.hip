@@ -29,6 +29,7 @@
 #include "../../include/singa_hip_beam.h"
 #include "../../include/singa_hip_units.h"
 #include "../../include/singa_hip_prefix.h"
+#include "../../include/singa_hip_data.h"
 #include "so3_index.h"
 
 namespace {
@@ -8420,6 +8421,174 @@ int singa_so3_rmsnorm_bwd_add(const float* x, const float* weight, const float* 
     SINGA_DISPATCH_L(lmax, 2, hipLaunchKernelGGL((rmsnorm_bwd4_kernel<L_, true>), dim3(singa_so3_rmsnorm_nparts(N)), dim3(64),
                                                  0, (hipStream_t)stream, x, weight, gy, g_add, gx, gw_part, gb_part, N, eps));
     return check_launch("so3_rmsnorm_bwd_add");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Batches from the device-resident packed dataset (include/singa_hip_data.h): a plan kernel (the scans of counts[ids]) and one
+// copy kernel over a table of ragged fields.  Memory-bound copies of 4-byte words; every store is a plain vector store.
+namespace {
+constexpr int COLLATE_SCAN = 128;      // ids per scan block of the plan kernel (one workgroup walks B in blocks of this width)
+constexpr int COLLATE_THREADS = 256;
+constexpr int COLLATE_CHUNK = 4096;    // items of a field's flat destination per workgroup of the copy kernel
+
+struct CollateArgs {
+    singa_collate_field_t f[SINGA_COLLATE_MAX_FIELDS];
+    long long items[SINGA_COLLATE_MAX_FIELDS];     // host total rows x width: the end of the destination
+    int blk0[SINGA_COLLATE_MAX_FIELDS + 1];        // first workgroup of every field
+    int n;
+};
+
+#ifndef SINGA_EMUL      // (workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
+__device__ __forceinline__ int collate_clamp_id(int id, int G) { return id < 0 ? 0 : (id >= G ? G - 1 : id); }
+
+__global__ __launch_bounds__(COLLATE_SCAN) void collate_plan_kernel(const int32_t* __restrict__ ids, int B, int G,
+                                                                     const int64_t* __restrict__ offsets,
+                                                                     int64_t* __restrict__ bases, int32_t* __restrict__ status) {
+    __shared__ long long s[SINGA_COLLATE_AXES][COLLATE_SCAN];
+    const int t = threadIdx.x;
+    long long carry[SINGA_COLLATE_AXES];
+#pragma unroll
+    for (int a = 0; a < SINGA_COLLATE_AXES; ++a) carry[a] = 0;
+    int bad = 0;
+    for (int c0 = 0; c0 < B; c0 += COLLATE_SCAN) {
+        const int b = c0 + t;
+        int id = 0;
+        if (b < B) {
+            id = ids[b];
+            if (id < 0 || id >= G) ++bad;
+            id = collate_clamp_id(id, G);
+        }
+#pragma unroll
+        for (int a = 0; a < SINGA_COLLATE_AXES; ++a) {
+            const int64_t* off = offsets + (long long)a * (G + 1);
+            s[a][t] = b < B ? (long long)(off[id + 1] - off[id]) : 0;
+        }
+        __syncthreads();
+        for (int d = 1; d < COLLATE_SCAN; d <<= 1) {       // inclusive Hillis-Steele scan of the block, all seven axes at once
+            long long v[SINGA_COLLATE_AXES];
+#pragma unroll
+            for (int a = 0; a < SINGA_COLLATE_AXES; ++a) v[a] = t >= d ? s[a][t - d] : 0;
+            __syncthreads();
+#pragma unroll
+            for (int a = 0; a < SINGA_COLLATE_AXES; ++a) s[a][t] += v[a];
+            __syncthreads();
+        }
+#pragma unroll
+        for (int a = 0; a < SINGA_COLLATE_AXES; ++a) {
+            if (b < B) bases[(long long)a * (B + 1) + b + 1] = carry[a] + s[a][t];
+            carry[a] += s[a][COLLATE_SCAN - 1];
+        }
+        __syncthreads();                                    // the next block overwrites s
+    }
+    if (t < SINGA_COLLATE_AXES) bases[(long long)t * (B + 1)] = 0;
+    s[0][t] = bad;
+    __syncthreads();
+    if (t == 0) {
+        long long n = 0;
+        for (int i = 0; i < COLLATE_SCAN; ++i) n += s[0][i];
+        status[0] = (int32_t)n;
+    }
+}
+
+__global__ __launch_bounds__(COLLATE_THREADS) void collate_copy_kernel(const CollateArgs A, const int32_t* __restrict__ ids, int B,
+                                                                        int G, const int64_t* __restrict__ offsets,
+                                                                        const int64_t* __restrict__ bases) {
+    __shared__ long long sb[SINGA_COLLATE_MAX_B + 1];       // the scanned bases of this field's axis
+    int fi = 0;
+    while (fi + 1 < A.n && (int)blockIdx.x >= A.blk0[fi + 1]) ++fi;      // workgroup-uniform
+    const singa_collate_field_t f = A.f[fi];
+    const int64_t* ab = bases + (long long)f.axis * (B + 1);
+    for (int i = threadIdx.x; i <= B; i += COLLATE_THREADS) sb[i] = ab[i];
+    __syncthreads();
+    // the end of the run: what the host sized the destination for, and no row the device's own scan does not have
+    long long lim = A.items[fi];
+    const long long dev_items = sb[B] * f.width;
+    if (dev_items < lim) lim = dev_items;
+    const long long w0 = (long long)((int)blockIdx.x - A.blk0[fi]) * COLLATE_CHUNK;
+    const long long wend = w0 + COLLATE_CHUNK < lim ? w0 + COLLATE_CHUNK : lim;
+    const unsigned width = (unsigned)f.width;
+    const int64_t* aoff = offsets + (long long)f.axis * (G + 1);
+    const int64_t* nbase = bases + (long long)f.base_axis * (B + 1);
+    int slot = -1;
+    long long soff = 0, nb = 0;                              // source row - destination row, and the node base, of `slot`
+    for (long long w = w0 + threadIdx.x; w < wend; w += COLLATE_THREADS) {
+        const unsigned wu = (unsigned)w;                     // items < 2^31 (checked by the entry point)
+        const unsigned r = width == 1 ? wu : wu / width;
+        const unsigned col = wu - r * width;
+        int sl = slot;
+        if (sl < 0) {                                        // largest sl with sb[sl] <= r; sb[0] = 0 <= r < sb[B]
+            int lo = 0, hi = B;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (sb[mid] <= (long long)r) lo = mid; else hi = mid;
+            }
+            sl = lo;
+        } else {
+            while ((long long)r >= sb[sl + 1]) ++sl;         // ends: r < sb[B]; slots without rows are stepped over
+        }
+        if (sl != slot) {
+            slot = sl;
+            soff = aoff[collate_clamp_id(ids[sl], G)] - sb[sl];
+            nb = f.kind == SINGA_COLLATE_WIDEN_BASE ? (long long)nbase[sl] : 0;
+        }
+        const long long si = (soff + (long long)r) * width + col;
+        if (f.kind == SINGA_COLLATE_COPY32)
+            ((uint32_t*)f.dst)[w] = ((const uint32_t*)f.src)[si];
+        else if (f.kind == SINGA_COLLATE_SLOT)
+            ((long long*)f.dst)[w] = (long long)sl;
+        else
+            ((long long*)f.dst)[w] = (long long)((const int32_t*)f.src)[si] + nb;
+    }
+}
+#endif
+}  // namespace
+
+int singa_collate_batch(const int32_t* ids, int B, int G, const int64_t* offsets, int64_t* bases, int32_t* status,
+                        const singa_collate_field_t* fields, int n_fields, const int64_t* totals, void* stream) {
+    const char* name = "collate_batch";
+    if (!ids || !offsets || !bases || !status || !totals || (!fields && n_fields > 0)) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (B < 1 || B > SINGA_COLLATE_MAX_B) return fail_at(SINGA_E_SHAPE, name, "B must be in [1, 2048]");
+    if (G < 1) return fail_at(SINGA_E_SHAPE, name, "G >= 1 graphs in the store");
+    if (n_fields < 0 || n_fields > SINGA_COLLATE_MAX_FIELDS) return fail_at(SINGA_E_SHAPE, name, "at most 32 fields");
+    if (((uintptr_t)ids & 3) || ((uintptr_t)offsets & 7) || ((uintptr_t)bases & 7) || ((uintptr_t)status & 3))
+        return fail_at(SINGA_E_SHAPE, name, "misaligned ids / offsets / bases / status");
+    if (totals[SINGA_COLLATE_AXES - 1] != B) return fail_at(SINGA_E_SHAPE, name, "totals[6] must be B (width mismatch)");
+    for (int a = 0; a < SINGA_COLLATE_AXES; ++a)
+        if (totals[a] < 0) return fail_at(SINGA_E_SHAPE, name, "negative total");
+    CollateArgs A;
+    memset(&A, 0, sizeof(A));
+    long long blocks = 0;
+    for (int i = 0; i < n_fields; ++i) {
+        const singa_collate_field_t& f = fields[i];
+        if (f.axis < 0 || f.axis >= SINGA_COLLATE_AXES) return fail_at(SINGA_E_SHAPE, name, "field axis outside [0, 7)");
+        if (f.width < 1) return fail_at(SINGA_E_SHAPE, name, "field width must be >= 1 (width mismatch)");
+        if (f.kind < 0 || f.kind > SINGA_COLLATE_SLOT) return fail_at(SINGA_E_SHAPE, name, "field kind outside [0, 4)");
+        if (f.kind == SINGA_COLLATE_WIDEN_BASE && (f.base_axis < 0 || f.base_axis > 1))
+            return fail_at(SINGA_E_SHAPE, name, "base_axis must be 0 or 1");
+        const long long items = (long long)totals[f.axis] * f.width;
+        if (items == 0) continue;                              // no rows of this axis in the batch
+        if (items >= (1LL << 31)) return fail_at(SINGA_E_SHAPE, name, "a field of 2^31 or more items");
+        if (!f.dst || (!f.src && f.kind != SINGA_COLLATE_SLOT)) return fail_at(SINGA_E_NULL, name, "null field pointer");
+        if (((uintptr_t)f.src & 3) || ((uintptr_t)f.dst & (f.kind == SINGA_COLLATE_COPY32 ? 3 : 7)))
+            return fail_at(SINGA_E_SHAPE, name, "misaligned field pointer");
+        A.f[A.n] = f;
+        if (f.kind != SINGA_COLLATE_WIDEN_BASE) A.f[A.n].base_axis = 0;
+        A.items[A.n] = items;
+        A.blk0[A.n] = (int)blocks;
+        blocks += (items + COLLATE_CHUNK - 1) / COLLATE_CHUNK;
+        ++A.n;
+    }
+    A.blk0[A.n] = (int)blocks;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(collate_plan_kernel, dim3(1), dim3(COLLATE_SCAN), 0, st, ids, B, G, offsets, bases, status);
+    if (blocks > 0)
+        hipLaunchKernelGGL(collate_copy_kernel, dim3((unsigned)blocks), dim3(COLLATE_THREADS), 0, st, A, ids, B, G, offsets,
+                           (const int64_t*)bases);
+    return check_launch(name);
+#endif
 }
 
 }  // extern "C"

@@ -5,9 +5,10 @@ validation every `val_freq` iterations with early stopping, checkpoints {'config
 'iteration'}.  The step itself runs through singa_amd.engine.TrainStep (HIP kernels + HIP-graph replay).
 
 The CrossDocked dataset and the RDKit/ODDT featurisation of the reference are out of scope, so graphs
-come from `--data golden` (the three example graphs the reference bundles, shipped under singa_amd/data/examples) or `--data synthetic`
-(singa_amd.graph.synthetic_graph).  Under `torch.distributed.run` every rank trains on its own shard of each batch and
-gradients are averaged with RCCL (singa_amd.dp).
+come from `--data golden` (the three example graphs the reference bundles, shipped under singa_amd/data/examples), `--data synthetic`
+(singa_amd.graph.synthetic_graph) or `--data packed --dataset DIR`: a packed dataset of already featurised graphs
+(singa_amd.dataset, made by tools/pack_dataset.py), held on the device, whose batches a kernel assembles.  Under
+`torch.distributed.run` every rank trains on its own shard of each batch and gradients are averaged with RCCL (singa_amd.dp).
 
     python train.py --config ./config/train.yml --device cuda --logdir ./logs --data synthetic --max-iters 20
 """
@@ -54,7 +55,15 @@ def main():
     ap.add_argument("--config", type=str, default=os.path.join(ROOT, "config", "train.yml"))
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--logdir", type=str, default="./logs")
-    ap.add_argument("--data", choices=["synthetic", "golden"], default="synthetic")
+    ap.add_argument("--data", choices=["synthetic", "golden", "packed"], default="synthetic")
+    ap.add_argument("--dataset", type=str, default=None, help="--data packed: directory of a packed dataset (tools/pack_dataset.py)")
+    ap.add_argument("--no-shuffle", action="store_true",
+                    help="--data packed: iteration `it` takes rows (it-1)*B .. it*B-1 of the train split instead of a shuffled epoch")
+    ap.add_argument("--val-batches", type=int, default=None,
+                    help="--data packed: validate on the first N batches of the val split (default: all of them)")
+    ap.add_argument("--host-dataset", action="store_true",
+                    help="--data packed: keep the pack on the host (batches gathered on the host and copied per step) - for a "
+                         "pack that does not fit on the device")
     ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 4 or 6)")
     ap.add_argument("--max-iters", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None, help="graphs per step over all ranks")
@@ -103,8 +112,22 @@ def main():
     batch_size = args.batch_size or cfg.train.batch_size
     lo, hi = dp.shard_range(batch_size, rank, world)     # equal-sized shards when world divides batch_size
 
+    store = None
+    if args.data == "packed":
+        from singa_amd import dataset as D
+        assert args.dataset, "--data packed needs --dataset DIR"
+        store = D.PackedDataset.load(args.dataset).to(dev, device_resident=not args.host_dataset)
+        log(f"packed dataset {args.dataset}: {store.G} graphs, {store.nbytes} bytes, "
+            f"{'host' if args.host_dataset else 'device'} resident; splits " +
+            ", ".join(f"{k} {len(v)}" for k, v in store.splits.items()))
+
     def make_batch(split, it):
-        """One batch of `batch_size` graphs; this rank materialises only its shard [lo, hi)."""
+        """One batch of `batch_size` graphs; this rank materialises only its shard [lo, hi).  `it` counts from 1 for the
+        packed dataset (dataset.batch_ids) and is the generator's batch number otherwise."""
+        if store is not None:
+            ids = D.batch_ids(store.splits[split], it, batch_size, cfg.train.seed, shuffle=not args.no_shuffle, rank=rank,
+                              world=world, train=split == "train")
+            return store.batch(ids)
         if args.data == "golden":
             # the three example graphs the reference bundles (example/*.pt), shipped with the package as plain arrays
             gs = [G.example_graph(i) for i in range(lo, hi)]
@@ -139,10 +162,23 @@ def main():
     early = EarlyStopping(patience=20, delta=0.00005)
 
     def evaluate(split, n_batches=2):
+        first = 0
+        if store is not None:
+            # the packed split in order: all of its batches (a last batch too short to give every rank a graph is left
+            # out), or --val-batches of them; a pack without this split has nothing to evaluate
+            n_graphs = len(store.splits.get(split, ()))
+            n_batches = D.n_batches(range(n_graphs), batch_size, train=False)
+            if n_batches and n_graphs - (n_batches - 1) * batch_size < world:
+                n_batches -= 1
+            if args.val_batches is not None:
+                n_batches = min(n_batches, args.val_batches)
+            if n_batches < 1:
+                return None
+            first = 1
         model.eval()
         tot = 0.0
         with torch.no_grad():
-            for b in range(n_batches):
+            for b in range(first, first + n_batches):
                 batch = make_batch(split, b)
                 model.prepare(batch)
                 logits = model(batch)
@@ -171,6 +207,9 @@ def main():
             f"LR {opt.param_groups[0]['lr']:.2e} | {time.perf_counter() - t0:.3f} s")
         if it % cfg.train.val_freq == 0 or it == max_iters:
             val = evaluate("val")
+            if val is None:
+                log(f"[Validate] Iter {it} | the dataset has no val split: scheduler and early stopping see the training loss")
+                val = loss_v
             sched.step(val)
             log(f"[Validate] Iter {it} | Loss {val:.6f}")
             if rank == 0:
@@ -179,7 +218,8 @@ def main():
             if early.step(val):
                 log("Early stopping")
                 break
-    log(f"[Test] Loss {evaluate('test'):.6f}")
+    test = evaluate("test")
+    log(f"[Test] Loss {test:.6f}" if test is not None else "[Test] the dataset has no test split")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
