@@ -127,7 +127,9 @@ class TrainStep:
     """bucket=True (graph mode): ragged batches - every real CrossDocked batch has its own atom and edge counts - are
     padded with inert atoms / edges (graph.pad_batch) to the capacities of a geometric size class (x `growth` per class),
     so that all batches of a class replay ONE capture; a few captures (`max_cached`, least recently used evicted) are
-    kept side by side.  Without it a batch whose shapes differ from the capture triggers a re-capture."""
+    kept side by side.  A class is per graph count: batches with the same totals but another number of graphs have
+    token / pointer tensors of another shape and get a capture of their own.  Without it a batch whose shapes differ
+    from the capture triggers a re-capture."""
 
     def __init__(self, model, optimizer, reducer=None, use_graph=True, max_grad_norm=float("inf"), bucket=False,
                  growth=1.08, max_cached=3, direct_grads=True):
@@ -235,7 +237,9 @@ class TrainStep:
                 self._knn_cap[(c, nt)] = -(-int(e * 1.04) // 1024) * 1024
         else:
             raise RuntimeError("TrainStep._stage: the kNN edge capacities of a size class did not settle in 3 attempts")
-        pb.extras["pad"]["sig"] = (c, self._mx[PA], self._mx[LA], self._knn_cap[(c, PA)], self._knn_cap[(c, LA)])
+        # the graph count is part of the signature: pointer, token and property tensors are [B(+1), ...], whatever the atom and
+        # edge totals (two graphs of 69 atoms and three of 46 fall into one size class)
+        pb.extras["pad"]["sig"] = (c, self._mx[PA], self._mx[LA], self._knn_cap[(c, PA)], self._knn_cap[(c, LA)], B)
         return pb
 
     # ------------------------------------------------------------------------------------------------ eager pieces

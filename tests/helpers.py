@@ -118,6 +118,47 @@ def grad_sample_errors(named_grads, z, tol):
     return bad
 
 
+def named_grads(model):
+    """{name: clone of .grad} of every parameter that has one, after a device synchronisation.  Clones: under a bucketed
+    TrainStep `.grad` lives in a capture's memory pool, and the next replay overwrites it."""
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    return {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
+
+
+def grad_mismatches(got, want, rel=2e-4):
+    """The per-parameter criterion of tests/test_padding_gpu.py on two {name: tensor} sets:
+    |got - want| <= rel * |want| + (rel / 2e-4) * 1e-7 * |all of want| (2-norms, formed in float64; the floor is for the
+    mathematically zero gradients of the dense attentions' key biases, which are rounding noise on both sides).  Both sides must
+    hold the same names.  Returns [(name, relative error)] of the parameters that break it."""
+    assert set(got) == set(want), sorted(set(got) ^ set(want))[:8]
+    total = float(torch.sqrt(sum((w.double() ** 2).sum() for w in want.values())))
+    bad = []
+    for n, w in want.items():
+        w = w.double()
+        d = float((got[n].double().to(w.device) - w).norm())
+        if not d <= rel * float(w.norm()) + (rel / 2e-4) * 1e-7 * total:
+            bad.append((n, d / (float(w.norm()) + 1e-300)))
+    return bad
+
+
+def bit_equal_report(got, want, label=None):
+    """(number of parameters whose tensors are torch.equal, number of parameters, largest |got - want| / |want| among the
+    rest that carry a gradient: norm above 1e-7 of the total) of two {name: tensor} sets with the same names; `label`:
+    prints the three."""
+    assert set(got) == set(want), sorted(set(got) ^ set(want))[:8]
+    total = float(torch.sqrt(sum((w.double() ** 2).sum() for w in want.values())))
+    same, worst = 0, 0.0
+    for n, w in want.items():
+        if torch.equal(got[n], w):
+            same += 1
+        elif float(w.double().norm()) > 1e-7 * total:
+            worst = max(worst, float((got[n].double() - w.double()).norm() / w.double().norm()))
+    if label is not None:
+        print(f"{label}: {same} of {len(want)} parameters bit-equal, largest relative difference {worst:.3e}")
+    return same, len(want), worst
+
+
 class pinned_relu_ties:
     """Context manager for the golden SINGA step: pins every PoswiseFeedForward ReLU gate whose pre-activation the REFERENCE
     saw within 1e-4 of its layer's scale from zero to the reference's recorded choice
@@ -162,6 +203,60 @@ class pinned_relu_ties:
         from singa_amd import ops
         ops._PosFFN.forward = staticmethod(self._orig)
         return False
+
+
+class relu_gate_log:
+    """Context manager: records the ReLU gates (saved activation > 0, [rows, 1024] bool) of every PoswiseFeedForward call, in
+    call order, in `.masks`.  capturing=True records only the calls made under HIP-graph capture: those masks are part of the
+    captured graph (one compare kernel per call, the step's own numbers are untouched), live in its memory pool and are
+    rewritten by every replay - `take()` copies the last pass's 18 out after a step."""
+
+    def __init__(self, capturing=False):
+        self.capturing, self.masks = capturing, []
+
+    def __enter__(self):
+        from singa_amd import ops
+        self._orig = ops._PosFFN.forward
+        orig = self._orig
+
+        def fwd(ctx, x, w1, b1, w2, b2):
+            y = orig(ctx, x, w1, b1, w2, b2)
+            if torch.cuda.is_current_stream_capturing() == self.capturing:
+                self.masks.append(ctx.to_save[3] > 0)
+            return y
+
+        ops._PosFFN.forward = staticmethod(fwd)
+        return self
+
+    def __exit__(self, *exc):
+        from singa_amd import ops
+        ops._PosFFN.forward = staticmethod(self._orig)
+        return False
+
+    def take(self, calls=18):
+        torch.cuda.synchronize()
+        assert len(self.masks) >= calls and len(self.masks) % calls == 0, len(self.masks)
+        return [m.clone() for m in self.masks[-calls:]]
+
+
+def relu_gate_flips(ref_masks, run_masks):
+    """The gates two runs of the SAME code on the same batch decided differently (`relu_gate_log` masks; the run's batch may
+    carry padding atoms behind the reference's rows), as `pinned_relu_ties(records=...)` takes them: pinned to the run's
+    choice.  Two such runs differ by rounding only, so a gate flips only where its pre-activation is within rounding of zero
+    - the tie of DESIGN section 2, "ReLU ties" - and ONE flipped gate moves its unit's row of conv1's gradient by a finite
+    amount whichever side is right."""
+    assert len(ref_masks) == len(run_masks)
+    layer, row, unit, on = [], [], [], []
+    for i, (e, r) in enumerate(zip(ref_masks, run_masks)):
+        assert r.shape[0] >= e.shape[0] and r.shape[1] == e.shape[1] == 1024
+        r = r[:e.shape[0]]
+        idx = (e != r).nonzero()
+        layer.append(torch.full((idx.shape[0],), i))
+        row.append(idx[:, 0].cpu())
+        unit.append(idx[:, 1].cpu())
+        on.append(r[idx[:, 0], idx[:, 1]].cpu())
+    return {"layer": torch.cat(layer), "row": torch.cat(row), "unit": torch.cat(unit), "on": torch.cat(on),
+            "rows": [int(e.shape[0]) for e in ref_masks]}
 
 
 class oracle_relu_ties:

@@ -188,7 +188,8 @@ def test_prefetched_steps_equal_plain_steps():
         return out
 
     a, b = run(False), run(True)
-    # not bit-equal even without prefetch: torch's index_add_ (atomics) orders its sums differently from run to run
+    # (the two sequences were bit-equal when measured, and so were two plain runs: no float atomics are left on the device
+    # path - tests/test_replay_parity_gpu.py asserts that for seeded replayed runs; the bound here is kept as it was)
     assert all(abs(x - y) < 2e-5 * abs(x) for x, y in zip(a, b)), (a, b)
 
 
