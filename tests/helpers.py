@@ -312,8 +312,9 @@ class oracle_pinned_relu_ties:
     """pinned_relu_ties for the CPU ORACLE (oracle.pos_ffn): the backward mask of the recorded near-zero gates follows the
     reference's run.  `.flipped` counts the gates where the oracle had decided the other way."""
 
-    def __init__(self, L):
-        z = golden(f"singa_L{L}_B3_relu_ties.npz")
+    def __init__(self, L=None, records=None):
+        """L: the golden's fixture; or records = relu_gate_flips(...) of two oracle runs (tests/symmetry.py)."""
+        z = golden(f"singa_L{L}_B3_relu_ties.npz") if records is None else records
         self.layer = torch.as_tensor(z["layer"]).long()
         self.flat = torch.as_tensor(z["row"]).long() * 1024 + torch.as_tensor(z["unit"]).long()
         self.on = torch.as_tensor(z["on"])
