@@ -365,10 +365,13 @@ class SO2EquivariantGraphAttention(nn.Module):
                  max_num_elements, edge_channels_list: list, use_atom_edge_embedding: bool = True,
                  use_m_share_rad: bool = False, activation: str = "scaled_silu", use_s2_act_attn: bool = False,
                  use_attn_renorm: bool = True, use_gate_act: bool = False, use_sep_s2_act: bool = True,
-                 alpha_drop: float = 0.0, device: str = "cuda"):
+                 alpha_drop: float = 0.0, device: str = "cuda", recompute: bool = False):
         super().__init__()
         assert not use_atom_edge_embedding and not use_m_share_rad and not use_s2_act_attn and use_attn_renorm
         assert not use_gate_act and use_sep_s2_act and alpha_drop == 0.0
+        if recompute and max(mmax_list) != 2:
+            raise ValueError(f"recompute=True: the attention block rebuilds its activation for mmax = 2 only, got mmax_list {mmax_list}")
+        self.recompute = recompute      # the S2 activation between the two SO(2) convolutions is rebuilt in backward, not held
         self.sphere_channels, self.hidden_channels, self.num_heads = sphere_channels, hidden_channels, num_heads
         self.attn_alpha_channels, self.attn_value_channels = attn_alpha_channels, attn_value_channels
         self.output_channels, self.lmax_list, self.mmax_list, self.device = output_channels, lmax_list, mmax_list, device
@@ -409,10 +412,17 @@ class SO2EquivariantGraphAttention(nn.Module):
         # separable S2 activation of the gated message (EF:1156-1160).  The softmax over each destination's edges follows
         # at once (it only needs the logits), so nothing streams between the conv2 GEMMs and the scatter kernel that
         # consumes their output: the per-m value tensors are then still largely resident in the Infinity Cache.
-        logits, act = ops.edge_head(h0, h1, h2, self.alpha_norm.weight, self.alpha_norm.bias, self.alpha_dot, heads, A, H,
-                                    L, M, self.alpha_norm.eps)
-        alpha = ops.segment_softmax(logits, es.row_ptr, 1e-16)
-        y0, y1, y2 = self.so2_conv_2(act)
+        if self.recompute:
+            c2 = self.so2_conv_2
+            logits, y0, y1, y2 = ops.edge_head_conv_recompute(
+                h0, h1, h2, self.alpha_norm.weight, self.alpha_norm.bias, self.alpha_dot, c2.fc_m0.weight, c2.fc_m0.bias,
+                c2.so2_m_conv[0].fc.weight, c2.so2_m_conv[1].fc.weight, heads, A, H, L, M, self.alpha_norm.eps)
+            alpha = ops.segment_softmax(logits, es.row_ptr, 1e-16)
+        else:
+            logits, act = ops.edge_head(h0, h1, h2, self.alpha_norm.weight, self.alpha_norm.bias, self.alpha_dot, heads, A, H,
+                                        L, M, self.alpha_norm.eps)
+            alpha = ops.segment_softmax(logits, es.row_ptr, 1e-16)
+            y0, y1, y2 = self.so2_conv_2(act)
         # k10: alpha * value, rotate back, sum over incoming edges
         agg = ops.rotate_back_scatter(y0, y1, y2, alpha, wr, es, heads, L, M)
         out = self.proj.apply_tensor(agg, residual)
@@ -425,9 +435,15 @@ class FeedForwardNetwork(nn.Module):
 
     def __init__(self, sphere_channels: int, hidden_channels: int, output_channels: int, lmax_list: list,
                  mmax_list: list, SO3_grid, activation: str = "scaled_silu", use_gate_act: bool = False,
-                 use_grid_mlp: bool = False, use_sep_s2_act: bool = True, device: str = "cuda") -> None:
+                 use_grid_mlp: bool = False, use_sep_s2_act: bool = True, device: str = "cuda",
+                 recompute: bool = False) -> None:
         super().__init__()
         assert not use_gate_act and not use_grid_mlp and use_sep_s2_act
+        if recompute and not (ops.USE_SKINNY_SO3 and (sphere_channels, hidden_channels, output_channels) == (16, 512, 16)):
+            raise ValueError("recompute=True: the feed-forward block is rebuilt by the 16 -> 512 -> 16 kernels only "
+                             f"(ops.USE_SKINNY_SO3, sphere_channels 16), got ffn_hidden_channels = {hidden_channels}, "
+                             f"sphere_channels = {sphere_channels}, output {output_channels}")
+        self.recompute = recompute      # neither [N, K, 512] tensor of the block is held for backward (ops._FFNRecompute)
         self.device, self.lmax_list, self.max_lmax = device, lmax_list, max(lmax_list)
         self.sphere_channels, self.hidden_channels, self.output_channels = sphere_channels, hidden_channels, output_channels
         self.so3_linear_1 = SO3_LinearV2(sphere_channels, hidden_channels, lmax=self.max_lmax, device=device)
@@ -437,6 +453,10 @@ class FeedForwardNetwork(nn.Module):
     def forward(self, input_embedding: SO3_Embedding, residual: Optional[Tensor] = None) -> SO3_Embedding:
         x = input_embedding.embedding
         gate = self.gating_linear(x[:, 0])
+        if self.recompute:
+            l1, l2 = self.so3_linear_1, self.so3_linear_2
+            out = ops.ffn_recompute(x, gate, l1.weight, l1.bias, l2.weight, l2.bias, self.max_lmax, residual)
+            return SO3_Embedding(0, input_embedding.lmax_list.copy(), self.output_channels, out.dtype, self.device, out)
         h = self.so3_linear_1.apply_tensor(x)
         if ops.USE_SKINNY_SO3 and self.hidden_channels == 512 and self.output_channels == 16:
             # activation + second linear (+ x_res of EF:1405-1406) as one autograd node: its backward forms the activation's
@@ -460,7 +480,7 @@ class TransBlockV2(nn.Module):
                  use_gate_act: bool = False, use_grid_mlp: bool = False, use_sep_s2_act: bool = True,
                  attn_activation: str = "silu", use_s2_act_attn: bool = False, use_attn_renorm: bool = True,
                  ffn_activation: str = "silu", norm_type: str = "rms_norm_sh", alpha_drop: float = 0.0,
-                 drop_path_rate: float = 0.0, proj_drop: float = 0.0, device: str = "cuda"):
+                 drop_path_rate: float = 0.0, proj_drop: float = 0.0, device: str = "cuda", recompute: bool = False):
         super().__init__()
         assert drop_path_rate == 0.0 and proj_drop == 0.0 and sphere_channels == output_channels
         self.device = device
@@ -475,11 +495,12 @@ class TransBlockV2(nn.Module):
             edge_channels_list=edge_channels_list, use_atom_edge_embedding=use_atom_edge_embedding,
             use_m_share_rad=use_m_share_rad, activation=attn_activation, use_s2_act_attn=use_s2_act_attn,
             use_attn_renorm=use_attn_renorm, use_gate_act=use_gate_act, use_sep_s2_act=use_sep_s2_act,
-            alpha_drop=alpha_drop, device=device)
+            alpha_drop=alpha_drop, device=device, recompute=recompute)
         self.ffn = FeedForwardNetwork(sphere_channels=sphere_channels, hidden_channels=ffn_hidden_channels,
                                       output_channels=output_channels, lmax_list=lmax_list, mmax_list=mmax_list,
                                       SO3_grid=SO3_grid, activation=ffn_activation, use_gate_act=use_gate_act,
-                                      use_grid_mlp=use_grid_mlp, use_sep_s2_act=use_sep_s2_act, device=device)
+                                      use_grid_mlp=use_grid_mlp, use_sep_s2_act=use_sep_s2_act, device=device,
+                                      recompute=recompute)
 
     def renorm_only(self, x: Dict, source_target: Tuple[str, str]) -> None:
         """The only effect of a hetero call whose return value the caller discards (EMB:415-428 keeps just the last

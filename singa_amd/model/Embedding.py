@@ -29,9 +29,13 @@ def barcode(x: torch.Tensor) -> torch.Tensor:
 
 
 class EquivariantEmbedding(nn.Module):
-    def __init__(self, config, device: str = "cuda") -> None:
+    def __init__(self, config, device: str = "cuda", recompute: bool = False) -> None:
+        """recompute: the blocks rebuild their largest saved activations in the backward pass (both [N, K, 512] tensors of every
+        feed-forward block, the [E, KR*128] S2 activation of every attention block) instead of holding them: less memory, a
+        little more time, the same parameters and state_dict."""
         super().__init__()
         self.device = device
+        self.recompute = bool(recompute)
         self.edge_channels = config.edge_channels
         self.sphere_channels = config.sphere_channels
         self.attn_hidden_channels = config.attn_hidden_channels
@@ -89,7 +93,7 @@ class EquivariantEmbedding(nn.Module):
                 use_atom_edge_embedding=self.block_use_atom_edge_embedding, norm_type=self.norm_type,
                 use_m_share_rad=False, use_s2_act_attn=False, use_attn_renorm=True, use_gate_act=False,
                 use_grid_mlp=False, use_sep_s2_act=True, alpha_drop=0.0, proj_drop=0.0, drop_path_rate=0.0,
-                device=device))
+                device=device, recompute=self.recompute))
         self.norm = get_normalization_layer(self.norm_type, lmax=max(self.lmax_list), num_channels=self.sphere_channels,
                                             device=device)
 

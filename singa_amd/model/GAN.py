@@ -20,11 +20,13 @@ def lap_pe(data, node_type: str):
 
 
 class SINGA(nn.Module):
-    def __init__(self, config, device="cuda"):
+    def __init__(self, config, device="cuda", recompute=False):
+        """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
+        depends on it, so checkpoints move freely between the two modes."""
         super().__init__()
         self.device = device
         self.config = config
-        self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device)
+        self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device, recompute=recompute)
         self.model = Transformer(config=self.config.model, protein_atom_feature_dim=self.config.model.featurizer_feat_dim,
                                  num_props=self.config.train.num_props, device=self.device)
 

@@ -484,56 +484,78 @@ class _EdgeHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, heads, A, C, L, M, eps):
         ctx.params = (ln_w, ln_b, dot)
-        h0, h1, h2 = _rows(h0), _rows(h1), _rows(h2)
-        ln_w, ln_b, dot = ln_w.contiguous(), ln_b.contiguous(), dot.contiguous()
-        _dev(h0, h1, h2, ln_w, ln_b, dot)
-        lay = so3.layout(L, M)
-        lib = _lib.lib()
-        E = h0.shape[0]
-        gate_off, x_off = heads * A, heads * A + C
-        logits = torch.empty(E, heads, device=h0.device, dtype=torch.float32)
-        _chk(lib.singa_alpha_logits_fwd(_p(h0), h0.stride(0), _p(ln_w), _p(ln_b), _p(dot), _p(logits), E, heads, A, eps,
-                                        _stream()), "singa_alpha_logits_fwd")
-        P, Q, Az = _grid_factors(L, M, True, h0.device)
-        act = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
-        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
-        _chk(lib.singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
-                                     _p(Az), _p(act), E, C, L, _stream()), "singa_s2act_sep_fwd")
-        ctx.save_for_backward(h0, h1, h2, ln_w, ln_b, dot)
         ctx.cfg = (heads, A, C, L, M, eps)
+        saved, logits, act = _edge_head_fwd(h0, h1, h2, ln_w, ln_b, dot, ctx.cfg)
+        ctx.save_for_backward(*saved)
         return logits, act
 
     @staticmethod
     def backward(ctx, g_logits, g_act):
-        h0, h1, h2, ln_w, ln_b, dot = ctx.saved_tensors
-        heads, A, C, L, M, eps = ctx.cfg
-        lay = so3.layout(L, M)
-        lib = _lib.lib()
-        E = h0.shape[0]
-        gate_off, x_off = heads * A, heads * A + C
-        g_logits, g_act = g_logits.contiguous(), g_act.contiguous()
-        # the gradients of the convolution's three outputs are assembled in place: h0's is [alpha inputs | gate | m = 0 rows],
-        # written by two kernels into column blocks of one buffer (the concatenation they replaced cost 0.6 ms per step)
-        n0, n1, n2 = (r * C for r in lay.seg_rows)
-        g_h0 = torch.empty(E, x_off + n0, device=h0.device, dtype=torch.float32)
-        g_h1 = torch.empty(E, n1, device=h0.device, dtype=torch.float32)
-        g_h2 = torch.empty(E, n2, device=h0.device, dtype=torch.float32)
-        nslots = lib.singa_alpha_logits_nslots(E)
-        part = torch.empty(nslots, (2 + heads) * A, device=h0.device, dtype=torch.float32)
+        return _edge_head_bwd(ctx.saved_tensors, ctx.cfg, ctx.params, g_logits, g_act) + (None,) * 6
+
+
+def _edge_act(h0, h1, h2, cfg):
+    """The activation launch of the edge head: the separable S2 activation of [gate | m = 0 rows] of h0, h1, h2 -> [E, KR*C]."""
+    heads, A, C, L, M, _ = cfg
+    lay = so3.layout(L, M)
+    E = h0.shape[0]
+    gate_off, x_off = heads * A, heads * A + C
+    P, Q, Az = _grid_factors(L, M, True, h0.device)
+    act = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
+    seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+    if E > 0:                                     # (an empty edge set has no address to hand over)
+        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
+                                            _p(Az), _p(act), E, C, L, _stream()), "singa_s2act_sep_fwd")
+    return act
+
+
+def _edge_head_fwd(h0, h1, h2, ln_w, ln_b, dot, cfg):
+    """The forward launches of _EdgeHead -> (the six tensors its backward needs, logits, act)."""
+    heads, A, C, L, M, eps = cfg
+    h0, h1, h2 = _rows(h0), _rows(h1), _rows(h2)
+    ln_w, ln_b, dot = ln_w.contiguous(), ln_b.contiguous(), dot.contiguous()
+    _dev(h0, h1, h2, ln_w, ln_b, dot)
+    E = h0.shape[0]
+    logits = torch.empty(E, heads, device=h0.device, dtype=torch.float32)
+    if E > 0:
+        _chk(_lib.lib().singa_alpha_logits_fwd(_p(h0), h0.stride(0), _p(ln_w), _p(ln_b), _p(dot), _p(logits), E, heads, A, eps,
+                                               _stream()), "singa_alpha_logits_fwd")
+    return (h0, h1, h2, ln_w, ln_b, dot), logits, _edge_act(h0, h1, h2, cfg)
+
+
+def _edge_head_bwd(saved, cfg, params, g_logits, g_act):
+    """The backward launches of _EdgeHead -> the gradients of (h0, h1, h2, ln_w, ln_b, dot); params: the three parameters as
+    the caller was given them (the targets of direct accumulation, _GradSink)."""
+    h0, h1, h2, ln_w, ln_b, dot = saved
+    heads, A, C, L, M, eps = cfg
+    lay = so3.layout(L, M)
+    lib = _lib.lib()
+    E = h0.shape[0]
+    gate_off, x_off = heads * A, heads * A + C
+    g_logits, g_act = g_logits.contiguous(), g_act.contiguous()
+    # the gradients of the convolution's three outputs are assembled in place: h0's is [alpha inputs | gate | m = 0 rows],
+    # written by two kernels into column blocks of one buffer (the concatenation they replaced cost 0.6 ms per step)
+    n0, n1, n2 = (r * C for r in lay.seg_rows)
+    g_h0 = torch.empty(E, x_off + n0, device=h0.device, dtype=torch.float32)
+    g_h1 = torch.empty(E, n1, device=h0.device, dtype=torch.float32)
+    g_h2 = torch.empty(E, n2, device=h0.device, dtype=torch.float32)
+    nslots = lib.singa_alpha_logits_nslots(E)
+    part = (torch.empty if E > 0 else torch.zeros)(nslots, (2 + heads) * A, device=h0.device, dtype=torch.float32)
+    if E > 0:
         _chk(lib.singa_alpha_logits_bwd_ld(_p(h0), h0.stride(0), _p(ln_w), _p(ln_b), _p(dot), _p(g_logits), _p(g_h0),
                                            g_h0.stride(0), _p(part), E, heads, A, eps, _stream()), "singa_alpha_logits_bwd_ld")
-        pw, pb, pd = ctx.params
-        g_lnw, g_lnb, g_dot = param_colsum(part, [(0, A, pw), (A, A, pb), (2 * A, heads * A, pd)])
-        if g_dot is not None:
-            g_dot = g_dot.view(heads, A)
-        P, Q, Az = _grid_factors(L, M, True, h0.device)
-        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
-        gseg, _ = _segs3((g_h0[:, x_off:], g_h1, g_h2), lay.seg_rows, C)
-        if E > 0:
-            _chk(lib.singa_s2act_sep_bwd_seg(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
-                                             _p(Az), _p(g_act), gseg, _p(g_h0[:, gate_off:]),
-                                             g_h0.stride(0), E, C, L, _stream()), "singa_s2act_sep_bwd_seg")
-        return (g_h0, g_h1, g_h2, g_lnw, g_lnb, g_dot, None, None, None, None, None, None)
+    pw, pb, pd = params
+    g_lnw, g_lnb, g_dot = param_colsum(part, [(0, A, pw), (A, A, pb), (2 * A, heads * A, pd)])
+    if g_dot is not None:
+        g_dot = g_dot.view(heads, A)
+    P, Q, Az = _grid_factors(L, M, True, h0.device)
+    seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
+    gseg, _ = _segs3((g_h0[:, x_off:], g_h1, g_h2), lay.seg_rows, C)
+    if E > 0:
+        _chk(lib.singa_s2act_sep_bwd_seg(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
+                                         _p(Az), _p(g_act), gseg, _p(g_h0[:, gate_off:]),
+                                         g_h0.stride(0), E, C, L, _stream()), "singa_s2act_sep_bwd_seg")
+    return (g_h0, g_h1, g_h2, g_lnw, g_lnb, g_dot)
 
 
 def edge_head(h0, h1, h2, ln_w, ln_b, alpha_dot, heads, A, C, L, M=2, eps=1e-5):
@@ -1814,50 +1836,62 @@ class _SO2Conv3M(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, w0, b0, w1, w2, n0, n1):
         ctx.params = (w0, w1, w2, b0)
-        X = _rows(X)
-        ws = [_rows(w0), w1.contiguous(), w2.contiguous()]
-        b0 = b0.contiguous()
-        _dev(X, *ws, b0)
-        E, nin = X.shape
-        ins = (n0, n1, nin - n0 - n1)
-        outs = tuple(w.shape[0] for w in ws)
-        assert ws[0].shape[1] == n0 and all(2 * w.shape[1] == k and w.shape[0] % 2 == 0 for w, k in zip(ws[1:], ins[1:]))
-        H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
-        xs, hs = X.split(ins, 1), H.split(outs, 1)
-        if E > 0:
-            _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True)
-            # A = [x_+ | x_-], B = fc.weight [Wr; Wi], C = [out_r | out_i]
-            _cgemm([_cprob(x.chunk(2, 1), w.chunk(2, 0), h.chunk(2, 1), True, True, 1.0)
-                    for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True)
+        X, ws, ctx.ins, hs = _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1)
         ctx.save_for_backward(X, *ws)
-        ctx.ins = ins
         return hs
 
     @staticmethod
     def backward(ctx, g0, g1, g2):
         X, *ws = ctx.saved_tensors
-        ins, outs = ctx.ins, tuple(w.shape[0] for w in ws)
-        E = X.shape[0]
-        gs = [_rows(g) for g in (g0, g1, g2)]
-        xs = X.split(ins, 1)
-        # weight gradients: reductions over the edges, split over workgroups into dense partial slabs (the fc weights' layouts).
-        # The two launches have few tiles each (conv1: 16 and 14): each gets the split count that fills the CUs.  They are
-        # issued in front of the input-gradient launches: nothing in the backward pass waits for them
-        S0 = _splits_few(E, -(-outs[0] // 128) * -(-ins[0] // 128))
-        Sc = _splits_few(E, sum(-(-(o // 2) // 128) * -(-(k // 2) // 64) for o, k in zip(outs[1:], ins[1:])))
-        pw0, pw1, pw2, pb0 = ctx.params
-        (gw0,), (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0)], S0)
-        (gw1, gw2), _ = _dw_grads([(gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], Sc, cplx=True)
-        gX = None
-        if ctx.needs_input_grad[0]:
-            gX = torch.empty_like(X)
-            if E > 0:
-                gxs = gX.split(ins, 1)
-                _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False)
-                # A = [g_r | g_i], B = fc.weight [Wr; Wi] as [r = n][j = k], C = [dx_+ | dx_-]
-                _cgemm([_cprob(g.chunk(2, 1), w.chunk(2, 0), gx.chunk(2, 1), True, False, -1.0)
-                        for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False)
+        gX, gw0, gb, gw1, gw2 = _so2_conv3m_bwd(X, ws, ctx.ins, ctx.params, (g0, g1, g2), ctx.needs_input_grad[0])
         return gX, gw0, gb, gw1, gw2, None, None
+
+
+def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1):
+    """The forward launches of _SO2Conv3M -> (X and the three weights as the launches read them, the input widths, the outputs)."""
+    X = _rows(X)
+    ws = [_rows(w0), w1.contiguous(), w2.contiguous()]
+    b0 = b0.contiguous()
+    _dev(X, *ws, b0)
+    E, nin = X.shape
+    ins = (n0, n1, nin - n0 - n1)
+    outs = tuple(w.shape[0] for w in ws)
+    assert ws[0].shape[1] == n0 and all(2 * w.shape[1] == k and w.shape[0] % 2 == 0 for w, k in zip(ws[1:], ins[1:]))
+    H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
+    xs, hs = X.split(ins, 1), H.split(outs, 1)
+    if E > 0:
+        _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True)
+        # A = [x_+ | x_-], B = fc.weight [Wr; Wi], C = [out_r | out_i]
+        _cgemm([_cprob(x.chunk(2, 1), w.chunk(2, 0), h.chunk(2, 1), True, True, 1.0)
+                for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True)
+    return X, ws, ins, hs
+
+
+def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx):
+    """The backward launches of _SO2Conv3M -> the gradients of (X, w0, b0, w1, w2); params = (w0, w1, w2, b0) as the caller was
+    given them (the targets of direct accumulation, _GradSink)."""
+    outs = tuple(w.shape[0] for w in ws)
+    E = X.shape[0]
+    gs = [_rows(g) for g in gs]
+    xs = X.split(ins, 1)
+    # weight gradients: reductions over the edges, split over workgroups into dense partial slabs (the fc weights' layouts).
+    # The two launches have few tiles each (conv1: 16 and 14): each gets the split count that fills the CUs.  They are
+    # issued in front of the input-gradient launches: nothing in the backward pass waits for them
+    S0 = _splits_few(E, -(-outs[0] // 128) * -(-ins[0] // 128))
+    Sc = _splits_few(E, sum(-(-(o // 2) // 128) * -(-(k // 2) // 64) for o, k in zip(outs[1:], ins[1:])))
+    pw0, pw1, pw2, pb0 = params
+    (gw0,), (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0)], S0)
+    (gw1, gw2), _ = _dw_grads([(gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], Sc, cplx=True)
+    gX = None
+    if need_gx:
+        gX = torch.empty_like(X)
+        if E > 0:
+            gxs = gX.split(ins, 1)
+            _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False)
+            # A = [g_r | g_i], B = fc.weight [Wr; Wi] as [r = n][j = k], C = [dx_+ | dx_-]
+            _cgemm([_cprob(g.chunk(2, 1), w.chunk(2, 0), gx.chunk(2, 1), True, False, -1.0)
+                    for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False)
+    return gX, gw0, gb, gw1, gw2
 
 
 def so2_conv3m(X, w0, b0, w1, w2, n0, n1):
@@ -1907,8 +1941,9 @@ class _SO3Linear(torch.autograd.Function):
             assert addend.shape == out.shape and not (USE_SKINNY_SO3 and cin == 16 and cout == 512)
         if USE_SKINNY_SO3 and cin == 16 and cout == 512:
             # k11s: a 16-long contraction - VALU kernel, thread = output channel, whole 2 KB rows per store
-            _chk(_lib.lib().singa_so3_skinny_expand(_p(x), _p(weight), cout * cin, cin, 1, _p(bias), _p(out), N, cout, L,
-                                                    _stream()), "singa_so3_skinny_expand")
+            if N > 0:                             # (an empty node set has no address to hand over)
+                _chk(_lib.lib().singa_so3_skinny_expand(_p(x), _p(weight), cout * cin, cin, 1, _p(bias), _p(out), N, cout, L,
+                                                        _stream()), "singa_so3_skinny_expand")
         elif N > 0:
             _gemm(_so3_linear_probs(x, weight, out, L, True, bias, addend), True, True)
         ctx.save_for_backward(x, weight)
@@ -1918,43 +1953,49 @@ class _SO3Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        L = ctx.L
         g = g.contiguous()
-        N, K, cin = x.shape
-        cout = weight.shape[1]
-        lib = _lib.lib()
-        # (wide, 16) pairs the VALU kernels are built for: the feed-forward block's 512 and the output projection's 112
-        skinny = USE_SKINNY_SO3 and N > 0 and ((cin == 16 and cout == 512) or (cin in (512, 112) and cout == 16))
-        wide = max(cin, cout)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            if skinny and cout == 16:
-                # k11s: d x = g expanded through weight[l][u][c] - again a 16-long contraction
-                _chk(lib.singa_so3_skinny_expand(_p(g), _p(weight), cout * cin, 1, cin, None, _p(gx), N, wide, L, _stream()),
-                     "singa_so3_skinny_expand(dx)")
-            elif N > 0:
-                _gemm(_so3_linear_probs(g, weight, gx, L, False), True, False)
-        if skinny:
-            # k11s: the weight gradient as a VALU reduction over whole 2 KB rows of the 512-channel tensor (16 -> 512:
-            # small = x, big = g, rows [l][c][u] + the bias gradient; 512 -> 16: small = g, big = x, rows [l][u][c])
-            wide_out = cout == wide
-            wsz = (L + 1) * 16 * wide
-            part = torch.empty(lib.singa_so3_skinny_nparts(N, L, wide), wsz + (wide if wide_out else 0), device=x.device,
-                               dtype=torch.float32)
-            small, big = (x, g) if wide_out else (g, x)
-            _chk(lib.singa_so3_skinny_reduce(_p(small), _p(big), _p(part), N, wide, L, int(wide_out), int(wide_out), _stream()),
-                 "singa_so3_skinny_reduce")
-            if wide_out:
-                gw, gb = param_colsum(part, [(0, wsz, ctx.params[0]), (wsz, wide, ctx.params[1])])
-            else:
-                gw = param_colsum(part, [(0, wsz, ctx.params[0])])[0]
-                gb = param_colsum(g[:, 0, :], [(0, cout, ctx.params[1])])[0]
-            return gx, (gw.view(L + 1, cout, cin) if gw is not None else None), gb, None, (g if ctx.has_addend else None)
-        # dW_l = sum over the (node, row) pairs of degree l of g_row^T x_row
-        (gw,), _ = _dw_grads([(gl, xl, ctx.params[0], None) for gl, xl in zip(_degrees(g, L), _degrees(x, L))],
-                             _splits_for(N * (2 * L + 1)))
-        return gx, gw, param_colsum(g[:, 0, :], [(0, cout, ctx.params[1])])[0], None, (g if ctx.has_addend else None)
+        gx, gw, gb = _so3_linear_bwd(x, weight, ctx.L, ctx.params, g, ctx.needs_input_grad[0])
+        return gx, gw, gb, None, (g if ctx.has_addend else None)
+
+
+def _so3_linear_bwd(x, weight, L, params, g, need_gx):
+    """The backward launches of _SO3Linear for the (contiguous) output gradient g -> the gradients of (x, weight, bias); params =
+    (weight, bias) as the caller was given them (the targets of direct accumulation, _GradSink)."""
+    N, K, cin = x.shape
+    cout = weight.shape[1]
+    lib = _lib.lib()
+    # (wide, 16) pairs the VALU kernels are built for: the feed-forward block's 512 and the output projection's 112
+    skinny = USE_SKINNY_SO3 and N > 0 and ((cin == 16 and cout == 512) or (cin in (512, 112) and cout == 16))
+    wide = max(cin, cout)
+    gx = None
+    if need_gx:
+        gx = torch.empty_like(x)
+        if skinny and cout == 16:
+            # k11s: d x = g expanded through weight[l][u][c] - again a 16-long contraction
+            _chk(lib.singa_so3_skinny_expand(_p(g), _p(weight), cout * cin, 1, cin, None, _p(gx), N, wide, L, _stream()),
+                 "singa_so3_skinny_expand(dx)")
+        elif N > 0:
+            _gemm(_so3_linear_probs(g, weight, gx, L, False), True, False)
+    if skinny:
+        # k11s: the weight gradient as a VALU reduction over whole 2 KB rows of the 512-channel tensor (16 -> 512:
+        # small = x, big = g, rows [l][c][u] + the bias gradient; 512 -> 16: small = g, big = x, rows [l][u][c])
+        wide_out = cout == wide
+        wsz = (L + 1) * 16 * wide
+        part = torch.empty(lib.singa_so3_skinny_nparts(N, L, wide), wsz + (wide if wide_out else 0), device=x.device,
+                           dtype=torch.float32)
+        small, big = (x, g) if wide_out else (g, x)
+        _chk(lib.singa_so3_skinny_reduce(_p(small), _p(big), _p(part), N, wide, L, int(wide_out), int(wide_out), _stream()),
+             "singa_so3_skinny_reduce")
+        if wide_out:
+            gw, gb = param_colsum(part, [(0, wsz, params[0]), (wsz, wide, params[1])])
+        else:
+            gw = param_colsum(part, [(0, wsz, params[0])])[0]
+            gb = param_colsum(g[:, 0, :], [(0, cout, params[1])])[0]
+        return gx, (gw.view(L + 1, cout, cin) if gw is not None else None), gb
+    # dW_l = sum over the (node, row) pairs of degree l of g_row^T x_row
+    (gw,), _ = _dw_grads([(gl, xl, params[0], None) for gl, xl in zip(_degrees(g, L), _degrees(x, L))],
+                         _splits_for(N * (2 * L + 1)))
+    return gx, gw, param_colsum(g[:, 0, :], [(0, cout, params[1])])[0]
 
 
 def so3_linear(x, weight, bias, L, addend=None):
@@ -1980,8 +2021,9 @@ class _FFNTail(torch.autograd.Function):
         P, Q, A = _grid_factors(L, L, False, h.device)
         a = torch.empty_like(h)
         seg, n = _capi.segs([(h.data_ptr(), K * cin, K)])
-        _chk(lib.singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(a), N, cin, L, _stream()),
-             "singa_s2act_sep_fwd(node)")
+        if N > 0:                                 # (an empty node set has no address to hand over)
+            _chk(lib.singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(a), N, cin, L, _stream()),
+                 "singa_s2act_sep_fwd(node)")
         out = torch.empty(N, K, cout, device=h.device, dtype=torch.float32)
         ctx.has_addend = addend is not None
         if addend is not None:
@@ -1997,32 +2039,137 @@ class _FFNTail(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         h, gate, a, weight = ctx.saved_tensors
-        L = ctx.L
         g = g.contiguous()
-        N, K, cin = h.shape
-        cout = weight.shape[1]
-        lib = _lib.lib()
-        P, Q, _ = _grid_factors(L, L, False, h.device)
-        gh, gg = torch.empty_like(h), torch.empty_like(gate)
-        if N > 0:
-            _chk(lib.singa_s2act_ffn_bwd(_p(h), _p(gate), gate.stride(0), _p(P), _p(Q), _p(g), _p(weight), _p(gh), _p(gg), N, cin, L,
-                                         _stream()), "singa_s2act_ffn_bwd")
-        # the linear's weight gradient: rows [l][u][c] summed over the nodes (k11s reduce: small = g, big = a)
-        wsz = (L + 1) * 16 * cin
-        gw = None
-        if N > 0:
-            part = torch.empty(lib.singa_so3_skinny_nparts(N, L, cin), wsz, device=h.device, dtype=torch.float32)
-            _chk(lib.singa_so3_skinny_reduce(_p(g), _p(a), _p(part), N, cin, L, 0, 0, _stream()), "singa_so3_skinny_reduce")
-            gw = param_colsum(part, [(0, wsz, ctx.params[0])])[0]
-        else:
-            gw = torch.zeros(wsz, device=h.device, dtype=torch.float32)
-        gb = param_colsum(g[:, 0, :], [(0, cout, ctx.params[1])])[0]
-        return gh, gg, (gw.view(L + 1, cout, cin) if gw is not None else None), gb, None, (g if ctx.has_addend else None)
+        gh, gg, gw, gb = _ffn_tail_bwd(h, gate, a, weight, ctx.L, ctx.params, g)
+        return gh, gg, gw, gb, None, (g if ctx.has_addend else None)
+
+
+def _ffn_tail_bwd(h, gate, a, weight, L, params, g):
+    """The backward launches of _FFNTail for the (contiguous) output gradient g -> the gradients of (h, gate, weight, bias);
+    params = (weight, bias) as the caller was given them (the targets of direct accumulation, _GradSink)."""
+    N, K, cin = h.shape
+    cout = weight.shape[1]
+    lib = _lib.lib()
+    P, Q, _ = _grid_factors(L, L, False, h.device)
+    gh, gg = torch.empty_like(h), torch.empty_like(gate)
+    if N > 0:
+        _chk(lib.singa_s2act_ffn_bwd(_p(h), _p(gate), gate.stride(0), _p(P), _p(Q), _p(g), _p(weight), _p(gh), _p(gg), N, cin, L,
+                                     _stream()), "singa_s2act_ffn_bwd")
+    # the linear's weight gradient: rows [l][u][c] summed over the nodes (k11s reduce: small = g, big = a)
+    wsz = (L + 1) * 16 * cin
+    gw = None
+    if N > 0:
+        part = torch.empty(lib.singa_so3_skinny_nparts(N, L, cin), wsz, device=h.device, dtype=torch.float32)
+        _chk(lib.singa_so3_skinny_reduce(_p(g), _p(a), _p(part), N, cin, L, 0, 0, _stream()), "singa_so3_skinny_reduce")
+        gw = param_colsum(part, [(0, wsz, params[0])])[0]
+    else:
+        gw = torch.zeros(wsz, device=h.device, dtype=torch.float32)
+    gb = param_colsum(g[:, 0, :], [(0, cout, params[1])])[0]
+    return gh, gg, (gw.view(L + 1, cout, cin) if gw is not None else None), gb
 
 
 def ffn_tail(h, gate, weight, bias, L, addend=None):
     """SO3_LinearV2(512 -> 16)(SeparableS2Activation(h, gate)) (+ addend) - see _FFNTail."""
     return _FFNTail.apply(h, gate, weight, bias, L, addend)
+
+
+# ---------------------------------------------------------------------------------------------- activation recomputation
+# `SINGA(..., recompute=True)`: the two places of the embedding where a step holds large activations for its backward pass that
+# are cheap functions of tensors it holds anyway.  Both nodes run the launches of the nodes they stand for, in their order, on
+# the same inputs (so their results are bit-identical to the default path's); what they do not save they rebuild at the start
+# of their backward pass.
+def _ffn_front(x, w1, b1, gate, L):
+    """(h, a) of the feed-forward block's front, h = SO3_LinearV2(16 -> 512)(x), a = SeparableS2Activation(h, gate): the k11s
+    expand launch of _SO3Linear.forward and the activation launch of _FFNTail.forward, into fresh tensors.  (One fused launch
+    that never writes h was built and measured for this place and lost to these two: profiles/recompute/README.md.)"""
+    N, K, cin = x.shape
+    C = w1.shape[1]
+    lib = _lib.lib()
+    h = torch.empty(N, K, C, device=x.device, dtype=torch.float32)
+    a = torch.empty_like(h)
+    if N > 0:
+        _chk(lib.singa_so3_skinny_expand(_p(x), _p(w1), C * cin, cin, 1, _p(b1), _p(h), N, C, L, _stream()),
+             "singa_so3_skinny_expand")
+        P, Q, A = _grid_factors(L, L, False, x.device)
+        seg, n = _capi.segs([(h.data_ptr(), K * C, K)])
+        _chk(lib.singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(a), N, C, L, _stream()),
+             "singa_s2act_sep_fwd(node)")
+    return h, a
+
+
+class _FFNRecompute(torch.autograd.Function):
+    """The feed-forward block SO3_LinearV2(16 -> 512) -> SeparableS2Activation -> SO3_LinearV2(512 -> 16) (+ residual) as one
+    autograd node that holds neither of its [N, K, 512] tensors: forward = the launches of _SO3Linear.forward and
+    _FFNTail.forward (h and a are dropped on return); backward = the first two of them again (_ffn_front), then the launches of
+    _FFNTail.backward and of _SO3Linear.backward.  The same kernels on the same inputs in the same order as so3_linear ->
+    ffn_tail: bit-identical results."""
+
+    @staticmethod
+    def forward(ctx, x, gate, w1, b1, w2, b2, L, addend=None):
+        ctx.params = (w1, b1, w2, b2)
+        x, gate, w1, b1, w2, b2 = (t.contiguous() for t in (x, gate, w1, b1, w2, b2))
+        _dev(x, gate, w1, b1, w2, b2)
+        if not USE_SKINNY_SO3 or tuple(w1.shape[1:]) != (512, 16) or tuple(w2.shape[1:]) != (16, 512) or x.shape[2] != 16:
+            raise RuntimeError("ffn_recompute: built for the skinny 16 -> 512 -> 16 feed-forward block (ffn_hidden_channels = 512)")
+        h, a = _ffn_front(x, w1, b1, gate, L)
+        del h
+        out = torch.empty(x.shape[0], x.shape[1], 16, device=x.device, dtype=torch.float32)
+        ctx.has_addend = addend is not None
+        if addend is not None:
+            addend = addend.contiguous()
+            _dev(addend)
+            assert addend.shape == out.shape
+        if x.shape[0] > 0:
+            _gemm(_so3_linear_probs(a, w2, out, L, True, b2, addend), True, True)
+        ctx.save_for_backward(x, gate, w1, b1, w2)
+        ctx.L = L
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gate, w1, b1, w2 = ctx.saved_tensors
+        pw1, pb1, pw2, pb2 = ctx.params
+        g = g.contiguous()
+        h, a = _ffn_front(x, w1, b1, gate, ctx.L)
+        gh, gg, gw2, gb2 = _ffn_tail_bwd(h, gate, a, w2, ctx.L, (pw2, pb2), g)
+        del h, a
+        gx, gw1, gb1 = _so3_linear_bwd(x, w1, ctx.L, (pw1, pb1), gh, ctx.needs_input_grad[0])
+        return gx, gg, gw1, gb1, gw2, gb2, None, (g if ctx.has_addend else None)
+
+
+def ffn_recompute(x, gate, w1, b1, w2, b2, L, addend=None):
+    """so3_linear(x, w1, b1) -> ffn_tail(., gate, w2, b2, addend) without saved [N, K, 512] tensors - see _FFNRecompute."""
+    return _FFNRecompute.apply(x, gate, w1, b1, w2, b2, L, addend)
+
+
+class _EdgeHeadConvRecompute(torch.autograd.Function):
+    """edge_head followed by the second SO(2) convolution (so2_conv3m) as one autograd node that does not hold the activated
+    tensor `act` [E, KR*C] between them: its backward pass rebuilds it from h0, h1, h2 (held anyway) with the activation's
+    forward launch, then runs the launches of _SO2Conv3M.backward and of _EdgeHead.backward.  -> (logits, y0, y1, y2)."""
+
+    @staticmethod
+    def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, w0, b0, w1, w2, heads, A, C, L, M, eps):
+        ctx.head_params, ctx.conv_params = (ln_w, ln_b, dot), (w0, w1, w2, b0)
+        ctx.cfg = (heads, A, C, L, M, eps)
+        saved, logits, act = _edge_head_fwd(h0, h1, h2, ln_w, ln_b, dot, ctx.cfg)
+        st = so3.layout(L, M).seg_start
+        _, ws, ctx.ins, hs = _so2_conv3m_fwd(act, w0, b0, w1, w2, st[1] * C, (st[2] - st[1]) * C)
+        ctx.save_for_backward(*saved, *ws)
+        return (logits,) + tuple(hs)
+
+    @staticmethod
+    def backward(ctx, g_logits, g0, g1, g2):
+        *head, w0, w1, w2 = ctx.saved_tensors
+        h0, h1, h2 = head[:3]
+        act = _edge_act(h0, h1, h2, ctx.cfg)
+        g_act, gw0, gb0, gw1, gw2 = _so2_conv3m_bwd(act, [w0, w1, w2], ctx.ins, ctx.conv_params, (g0, g1, g2), True)
+        del act
+        return _edge_head_bwd(head, ctx.cfg, ctx.head_params, g_logits, g_act) + (gw0, gb0, gw1, gw2) + (None,) * 6
+
+
+def edge_head_conv_recompute(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M=2, eps=1e-5):
+    """edge_head(...) -> so2_conv3m(act, w0, b0, w1, w2, ...) without a saved `act` - see _EdgeHeadConvRecompute."""
+    return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps)
 
 
 class _GroupedLinear3(torch.autograd.Function):

@@ -78,6 +78,10 @@ def main():
     ap.add_argument("--no-dropout", action="store_true",
                     help="switch the decoder's positional-encoding dropout (reference CProMG.py:198, p = 0.1: the only stochastic "
                          "op of the step besides the edge-frame draws) off - reproducible runs for parity checks")
+    ap.add_argument("--recompute", action="store_true",
+                    help="rebuild the embedding's largest saved activations in the backward pass instead of holding them (both "
+                         "[N, K, 512] tensors of every feed-forward block, the S2 activation of every attention block): less memory, "
+                         "slightly longer steps, the same checkpoints")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
 
@@ -136,7 +140,7 @@ def main():
             gs = [G.synthetic_graph(base + i) for i in range(lo, hi)]
         return G.collate(gs).to(dev)
 
-    model = SINGA(cfg, device=dev)
+    model = SINGA(cfg, device=dev, recompute=args.recompute)
     if args.no_dropout:
         model.model.decoder.pos_emb.dropout.p = 0.0
     o = cfg.train.optimizer
