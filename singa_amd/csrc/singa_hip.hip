@@ -3905,6 +3905,18 @@ __global__ void __launch_bounds__(256) grad_norm_finish_kernel(const float* __re
 // rows as wave-uniform scalars: u = to[g,:].x, s = SiLU(u), y += from[g,:] * s.  Row 0 of the result is SiLU(gate).
 // KIN rows, C channels (compile time).  EDGE: the rows come in the three per-m segments of an SO(2) convolution
 // ((L+1) | 2L | 2(L-1) rows, KIN = 5L-1); otherwise one contiguous [KIN, C] record per row of the batch.
+// s2_rows(x, e, c)(i): where coefficient row i of batch row e starts, at channel c, in either form (x: Segs or SegsMut; i is
+// an unrolled loop counter, so the segment choice folds away).
+template <bool EDGE, int L, int C, class SEGS>
+__device__ __forceinline__ auto s2_rows(const SEGS& x, long long e, int c) {
+    const auto b0 = x.p[0] + e * x.ld[0] + c;
+    const auto b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
+    const auto b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
+    return [=](int i) {
+        constexpr int r0 = L + 1, r01 = 3 * L + 1;
+        return !EDGE || i < r0 ? b0 + i * C : (i < r01 ? b1 + (i - r0) * C : b2 + (i - r01) * C);
+    };
+}
 template <int KIN, int C, bool EDGE>
 __global__ void __launch_bounds__(256) s2act_fwd_kernel(Segs x, const float* __restrict__ gate, long long ldg,
                                                         const float* __restrict__ to_grid,
@@ -3914,15 +3926,11 @@ __global__ void __launch_bounds__(256) s2act_fwd_kernel(Segs x, const float* __r
     if (tid >= EC) return;
     long long e = tid / C;
     int c = (int)(tid - e * C);
-    constexpr int LL = (KIN + 1) / 5;
-    constexpr int r0 = EDGE ? LL + 1 : KIN, r01 = EDGE ? 3 * LL + 1 : KIN;
-    const float* b0 = x.p[0] + e * x.ld[0] + c;
-    const float* b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
-    const float* b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
+    const auto xrow = s2_rows<EDGE, (KIN + 1) / 5, C>(x, e, c);
     float xv[KIN], yv[KIN];
 #pragma unroll
     for (int i = 0; i < KIN; ++i) {
-        xv[i] = i < r0 ? b0[i * C] : (i < r01 ? b1[(i - r0) * C] : b2[(i - r01) * C]);
+        xv[i] = *xrow(i);
         yv[i] = 0.f;
     }
     for (int g = 0; g < G; ++g) {
@@ -3953,16 +3961,12 @@ __global__ void __launch_bounds__(256) s2act_bwd_kernel(Segs x, const float* __r
     if (tid >= EC) return;
     long long e = tid / C;
     int c = (int)(tid - e * C);
-    constexpr int LL = (KIN + 1) / 5;
-    constexpr int r0 = EDGE ? LL + 1 : KIN, r01 = EDGE ? 3 * LL + 1 : KIN;
-    const float* b0 = x.p[0] + e * x.ld[0] + c;
-    const float* b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
-    const float* b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
+    const auto xrow = s2_rows<EDGE, (KIN + 1) / 5, C>(x, e, c);
     const float* gi = g_out + e * KIN * C + c;
     float xv[KIN], gy[KIN], ga[KIN];
 #pragma unroll
     for (int i = 0; i < KIN; ++i) {
-        xv[i] = i < r0 ? b0[i * C] : (i < r01 ? b1[(i - r0) * C] : b2[(i - r01) * C]);
+        xv[i] = *xrow(i);
         gy[i] = gi[i * C];
         ga[i] = 0.f;
     }
@@ -4051,7 +4055,27 @@ constexpr FourTab<RA, MM> make_four_tab() {
         }
     return t;
 }
+// The forward kernel and the ring transforms are written once for a lane type T: `float`, one channel per thread, or `v2f`, two
+// adjacent channels per thread on packed f32 arithmetic (v_pk_fma_f32: two FMAs per lane and instruction).  The Legendre /
+// Fourier coefficients are wave-uniform scalars, so every FMA pairs one coefficient with the lane's channel values; the two
+// overloads below keep each type's arithmetic form (fmaf for float; `c * v + a`, which contracts to v_pk_fma_f32, for v2f).
+// Same operations per channel in the same order: bit-identical results, held by tests/test_s2_lanes_gpu.py.  That rests on
+// the compiler contracting alike in both forms: it fuses SiLU's product u * sigmoid(u) into the sums s[a] +- s[RA - a] of
+// ring_from_grid (see the ring-pair loop of the kernel for the one place where it did not).
+#ifndef SINGA_V2F
+typedef float v2f __attribute__((ext_vector_type(2)));
+#else
+typedef SINGA_V2F v2f;
+#endif
+__device__ __forceinline__ float lane_fma(float c, float v, float a) { return fmaf(c, v, a); }
+__device__ __forceinline__ v2f lane_fma(float c, v2f v, v2f a) { return c * v + a; }
 __device__ __forceinline__ float silu_fast(float u) { return u * SINGA_RCP(1.0f + __expf(-u)); }
+__device__ __forceinline__ v2f silu_fast(v2f u) {
+    v2f r;
+    r[0] = silu_fast(u[0]);
+    r[1] = silu_fast(u[1]);
+    return r;
+}
 __device__ __forceinline__ float silu_grad_fast(float u) {
     const float sg = SINGA_RCP(1.0f + __expf(-u));
     return sg * (1.0f + u * (1.0f - sg));
@@ -4059,33 +4083,33 @@ __device__ __forceinline__ float silu_grad_fast(float u) {
 
 // u[a] = sum_m A[a, m] v[m] over the RA points of one ring (A[a, +k] = sqrt2 cos(k alpha_a), A[a, -k] = sqrt2 sin(k alpha_a),
 // A[a, 0] = 1; v[MM + m]) through the even / odd split: u[a] = E[a] + O[a], u[RA - a] = E[a] - O[a].
-template <int RA, int MM>
-__device__ __forceinline__ void ring_to_grid(const float (&v)[2 * MM + 1], float (&u)[RA]) {
-    constexpr auto T = make_four_tab<RA, MM>();
+template <int RA, int MM, class T>
+__device__ __forceinline__ void ring_to_grid(const T (&v)[2 * MM + 1], T (&u)[RA]) {
+    constexpr auto F = make_four_tab<RA, MM>();
     constexpr int HA = (RA - 1) / 2;
-    float e0 = v[MM];
+    T e0 = v[MM];
 #pragma unroll
-    for (int k = 1; k <= MM; ++k) e0 = fmaf(T.c[k][0], v[MM + k], e0);
+    for (int k = 1; k <= MM; ++k) e0 = lane_fma(F.c[k][0], v[MM + k], e0);
     u[0] = e0;
 #pragma unroll
     for (int a = 1; a <= HA; ++a) {
-        float ev = v[MM], od = 0.f;
+        T ev = v[MM], od = T{};
 #pragma unroll
         for (int k = 1; k <= MM; ++k) {
-            ev = fmaf(T.c[k][a], v[MM + k], ev);
-            od = fmaf(T.s[k][a], v[MM - k], od);
+            ev = lane_fma(F.c[k][a], v[MM + k], ev);
+            od = lane_fma(F.s[k][a], v[MM - k], od);
         }
         u[a] = ev + od;
         u[RA - a] = ev - od;
     }
 }
 // w[m] += sum_a A[a, m] s[a] (the transpose of ring_to_grid)
-template <int RA, int MM>
-__device__ __forceinline__ void ring_from_grid(const float (&sv)[RA], float (&w)[2 * MM + 1]) {
-    constexpr auto T = make_four_tab<RA, MM>();
+template <int RA, int MM, class T>
+__device__ __forceinline__ void ring_from_grid(const T (&sv)[RA], T (&w)[2 * MM + 1]) {
+    constexpr auto F = make_four_tab<RA, MM>();
     constexpr int HA = (RA - 1) / 2;
-    float sp[HA + 1], sm[HA + 1];
-    float tot = sv[0];
+    T sp[HA + 1], sm[HA + 1];
+    T tot = sv[0];
 #pragma unroll
     for (int a = 1; a <= HA; ++a) {
         sp[a] = sv[a] + sv[RA - a];
@@ -4095,56 +4119,60 @@ __device__ __forceinline__ void ring_from_grid(const float (&sv)[RA], float (&w)
     w[MM] = tot;
 #pragma unroll
     for (int k = 1; k <= MM; ++k) {
-        float wc = T.c[k][0] * sv[0], ws = 0.f;
+        T wc = F.c[k][0] * sv[0], ws = T{};
 #pragma unroll
         for (int a = 1; a <= HA; ++a) {
-            wc = fmaf(T.c[k][a], sp[a], wc);
-            ws = fmaf(T.s[k][a], sm[a], ws);
+            wc = lane_fma(F.c[k][a], sp[a], wc);
+            ws = lane_fma(F.s[k][a], sm[a], ws);
         }
         w[MM + k] = wc;
         w[MM - k] = ws;
     }
 }
 
-// thread = (row e, channel c), the KIN coefficient rows in registers.  Rings are handled in mirror pairs (b, RB-1-b): one
-// Legendre pass with the table row of ring b gives both rings' Fourier coefficients (even / odd parts), and both rings'
-// results are folded back with one pass.  Per ring the Fourier transform over alpha and its transpose use the even / odd
-// split above.  SiLU fused; row 0 of the result := SiLU(gate).  P, Q: [RB, KIN] Legendre tables (to-grid / from-grid) in
-// the row order of x, read as wave-uniform scalars.
-template <int L, bool EDGE, int C>
+// thread = (row e, sizeof(T) / 4 adjacent channels from c), the KIN coefficient rows in registers.  Rings are handled in mirror
+// pairs (b, RB-1-b): one Legendre pass with the table row of ring b gives both rings' Fourier coefficients (even / odd parts),
+// and both rings' results are folded back with one pass.  Per ring the Fourier transform over alpha and its transpose use the
+// even / odd split above.  SiLU fused; row 0 of the result := SiLU(gate).  P, Q: [RB, KIN] Legendre tables (to-grid / from-grid)
+// in the row order of x, read as wave-uniform scalars.  NT threads in all.  T = v2f wants every row start 8-byte aligned (the
+// launcher's pairing rule); one channel per thread issues its ~700 FMAs per ring pair one by one and sits at the scalar-FMA rate
+// of the vector unit (edge grid: 0.55 TB/s of traffic, ~72 TFLOP/s).
+template <int L, bool EDGE, int C, class T>
 __global__ void __launch_bounds__(256) s2act_sep_fwd_kernel(Segs x, const float* __restrict__ gate, long long ldg,
                                                             const float* __restrict__ P, const float* __restrict__ Q,
-                                                            const float* __restrict__ A, float* __restrict__ out,
-                                                            long long EC) {
+                                                            float* __restrict__ out, long long NT) {
     using S = S2Sep<L, EDGE>;
-    constexpr int KIN = S::KIN, NM = S::NM, RA = S::RA, MM = S::MM;
-    (void)A;
+    constexpr int KIN = S::KIN, NM = S::NM, RA = S::RA, MM = S::MM, W = sizeof(T) / sizeof(float), CW = C / W;
     long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= EC) return;
-    long long e = tid / C;
-    int c = (int)(tid - e * C);
-    constexpr int r0 = EDGE ? L + 1 : KIN, r01 = EDGE ? 3 * L + 1 : KIN;
-    const float* b0 = x.p[0] + e * x.ld[0] + c;
-    const float* b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
-    const float* b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
-    float xv[KIN], yv[KIN];
+    if (tid >= NT) return;
+    long long e = tid / CW;
+    int c = W * (int)(tid - e * CW);
+    const auto xrow = s2_rows<EDGE, L, C>(x, e, c);
+    T xv[KIN], yv[KIN];
 #pragma unroll
     for (int i = 0; i < KIN; ++i) {
-        xv[i] = i < r0 ? b0[i * C] : (i < r01 ? b1[(i - r0) * C] : b2[(i - r01) * C]);
-        yv[i] = 0.f;
+        xv[i] = *reinterpret_cast<const T*>(xrow(i));
+        yv[i] = T{};
     }
+    // The ring-pair loop: unrolled for L <= 4 and rolled for L = 6, as the compiler chose on its own - except in the one-channel
+    // kernel of the L = 6 edge grid.  Rolled, the SLP vectoriser packed eight of that kernel's ten SiLU products per ring pair
+    // into v_pk_mul_f32 before the contraction noted above could fuse them, and its results differed from the two-channel form's
+    // (7247 of 18560 elements, up to 5.4e-7 at |y| ~ 5); unrolled it contracts as every other instantiation does.  Only a
+    // caller with misaligned operands reaches that kernel.
+    constexpr int UNR = (L <= 4 || (EDGE && W == 1)) ? S::RB / 2 : 1;
+#pragma unroll UNR
     for (int b = 0; b < S::RB / 2; ++b) {
         const float* Pb = P + b * KIN;
         const float* Qb = Q + b * KIN;
-        float ve[NM], vo[NM];
+        T ve[NM], vo[NM];
 #pragma unroll
-        for (int m = 0; m < NM; ++m) { ve[m] = 0.f; vo[m] = 0.f; }
+        for (int m = 0; m < NM; ++m) { ve[m] = T{}; vo[m] = T{}; }
 #pragma unroll
         for (int i = 0; i < KIN; ++i) {
-            if (S::par(i)) vo[S::mc(i)] = fmaf(Pb[i], xv[i], vo[S::mc(i)]);
-            else ve[S::mc(i)] = fmaf(Pb[i], xv[i], ve[S::mc(i)]);
+            if (S::par(i)) vo[S::mc(i)] = lane_fma(Pb[i], xv[i], vo[S::mc(i)]);
+            else ve[S::mc(i)] = lane_fma(Pb[i], xv[i], ve[S::mc(i)]);
         }
-        float v1[NM], v2[NM], w1[NM], w2[NM], u[RA];
+        T v1[NM], v2[NM], w1[NM], w2[NM], u[RA];
 #pragma unroll
         for (int m = 0; m < NM; ++m) { v1[m] = ve[m] + vo[m]; v2[m] = ve[m] - vo[m]; }
         ring_to_grid<RA, MM>(v1, u);
@@ -4158,128 +4186,12 @@ __global__ void __launch_bounds__(256) s2act_sep_fwd_kernel(Segs x, const float*
 #pragma unroll
         for (int m = 0; m < NM; ++m) { ve[m] = w1[m] + w2[m]; vo[m] = w1[m] - w2[m]; }
 #pragma unroll
-        for (int i = 1; i < KIN; ++i) yv[i] = fmaf(Qb[i], S::par(i) ? vo[S::mc(i)] : ve[S::mc(i)], yv[i]);
+        for (int i = 1; i < KIN; ++i) yv[i] = lane_fma(Qb[i], S::par(i) ? vo[S::mc(i)] : ve[S::mc(i)], yv[i]);
     }
     float* o = out + e * KIN * C + c;
-    o[0] = silu_fast(gate[e * ldg + c]);
+    *reinterpret_cast<T*>(o) = silu_fast(*reinterpret_cast<const T*>(gate + e * ldg + c));
 #pragma unroll
-    for (int i = 1; i < KIN; ++i) o[i * C] = yv[i];
-}
-
-// Two channels per thread on packed f32 arithmetic (v_pk_fma_f32: two FMAs per lane and instruction).  The one-channel
-// kernel above issues its ~700 FMAs per ring pair one by one and sits at the scalar-FMA rate of the vector unit (edge grid:
-// 0.55 TB/s of traffic, ~72 TFLOP/s); the Legendre / Fourier coefficients are wave-uniform scalars, so every FMA pairs the
-// same coefficient with the two channels' values.  Same operations per channel in the same order: bit-identical results.
-// (The backward kernel keeps one channel per thread.  Its two-channel twin was built and measured: 255 registers + 76 bytes of
-// scratch at two wavefronts per SIMD for the L = 4 node grid, 2674 vs 2171 us at 49 k nodes; only the L = 2 grid gained, 9 %.)
-#ifndef SINGA_V2F
-typedef float v2f __attribute__((ext_vector_type(2)));
-#else
-typedef SINGA_V2F v2f;
-#endif
-__device__ __forceinline__ v2f silu_fast2(v2f u) {
-    v2f r;
-    r[0] = silu_fast(u[0]);
-    r[1] = silu_fast(u[1]);
-    return r;
-}
-template <int RA, int MM>
-__device__ __forceinline__ void ring_to_grid2(const v2f (&v)[2 * MM + 1], v2f (&u)[RA]) {
-    constexpr auto T = make_four_tab<RA, MM>();
-    constexpr int HA = (RA - 1) / 2;
-    v2f e0 = v[MM];
-#pragma unroll
-    for (int k = 1; k <= MM; ++k) e0 = T.c[k][0] * v[MM + k] + e0;
-    u[0] = e0;
-#pragma unroll
-    for (int a = 1; a <= HA; ++a) {
-        v2f ev = v[MM], od = {0.f, 0.f};
-#pragma unroll
-        for (int k = 1; k <= MM; ++k) {
-            ev = T.c[k][a] * v[MM + k] + ev;
-            od = T.s[k][a] * v[MM - k] + od;
-        }
-        u[a] = ev + od;
-        u[RA - a] = ev - od;
-    }
-}
-template <int RA, int MM>
-__device__ __forceinline__ void ring_from_grid2(const v2f (&sv)[RA], v2f (&w)[2 * MM + 1]) {
-    constexpr auto T = make_four_tab<RA, MM>();
-    constexpr int HA = (RA - 1) / 2;
-    v2f sp[HA + 1], sm[HA + 1];
-    v2f tot = sv[0];
-#pragma unroll
-    for (int a = 1; a <= HA; ++a) {
-        sp[a] = sv[a] + sv[RA - a];
-        sm[a] = sv[a] - sv[RA - a];
-        tot += sp[a];
-    }
-    w[MM] = tot;
-#pragma unroll
-    for (int k = 1; k <= MM; ++k) {
-        v2f wc = T.c[k][0] * sv[0], ws = {0.f, 0.f};
-#pragma unroll
-        for (int a = 1; a <= HA; ++a) {
-            wc = T.c[k][a] * sp[a] + wc;
-            ws = T.s[k][a] * sm[a] + ws;
-        }
-        w[MM + k] = wc;
-        w[MM - k] = ws;
-    }
-}
-template <int L, bool EDGE, int C>
-__global__ void __launch_bounds__(256) s2act_sep_fwd2_kernel(Segs x, const float* __restrict__ gate, long long ldg,
-                                                             const float* __restrict__ P, const float* __restrict__ Q,
-                                                             float* __restrict__ out, long long EC2) {
-    using S = S2Sep<L, EDGE>;
-    constexpr int KIN = S::KIN, NM = S::NM, RA = S::RA, MM = S::MM, C2 = C / 2;
-    long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= EC2) return;
-    long long e = tid / C2;
-    int c = 2 * (int)(tid - e * C2);
-    constexpr int r0 = EDGE ? L + 1 : KIN, r01 = EDGE ? 3 * L + 1 : KIN;
-    const float* b0 = x.p[0] + e * x.ld[0] + c;
-    const float* b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
-    const float* b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
-    v2f xv[KIN], yv[KIN];
-#pragma unroll
-    for (int i = 0; i < KIN; ++i) {
-        xv[i] = *reinterpret_cast<const v2f*>(i < r0 ? b0 + i * C : (i < r01 ? b1 + (i - r0) * C : b2 + (i - r01) * C));
-        yv[i] = v2f{0.f, 0.f};
-    }
-    for (int b = 0; b < S::RB / 2; ++b) {
-        const float* Pb = P + b * KIN;
-        const float* Qb = Q + b * KIN;
-        v2f ve[NM], vo[NM];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) { ve[m] = v2f{0.f, 0.f}; vo[m] = v2f{0.f, 0.f}; }
-#pragma unroll
-        for (int i = 0; i < KIN; ++i) {
-            if (S::par(i)) vo[S::mc(i)] = Pb[i] * xv[i] + vo[S::mc(i)];
-            else ve[S::mc(i)] = Pb[i] * xv[i] + ve[S::mc(i)];
-        }
-        v2f v1[NM], v2[NM], w1[NM], w2[NM], u[RA];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) { v1[m] = ve[m] + vo[m]; v2[m] = ve[m] - vo[m]; }
-        ring_to_grid2<RA, MM>(v1, u);
-#pragma unroll
-        for (int a = 0; a < RA; ++a) u[a] = silu_fast2(u[a]);
-        ring_from_grid2<RA, MM>(u, w1);
-        ring_to_grid2<RA, MM>(v2, u);
-#pragma unroll
-        for (int a = 0; a < RA; ++a) u[a] = silu_fast2(u[a]);
-        ring_from_grid2<RA, MM>(u, w2);
-#pragma unroll
-        for (int m = 0; m < NM; ++m) { ve[m] = w1[m] + w2[m]; vo[m] = w1[m] - w2[m]; }
-#pragma unroll
-        for (int i = 1; i < KIN; ++i) yv[i] = Qb[i] * (S::par(i) ? vo[S::mc(i)] : ve[S::mc(i)]) + yv[i];
-    }
-    float* o = out + e * KIN * C + c;
-    const v2f g2 = *reinterpret_cast<const v2f*>(gate + e * ldg + c);
-    *reinterpret_cast<v2f*>(o) = silu_fast2(g2);
-#pragma unroll
-    for (int i = 1; i < KIN; ++i) *reinterpret_cast<v2f*>(o + i * C) = yv[i];
+    for (int i = 1; i < KIN; ++i) *reinterpret_cast<T*>(o + i * C) = yv[i];
 }
 
 // Backward (recompute), same pairing: per ring v = P x and gq = Q^T gy (rows i >= 1); per alpha u = A v,
@@ -4291,36 +4203,29 @@ __global__ void __launch_bounds__(256) s2act_sep_fwd2_kernel(Segs x, const float
 // gs are staged in LDS once and read back as broadcasts (every lane the same address: conflict-free), each degree's 16 weights of
 // the thread's channel sit in registers while its 2l+1 rows are formed.  This removes the [N, K, 512] gradient tensor's write
 // (the k11s expand launch) and its re-read here: 2 x 2.5 GB per layer pass at config 3.
+// One channel per thread, one ring at a time.  Two packed forms were built, measured and dropped: two channels per thread (255
+// registers + 76 bytes of scratch at two wavefronts per SIMD for the L = 4 node grid, 2674 vs 2171 us at 49 k nodes; only the
+// L = 2 grid gained, 9 %), and the two rings of a mirror pair in the halves of v_pk_fma_f32 operands (2.45 instead of 2.41 ms on
+// the feed-forward grid, 565 instead of 520 us on the attention grid: the ~110 exp + rcp pairs per thread, quarter rate, and the
+// moves that build the pairs cost what the halved FMA count saves).
 template <int L, bool EDGE, int C, bool FFN = false>
 __global__ void __launch_bounds__(256, (FFN && L == 4) ? 3 : 1) s2act_sep_bwd_kernel(Segs x, const float* __restrict__ gate, long long ldg,
                                                             const float* __restrict__ P, const float* __restrict__ Q,
-                                                            const float* __restrict__ A, const float* __restrict__ g_out,
+                                                            const float* __restrict__ g_out,
                                                             SegsMut gx, float* __restrict__ g_gate, long long ldgg,
                                                             long long EC, const float* __restrict__ W2) {
     using S = S2Sep<L, EDGE>;
     constexpr int KIN = S::KIN, NM = S::NM, RA = S::RA, MM = S::MM;
-    // (round 4, measured and left off: the two rings of a mirror pair packed into v_pk_fma_f32 halves - 2.45 instead of 2.41 ms on
-    // the feed-forward grid, 565 instead of 520 us on the attention grid: the ~110 exp + rcp pairs per thread, quarter rate,
-    // and the moves that build the pairs cost what the halved FMA count saves)
-#ifdef SINGA_S2_BWD_PACK_RINGS
-    constexpr bool PACK_RINGS = true;
-#else
-    constexpr bool PACK_RINGS = false;
-#endif
-    (void)A;
     static_assert(!FFN || (!EDGE && C % 256 == 0), "the fused form is the node grid's, one node per workgroup");
     long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (!FFN && tid >= EC) return;               // (FFN: EC is a multiple of the workgroup size - no partial workgroup, checked by the host)
     long long e = tid / C;
     int c = (int)(tid - e * C);
-    constexpr int r0 = EDGE ? L + 1 : KIN, r01 = EDGE ? 3 * L + 1 : KIN;
-    const float* b0 = x.p[0] + e * x.ld[0] + c;
-    const float* b1 = EDGE ? x.p[1] + e * x.ld[1] + c : b0;
-    const float* b2 = EDGE ? x.p[2] + e * x.ld[2] + c : b0;
+    const auto xrow = s2_rows<EDGE, L, C>(x, e, c);
     float xv[KIN], gy[KIN], ga[KIN];
 #pragma unroll
     for (int i = 0; i < KIN; ++i) {
-        xv[i] = i < r0 ? b0[i * C] : (i < r01 ? b1[(i - r0) * C] : b2[(i - r01) * C]);
+        xv[i] = *xrow(i);
         ga[i] = 0.f;
     }
     if constexpr (FFN) {
@@ -4381,44 +4286,21 @@ __global__ void __launch_bounds__(256, (FFN && L == 4) ? 3 : 1) s2act_sep_bwd_ke
             if (S::par(i)) go[S::mc(i)] = fmaf(Qb[i], gy[i], go[S::mc(i)]);
             else ge[S::mc(i)] = fmaf(Qb[i], gy[i], ge[S::mc(i)]);
         }
-        float acc1[NM], acc2[NM];
-        if constexpr (PACK_RINGS) {
-            // the two rings of the mirror pair go through the SAME Fourier steps with the same (compile-time) coefficients: packed
-            // into the two halves of v_pk_fma_f32 operands the three transforms of a pair cost the instructions of one ring
-            // (the same operations per ring in the same order: bit-identical to the scalar form below)
-            v2f v[NM], q[NM], u[RA], t[RA], acc[NM];
+        float acc1[NM], acc2[NM], v[NM], q[NM], u[RA], t[RA];
 #pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                v[m] = v2f{ve[m] + vo[m], ve[m] - vo[m]};
-                q[m] = v2f{ge[m] + go[m], ge[m] - go[m]};
-            }
-            ring_to_grid2<RA, MM>(v, u);
-            ring_to_grid2<RA, MM>(q, t);
+        for (int m = 0; m < NM; ++m) { v[m] = ve[m] + vo[m]; q[m] = ge[m] + go[m]; }
+        ring_to_grid<RA, MM>(v, u);
+        ring_to_grid<RA, MM>(q, t);
 #pragma unroll
-            for (int a = 0; a < RA; ++a) {
-                t[a][0] *= silu_grad_fast(u[a][0]);
-                t[a][1] *= silu_grad_fast(u[a][1]);
-            }
-            ring_from_grid2<RA, MM>(t, acc);
+        for (int a = 0; a < RA; ++a) t[a] *= silu_grad_fast(u[a]);
+        ring_from_grid<RA, MM>(t, acc1);
 #pragma unroll
-            for (int m = 0; m < NM; ++m) { acc1[m] = acc[m][0]; acc2[m] = acc[m][1]; }
-        } else {
-            float v[NM], q[NM], u[RA], t[RA];
+        for (int m = 0; m < NM; ++m) { v[m] = ve[m] - vo[m]; q[m] = ge[m] - go[m]; }
+        ring_to_grid<RA, MM>(v, u);
+        ring_to_grid<RA, MM>(q, t);
 #pragma unroll
-            for (int m = 0; m < NM; ++m) { v[m] = ve[m] + vo[m]; q[m] = ge[m] + go[m]; }
-            ring_to_grid<RA, MM>(v, u);
-            ring_to_grid<RA, MM>(q, t);
-#pragma unroll
-            for (int a = 0; a < RA; ++a) t[a] *= silu_grad_fast(u[a]);
-            ring_from_grid<RA, MM>(t, acc1);
-#pragma unroll
-            for (int m = 0; m < NM; ++m) { v[m] = ve[m] - vo[m]; q[m] = ge[m] - go[m]; }
-            ring_to_grid<RA, MM>(v, u);
-            ring_to_grid<RA, MM>(q, t);
-#pragma unroll
-            for (int a = 0; a < RA; ++a) t[a] *= silu_grad_fast(u[a]);
-            ring_from_grid<RA, MM>(t, acc2);
-        }
+        for (int a = 0; a < RA; ++a) t[a] *= silu_grad_fast(u[a]);
+        ring_from_grid<RA, MM>(t, acc2);
 #pragma unroll
         for (int m = 0; m < NM; ++m) { ve[m] = acc1[m] + acc2[m]; vo[m] = acc1[m] - acc2[m]; }
 #pragma unroll
@@ -4426,15 +4308,9 @@ __global__ void __launch_bounds__(256, (FFN && L == 4) ? 3 : 1) s2act_sep_bwd_ke
     }
     // the gradient goes out in the segments the caller names (e.g. straight into the column blocks of the gradient of the
     // SO(2) convolution's three outputs - no concatenation afterwards)
-    float* o0 = gx.p[0] + e * gx.ld[0] + c;
-    float* o1 = EDGE ? gx.p[1] + e * gx.ld[1] + c : o0;
-    float* o2 = EDGE ? gx.p[2] + e * gx.ld[2] + c : o0;
+    const auto grow = s2_rows<EDGE, L, C>(gx, e, c);
 #pragma unroll
-    for (int i = 0; i < KIN; ++i) {
-        if (i < r0) o0[i * C] = ga[i];
-        else if (i < r01) o1[(i - r0) * C] = ga[i];
-        else o2[(i - r01) * C] = ga[i];
-    }
+    for (int i = 0; i < KIN; ++i) *grow(i) = ga[i];
     g_gate[e * ldgg + c] = gy[0] * silu_grad_fast(gate[e * ldg + c]);
 }
 
@@ -7132,54 +7008,58 @@ int singa_gather_wsum_bwd(const float* g, const float* alpha, const float* wv, c
     return check_launch("gather_wsum_bwd");
 }
 
+// the separable kernels: EDGE_ / C_ from the form, L_ from one switch (the body sees all three as constants)
 #define SINGA_DISPATCH_S2SEP(lmax, edge, ...)                                                            \
     do {                                                                                                 \
-        if (edge) {                                                                                      \
-            constexpr bool EDGE_ = true; constexpr int C_ = 128;                                         \
+        int rc_ = SINGA_OK;                                                                              \
+        dispatch_flag(edge, [&](auto edge_) {                                                            \
+            constexpr bool EDGE_ = decltype(edge_)::value;                                               \
+            constexpr int C_ = EDGE_ ? 128 : 512;                                                        \
             switch (lmax) {                                                                              \
                 case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                                    \
                 case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                                    \
                 case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                                    \
-                default: return fail(SINGA_E_LMAX, "s2act_sep: lmax must be 2, 4 or 6");                 \
+                default: rc_ = fail(SINGA_E_LMAX, "s2act_sep: lmax must be 2, 4 or 6");                  \
             }                                                                                            \
-        } else {                                                                                         \
-            constexpr bool EDGE_ = false; constexpr int C_ = 512;                                        \
-            switch (lmax) {                                                                              \
-                case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                                    \
-                case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                                    \
-                case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                                    \
-                default: return fail(SINGA_E_LMAX, "s2act_sep: lmax must be 2, 4 or 6");                 \
-            }                                                                                            \
-        }                                                                                                \
+        });                                                                                              \
+        if (rc_ != SINGA_OK) return rc_;                                                                 \
     } while (0)
 
-int singa_s2act_sep_fwd(const singa_seg_t* x, int nseg, const float* gate, int64_t ldg, const float* P, const float* Q,
-                        const float* A, float* out, int E, int C, int lmax, void* stream) {
-    Segs s;
-    if (!pack(x, nseg, &s) || !gate || !P || !Q || !A || !out) return fail(SINGA_E_NULL, "s2act_sep_fwd: null pointer");
+// The checks singa_s2act_sep_fwd and singa_s2act_sep_bwd_seg share: form against C, segment rows against lmax.  *EC: the
+// threads of a one-channel launch, 0 where there are no rows (the caller returns SINGA_OK behind its own checks).
+static int s2sep_check(const Segs& s, int nseg, int E, int C, int lmax, long long* EC) {
     const bool edge = nseg == 3;
     if (!(edge && C == 128) && !(nseg == 1 && C == 512))
         return fail(SINGA_E_SHAPE, "s2act_sep: built for (3 segments, C = 128) and (1 segment, C = 512)");
     if (edge && (s.rows[0] != lmax + 1 || s.rows[1] != 2 * lmax || s.rows[2] != 2 * (lmax - 1)))
         return fail(SINGA_E_SHAPE, "s2act_sep(edge): segment rows must be L+1, 2L, 2(L-1)");
     if (!edge && s.rows[0] != (lmax + 1) * (lmax + 1)) return fail(SINGA_E_SHAPE, "s2act_sep(node): rows must be (L+1)^2");
-    if (E <= 0) return SINGA_OK;
-    long long EC = (long long)E * C;
-    int blocks = (int)((EC + 255) / 256);
+    *EC = E <= 0 ? 0 : (long long)E * C;
+    return SINGA_OK;
+}
+
+int singa_s2act_sep_fwd(const singa_seg_t* x, int nseg, const float* gate, int64_t ldg, const float* P, const float* Q,
+                        const float* A, float* out, int E, int C, int lmax, void* stream) {
+    Segs s;
+    long long EC;
+    if (!pack(x, nseg, &s) || !gate || !P || !Q || !A || !out) return fail(SINGA_E_NULL, "s2act_sep_fwd: null pointer");
+    if (int rc = s2sep_check(s, nseg, E, C, lmax, &EC)) return rc;
+    if (!EC) return SINGA_OK;
+    const bool edge = nseg == 3;
     const int tag = edge ? SINGA_PROF_S2_EDGE_FWD : SINGA_PROF_S2_NODE_FWD;
     // two channels per thread (packed f32) where every row start is 8-byte aligned and the registers allow it (not the
-    // L = 6 node grid: 167 registers per channel)
+    // L = 6 node grid: 167 registers per channel; 256 VGPRs + 24 AGPRs as a pair, so that instantiation is not built)
     bool pair = (((uintptr_t)gate | (uintptr_t)out) & 7) == 0 && ldg % 2 == 0 && (edge || lmax <= 4);
     for (int i = 0; i < nseg; ++i) pair = pair && ((uintptr_t)s.p[i] & 7) == 0 && s.ld[i] % 2 == 0;
-    if (pair) {
-        const long long EC2 = EC / 2;
-        blocks = (int)((EC2 + 255) / 256);
-        SINGA_DISPATCH_S2SEP(lmax, edge, SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd2_kernel<L_, EDGE_, C_>), dim3(blocks), dim3(256),
-                                                      (hipStream_t)stream, s, gate, (long long)ldg, P, Q, out, EC2));
-        return check_launch("s2act_sep_fwd");
-    }
-    SINGA_DISPATCH_S2SEP(lmax, edge, SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd_kernel<L_, EDGE_, C_>), dim3(blocks), dim3(256),
-                                                  (hipStream_t)stream, s, gate, (long long)ldg, P, Q, A, out, EC));
+    const long long NT = pair ? EC / 2 : EC;
+    const int blocks = (int)((NT + 255) / 256);
+    SINGA_DISPATCH_S2SEP(lmax, edge, {
+        using T2_ = std::conditional_t<EDGE_ || L_ <= 4, v2f, float>;
+        if (pair) SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd_kernel<L_, EDGE_, C_, T2_>), dim3(blocks), dim3(256), (hipStream_t)stream, s,
+                               gate, (long long)ldg, P, Q, out, NT);
+        else SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd_kernel<L_, EDGE_, C_, float>), dim3(blocks), dim3(256), (hipStream_t)stream, s,
+                          gate, (long long)ldg, P, Q, out, NT);
+    });
     return check_launch("s2act_sep_fwd");
 }
 
@@ -7188,24 +7068,20 @@ int singa_s2act_sep_bwd_seg(const singa_seg_t* x, int nseg, const float* gate, i
                             int C, int lmax, void* stream) {
     Segs s;
     SegsMut so;
+    long long EC;
     if (!pack(x, nseg, &s) || !pack_mut(gx, nseg, &so) || !gate || !P || !Q || !A || !g_out || !g_gate)
         return fail(SINGA_E_NULL, "s2act_sep_bwd: null pointer");
-    const bool edge = nseg == 3;
-    if (!(edge && C == 128) && !(nseg == 1 && C == 512))
-        return fail(SINGA_E_SHAPE, "s2act_sep: built for (3 segments, C = 128) and (1 segment, C = 512)");
-    if (edge && (s.rows[0] != lmax + 1 || s.rows[1] != 2 * lmax || s.rows[2] != 2 * (lmax - 1)))
-        return fail(SINGA_E_SHAPE, "s2act_sep(edge): segment rows must be L+1, 2L, 2(L-1)");
-    if (!edge && s.rows[0] != (lmax + 1) * (lmax + 1)) return fail(SINGA_E_SHAPE, "s2act_sep(node): rows must be (L+1)^2");
+    if (int rc = s2sep_check(s, nseg, E, C, lmax, &EC)) return rc;
     for (int i = 0; i < nseg; ++i)
         if (so.rows[i] != s.rows[i] || so.ld[i] < (long long)s.rows[i] * C)
             return fail(SINGA_E_SHAPE, "s2act_sep_bwd: gradient segments must mirror the input segments");
     if (ld_gg < C) return fail(SINGA_E_SHAPE, "s2act_sep_bwd: row stride of g_gate below C");
-    if (E <= 0) return SINGA_OK;
-    long long EC = (long long)E * C;
-    int blocks = (int)((EC + 255) / 256);
+    if (!EC) return SINGA_OK;
+    const bool edge = nseg == 3;
+    const int blocks = (int)((EC + 255) / 256);
     const int tag = edge ? SINGA_PROF_S2_EDGE_BWD : SINGA_PROF_S2_NODE_BWD;
     SINGA_DISPATCH_S2SEP(lmax, edge, SINGA_LAUNCH(tag, E, 0, (s2act_sep_bwd_kernel<L_, EDGE_, C_>), dim3(blocks), dim3(256),
-                                                  (hipStream_t)stream, s, gate, (long long)ldg, P, Q, A, g_out, so, g_gate,
+                                                  (hipStream_t)stream, s, gate, (long long)ldg, P, Q, g_out, so, g_gate,
                                                   (long long)ld_gg, EC, (const float*)nullptr));
     return check_launch("s2act_sep_bwd");
 }
@@ -7226,11 +7102,9 @@ int singa_s2act_ffn_bwd(const float* x, const float* gate, int64_t ldg, const fl
     so.p[0] = gx; so.ld[0] = (long long)K * C; so.rows[0] = K;
     const long long EC = (long long)N * C;                 // a multiple of 256: whole workgroups only (they share LDS + a barrier)
     const int blocks = (int)(EC / 256);
-    const bool edge = false;
-    SINGA_DISPATCH_S2SEP(lmax, edge, SINGA_LAUNCH(SINGA_PROF_S2_NODE_BWD, N, 0, (s2act_sep_bwd_kernel<L_, false, 512, true>), dim3(blocks),
-                                                  dim3(256), (hipStream_t)stream, s, gate, (long long)ldg, P, Q, (const float*)nullptr,
-                                                  g_small, so, g_gate, (long long)C, EC, W2));
-    (void)edge;
+    SINGA_DISPATCH_S2SEP(lmax, false, SINGA_LAUNCH(SINGA_PROF_S2_NODE_BWD, N, 0, (s2act_sep_bwd_kernel<L_, false, 512, true>), dim3(blocks),
+                                                   dim3(256), (hipStream_t)stream, s, gate, (long long)ldg, P, Q, g_small, so, g_gate,
+                                                   (long long)C, EC, W2));
     return check_launch("s2act_ffn_bwd");
 }
 

@@ -431,6 +431,54 @@ def _grid_factors(L, M, m_primary, device):
     return _grid_cache[key]
 
 
+# The k8 launches.  `src`: the leading arguments every one of them takes - segments, gate, tables - from _s2_edge_src (the three
+# m-primary SO(2)-conv outputs; h0 = [alpha inputs | gate | m = 0 rows]) or _s2_node_src (one l-primary [N, K, C] record).  No rows,
+# no launch: an empty tensor has no address to hand over.
+def _s2_edge_src(h0, h1, h2, gate_off, x_off, C, L, M):
+    seg, n = _segs3((h0[:, x_off:], h1, h2), so3.layout(L, M).seg_rows, C)
+    return (seg, n, _p(h0[:, gate_off:]), h0.stride(0)) + tuple(_p(t) for t in _grid_factors(L, M, True, h0.device))
+
+
+def _s2_node_src(x, gate, L):
+    seg, n = _capi.segs([(x.data_ptr(), x.shape[1] * x.shape[2], x.shape[1])])
+    return (seg, n, _p(gate), gate.stride(0)) + tuple(_p(t) for t in _grid_factors(L, L, False, x.device))
+
+
+def _s2_fwd_edge(h0, h1, h2, gate_off, x_off, C, L, M):
+    """-> the activated m-primary tensor [E, KR*C]"""
+    E = h0.shape[0]
+    out = torch.empty(E, so3.layout(L, M).KR * C, device=h0.device, dtype=torch.float32)
+    if E > 0:
+        _chk(_lib.lib().singa_s2act_sep_fwd(*_s2_edge_src(h0, h1, h2, gate_off, x_off, C, L, M), _p(out), E, C, L, _stream()),
+             "singa_s2act_sep_fwd")
+    return out
+
+
+def _s2_fwd_node(x, gate, L):
+    """-> the activated [N, K, C] tensor"""
+    out = torch.empty_like(x)
+    if x.shape[0] > 0:
+        _chk(_lib.lib().singa_s2act_sep_fwd(*_s2_node_src(x, gate, L), _p(out), x.shape[0], x.shape[2], L, _stream()),
+             "singa_s2act_sep_fwd(node)")
+    return out
+
+
+def _s2_bwd(src, g, E, KC, C, L, what):
+    """-> (the input gradient as one contiguous [E, KC] tensor, the gate's gradient [E, C])"""
+    gx = torch.empty(E, KC, device=g.device, dtype=torch.float32)
+    gg = torch.empty(E, C, device=g.device, dtype=torch.float32)
+    if E > 0:
+        _chk(_lib.lib().singa_s2act_sep_bwd(*src, _p(g), _p(gx), _p(gg), E, C, L, _stream()), what)
+    return gx, gg
+
+
+def _s2_bwd_seg(src, g, gseg, g_gate, E, C, L):
+    """The input gradient into the segments `gseg`, the gate's gradient into the column block `g_gate` of a wider tensor."""
+    if E > 0:
+        _chk(_lib.lib().singa_s2act_sep_bwd_seg(*src, _p(g), gseg, _p(g_gate), g_gate.stride(0), E, C, L, _stream()),
+             "singa_s2act_sep_bwd_seg")
+
+
 class _S2ActEdge(torch.autograd.Function):
     """SeparableS2Activation on the attention grid [L][M] applied directly to the three SO(2)-conv GEMM outputs
     (m-primary).  h0 = [alpha inputs | gate | m=0 rows]; returns the activated m-primary tensor [E, KR*C]."""
@@ -439,31 +487,17 @@ class _S2ActEdge(torch.autograd.Function):
     def forward(ctx, h0, h1, h2, gate_off, x_off, C, L, M):
         h0, h1, h2 = _rows(h0), _rows(h1), _rows(h2)
         _dev(h0, h1, h2)
-        lay = so3.layout(L, M)
-        P, Q, A = _grid_factors(L, M, True, h0.device)
-        E = h0.shape[0]
-        out = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
-        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
-        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P),
-                                            _p(Q), _p(A), _p(out), E, C, L, _stream()), "singa_s2act_sep_fwd")
         ctx.save_for_backward(h0, h1, h2)
         ctx.cfg = (gate_off, x_off, C, L, M)
-        return out
+        return _s2_fwd_edge(h0, h1, h2, gate_off, x_off, C, L, M)
 
     @staticmethod
     def backward(ctx, g):
         h0, h1, h2 = ctx.saved_tensors
         gate_off, x_off, C, L, M = ctx.cfg
         lay = so3.layout(L, M)
-        P, Q, A = _grid_factors(L, M, True, h0.device)
-        g = g.contiguous()
-        E = h0.shape[0]
-        gx = torch.empty(E, lay.KR * C, device=g.device, dtype=torch.float32)
-        gg = torch.empty(E, C, device=g.device, dtype=torch.float32)
-        seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
-        _chk(_lib.lib().singa_s2act_sep_bwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P),
-                                            _p(Q), _p(A), _p(g), _p(gx), _p(gg), E, C, L, _stream()),
-             "singa_s2act_sep_bwd")
+        gx, gg = _s2_bwd(_s2_edge_src(h0, h1, h2, *ctx.cfg), g.contiguous(), h0.shape[0], lay.KR * C, C, L,
+                         "singa_s2act_sep_bwd")
         n0, n1 = lay.seg_rows[0] * C, lay.seg_rows[1] * C
         g0 = torch.zeros_like(h0)
         g0[:, gate_off:gate_off + C] = gg
@@ -497,16 +531,7 @@ class _EdgeHead(torch.autograd.Function):
 def _edge_act(h0, h1, h2, cfg):
     """The activation launch of the edge head: the separable S2 activation of [gate | m = 0 rows] of h0, h1, h2 -> [E, KR*C]."""
     heads, A, C, L, M, _ = cfg
-    lay = so3.layout(L, M)
-    E = h0.shape[0]
-    gate_off, x_off = heads * A, heads * A + C
-    P, Q, Az = _grid_factors(L, M, True, h0.device)
-    act = torch.empty(E, lay.KR * C, device=h0.device, dtype=torch.float32)
-    seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
-    if E > 0:                                     # (an empty edge set has no address to hand over)
-        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
-                                            _p(Az), _p(act), E, C, L, _stream()), "singa_s2act_sep_fwd")
-    return act
+    return _s2_fwd_edge(h0, h1, h2, heads * A, heads * A + C, C, L, M)
 
 
 def _edge_head_fwd(h0, h1, h2, ln_w, ln_b, dot, cfg):
@@ -548,13 +573,8 @@ def _edge_head_bwd(saved, cfg, params, g_logits, g_act):
     g_lnw, g_lnb, g_dot = param_colsum(part, [(0, A, pw), (A, A, pb), (2 * A, heads * A, pd)])
     if g_dot is not None:
         g_dot = g_dot.view(heads, A)
-    P, Q, Az = _grid_factors(L, M, True, h0.device)
-    seg, n = _segs3((h0[:, x_off:], h1, h2), lay.seg_rows, C)
     gseg, _ = _segs3((g_h0[:, x_off:], g_h1, g_h2), lay.seg_rows, C)
-    if E > 0:
-        _chk(lib.singa_s2act_sep_bwd_seg(seg, n, _p(h0[:, gate_off:]), h0.stride(0), _p(P), _p(Q),
-                                         _p(Az), _p(g_act), gseg, _p(g_h0[:, gate_off:]),
-                                         g_h0.stride(0), E, C, L, _stream()), "singa_s2act_sep_bwd_seg")
+    _s2_bwd_seg(_s2_edge_src(h0, h1, h2, gate_off, x_off, C, L, M), g_act, gseg, g_h0[:, gate_off:], E, C, L)
     return (g_h0, g_h1, g_h2, g_lnw, g_lnb, g_dot)
 
 
@@ -570,28 +590,16 @@ class _S2ActNode(torch.autograd.Function):
     def forward(ctx, x, gate, L):
         x, gate = x.contiguous(), gate.contiguous()
         _dev(x, gate)
-        P, Q, A = _grid_factors(L, L, False, x.device)
-        N, K, C = x.shape
-        out = torch.empty_like(x)
-        seg, n = _capi.segs([(x.data_ptr(), K * C, K)])
-        _chk(_lib.lib().singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(out), N, C, L,
-                                            _stream()), "singa_s2act_sep_fwd(node)")
         ctx.save_for_backward(x, gate)
         ctx.L = L
-        return out
+        return _s2_fwd_node(x, gate, L)
 
     @staticmethod
     def backward(ctx, g):
         x, gate = ctx.saved_tensors
-        L = ctx.L
-        P, Q, A = _grid_factors(L, L, False, x.device)
-        g = g.contiguous()
         N, K, C = x.shape
-        gx, gg = torch.empty_like(x), torch.empty_like(gate)
-        seg, n = _capi.segs([(x.data_ptr(), K * C, K)])
-        _chk(_lib.lib().singa_s2act_sep_bwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(g), _p(gx), _p(gg),
-                                            N, C, L, _stream()), "singa_s2act_sep_bwd(node)")
-        return gx, gg, None
+        gx, gg = _s2_bwd(_s2_node_src(x, gate, ctx.L), g.contiguous(), N, K * C, C, ctx.L, "singa_s2act_sep_bwd(node)")
+        return gx.view(N, K, C), gg, None
 
 
 def s2act_node(x, gate, L):
@@ -2017,13 +2025,7 @@ class _FFNTail(torch.autograd.Function):
         N, K, cin = h.shape
         cout = weight.shape[1]
         assert cin == 512 and cout == 16 and weight.shape[2] == cin
-        lib = _lib.lib()
-        P, Q, A = _grid_factors(L, L, False, h.device)
-        a = torch.empty_like(h)
-        seg, n = _capi.segs([(h.data_ptr(), K * cin, K)])
-        if N > 0:                                 # (an empty node set has no address to hand over)
-            _chk(lib.singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(a), N, cin, L, _stream()),
-                 "singa_s2act_sep_fwd(node)")
+        a = _s2_fwd_node(h, gate, L)
         out = torch.empty(N, K, cout, device=h.device, dtype=torch.float32)
         ctx.has_addend = addend is not None
         if addend is not None:
@@ -2084,17 +2086,11 @@ def _ffn_front(x, w1, b1, gate, L):
     that never writes h was built and measured for this place and lost to these two: profiles/recompute/README.md.)"""
     N, K, cin = x.shape
     C = w1.shape[1]
-    lib = _lib.lib()
     h = torch.empty(N, K, C, device=x.device, dtype=torch.float32)
-    a = torch.empty_like(h)
     if N > 0:
-        _chk(lib.singa_so3_skinny_expand(_p(x), _p(w1), C * cin, cin, 1, _p(b1), _p(h), N, C, L, _stream()),
+        _chk(_lib.lib().singa_so3_skinny_expand(_p(x), _p(w1), C * cin, cin, 1, _p(b1), _p(h), N, C, L, _stream()),
              "singa_so3_skinny_expand")
-        P, Q, A = _grid_factors(L, L, False, x.device)
-        seg, n = _capi.segs([(h.data_ptr(), K * C, K)])
-        _chk(lib.singa_s2act_sep_fwd(seg, n, _p(gate), gate.stride(0), _p(P), _p(Q), _p(A), _p(a), N, C, L, _stream()),
-             "singa_s2act_sep_fwd(node)")
-    return h, a
+    return h, _s2_fwd_node(h, gate, L)
 
 
 class _FFNRecompute(torch.autograd.Function):

@@ -465,3 +465,31 @@ def arena_runs(case, device, **kw):
         reps.append(ar.report())
     differ = [n for n in reps[0].bits if not torch.equal(reps[0].bits[n], reps[1].bits[n])]
     return reps[0], reps[1], differ, ret
+
+
+# The clauses of singa_s2act_sep_fwd's pairing rule (two channels per thread where gate, every segment and `out` start 8-byte
+# aligned and every pitch is even), defeated one at a time; "paired" satisfies all of them.
+S2_LANE_LAYOUTS = ("paired", "gate + 1", "ldg odd", "segment + 1", "segment pitch odd", "out + 1")
+
+
+def s2_lane_layout(name, rows, C, E, alloc):
+    """The operands of one singa_s2act_sep_fwd call laid out as `name` (one of S2_LANE_LAYOUTS) asks, each in a NaN-filled buffer of
+    its own.  alloc(n) -> (flat float32 buffer of n NaNs - numpy or torch -, its address, 8-byte aligned).  -> dict: `gate`
+    [E, C] and `x` (one [E, r * C] view per segment) to fill; `out` [E, KIN * C] to read, `margins` (the floats in front of and
+    behind it); `items` for _capi.segs, `gate_ptr`, `ldg`, `out_ptr`."""
+    assert name in S2_LANE_LAYOUTS
+    last, kc = len(rows) - 1, sum(rows) * C
+
+    def block(width, off, ld, tail=0):
+        buf, addr = alloc(off + E * ld + tail)
+        assert addr % 8 == 0
+        return buf, buf[off:off + E * ld].reshape(E, ld)[:, :width], addr + 4 * off
+
+    ldg = C + 2 + (name == "ldg odd")
+    _, gate, gate_ptr = block(C, 2 + (name == "gate + 1"), ldg)
+    lds = [r * C + 2 + (name == "segment pitch odd" and k == last) for k, r in enumerate(rows)]
+    segs = [block(r * C, 2 + (name == "segment + 1" and k == last), ld) for k, (r, ld) in enumerate(zip(rows, lds))]
+    off = 2 + (name == "out + 1")
+    obuf, out, out_ptr = block(kc, off, kc, tail=3)
+    return dict(gate=gate, x=[s[1] for s in segs], out=out, margins=(obuf[:off], obuf[off + E * kc:]),
+                items=[(s[2], ld, r) for s, ld, r in zip(segs, lds, rows)], gate_ptr=gate_ptr, ldg=ldg, out_ptr=out_ptr)

@@ -404,6 +404,45 @@ def test_s2act_separable(emul, L, edge):
                                         iptr(bufs[0]), C, E, C, L, None) == -3
 
 
+@pytest.mark.parametrize("L,edge", [(2, True), (4, True), (6, True), (2, False), (4, False), (6, False)])
+def test_s2act_separable_lane_layouts(emul, L, edge):
+    """The separable forward in its one-channel and its two-channel form: the layouts of tests/helpers.py that satisfy the
+    launcher's pairing rule or miss it by one clause, each against the dense-grid oracle at test_s2act_separable's forward bound,
+    with the margins around `out` untouched.  (tests/test_s2_lanes_gpu.py holds the two forms to each other bit for bit on the
+    GPU; g++ does not fuse the vector form's a * b + c, so here they differ in the last bits.)"""
+    from tests.helpers import S2_LANE_LAYOUTS, s2_lane_layout
+    rs = np.random.RandomState(177 + L)
+    M, C, E = (2, 128, 5) if edge else (L, 512, 2)
+    lay = so3.layout(L, M)
+    P, Q, A = (np.ascontiguousarray(t, np.float32) for t in so3.s2_grid_factors(L, M, edge))
+    rows = list(lay.seg_rows) if edge else [P.shape[1]]
+    KIN = sum(rows)
+    x = rs.randn(E, KIN, C).astype(np.float32)
+    gate = rs.randn(E, C).astype(np.float32)
+    if edge:
+        to_m = torch.as_tensor(lay.to_m)
+        ref = O.sep_s2_act(torch.tensor(gate), torch.tensor(x)[:, torch.argsort(to_m)], L, M)[:, to_m].numpy()
+    else:
+        ref = O.sep_s2_act(torch.tensor(gate), torch.tensor(x), L, M).numpy()
+
+    def alloc(n):
+        buf = np.full(n, np.nan, np.float32)
+        return buf, iptr(buf)
+
+    for name in S2_LANE_LAYOUTS:
+        lo = s2_lane_layout(name, rows, C, E, alloc)
+        lo["gate"][:] = gate
+        at = 0
+        for v, r in zip(lo["x"], rows):
+            v[:] = x[:, at:at + r].reshape(E, r * C)
+            at += r
+        seg, n = _capi.segs(lo["items"])
+        code = emul.singa_s2act_sep_fwd(seg, n, lo["gate_ptr"], lo["ldg"], ptr(P), ptr(Q), ptr(A), lo["out_ptr"], E, C, L, None)
+        assert code == 0, (name, emul.singa_last_error_string())
+        assert np.abs(lo["out"].reshape(E, KIN, C) - ref).max() < 3e-5 * max(1.0, float(np.abs(ref).max())), name
+        assert all(np.isnan(m).all() for m in lo["margins"]), name
+
+
 @pytest.mark.parametrize("L,C", [(2, 512), (4, 512), (6, 512), (4, 112), (6, 112)])
 def test_so3_skinny_kernels(emul, L, C):
     """k11s: the 16 <-> 512 channel SO3 linears as VALU kernels - expand (forward 16 -> 512 with bias, and d x of 512 -> 16

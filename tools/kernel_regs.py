@@ -17,7 +17,7 @@ for m in re.finditer(r"- \.agpr_count:\s+(\d+)(.*?)\.wavefront_size", s, re.S):
     body = m.group(0)
     name = re.search(r"\.name:\s+(\S+)", body).group(1)
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r"\(anonymous namespace\)::", "", dem).replace("void ", "")
+    dem = re.sub(r"\(anonymous namespace\)::", "", dem).replace("void ", "").replace("float __vector(2)", "v2f")
     dem = re.sub(r"\(Rule\)(\d)", lambda m: ("RULE_NONE", "RULE_SMILES", "RULE_VALENCE")[int(m.group(1))], dem)
     dem = dem[:dem.index("(")] if "(" in dem else dem
     if flt not in dem:
