@@ -210,13 +210,23 @@ _DATA_SIGS = {
 }
 DATA_EXPORTS = tuple(_DATA_SIGS)
 
+# include/singa_hip_attn_tiles.h: dense attention over the score tiles the mask leaves standing (`ops.attn_tiles`,
+# `ops.attention(..., tiles=...)`); a table of its own
+_ATTN_TILES_SIGS = {
+    "singa_attn_tiles": ([P, I64, I64, P, P, I32, I32, I32, P], I32),
+    "singa_attn_tiled_fwd": (_SIGS["singa_attn_fwd"][0][:-1] + [P, P], I32),
+    "singa_attn_tiled_bwd": (_SIGS["singa_attn_bwd"][0][:-1] + [P, P, P], I32),
+}
+ATTN_TILES_EXPORTS = tuple(_ATTN_TILES_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
     lib = C.CDLL(path)
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
-            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()):
+            list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
+            list(_ATTN_TILES_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -28,6 +28,7 @@
 #include "../../include/singa_hip_valence.h"
 #include "../../include/singa_hip_beam.h"
 #include "../../include/singa_hip_units.h"
+#include "../../include/singa_hip_attn_tiles.h"
 #include "../../include/singa_hip_prefix.h"
 #include "../../include/singa_hip_data.h"
 #include "so3_index.h"
@@ -3285,10 +3286,36 @@ __device__ __forceinline__ bool attn_mask_bit(const unsigned (&w)[4], int k0, in
     return (sh < 32) & (((w[r >> 2] >> (sh & 31)) & 0xffu) != 0u);      // no short circuit: no branch per key
 }
 
+// The computed tiles of one wavefront's row of the tile map (include/singa_hip_attn_tiles.h): bit t & 31 of word t >> 5 says
+// "compute tile t".  The words are wave-uniform, so the walk lives in scalar registers; next() is the next set bit (the
+// number of tiles when none is left) and reloads only when a word of 32 tiles is used up.  Bits past the last tile are
+// dropped at the load: whatever the words hold, no tile index leaves [0, nt].
+struct AttnWalk {
+    const unsigned* w;
+    int nt, base;
+    unsigned cur;
+    __device__ __forceinline__ unsigned word(int b0) const {
+        const unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)w[b0 >> 5]);
+        return nt - b0 < 32 ? x & ((1u << (nt - b0)) - 1u) : x;
+    }
+    __device__ __forceinline__ void start(const unsigned* words, int ntiles) { w = words, nt = ntiles, base = 0, cur = word(0); }
+    __device__ __forceinline__ int next() {
+        while (cur == 0u && base + 32 < nt) base += 32, cur = word(base);
+        if (cur == 0u) return nt;
+        const int t = base + __builtin_ctz(cur);
+        cur &= cur - 1u;
+        return t;
+    }
+};
+
+// TILED: `tiles` is the query-tile orientation of the tile map and the key loop visits computed tiles only; otherwise
+// every tile, and `tiles` is not looked at.
+template <bool TILED>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, const unsigned char* __restrict__ mask,
                                                        long long msb, long long mst, float* __restrict__ ctx,
-                                                       float* __restrict__ lse, int BH, int T, int S, int heads, int tm, float scale, AttnPitch ld) {
+                                                       float* __restrict__ lse, int BH, int T, int S, int heads, int tm, float scale, AttnPitch ld,
+                                                       const unsigned* __restrict__ tiles) {
     const int lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
     const int qtiles = (T + 31) / 32;
     // XCD b % 8 takes a contiguous eighth of the (batch x head, tile) list: the keys / values of one (batch, head) are
@@ -3321,8 +3348,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
         for (int m4 = 0; m4 < 4; ++m4) knext[m4] = *reinterpret_cast<const float4*>(kb + (long long)ka * A.ks + 16 * half + 4 * m4);
         attn_mask_fetch(mrow, k0, half, S, mnext);
     };
-    fetch_k(0);
-    for (int k0 = 0; k0 < S; k0 += 32) {
+    // one key tile k0; knx: the tile whose key rows and mask bytes are fetched meanwhile
+    auto tile = [&](int k0, int knx) __attribute__((always_inline)) {
         float kreg[16], vreg[32];
         unsigned mb[4];
 #pragma unroll
@@ -3337,7 +3364,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
             const float* vr = vb + (long long)(ks < S ? ks : S - 1) * A.vs + i;
             vreg[2 * s] = vr[0], vreg[2 * s + 1] = vr[32];
         }
-        fetch_k(k0 + 32 < S ? k0 + 32 : k0);      // unconditional (the last tile re-reads itself): behind a branch the
+        fetch_k(knx);                              // unconditional (the last tile re-reads itself): behind a branch the
                                                    // compiler's vmcnt counts assume the shorter path and wait for the prefetch
         floatx16 sc;
 #pragma unroll
@@ -3372,6 +3399,23 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
             o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vreg[2 * s], sc[s], o0, 0, 0, 0);
             o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vreg[2 * s + 1], sc[s], o1, 0, 0, 0);
         }
+    };
+    if constexpr (TILED) {
+        // a skipped tile is masked in every element and no query of this tile is masked in all keys: its probabilities are
+        // exp(-1e9 - m) = 0 and its rescale exp(0) = 1, so the sums below are the ones the full loop makes
+        const int ktiles = (S + 31) / 32;
+        AttnWalk walk;
+        walk.start(tiles + ((long long)(bh / heads) * qtiles + qt) * ((ktiles + 31) / 32), ktiles);
+        int kt = walk.next();
+        fetch_k(32 * kt);
+        while (kt < ktiles) {
+            const int nx = walk.next();             // ahead of the tile: the prefetch inside it stays free of branches
+            tile(32 * kt, 32 * (nx < ktiles ? nx : kt));
+            kt = nx;
+        }
+    } else {
+        fetch_k(0);
+        for (int k0 = 0; k0 < S; k0 += 32) tile(k0, k0 + 32 < S ? k0 + 32 : k0);
     }
     lrun += __shfl_xor(lrun, 32, 64);
     if (tq < T) {
@@ -3398,12 +3442,14 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
 //     dQ^T[dk x query] += K^T . dS^T takes dS^T as B operand;
 //   pass B (a wavefront = 32 keys, lane = key): s[query x key] = Q . K^T and dP = dO . V^T with the key on the lane and 16
 //     queries in registers, then dV^T[dv x key] += dO^T . P and dK^T[dk x key] += Q^T . dS with P / dS as B operands.
+template <bool TILED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                           const float* __restrict__ v, const unsigned char* __restrict__ mask,
                                                           long long msb, long long mst, const float* __restrict__ ctx,
                                                           const float* __restrict__ lse, const float* __restrict__ go,
                                                           float* __restrict__ gq, float* __restrict__ dsum, int BH, int T, int S,
-                                                          int heads, int tm, float scale, AttnPitch ld) {
+                                                          int heads, int tm, float scale, AttnPitch ld,
+                                                          const unsigned* __restrict__ tiles) {
     const int lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
     const int qtiles = (T + 31) / 32;
     // XCD b % 8 takes a contiguous eighth of the (batch x head, tile) list: the keys / values of one (batch, head) are
@@ -3447,8 +3493,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         for (int m4 = 0; m4 < 8; ++m4) vn[m4] = *reinterpret_cast<const float4*>(vb + (long long)ka * A.vs + 32 * half + 4 * m4);
         attn_mask_fetch(mrow, k0, half, S, mnext);
     };
-    fetch(0);
-    for (int k0 = 0; k0 < S; k0 += 32) {
+    auto tile = [&](int k0, int knx) __attribute__((always_inline)) {       // as in attn_fwd_kernel
         float kreg[16], vreg[32], kd[16];
         unsigned mb[4];
 #pragma unroll
@@ -3462,7 +3507,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             const int ks = k0 + 8 * (s >> 2) + 4 * half + (s & 3);
             kd[s] = kb[(long long)(ks < S ? ks : S - 1) * A.ks + i];
         }
-        fetch(k0 + 32 < S ? k0 + 32 : k0);        // unconditional, as in attn_fwd_kernel
+        fetch(knx);                               // unconditional, as in attn_fwd_kernel
         floatx16 sc, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[r] = 0.f, dp[r] = 0.f;
@@ -3481,6 +3526,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) dq = __builtin_amdgcn_mfma_f32_32x32x2f32(kd[s], sc[s], dq, 0, 0, 0);
+    };
+    if constexpr (TILED) {                          // a skipped tile: dS^T = 0 in every element
+        const int ktiles = (S + 31) / 32;
+        AttnWalk walk;
+        walk.start(tiles + ((long long)(bh / heads) * qtiles + qt) * ((ktiles + 31) / 32), ktiles);
+        int kt = walk.next();
+        fetch(32 * kt);
+        while (kt < ktiles) {
+            const int nx = walk.next();
+            tile(32 * kt, 32 * (nx < ktiles ? nx : kt));
+            kt = nx;
+        }
+    } else {
+        fetch(0);
+        for (int k0 = 0; k0 < S; k0 += 32) tile(k0, k0 + 32 < S ? k0 + 32 : k0);
     }
     if (tq < T) {
         float* dst = gq + A.qb + (long long)tq * A.qs + 4 * half;
@@ -3491,17 +3551,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 }
 
 // (one wavefront per SIMD by design: asked for two, the compiler parks the prefetched rows in scratch and waits for them)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) attn_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
+// WPB wavefronts per workgroup; they share nothing.  A workgroup holds its place on the compute unit until its last wavefront
+// ends, so the tiled form, whose wavefronts differ in length (a key tile without a computed pair returns at once), runs one
+// wavefront per workgroup: with four, the short ones freed nothing (measured: the cross-attention launch did not move).
+template <bool TILED, int WPB>
+__global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(1, 1))) attn_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, const unsigned char* __restrict__ mask,
                                                            long long msb, long long mst, const float* __restrict__ lse,
                                                            const float* __restrict__ dsum, const float* __restrict__ go,
                                                            float* __restrict__ gk, float* __restrict__ gv, int BH, int T, int S,
-                                                           int heads, int tm, float scale, AttnPitch ld) {
+                                                           int heads, int tm, float scale, AttnPitch ld,
+                                                           const unsigned* __restrict__ tiles) {
     const int lane = threadIdx.x & 63, i = lane & 31, half = lane >> 5;
     const int ktiles = (S + 31) / 32;
     // XCD b % 8 takes a contiguous eighth of the (batch x head, tile) list: the keys / values of one (batch, head) are
     // then read into ONE L2 instead of all eight (grid: a multiple of 8 workgroups)
-    const long long w = (long long)xcd_range_id((int)blockIdx.x, (int)gridDim.x) * 4 + (threadIdx.x >> 6);
+    const long long w = (long long)xcd_range_id((int)blockIdx.x, (int)gridDim.x) * WPB + (threadIdx.x >> 6);
     if (w >= (long long)BH * ktiles) return;
     const int bh = (int)(w / ktiles), kt = (int)(w - (long long)bh * ktiles);
     const int key = kt * 32 + i, keyc = key < S ? key : S - 1;
@@ -3533,8 +3598,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     // one by one - and a branch around the prefetch cost a vmcnt(0) per tile: MFMA-busy 0.27.)  The per-query softmax
     // statistics (row maximum, 1 / row sum, D = rowsum(dO . O)) ride along: one query per lane, read back per register row.
     constexpr int QS = 100;                                        // row pitch (floats): 16-byte aligned rows, q at 0, dO at 32
-    __shared__ __attribute__((aligned(16))) float qimg[4][32 * QS];
-    __shared__ float sstat[4][96];
+    __shared__ __attribute__((aligned(16))) float qimg[WPB][32 * QS];
+    __shared__ float sstat[WPB][96];
     float* lw = qimg[threadIdx.x >> 6];
     float* ss = sstat[threadIdx.x >> 6];
     float sn0 = 0.f, sn1 = 0.f, sn2 = 0.f;
@@ -3557,8 +3622,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             mraw[r_] = mb[(long long)(tr_ < T ? tr_ : T - 1) * mst];                                                             \
         }                                                                                                                        \
     } while (0)
-    SINGA_DKV_FETCH(0);
-    for (int t0 = 0; t0 < T; t0 += 32) {
+    auto tile = [&](int t0, int tnext) __attribute__((always_inline)) {     // one query tile t0; tnext is fetched meanwhile
         if (half == 0) ss[i] = sn0, ss[32 + i] = sn1, ss[64 + i] = sn2;
         {
             float* qw = lw + i * QS + 16 * half;
@@ -3573,8 +3637,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         unsigned mbits = 0;                             // this tile's mask bits (fetched with its rows, one tile ago)
 #pragma unroll
         for (int r = 0; r < 16; ++r) mbits |= (mraw[r] != 0 ? 1u : 0u) << r;
-        const int tnext = t0 + 32 < T ? t0 + 32 : t0;  // unconditional (the last tile re-reads its own rows): no branch, no vmcnt(0)
-        SINGA_DKV_FETCH(tnext);
+        SINGA_DKV_FETCH(tnext);                        // unconditional (the last tile re-reads its own rows): no branch, no vmcnt(0)
         floatx16 sc, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[r] = 0.f, dp[r] = 0.f;
@@ -3612,6 +3675,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             dv1 = __builtin_amdgcn_mfma_f32_32x32x2f32(row[64 + i], pr[s], dv1, 0, 0, 0);
             dk = __builtin_amdgcn_mfma_f32_32x32x2f32(row[i], sc[s], dk, 0, 0, 0);
         }
+    };
+    if constexpr (TILED) {
+        // the key-tile orientation of the map, over query tiles: in a skipped tile P = dS = 0 in every element.  A key
+        // tile without any computed tile runs no loop and stores the zeros dK / dV start from.
+        const int qtiles = (T + 31) / 32;
+        AttnWalk walk;
+        walk.start(tiles + ((long long)(bh / heads) * ktiles + kt) * ((qtiles + 31) / 32), qtiles);
+        int qt = walk.next();
+        if (qt < qtiles) SINGA_DKV_FETCH(32 * qt);
+        while (qt < qtiles) {
+            const int nx = walk.next();
+            tile(32 * qt, 32 * (nx < qtiles ? nx : qt));
+            qt = nx;
+        }
+    } else {
+        SINGA_DKV_FETCH(0);
+        for (int t0 = 0; t0 < T; t0 += 32) tile(t0, t0 + 32 < T ? t0 + 32 : t0);
     }
 #undef SINGA_DKV_FETCH
     if (kin) {
@@ -3626,6 +3706,75 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
     }
 }
+
+#ifndef SINGA_EMUL      // (cross-lane / workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
+// The tile map of k19 (include/singa_hip_attn_tiles.h), one workgroup per batch entry.  A wavefront takes a query tile and
+// walks its key tiles two at a time with the KEY on the lane: the tile's rows are 64 consecutive bytes each, every lane ORs
+// "unmasked" over the rows (its ballot halves are the two pairs' bits) and the ballot of each row says whether that row has an
+// unmasked key - if a row q < T has none in all of [0, S), the tile keeps all its bits.  With one mask row for all queries
+// (mst == 0) one row is read and tile 0's words serve every query tile.  Then the workgroup transposes its own words into the
+// key-tile orientation.  (The first form had the row on the lane and 16 byte loads per lane and tile, one tile after the
+// other: 21 - 226 us per launch of the default workload.)
+constexpr int ATTN_TILES_THREADS = 512;
+__global__ void __launch_bounds__(ATTN_TILES_THREADS) attn_tiles_kernel(const unsigned char* __restrict__ mask, long long msb,
+                                                                        long long mst, unsigned* rows, unsigned* __restrict__ cols,
+                                                                        int T, int S) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qtiles = (T + 31) / 32, ktiles = (S + 31) / 32, nkw = (ktiles + 31) / 32, nqw = (qtiles + 31) / 32;
+    const unsigned char* mb = mask + (long long)blockIdx.x * msb;
+    unsigned* rb = rows + (long long)blockIdx.x * qtiles * nkw;
+    unsigned* cb = cols + (long long)blockIdx.x * ktiles * nqw;
+    const int qcomp = mst == 0 ? 1 : qtiles;
+    for (int qt = wave; qt < qcomp; qt += ATTN_TILES_THREADS / 64) {
+        const int nrow = mst == 0 ? 1 : (T - 32 * qt < 32 ? T - 32 * qt : 32);     // rows to look at (one stands for all)
+        const unsigned char* m0 = mb + (long long)(32 * qt) * mst;
+        unsigned rowlive = 0, word = 0;                 // wave-uniform: rows with an unmasked key; bits of the current word
+        for (int kp = 0; kp < ktiles; kp += 2) {
+            const int kk = 32 * kp + lane;
+            const bool kin = kk < S;
+            const unsigned char* mk = m0 + (kin ? kk : S - 1);
+            bool klive = false;
+            auto look = [&](int r) __attribute__((always_inline)) {
+                const bool u = kin & (mk[(long long)r * mst] == 0);
+                klive |= u;
+                if (__ballot(u) != 0ull) rowlive |= 1u << r;
+            };
+            if (nrow == 1) {
+                look(0);
+            } else {                                    // 32 loads in flight; past the last row the last row again
+#pragma unroll
+                for (int r = 0; r < 32; ++r) look(r < nrow ? r : nrow - 1);
+            }
+            const unsigned long long kb = __ballot(klive);
+            if ((unsigned)kb != 0u) word |= 1u << (kp & 31);
+            if ((unsigned)(kb >> 32) != 0u) word |= 1u << ((kp + 1) & 31);          // (tile kp + 1 >= ktiles: no key in, no bit)
+            if (((kp + 2) & 31) == 0 || kp + 2 >= ktiles) {
+                if (lane == 0) rb[qt * nkw + (kp >> 5)] = word;
+                word = 0;
+            }
+        }
+        const unsigned valid = nrow >= 32 ? 0xffffffffu : (1u << nrow) - 1u;
+        if ((~rowlive & valid) != 0u && lane == 0) {    // a query masked in all keys spreads its weight over them: compute every tile
+            for (int kw = 0; kw < nkw; ++kw) {          // (lane 0 again: its stores to one word keep their order)
+                const int kend = ktiles - 32 * kw;
+                rb[qt * nkw + kw] = kend >= 32 ? 0xffffffffu : (1u << kend) - 1u;
+            }
+        }
+    }
+    __syncthreads();
+    if (mst == 0) {
+        for (int idx = nkw + (int)threadIdx.x; idx < qtiles * nkw; idx += ATTN_TILES_THREADS) rb[idx] = rb[idx % nkw];
+        __syncthreads();
+    }
+    for (int idx = (int)threadIdx.x; idx < ktiles * nqw; idx += ATTN_TILES_THREADS) {
+        const int kt = idx / nqw, qw = idx - kt * nqw;
+        const int qend = qtiles - 32 * qw < 32 ? qtiles - 32 * qw : 32;
+        unsigned word = 0;
+        for (int t = 0; t < qend; ++t) word |= ((rb[(32 * qw + t) * nkw + (kt >> 5)] >> (kt & 31)) & 1u) << t;
+        cb[idx] = word;
+    }
+}
+#endif
 
 
 // ------------------------------------------------------------------------------------------------ column sums
@@ -8126,27 +8275,35 @@ int singa_masked_softmax_bwd(const float* p, const float* gp, const unsigned cha
     return check_launch("masked_softmax_bwd");
 }
 
-int singa_attn_fwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
-                   long long mask_stride_t, float* ctx, float* lse, int BH, int T, int S, int heads, int DK, int DV,
-                   int token_major, long long ld_q, long long ld_k, long long ld_v, float scale, void* stream) {
-    if (!q || !k || !v || !mask || !ctx || !lse) return fail(SINGA_E_NULL, "attn_fwd: null pointer");
+// k19 behind singa_attn_fwd / singa_attn_bwd (tile maps null: every tile) and their tiled forms (include/singa_hip_attn_tiles.h)
+static int attn_fwd_launch(const char* name, const float* q, const float* k, const float* v, const unsigned char* mask,
+                           long long mask_stride_b, long long mask_stride_t, float* ctx, float* lse, int BH, int T, int S, int heads,
+                           int DK, int DV, int token_major, long long ld_q, long long ld_k, long long ld_v, float scale,
+                           const uint32_t* tile_rows, void* stream) {
+    if (!q || !k || !v || !mask || !ctx || !lse) return fail_at(SINGA_E_NULL, name, "null pointer");
     if (DK != 32 || DV != 64) return fail(SINGA_E_SHAPE, "attn: built for 32 key / 64 value channels per head");
     if (heads <= 0 || BH % heads) return fail(SINGA_E_SHAPE, "attn: BH must be batch x heads");
     if (BH <= 0 || T <= 0 || S <= 0) return SINGA_OK;
     AttnPitch ld;
     if (!attn_pitch(token_major, heads, ld_q, ld_k, ld_v, q, k, v, &ld)) return fail(SINGA_E_SHAPE, "attn: token pitches must be multiples of 4 floats, at least heads * D, 16-byte aligned bases");
     const long long waves = (long long)BH * ((T + 31) / 32);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)(((waves + 3) / 4 + 7) / 8 * 8)), dim3(256), 0, (hipStream_t)stream, q, k, v, mask,
-                       mask_stride_b, mask_stride_t, ctx, lse, BH, T, S, heads, token_major ? 1 : 0, scale, ld);
-    return check_launch("attn_fwd");
+    const dim3 grid((unsigned)(((waves + 3) / 4 + 7) / 8 * 8));
+    if (tile_rows)
+        hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, mask, mask_stride_b, mask_stride_t,
+                           ctx, lse, BH, T, S, heads, token_major ? 1 : 0, scale, ld, tile_rows);
+    else
+        hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, mask, mask_stride_b, mask_stride_t,
+                           ctx, lse, BH, T, S, heads, token_major ? 1 : 0, scale, ld, nullptr);
+    return check_launch(name);
 }
 
-int singa_attn_bwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
-                   long long mask_stride_t, const float* ctx, const float* lse, const float* g_ctx, float* g_q, float* g_k,
-                   float* g_v, float* dsum, int BH, int T, int S, int heads, int DK, int DV, int token_major, long long ld_q,
-                   long long ld_k, long long ld_v, float scale, void* stream) {
+static int attn_bwd_launch(const char* name, const float* q, const float* k, const float* v, const unsigned char* mask,
+                           long long mask_stride_b, long long mask_stride_t, const float* ctx, const float* lse, const float* g_ctx,
+                           float* g_q, float* g_k, float* g_v, float* dsum, int BH, int T, int S, int heads, int DK, int DV,
+                           int token_major, long long ld_q, long long ld_k, long long ld_v, float scale, const uint32_t* tile_rows,
+                           const uint32_t* tile_cols, void* stream) {
     if (!q || !k || !v || !mask || !ctx || !lse || !g_ctx || !g_q || !g_k || !g_v || !dsum)
-        return fail(SINGA_E_NULL, "attn_bwd: null pointer");
+        return fail_at(SINGA_E_NULL, name, "null pointer");
     if (DK != 32 || DV != 64) return fail(SINGA_E_SHAPE, "attn: built for 32 key / 64 value channels per head");
     if (heads <= 0 || BH % heads) return fail(SINGA_E_SHAPE, "attn: BH must be batch x heads");
     if (BH <= 0 || T <= 0 || S <= 0) return SINGA_OK;
@@ -8154,11 +8311,68 @@ int singa_attn_bwd(const float* q, const float* k, const float* v, const unsigne
     if (!attn_pitch(token_major, heads, ld_q, ld_k, ld_v, q, k, v, &ld) || ((uintptr_t)g_q & 15) || ((uintptr_t)g_k & 15) || ((uintptr_t)g_v & 15))
         return fail(SINGA_E_SHAPE, "attn: token pitches must be multiples of 4 floats, at least heads * D, 16-byte aligned bases");
     const long long wq = (long long)BH * ((T + 31) / 32), wk = (long long)BH * ((S + 31) / 32);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((unsigned)(((wq + 3) / 4 + 7) / 8 * 8)), dim3(256), 0, (hipStream_t)stream, q, k, v, mask,
-                       mask_stride_b, mask_stride_t, ctx, lse, g_ctx, g_q, dsum, BH, T, S, heads, token_major ? 1 : 0, scale, ld);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((unsigned)(((wk + 3) / 4 + 7) / 8 * 8)), dim3(256), 0, (hipStream_t)stream, q, k, v, mask,
-                       mask_stride_b, mask_stride_t, lse, dsum, g_ctx, g_k, g_v, BH, T, S, heads, token_major ? 1 : 0, scale, ld);
-    return check_launch("attn_bwd");
+    const dim3 gq((unsigned)(((wq + 3) / 4 + 7) / 8 * 8)), gk((unsigned)(((wk + 3) / 4 + 7) / 8 * 8));
+    const int tm = token_major ? 1 : 0;
+    if (tile_rows)
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, dim3(256), 0, (hipStream_t)stream, q, k, v, mask, mask_stride_b, mask_stride_t,
+                           ctx, lse, g_ctx, g_q, dsum, BH, T, S, heads, tm, scale, ld, tile_rows);
+    else
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, dim3(256), 0, (hipStream_t)stream, q, k, v, mask, mask_stride_b, mask_stride_t,
+                           ctx, lse, g_ctx, g_q, dsum, BH, T, S, heads, tm, scale, ld, nullptr);
+    if (tile_cols)
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 1>), dim3((unsigned)((wk + 7) / 8 * 8)), dim3(64), 0, (hipStream_t)stream, q, k, v,
+                           mask, mask_stride_b, mask_stride_t, lse, dsum, g_ctx, g_k, g_v, BH, T, S, heads, tm, scale, ld, tile_cols);
+    else
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 4>), gk, dim3(256), 0, (hipStream_t)stream, q, k, v, mask, mask_stride_b, mask_stride_t,
+                           lse, dsum, g_ctx, g_k, g_v, BH, T, S, heads, tm, scale, ld, nullptr);
+    return check_launch(name);
+}
+
+int singa_attn_fwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
+                   long long mask_stride_t, float* ctx, float* lse, int BH, int T, int S, int heads, int DK, int DV,
+                   int token_major, long long ld_q, long long ld_k, long long ld_v, float scale, void* stream) {
+    return attn_fwd_launch("attn_fwd", q, k, v, mask, mask_stride_b, mask_stride_t, ctx, lse, BH, T, S, heads, DK, DV, token_major,
+                           ld_q, ld_k, ld_v, scale, nullptr, stream);
+}
+
+int singa_attn_bwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
+                   long long mask_stride_t, const float* ctx, const float* lse, const float* g_ctx, float* g_q, float* g_k,
+                   float* g_v, float* dsum, int BH, int T, int S, int heads, int DK, int DV, int token_major, long long ld_q,
+                   long long ld_k, long long ld_v, float scale, void* stream) {
+    return attn_bwd_launch("attn_bwd", q, k, v, mask, mask_stride_b, mask_stride_t, ctx, lse, g_ctx, g_q, g_k, g_v, dsum, BH, T, S,
+                           heads, DK, DV, token_major, ld_q, ld_k, ld_v, scale, nullptr, nullptr, stream);
+}
+
+int singa_attn_tiles(const unsigned char* mask, long long mask_stride_b, long long mask_stride_t, uint32_t* tile_rows,
+                     uint32_t* tile_cols, int B, int T, int S, void* stream) {
+    const char* name = "attn_tiles";
+    if (!mask || !tile_rows || !tile_cols) return fail_at(SINGA_E_NULL, name, "null pointer");
+    if (mask_stride_b < 0 || mask_stride_t < 0) return fail_at(SINGA_E_SHAPE, name, "mask strides must not be negative");
+    if (B <= 0 || T <= 0 || S <= 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, name, "not part of the emulation build");
+#else
+    hipLaunchKernelGGL(attn_tiles_kernel, dim3((unsigned)B), dim3(ATTN_TILES_THREADS), 0, (hipStream_t)stream, mask, mask_stride_b, mask_stride_t,
+                       tile_rows, tile_cols, T, S);
+    return check_launch(name);
+#endif
+}
+
+int singa_attn_tiled_fwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
+                         long long mask_stride_t, float* ctx, float* lse, int BH, int T, int S, int heads, int DK, int DV,
+                         int token_major, long long ld_q, long long ld_k, long long ld_v, float scale, const uint32_t* tile_rows,
+                         void* stream) {
+    return attn_fwd_launch("attn_tiled_fwd", q, k, v, mask, mask_stride_b, mask_stride_t, ctx, lse, BH, T, S, heads, DK, DV,
+                           token_major, ld_q, ld_k, ld_v, scale, tile_rows, stream);
+}
+
+int singa_attn_tiled_bwd(const float* q, const float* k, const float* v, const unsigned char* mask, long long mask_stride_b,
+                         long long mask_stride_t, const float* ctx, const float* lse, const float* g_ctx, float* g_q, float* g_k,
+                         float* g_v, float* dsum, int BH, int T, int S, int heads, int DK, int DV, int token_major, long long ld_q,
+                         long long ld_k, long long ld_v, float scale, const uint32_t* tile_rows, const uint32_t* tile_cols,
+                         void* stream) {
+    return attn_bwd_launch("attn_tiled_bwd", q, k, v, mask, mask_stride_b, mask_stride_t, ctx, lse, g_ctx, g_q, g_k, g_v, dsum, BH,
+                           T, S, heads, DK, DV, token_major, ld_q, ld_k, ld_v, scale, tile_rows, tile_cols, stream);
 }
 
 long long singa_colsum_work(long long M, int n) {

@@ -275,7 +275,14 @@ class MultiHeadAttention(nn.Module):
         return ops.layer_norm_residual(self.out_transform(out), None, self.layer_norm)
 
 
-def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels):
+def _uses_k19(module, key_channels, hidden_channels):
+    """The shipped head geometry, 32 key and 64 value channels per head: the dense attention runs on k19."""
+    return key_channels // module.num_heads == 32 and hidden_channels // module.num_heads == 64
+
+
+def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels, tiles=None):
+    """tiles: `ops.attn_tiles` of attn_mask (k19 then skips the score tiles that are masked in every element); the generic
+    branch does not look at it."""
     B, heads = Q.size(0), module.num_heads
     dk, dv = key_channels // heads, hidden_channels // heads
     scale = 1.0 / math.sqrt(dk)
@@ -292,7 +299,7 @@ def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels):
         else:
             q_s, k_s, v_s = module.W_Q(Q), module.W_K(K), module.W_V(V)
         context = ops.attention(q_s.view(B, -1, heads, dk), k_s.view(B, -1, heads, dk), v_s.view(B, -1, heads, dv), attn_mask,
-                                scale, heads, token_major=True)
+                                scale, heads, token_major=True, tiles=tiles)
         return ops.layer_norm_residual(module.linear(context.view(B, -1, hidden_channels)), Q, module.layer_norm)
     q_s = module.W_Q(Q).view(B, -1, heads, dk).transpose(1, 2)
     k_s = module.W_K(K).view(B, -1, heads, dk).transpose(1, 2)
@@ -317,8 +324,11 @@ class MultiHeadAttention2(nn.Module):
         self.linear = Linear(hidden_channels, hidden_channels, device=device)
         self.layer_norm = LayerNorm(hidden_channels, device=device)
 
-    def forward(self, Q, K, V, attn_mask):
-        return _dense_attention(self, Q, K, V, attn_mask, self.keys_channels, self.hidden_channls)
+    def uses_k19(self):
+        return _uses_k19(self, self.keys_channels, self.hidden_channls)
+
+    def forward(self, Q, K, V, attn_mask, tiles=None):
+        return _dense_attention(self, Q, K, V, attn_mask, self.keys_channels, self.hidden_channls, tiles)
 
 
 class MultiHeadDeAttention(nn.Module):
@@ -333,8 +343,11 @@ class MultiHeadDeAttention(nn.Module):
         self.linear = Linear(hidden_channels, hidden_channels, device=device)
         self.layer_norm = LayerNorm(hidden_channels, device=device)
 
-    def forward(self, Q, K, V, attn_mask):
-        return _dense_attention(self, Q, K, V, attn_mask, self.key_channels, self.hidden_channels)
+    def uses_k19(self):
+        return _uses_k19(self, self.key_channels, self.hidden_channels)
+
+    def forward(self, Q, K, V, attn_mask, tiles=None):
+        return _dense_attention(self, Q, K, V, attn_mask, self.key_channels, self.hidden_channels, tiles)
 
 
 class PoswiseFeedForwardNet(nn.Module):
@@ -403,13 +416,13 @@ class EncoderLayer2(nn.Module):
         self.layer_norm = LayerNorm(config.hidden_channels, device=device)
         self.pos_ffn = PoswiseFeedForwardNet(config.hidden_channels, device=device)
 
-    def forward(self, node_attr, edges, idx, atom_msa_outputs, atom_mask, dm, before_cross=None):
+    def forward(self, node_attr, edges, idx, atom_msa_outputs, atom_mask, dm, before_cross=None, cross_tiles=None):
         msa_outputs = self.enc_self_attn(node_attr, edges)
         if idx == 2 or idx == 5:                                                   # CP:262
             if before_cross is not None:
                 before_cross(idx)
             kv = self.proj(atom_msa_outputs[idx])
-            cross = self.cross_attn(dm.dense(msa_outputs), kv, kv, atom_mask)
+            cross = self.cross_attn(dm.dense(msa_outputs), kv, kv, atom_mask, cross_tiles)
             msa_outputs = ops.layer_norm_residual(msa_outputs, dm.gather(cross.reshape(-1, cross.size(-1))), self.layer_norm)
         return self.pos_ffn(msa_outputs)
 
@@ -477,8 +490,12 @@ class Encoder2(nn.Module):
             prep = self.prepare(aa_pos, aa_batch, int(aa_batch.max()) + 1 if batch_size is None else batch_size, knn)
         dm, edges = prep["dense"], prep["edges"]
         node_attr = ops.linear_add(aa_feature, self.aa_emb.weight, self.aa_emb.bias, self.laplacian_emb(aa_laplacian))
+        # layers 2 and 5 attend to the protein atoms under one mask: one tile map for both (ops.attn_tiles)
+        cross_tiles = None
+        if len(self.layers) > 2 and self.layers[2].cross_attn.uses_k19():
+            cross_tiles = ops.attn_tiles(atom_mask, dm.mx, atom_mask.size(2))
         for idx, layer in enumerate(self.layers):
-            node_attr = layer(node_attr, edges, idx, atom_msa_outputs, atom_mask, dm, before_cross)
+            node_attr = layer(node_attr, edges, idx, atom_msa_outputs, atom_mask, dm, before_cross, cross_tiles)
         return dm.dense(node_attr), dm.pad_mask
 
 
@@ -489,9 +506,9 @@ class DecoderLayer(nn.Module):
         self.dec_enc_attn = MultiHeadDeAttention(config.hidden_channels, config.key_channels, config.num_heads, device=device)
         self.pos_ffn = PoswiseFeedForwardDeNet(config.hidden_channels, device=device)
 
-    def forward(self, dec_inputs, enc_outputs, dec_self_attn_mask, dec_enc_attn_mask):
-        dec_outputs = self.dec_self_attn(dec_inputs, dec_inputs, dec_inputs, dec_self_attn_mask)
-        dec_outputs = self.dec_enc_attn(dec_outputs, enc_outputs, enc_outputs, dec_enc_attn_mask)
+    def forward(self, dec_inputs, enc_outputs, dec_self_attn_mask, dec_enc_attn_mask, self_tiles=None, enc_tiles=None):
+        dec_outputs = self.dec_self_attn(dec_inputs, dec_inputs, dec_inputs, dec_self_attn_mask, self_tiles)
+        dec_outputs = self.dec_enc_attn(dec_outputs, enc_outputs, enc_outputs, dec_enc_attn_mask, enc_tiles)
         return self.pos_ffn(dec_outputs)
 
 
@@ -527,8 +544,13 @@ class Decoder(nn.Module):
         causal = torch.triu(torch.ones(n, n, dtype=torch.bool, device=dev), diagonal=1)
         dec_self_attn_mask = pad | causal.unsqueeze(0)
         dec_enc_attn_mask = enc_pad_mask.expand(b, tgt_len + num, enc_pad_mask.size(2))
+        # the two masks serve every layer: one tile map each (ops.attn_tiles), made here and reused forward and backward
+        self_tiles = enc_tiles = None
+        if len(self.layers) and self.layers[0].dec_self_attn.uses_k19():
+            self_tiles = ops.attn_tiles(dec_self_attn_mask, n, n)
+            enc_tiles = ops.attn_tiles(dec_enc_attn_mask, n, dec_enc_attn_mask.size(2))
         for layer in self.layers:
-            dec_inputs = layer(dec_inputs, enc_outputs, dec_self_attn_mask, dec_enc_attn_mask)
+            dec_inputs = layer(dec_inputs, enc_outputs, dec_self_attn_mask, dec_enc_attn_mask, self_tiles, enc_tiles)
         return dec_inputs
 
 

@@ -1222,7 +1222,7 @@ class _Attention(torch.autograd.Function):
     projection's backward takes them without a copy."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, scale, heads, token_major):
+    def forward(ctx, q, k, v, mask, scale, heads, token_major, tile_rows=None, tile_cols=None):
         assert mask.dtype == torch.bool and mask.dim() == 3 and mask.stride(2) == 1 and mask.is_cuda
         if token_major:
             B, T, _, DK = q.shape
@@ -1241,15 +1241,22 @@ class _Attention(torch.autograd.Function):
         assert mask.shape[0] * heads == BH and mask.shape[2] == S and mask.shape[1] in (1, T)
         ctx.mst = 0 if mask.shape[1] == 1 else mask.stride(1)
         lse = torch.empty(BH, T, 2, device=q.device, dtype=torch.float32)       # (row maximum, 1 / row sum)
-        _chk(_lib.lib().singa_attn_fwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), BH, T, S, heads,
-                                       DK, DV, int(token_major), lq, lk, lv, scale, _stream()), "singa_attn_fwd")
-        ctx.save_for_backward(q, k, v, mask, out, lse)
+        if tile_rows is None:
+            _chk(_lib.lib().singa_attn_fwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), BH, T, S, heads,
+                                           DK, DV, int(token_major), lq, lk, lv, scale, _stream()), "singa_attn_fwd")
+            ctx.save_for_backward(q, k, v, mask, out, lse)
+        else:
+            _check_tiles(tile_rows, tile_cols, mask.shape[0], T, S)
+            _chk(_lib.lib().singa_attn_tiled_fwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), BH, T, S,
+                                                 heads, DK, DV, int(token_major), lq, lk, lv, scale, _p(tile_rows), _stream()),
+                 "singa_attn_tiled_fwd")
+            ctx.save_for_backward(q, k, v, mask, out, lse, tile_rows, tile_cols)
         ctx.scale, ctx.heads, ctx.tm, ctx.dims, ctx.ld = scale, heads, bool(token_major), (BH, T, S, DK, DV), (lq, lk, lv)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        q, k, v, mask, out, lse = ctx.saved_tensors
+        q, k, v, mask, out, lse, *tiles = ctx.saved_tensors
         g = g.contiguous()
         BH, T, S, DK, DV = ctx.dims
         lq, lk, lv = ctx.ld
@@ -1280,17 +1287,50 @@ class _Attention(torch.autograd.Function):
             # the kernels address the gradients with the operands' pitches: they agree by construction
             assert (lq, lk, lv) == (q.stride(1), k.stride(1), v.stride(1))
         dsum = torch.empty(BH, T, device=q.device, dtype=torch.float32)
-        _chk(_lib.lib().singa_attn_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g), _p(gq),
-                                       _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk, lv, ctx.scale,
-                                       _stream()), "singa_attn_bwd")
-        return gq, gk, gv, None, None, None, None
+        if tiles:
+            _chk(_lib.lib().singa_attn_tiled_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g),
+                                                 _p(gq), _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk,
+                                                 lv, ctx.scale, _p(tiles[0]), _p(tiles[1]), _stream()), "singa_attn_tiled_bwd")
+        else:
+            _chk(_lib.lib().singa_attn_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g), _p(gq),
+                                           _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk, lv, ctx.scale,
+                                           _stream()), "singa_attn_bwd")
+        return gq, gk, gv, None, None, None, None, None, None
 
 
-def attention(q, k, v, mask, scale, heads, token_major=False):
+def _tile_shapes(B, T, S):
+    qt, kt = (T + 31) // 32, (S + 31) // 32
+    return (B, qt, (kt + 31) // 32), (B, kt, (qt + 31) // 32)
+
+
+def _check_tiles(tile_rows, tile_cols, B, T, S):
+    for t, shape in zip((tile_rows, tile_cols), _tile_shapes(B, T, S)):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+
+
+def attn_tiles(mask, T, S):
+    """The tile map of a boolean attention mask [B, T|1, S] (include/singa_hip_attn_tiles.h): which 32 x 32 tiles of the score
+    matrix `attention(..., tiles=...)` has to compute.  It depends on the mask alone: build it once per mask and pass it to
+    every attention that uses that mask.  Returns (tile_rows, tile_cols), the two orientations of the bits."""
+    assert mask.dtype == torch.bool and mask.dim() == 3 and mask.stride(2) == 1 and mask.is_cuda
+    assert mask.shape[2] == S and mask.shape[1] in (1, T)
+    B = mask.shape[0]
+    rs, cs = _tile_shapes(B, T, S)
+    rows = torch.empty(rs, device=mask.device, dtype=torch.int32)
+    cols = torch.empty(cs, device=mask.device, dtype=torch.int32)
+    mst = 0 if mask.shape[1] == 1 else mask.stride(1)
+    _chk(_lib.lib().singa_attn_tiles(_p(mask), mask.stride(0), mst, _p(rows), _p(cols), B, T, S, _stream()), "singa_attn_tiles")
+    return rows, cols
+
+
+def attention(q, k, v, mask, scale, heads, token_major=False, tiles=None):
     """Dense attention core (k19) for q[B*heads,T,32], k[B*heads,S,32], v[B*heads,S,64] - or, token_major, q[B,T,heads,32],
     k[B,S,heads,32], v[B,S,heads,64] (dense, or column blocks of a fused projection output) -> context in the same layout
-    - and a boolean mask [B, T|1, S]."""
-    return _Attention.apply(q, k, v, mask, scale, heads, token_major)
+    - and a boolean mask [B, T|1, S].  tiles: `attn_tiles(mask, T, S)` of the same mask - the kernels then skip the score
+    tiles that are masked in every element; the result is the same."""
+    if tiles is None:
+        return _Attention.apply(q, k, v, mask, scale, heads, token_major)
+    return _Attention.apply(q, k, v, mask, scale, heads, token_major, tiles[0], tiles[1])
 
 
 class _LayerNorm256(torch.autograd.Function):
