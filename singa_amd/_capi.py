@@ -219,6 +219,12 @@ _ATTN_TILES_SIGS = {
 }
 ATTN_TILES_EXPORTS = tuple(_ATTN_TILES_SIGS)
 
+# include/singa_hip_bf16.h: the real GEMM with bf16 operands (`precision="bf16"` of ops._gemm); a table of its own
+_BF16_SIGS = {
+    "singa_gemm_bf16": (_SIGS["singa_gemm_f32"][0], I32),
+}
+BF16_EXPORTS = tuple(_BF16_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -226,7 +232,7 @@ def bind(path):
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
-            list(_ATTN_TILES_SIGS.items()):
+            list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

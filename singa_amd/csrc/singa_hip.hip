@@ -31,6 +31,7 @@
 #include "../../include/singa_hip_attn_tiles.h"
 #include "../../include/singa_hip_prefix.h"
 #include "../../include/singa_hip_data.h"
+#include "../../include/singa_hip_bf16.h"
 #include "so3_index.h"
 
 namespace {
@@ -5151,13 +5152,84 @@ __device__ __forceinline__ void gemm_k_loop(AllC all_c, long long r_begin, long 
     }
 }
 
-template <bool A_RC, bool B_RC, int CFG>
-__global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
+// ---- k7b: the same GEMM with bf16 operands (singa_gemm_bf16, include/singa_hip_bf16.h).  Everything up to the registers is
+// k7's: the tile walk, the f32 float4 global loads with their masks, the K loop, asum, the epilogue.  The registers are
+// rounded to bf16 (round to nearest even: v_cvt_pk_bf16_f32) on their way to LDS, the images hold bf16, and a K step of 32
+// is two v_mfma_f32_32x32x16_bf16 per 32 x 32 block (f32 products and sums; the accumulator map is the one of 32x32x2f32, so
+// the epilogue is k7's).  Lane l (row or column l % 32, half h = l / 32) gives the MFMA the 8 reduction indices 8 h .. 8 h + 7
+// of its 16: MFMA m of a step takes r = 16 m + 8 h + j, j = 0..7, from both operands.
+//   Reduction-contiguous image [row][r], 80 bytes a row (64 of data): a register's four r are one ds_write_b64, a lane's 8 r one
+//   ds_read_b128 at 16-byte slot 5 row + 2 m + h - the 16 rows of each of ds_read_b128's lane groups ({0-3, 12-15, 20-27},
+//   ...: all residues mod 16) times an odd slot pitch land in 16 different slots of the 256-byte bank row.
+//   Output-contiguous image [r][col] as it arrives (a register = four columns of one r = one ds_write_b64), read TRANSPOSED by
+//   ds_read_b64_tr_b16: per 16 lanes a block of 4 r x 16 columns, lane 4 q + p of the group gives the address of (r q, columns
+//   4 p .. 4 p + 3) and lane i receives column i of the four r - two reads (r and r + 4) make a lane's 8.  Addresses are
+//   multiples of 8 bytes (the instruction returns other data, silently, when they are not); EXEC is full wherever the K loop
+//   runs (no wavefront leaves the kernel early, the branches around the MFMAs are wave-uniform).  Row pitch 2 W + 64 bytes for a
+//   W-wide tile (64 bytes for W = 32), i.e. 16 or 48 dwords mod 64: the four r of a 32-lane half's read lie in four different
+//   16-bank quarters, each holding the half's 32 columns - no conflict.  (The other route - transposing in the store, four
+//   ds_write_b16 per register into a [col][r] image - costs 32 LDS stores per thread and K step in the (0, 0) form instead of 8.)
+//   Both pitches are derived from the bank rules as described; no LDS bank-conflict counter was read for this kernel.
+constexpr int GEMM_BF16_PR = 40;                                    // bf16 per row of a [row][r] image
+constexpr int gemm_bf16_pitch(int w) { return w == 32 ? 32 : w + 32; }   // bf16 per row of an [r][W columns] image
+#ifndef SINGA_EMUL      // (bf16 matrix cores and the transposing LDS read: no stand-in in the CPU emulation build of tests/emul)
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float floatx2 __attribute__((ext_vector_type(2)));
+struct GemmBf16 {
+    typedef bf16x8 Frag;
+    static __device__ __forceinline__ uint2 pack(const float4& v) {              // bf16(x) | bf16(y) << 16, bf16(z) | bf16(w) << 16
+        const floatx2 lo = {v.x, v.y}, hi = {v.z, v.w};
+        return make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)),
+                          __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
+    }
+    // register j of the thread: float4 kq of row rr + 32 j
+    static __device__ __forceinline__ void store_rc(float* S, const float4* reg, unsigned mask, int n, int rr, int kq) {
+        char* base = reinterpret_cast<char*>(S) + rr * (2 * GEMM_BF16_PR) + 8 * kq;
+#pragma unroll
+        for (int j = 0; j < n; ++j)
+            *reinterpret_cast<uint2*>(base + 32 * j * (2 * GEMM_BF16_PR)) =
+                pack((mask >> j) & 1u ? reg[j] : make_float4(0.f, 0.f, 0.f, 0.f));
+    }
+    // register j of the thread: columns 4 c4 .. + 3 of reduction row rq + rows j
+    static __device__ __forceinline__ void store_oc(float* S, const float4* reg, unsigned mask, int pitch, int n, int width4, int tid) {
+        const int c4 = tid % width4, rq = tid / width4, rows = 256 / width4;
+#pragma unroll
+        for (int j = 0; j < n; ++j)
+            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(S) + (rq + rows * j) * (2 * pitch) + 8 * c4) =
+                pack((mask >> j) & 1u ? reg[j] : make_float4(0.f, 0.f, 0.f, 0.f));
+    }
+    // the fragment of MFMA m (reduction indices 16 m .. 16 m + 15 of the step) of the 32-wide block whose lane-l31 row / column
+    // is `col` (blocks start at multiples of 32)
+    static __device__ __forceinline__ Frag frag(const float* S, bool rc, int pitch, int col, int m, int lane) {
+        const int half = lane >> 5;
+        const char* base = reinterpret_cast<const char*>(S);
+        if (rc) return __builtin_bit_cast(Frag, *reinterpret_cast<const uint4*>(base + col * (2 * GEMM_BF16_PR) + 32 * m + 16 * half));
+        const int q = (lane >> 2) & 3, p = lane & 3, c0 = (col & ~31) + (lane & 16);
+        const char* a = base + (16 * m + 8 * half + q) * (2 * pitch) + 2 * (c0 + 4 * p);
+        typedef __attribute__((address_space(3))) bf16x4* lds4;
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)a);
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(a + 4 * (2 * pitch)));
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+    static __device__ __forceinline__ floatx16 mfma(const Frag& a, const Frag& b, const floatx16& c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+#endif
+
+// The body of k7 (BF = void) and k7b (BF = GemmBf16): one workgroup, one tile.
+template <bool A_RC, bool B_RC, int CFG, class BF>
+__device__ __forceinline__ void gemm_real_tile(const GemmBatch& gb) {
+    constexpr bool BF16 = !std::is_void<BF>::value;
     constexpr int BM = CFG == 2 ? 32 : (CFG == 3 ? 64 : 128), BN = CFG == 1 ? 32 : (CFG == 3 ? 64 : 128), BK = 32, PR = BK + 4;
     constexpr int MT = CFG == 0 ? 2 : 1, NT = CFG == 0 ? 2 : 1;   // 32 x 32 MFMA tiles per wavefront
     constexpr int NA = BM / 32, NB = BN / 32;                      // float4 loads per thread and K step
-    constexpr int LDA = BM + 4, LDB = BN + 4;                      // pitches of the [r][col] images
-    constexpr int SZA = A_RC ? BM * PR : BK * LDA, SZB = B_RC ? BN * PR : BK * LDB;
+    constexpr int LDA = BF16 ? gemm_bf16_pitch(BM) : BM + 4, LDB = BF16 ? gemm_bf16_pitch(BN) : BN + 4;   // pitches of the [r][col] images
+    // image sizes in floats (a bf16 image: two elements per float)
+    constexpr int SZA = BF16 ? (A_RC ? BM * GEMM_BF16_PR : BK * LDA) / 2 : (A_RC ? BM * PR : BK * LDA);
+    constexpr int SZB = BF16 ? (B_RC ? BN * GEMM_BF16_PR : BK * LDB) / 2 : (B_RC ? BN * PR : BK * LDB);
     constexpr int PE = 32 * NT + 4;                                // epilogue staging pitch (floats)
     constexpr int SMEM = 2 * SZA + 2 * SZB > 4 * 32 * PE ? 2 * SZA + 2 * SZB : 4 * 32 * PE;
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
@@ -5253,10 +5325,17 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
                 asum4.z = fmaf(wj, s.a[j].z, asum4.z); asum4.w = fmaf(wj, s.a[j].w, asum4.w);
             }
         }
-        if (A_RC) store_rc(As0 + buf * SZA, s.a, s.ma, NA);
-        else store_oc(As0 + buf * SZA, s.a, s.ma, LDA, NA, BM / 4);
-        if (B_RC) store_rc(Bs0 + buf * SZB, s.b, s.mb, NB);
-        else store_oc(Bs0 + buf * SZB, s.b, s.mb, LDB, NB, BN / 4);
+        if constexpr (BF16) {
+            if (A_RC) BF::store_rc(As0 + buf * SZA, s.a, s.ma, NA, rr, kq);
+            else BF::store_oc(As0 + buf * SZA, s.a, s.ma, LDA, NA, BM / 4, tid);
+            if (B_RC) BF::store_rc(Bs0 + buf * SZB, s.b, s.mb, NB, rr, kq);
+            else BF::store_oc(Bs0 + buf * SZB, s.b, s.mb, LDB, NB, BN / 4, tid);
+        } else {
+            if (A_RC) store_rc(As0 + buf * SZA, s.a, s.ma, NA);
+            else store_oc(As0 + buf * SZA, s.a, s.ma, LDA, NA, BM / 4);
+            if (B_RC) store_rc(Bs0 + buf * SZB, s.b, s.mb, NB);
+            else store_oc(Bs0 + buf * SZB, s.b, s.mb, LDB, NB, BN / 4);
+        }
     };
     // the wavefront's MT / NT 32-wide blocks
     const int ia = wrow + l31, jb = wcol + l31;
@@ -5284,6 +5363,31 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
     auto compute = [&](auto all_c, int buf, int nt8) __attribute__((always_inline)) {
         const float* Sa = As0 + buf * SZA;
         const float* Sb = Bs0 + buf * SZB;
+        if constexpr (BF16) {            // two MFMAs of 16 reduction indices per block; the second only where k-groups 2, 3 hold data
+            typename BF::Frag fa[2][MT], fb[2][NT];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+#pragma unroll
+                for (int a = 0; a < MT; ++a) fa[m][a] = BF::frag(Sa, A_RC, LDA, ia + 32 * a, m, lane);
+#pragma unroll
+                for (int b = 0; b < NT; ++b) fb[m][b] = BF::frag(Sb, B_RC, LDB, jb + 32 * b, m, lane);
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                if (2 * m >= nt8) break;
+#pragma unroll
+                for (int a = 0; a < MT; ++a)
+#pragma unroll
+                    for (int b = 0; b < NT; ++b) {
+                        if constexpr (!decltype(all_c)::value) {      // ragged tiles skip padding blocks
+                            if ((blkv >> (a * NT + b)) & 1u) acc[a][b] = BF::mfma(fa[m][a], fb[m][b], acc[a][b]);
+                        } else {
+                            acc[a][b] = BF::mfma(fa[m][a], fb[m][b], acc[a][b]);
+                        }
+                    }
+            }
+            return;
+        }
         float fa[2][MT][4], fb[2][NT][4];
 #pragma unroll
         for (int a = 0; a < MT; ++a) gemm_frag<PR>(Sa, A_RC, LDA, ia + 32 * a, 0, half, fa[0][a]);
@@ -5345,7 +5449,8 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
         }
     };
     auto k_loop = [&](auto all_c) __attribute__((always_inline)) {
-        gemm_k_loop<BK, NA, NB, SINGA_GEMM_PIPE && CFG == 0>(all_c, r_begin, nsteps, last8, load_ab, store_ab, compute, pipeline);
+        // (`pipeline` places k7's 64 MFMAs of a step: k7b, with 8, takes the fenced phases)
+        gemm_k_loop<BK, NA, NB, SINGA_GEMM_PIPE && CFG == 0 && !BF16>(all_c, r_begin, nsteps, last8, load_ab, store_ab, compute, pipeline);
     };
     // `full` tiles of ungrouped operands take the unpredicated loads
     if (full && P.a_group == (1 << 30) && P.b_group == (1 << 30)) k_loop(std::true_type{});
@@ -5405,6 +5510,17 @@ __global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
         }
     }
 }
+
+template <bool A_RC, bool B_RC, int CFG>
+__global__ void __launch_bounds__(256, 2) gemm_f32_kernel(GemmBatch gb) {
+    gemm_real_tile<A_RC, B_RC, CFG, void>(gb);
+}
+#ifndef SINGA_EMUL
+template <bool A_RC, bool B_RC, int CFG>
+__global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(GemmBatch gb) {
+    gemm_real_tile<A_RC, B_RC, CFG, GemmBf16>(gb);
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------ k7c: complex f32 MFMA GEMM (3M)
 // The order-m > 0 blocks of an SO(2) convolution (EF:677-729) are COMPLEX products: with x = x_+m + i x_-m and W = Wr + i Wi
@@ -7472,9 +7588,11 @@ int singa_gemm_force_cfg(int cfg) {
     return SINGA_OK;
 }
 
-int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
-    if (!probs || n < 1 || n > SINGA_GEMM_MAX) return fail(SINGA_E_SHAPE, "gemm_f32: 1..SINGA_GEMM_MAX problems per launch");
-    if (int bad = gemm_check_launch("gemm_f32", a_r_contig, b_r_contig, splits)) return bad;
+// singa_gemm_f32 and singa_gemm_bf16: the same checks, tile plan and grid; `entry` names the caller in the error text.
+static int gemm_real_launch(const char* entry, bool bf16, const singa_gemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits,
+                            void* stream) {
+    if (!probs || n < 1 || n > SINGA_GEMM_MAX) return fail_at(SINGA_E_SHAPE, entry, "1..SINGA_GEMM_MAX problems per launch");
+    if (int bad = gemm_check_launch(entry, a_r_contig, b_r_contig, splits)) return bad;
     GemmBatch gb;
     memset(&gb, 0, sizeof(gb));
     gb.n = n;
@@ -7495,25 +7613,25 @@ int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_con
     for (int k = 0; k < n; ++k) {
         const singa_gemm_t& q = probs[k];
         GemmProb& P = gb.p[k];
-        if (int bad = gemm_check_operands("gemm_f32", q)) return bad;
+        if (int bad = gemm_check_operands(entry, q)) return bad;
         // float4 accesses: the contiguous axis of each operand must be a multiple of 4 floats and 16-byte aligned
         const bool a_ok = a_r_contig ? (q.R % 4 == 0) : (q.I % 4 == 0);
         const bool b_ok = b_r_contig ? (q.R % 4 == 0) : (q.J % 4 == 0);
         if (!a_ok || !b_ok || q.lda % 4 || q.ldb % 4 || q.a_group_ld % 4 || q.b_group_ld % 4 || ((uintptr_t)q.a & 15) ||
             ((uintptr_t)q.b & 15))
-            return fail(SINGA_E_SHAPE, "gemm_f32: contiguous axes must be multiples of 4 floats and 16-byte aligned");
-        if (b_r_contig && q.b_group > 0) return fail(SINGA_E_SHAPE, "gemm_f32: a reduction-contiguous B has plain rows");
+            return fail_at(SINGA_E_SHAPE, entry, "contiguous axes must be multiples of 4 floats and 16-byte aligned");
+        if (b_r_contig && q.b_group > 0) return fail_at(SINGA_E_SHAPE, entry, "a reduction-contiguous B has plain rows");
         // float4 stores of the result: J, the row pitches and the base must be multiples of 4 floats / 16 bytes
         if (q.J % 4 || q.ldc % 4 || q.c_group_ld % 4 || q.c_split_stride % 4 || ((uintptr_t)q.c & 15) ||
             (q.bias && ((uintptr_t)q.bias & 15)))
-            return fail(SINGA_E_SHAPE, "gemm_f32: the result's columns, pitches and base must be multiples of 4 floats / 16 bytes");
+            return fail_at(SINGA_E_SHAPE, entry, "the result's columns, pitches and base must be multiples of 4 floats / 16 bytes");
         if (splits > 1 && (q.c_group > 0 || q.ldc != q.J || q.bias || q.mask || q.addend || q.relu ||
                            q.c_split_stride < (long long)q.I * q.J))
-            return fail(SINGA_E_SHAPE, "gemm_f32: split reductions write dense [I, J] partial slabs (c_split_stride apart), no epilogue options");
+            return fail_at(SINGA_E_SHAPE, entry, "split reductions write dense [I, J] partial slabs (c_split_stride apart), no epilogue options");
         if ((q.mask && q.c_group > 0) || ((uintptr_t)q.mask & 15) || ((uintptr_t)q.addend & 15))
-            return fail(SINGA_E_SHAPE, "gemm_f32: mask / addend have the result's layout (a mask: plain rows only) and are 16-byte aligned");
+            return fail_at(SINGA_E_SHAPE, entry, "mask / addend have the result's layout (a mask: plain rows only) and are 16-byte aligned");
         if (q.asum && (a_r_contig || q.a_group > 0 || q.asum_stride < q.I))
-            return fail(SINGA_E_SHAPE, "gemm_f32: asum goes with the (0, 0) form, plain A rows, a slab of at least I floats per split");
+            return fail_at(SINGA_E_SHAPE, entry, "asum goes with the (0, 0) form, plain A rows, a slab of at least I floats per split");
         P.A = q.a; P.B = q.b; P.C = q.c; P.bias = q.bias; P.mask = q.mask; P.addend = q.addend; P.relu = q.relu;
         P.asum = q.asum; P.asum_stride = q.asum_stride;
         P.lda = q.lda; P.ldb = q.ldb; P.ldc = q.ldc;
@@ -7527,7 +7645,7 @@ int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_con
         P.I = q.I; P.J = q.J; P.R = q.R;
     }
     unsigned nwg = 0;
-    if (int bad = gemm_plan(gb, cfg == 2 ? 32 : (cfg == 3 ? 64 : 128), cfg == 1 ? 32 : (cfg == 3 ? 64 : 128), 32, "gemm_f32", &nwg))
+    if (int bad = gemm_plan(gb, cfg == 2 ? 32 : (cfg == 3 ? 64 : 128), cfg == 1 ? 32 : (cfg == 3 ? 64 : 128), 32, entry, &nwg))
         return bad;
     if (nwg == 0) return SINGA_OK;
     const dim3 grid(nwg), block(256);
@@ -7536,10 +7654,28 @@ int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_con
         constexpr bool A_RC = decltype(a)::value, B_RC = decltype(b)::value;
         constexpr int tag = B_RC ? SINGA_PROF_GEMM_NT : (A_RC ? SINGA_PROF_GEMM_NN : SINGA_PROF_GEMM_TN);
         dispatch_gemm_cfg(cfg, [&](auto c) {
+#ifndef SINGA_EMUL
+            if (bf16) {
+                SINGA_LAUNCH(tag, 0, gb.tiles_total, (gemm_bf16_kernel<A_RC, B_RC, decltype(c)::value>), grid, block, st, gb);
+                return;
+            }
+#endif
             SINGA_LAUNCH(tag, 0, gb.tiles_total, (gemm_f32_kernel<A_RC, B_RC, decltype(c)::value>), grid, block, st, gb);
         });
     });
-    return check_launch("gemm_f32");
+    return check_launch(entry);
+}
+
+int singa_gemm_f32(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
+    return gemm_real_launch("gemm_f32", false, probs, n, a_r_contig, b_r_contig, splits, stream);
+}
+
+int singa_gemm_bf16(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "gemm_bf16: not part of the emulation build");
+#else
+    return gemm_real_launch("gemm_bf16", true, probs, n, a_r_contig, b_r_contig, splits, stream);
+#endif
 }
 
 int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {

@@ -223,8 +223,21 @@ class KnnEdges:
 
 
 # ----------------------------------------------------------------------------------------------- attention modules
+def set_precision(module, precision):
+    """The precision of the real GEMMs of every module under `module` ("f32" / "bf16", ops._gemm): the modules below and
+    nn.Linear hand their `precision` attribute to the ops they call, which keep it for their backward launches.  A class
+    attribute "f32" is the default, so a module built on its own - and everything outside the transformer - stays f32.
+    Only the classes that declare the attribute, i.e. those that launch GEMMs, are written to; a module class that launches
+    one without declaring and passing it stays f32."""
+    ops.check_precision(precision)
+    for m in module.modules():
+        if hasattr(type(m), "precision"):
+            m.precision = precision
+
+
 class MultiHeadAttention(nn.Module):
     """Graph attention over the kNN edges (CP:19-78)."""
+    precision = "f32"
 
     def __init__(self, hidden_channels, edge_channels, key_channels, num_heads=1, device="cuda"):
         super().__init__()
@@ -245,7 +258,7 @@ class MultiHeadAttention(nn.Module):
 
     def _edge_mlp(self, net, x):
         # first Linear as a plain GEMM, its bias inside the activation kernel (one pass instead of three)
-        return net[2](ops.bias_ssp(ops.linear(x, net[0].weight), net[0].bias))
+        return net[2](ops.bias_ssp(ops.linear(x, net[0].weight, precision=self.precision), net[0].bias))
 
     def forward(self, node_attr, edges: KnnEdges):
         """CP:50-78.  weight_k_lin and weight_v_lin act on the last axis only, so they commute with the per-edge
@@ -254,7 +267,7 @@ class MultiHeadAttention(nn.Module):
         contractions run as fused gather kernels without any [E,heads,channels] intermediate."""
         N = node_attr.size(0)
         h_keys, h_queries, h_values = ops.grouped_linear3(node_attr, self.k_lin.weight, self.q_lin.weight, self.v_lin.weight,
-                                                          self.num_heads)
+                                                          self.num_heads, self.precision)
         scale = 1.0 / math.sqrt(h_keys.size(-1))
         if edges.attr.shape[1] == 64 and self.weight_k_net[0].out_features == 32 and self.weight_v_net[0].out_features == 64:
             W_k, W_v = ops.edge_mlp_pair(edges.attr, (self.weight_k_net[0], self.weight_k_net[2]),
@@ -263,15 +276,16 @@ class MultiHeadAttention(nn.Module):
         else:                                    # other widths: the same two MLPs as library GEMMs + the k15d kernel
             W_k = self._edge_mlp(self.weight_k_net, edges.attr)
             W_v = self._edge_mlp(self.weight_v_net, edges.attr)
-        qp = ops.linear_nn(h_queries, self.weight_k_lin.weight)                  # (q W)[n,h,:]
+        qp = ops.linear_nn(h_queries, self.weight_k_lin.weight, self.precision)  # (q W)[n,h,:]
         cterm = ops.rowdot_bias(h_queries, self.weight_k_lin.bias, scale)
         qk_ij = ops.edge_logits(qp, W_k, h_keys, cterm, edges, scale)
         alpha = ops.segment_softmax(qk_ij, edges.row_ptr, 0.0)
         S = ops.gather_wsum(alpha, W_v, h_values, edges)                         # [N, heads, 64]
-        aggr_msg = ops.linear(S, self.weight_v_lin.weight, self.weight_v_lin.bias).view(N, -1)
+        aggr_msg = ops.linear(S, self.weight_v_lin.weight, self.weight_v_lin.bias, self.precision).view(N, -1)
         # centroid_lin(node_attr) + aggr_msg, then ShiftedSoftplus (CP:76-77): the sum rides in the GEMM's epilogue, the
         # Linear's bias in the activation kernel (k15d)
-        out = ops.bias_ssp(ops.linear_add(node_attr, self.centroid_lin.weight, None, aggr_msg), self.centroid_lin.bias)
+        out = ops.bias_ssp(ops.linear_add(node_attr, self.centroid_lin.weight, None, aggr_msg, self.precision),
+                           self.centroid_lin.bias)
         return ops.layer_norm_residual(self.out_transform(out), None, self.layer_norm)
 
 
@@ -292,10 +306,10 @@ def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels, 
         # attention); the kernel reads their column blocks in place
         WQ, WK, WV = ((m.weight, m.bias) for m in (module.W_Q, module.W_K, module.W_V))
         if Q is K and K is V:
-            q_s, k_s, v_s = ops.linear_multi(Q, [WQ, WK, WV])
+            q_s, k_s, v_s = ops.linear_multi(Q, [WQ, WK, WV], module.precision)
         elif K is V:
             q_s = module.W_Q(Q)
-            k_s, v_s = ops.linear_multi(K, [WK, WV])
+            k_s, v_s = ops.linear_multi(K, [WK, WV], module.precision)
         else:
             q_s, k_s, v_s = module.W_Q(Q), module.W_K(K), module.W_V(V)
         context = ops.attention(q_s.view(B, -1, heads, dk), k_s.view(B, -1, heads, dk), v_s.view(B, -1, heads, dv), attn_mask,
@@ -314,6 +328,7 @@ def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels, 
 
 class MultiHeadAttention2(nn.Module):
     """Dense cross-attention ligand atoms -> protein atoms (CP:81-105)."""
+    precision = "f32"
 
     def __init__(self, hidden_channels, key_channels, num_heads, device="cuda"):
         super().__init__()
@@ -333,6 +348,7 @@ class MultiHeadAttention2(nn.Module):
 
 class MultiHeadDeAttention(nn.Module):
     """Decoder self / encoder-decoder attention (CP:134-158)."""
+    precision = "f32"
 
     def __init__(self, hidden_channels, key_channels, num_heads, device="cuda"):
         super().__init__()
@@ -352,6 +368,7 @@ class MultiHeadDeAttention(nn.Module):
 
 class PoswiseFeedForwardNet(nn.Module):
     """1x1 Conv1d pair + residual LayerNorm on node rows (CP:161-176); batch_norm exists but is never called (Q10)."""
+    precision = "f32"
 
     def __init__(self, hidden_channels, device="cuda"):
         super().__init__()
@@ -361,11 +378,13 @@ class PoswiseFeedForwardNet(nn.Module):
         self.batch_norm = BatchNorm1d(hidden_channels, device=device)
 
     def forward(self, inputs):
-        h = ops.pos_ffn(inputs, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias)
+        h = ops.pos_ffn(inputs, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self.precision)
         return ops.layer_norm_residual(h, inputs, self.layer_norm)
 
 
 class PoswiseFeedForwardDeNet(nn.Module):
+    precision = "f32"
+
     def __init__(self, hidden_channels, device="cuda"):
         super().__init__()
         self.conv1 = Conv1d(hidden_channels, 1024, 1, device=device)
@@ -373,7 +392,7 @@ class PoswiseFeedForwardDeNet(nn.Module):
         self.layer_norm = LayerNorm(hidden_channels, device=device)
 
     def forward(self, inputs):
-        h = ops.pos_ffn(inputs, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias)
+        h = ops.pos_ffn(inputs, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self.precision)
         return ops.layer_norm_residual(h, inputs, self.layer_norm)
 
 
@@ -428,6 +447,8 @@ class EncoderLayer2(nn.Module):
 
 
 class Encoder(nn.Module):
+    precision = "f32"
+
     def __init__(self, config, protein_atom_feature_dim, device="cuda"):
         super().__init__()
         self.config = config
@@ -455,7 +476,7 @@ class Encoder(nn.Module):
         dm, edges = prep["dense"], prep["edges"]
         # protein_atom_emb(x) + laplacian_emb(pe) (CP:300): the sum rides in the second GEMM's epilogue
         node_attr = ops.linear_add(protein_atom_feature, self.protein_atom_emb.weight, self.protein_atom_emb.bias,
-                                   self.laplacian_emb(atom_laplacian))
+                                   self.laplacian_emb(atom_laplacian), self.precision)
         msa_outputs1 = []
         for idx, layer in enumerate(self.layers):
             msa_outputs, node_attr = layer(node_attr, edges)
@@ -468,6 +489,8 @@ class Encoder(nn.Module):
 
 
 class Encoder2(nn.Module):
+    precision = "f32"
+
     def __init__(self, config, aa_feature_dim, device="cuda"):
         super().__init__()
         self.config = config
@@ -489,7 +512,8 @@ class Encoder2(nn.Module):
         if prep is None:
             prep = self.prepare(aa_pos, aa_batch, int(aa_batch.max()) + 1 if batch_size is None else batch_size, knn)
         dm, edges = prep["dense"], prep["edges"]
-        node_attr = ops.linear_add(aa_feature, self.aa_emb.weight, self.aa_emb.bias, self.laplacian_emb(aa_laplacian))
+        node_attr = ops.linear_add(aa_feature, self.aa_emb.weight, self.aa_emb.bias, self.laplacian_emb(aa_laplacian),
+                                   self.precision)
         # layers 2 and 5 attend to the protein atoms under one mask: one tile map for both (ops.attn_tiles)
         cross_tiles = None
         if len(self.layers) > 2 and self.layers[2].cross_attn.uses_k19():
@@ -555,13 +579,15 @@ class Decoder(nn.Module):
 
 
 class Transformer(nn.Module):
-    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda"):
+    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda", precision="f32"):
+        ops.check_precision(precision)
         super().__init__()
         self.config, self.num_props, self.device = config, num_props, device
         self.encoder = Encoder(config.encoder, protein_atom_feature_dim, device=device)
         self.encoder2 = Encoder2(config.encoder, protein_atom_feature_dim, device=device)
         self.decoder = Decoder(config.decoder, self.num_props, device=device)
         self.projection = Linear(config.hidden_channels, len(config.decoder.smiVoc), bias=False, device=device)
+        set_precision(self, precision)
 
     overlap_encoders = os.environ.get("SINGA_OVERLAP_ENCODERS", "1") == "1"      # (0: one stream, lab)
 

@@ -9,6 +9,7 @@ node store; SURVEY.md §8c: unpinnable in the reference, computed deterministica
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..graph import LA, PA
 from .CProMG import Transformer
 from .Embedding import EquivariantEmbedding
@@ -20,15 +21,19 @@ def lap_pe(data, node_type: str):
 
 
 class SINGA(nn.Module):
-    def __init__(self, config, device="cuda", recompute=False):
+    def __init__(self, config, device="cuda", recompute=False, precision="f32"):
         """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
-        depends on it, so checkpoints move freely between the two modes."""
+        depends on it, so checkpoints move freely between the two modes.
+        precision: "f32", or "bf16" - the CProMG transformer's real GEMMs (forward, input and weight gradients) round their
+        operands to bfloat16 inside the kernel and accumulate in f32 (ops._gemm).  It reaches the transformer only; the
+        embedding, every tensor in memory, the optimizer state and the checkpoints are f32 in both settings."""
+        ops.check_precision(precision)
         super().__init__()
         self.device = device
         self.config = config
         self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device, recompute=recompute)
         self.model = Transformer(config=self.config.model, protein_atom_feature_dim=self.config.model.featurizer_feat_dim,
-                                 num_props=self.config.train.num_props, device=self.device)
+                                 num_props=self.config.train.num_props, device=self.device, precision=precision)
 
     def backward_phases(self):
         """Parameter groups in the order their gradients become final in a backward pass: the transformer (it consumes the

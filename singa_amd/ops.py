@@ -1735,9 +1735,31 @@ def _cprob(A, B, C, a_rc, b_rc, sigma):
     return it
 
 
-def _gemm(items, a_rc, b_rc, splits=1):
+# precision -> entry point of the real GEMM.  "bf16" (include/singa_hip_bf16.h): the operands are rounded to bfloat16 inside
+# the kernel, products and sums stay f32; tensors in memory are f32 either way.  The autograd functions below that take a
+# `precision` keep it on ctx: backward runs on autograd's thread, where a switch set around the forward call is not seen, and
+# the input- and weight-gradient launches have to follow the forward's.  No (operand form, tile shape) class is sent back to
+# f32 under "bf16": each of the nine classes a config-3 step launches under the flag takes less time per step in the bf16 kernel
+# (bf16 / f32 0.27 - 0.94 per class, profiles/bf16/README.md; the 32 x 128 tile is launched by the embedding only).
+_GEMM_ENTRY = {"f32": "singa_gemm_f32", "bf16": "singa_gemm_bf16"}
+
+
+def check_precision(precision):
+    if precision not in _GEMM_ENTRY:
+        raise ValueError(f"precision must be one of {sorted(_GEMM_ENTRY)}, got {precision!r}")
+    return precision
+
+
+def _pk(precision):
+    """The keyword of _gemm for a launch in `precision`: none for "f32", whose call is the one made before the switch existed."""
+    return {} if precision == "f32" else {"precision": precision}
+
+
+def _gemm(items, a_rc, b_rc, splits=1, precision="f32"):
+    """The one place that picks the real GEMM's entry point."""
+    name = _GEMM_ENTRY[check_precision(precision)]
     arr, n = _capi.gemm_probs(items)
-    _chk(_lib.lib().singa_gemm_f32(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), "singa_gemm_f32")
+    _chk(getattr(_lib.lib(), name)(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), name)
 
 
 def _cgemm(items, a_rc, b_rc, splits=1):
@@ -1775,7 +1797,7 @@ def _splits_few(rows, tiles):
     return best
 
 
-def _dw_grads(probs, splits, cplx=False):
+def _dw_grads(probs, splits, cplx=False, precision="f32"):
     """The weight gradients of ONE split-reduction launch.  probs: [(A, B, weight parameter, bias parameter or None)] - the
     (0, 0)-form products dW = A^T B over the rows of the views A [rows, out] and B [rows, in] (grouped rows allowed), whose
     result is (a part of) the parameter in the parameter's own layout; problems in a row that name the same parameter fill it
@@ -1811,12 +1833,15 @@ def _dw_grads(probs, splits, cplx=False):
                 items.append(_cprob(A.chunk(2, 1), B.chunk(2, 1), slab.chunk(2, 1), False, False, -1.0))
             else:
                 items.append(_prob(A, B, slab, False, False, asum=next(asums) if bias is not None else None))
-        (_cgemm if cplx else _gemm)(items, False, False, splits)
+        if cplx:
+            _cgemm(items, False, False, splits)
+        else:
+            _gemm(items, False, False, splits, **_pk(precision))
         res = param_colsum(part, targets)
     return [g.view(p.shape) if g is not None else None for g, (_, _, p) in zip(res[:nw], targets)], res[nw:]
 
 
-def gemm_nt(x, w, bias=None, out=None):
+def gemm_nt(x, w, bias=None, out=None, precision="f32"):
     """y = x w^T (+ bias) on the library's own MFMA kernel; x [M, K] (row-strided views allowed), w [N, K]."""
     x, w = _rows(x), _rows(w)
     _dev(x, w)
@@ -1824,7 +1849,7 @@ def gemm_nt(x, w, bias=None, out=None):
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    _gemm([_prob(x, w, out, True, True, bias=bias)], True, True)
+    _gemm([_prob(x, w, out, True, True, bias=bias)], True, True, **_pk(precision))
     return out
 
 
@@ -2216,8 +2241,9 @@ class _GroupedLinear3(torch.autograd.Function):
     previous one's result in its epilogue: no separate additions) and one split-reduction launch for all weight gradients."""
 
     @staticmethod
-    def forward(ctx, h, wk, wq, wv, heads):
+    def forward(ctx, h, wk, wq, wv, heads, precision):
         ctx.params = (wk, wq, wv)
+        ctx.precision = check_precision(precision)
         h = _rows(h)
         ws = [_rows(w.view(w.shape[0], w.shape[1])) for w in (wk, wq, wv)]       # [heads * og, ig] (the Conv1d weight as it is)
         _dev(h, *ws)
@@ -2227,7 +2253,7 @@ class _GroupedLinear3(torch.autograd.Function):
         if N > 0:
             hs = h.split(ig, 1)                                      # the heads' column blocks of h, row blocks of a weight
             _gemm([_prob(hh, wh, oh, True, True) for w, o, og in zip(ws, outs, ogs)
-                   for hh, wh, oh in zip(hs, w.split(og, 0), o.unbind(1))], True, True)
+                   for hh, wh, oh in zip(hs, w.split(og, 0), o.unbind(1))], True, True, **_pk(precision))
         ctx.save_for_backward(h, *ws)
         ctx.heads, ctx.ogs = heads, ogs
         return tuple(outs)
@@ -2245,17 +2271,18 @@ class _GroupedLinear3(torch.autograd.Function):
                 gh = torch.empty(N, heads * ig, device=h.device, dtype=torch.float32)
                 cur = gh.split(ig, 1)
                 _gemm([_prob(gg, wh, c, True, False, addend=ad)
-                       for gg, wh, c, ad in zip(g.split(og, 1), w.split(og, 0), cur, prev)], True, False)
+                       for gg, wh, c, ad in zip(g.split(og, 1), w.split(og, 0), cur, prev)], True, False,
+                      **_pk(ctx.precision))
                 prev = cur
         elif ctx.needs_input_grad[0]:
             gh = torch.zeros_like(h)
         hs = h.split(ig, 1)                                          # dW[layer][head] [og, ig] = g_head^T h_head
         gws, _ = _dw_grads([(gg, hh, p, None) for g, og, p in zip(gs, ogs, ctx.params) for gg, hh in zip(g.split(og, 1), hs)],
-                           _tn_splits(N, max(ogs), ig))
-        return gh, gws[0], gws[1], gws[2], None
+                           _tn_splits(N, max(ogs), ig), precision=ctx.precision)
+        return gh, gws[0], gws[1], gws[2], None, None
 
 
-def grouped_linear3(h, wk, wq, wv, heads):
+def grouped_linear3(h, wk, wq, wv, heads, precision="f32"):
     """(k_lin(h), q_lin(h), v_lin(h)) for grouped 1x1 Conv1d weights [heads * og, ig, 1] -> three [N, heads, og] tensors."""
     ig = wk.shape[1]
     ok = (h.is_cuda and ig % 4 == 0 and all((w.shape[0] // heads) % 4 == 0 and w.shape[1] == ig for w in (wk, wq, wv))
@@ -2263,7 +2290,7 @@ def grouped_linear3(h, wk, wq, wv, heads):
     if not ok:
         raise ValueError("grouped_linear3: channel counts per head must be multiples of 4 and heads <= 4 (the own GEMM's "
                          "float4 accesses, 12 problems per launch)")
-    return _GroupedLinear3.apply(h, wk, wq, wv, heads)
+    return _GroupedLinear3.apply(h, wk, wq, wv, heads, precision)
 
 
 def _tn_splits(rows, out, cin):
@@ -2290,8 +2317,9 @@ class _LinearOwn(torch.autograd.Function):
     column-sum launch (ops._GradSink)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, addend):
+    def forward(ctx, x, w, b, addend, precision="f32"):
         ctx.params = (w, b)
+        ctx.precision = check_precision(precision)
         K, N = x.shape[-1], w.shape[0]
         x2 = _rows(x.reshape(-1, K))
         w2 = _rows(w.view(N, K))
@@ -2302,7 +2330,7 @@ class _LinearOwn(torch.autograd.Function):
         if addend is not None:
             ad = addend.reshape(M, N).contiguous()
             _dev(ad)
-        _gemm([_prob(x2, w2, y, True, True, bias=b, addend=ad)], True, True)
+        _gemm([_prob(x2, w2, y, True, True, bias=b, addend=ad)], True, True, **_pk(precision))
         ctx.save_for_backward(x2, w2)
         ctx.xshape, ctx.has_bias, ctx.ashape = x.shape, b is not None, (addend.shape if addend is not None else None)
         return y.view(*x.shape[:-1], N)
@@ -2317,18 +2345,18 @@ class _LinearOwn(torch.autograd.Function):
         gx = gw = gb = None
         # the weight gradient first: nothing in the backward pass waits for it, the input gradient's launch follows it
         if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2] and M > 0:
-            gw, gb = _tn_grad(g2, x2, wp, bp)                         # the bias gradient rides in the weight gradient's launch
+            gw, gb = _tn_grad(g2, x2, wp, bp, ctx.precision)          # the bias gradient rides in the weight gradient's launch
         else:
             if ctx.needs_input_grad[1]:
-                gw = _tn_grad(g2, x2, wp)
+                gw = _tn_grad(g2, x2, wp, precision=ctx.precision)
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 gb = param_colsum(g2, [(0, N, bp)])[0]
         if ctx.needs_input_grad[0]:
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(g2, w2, gx, True, False)], True, False)
+            _gemm([_prob(g2, w2, gx, True, False)], True, False, **_pk(ctx.precision))
             gx = gx.view(ctx.xshape)
         ga = g.reshape(ctx.ashape) if ctx.ashape is not None and ctx.needs_input_grad[3] else None
-        return gx, gw, gb, ga
+        return gx, gw, gb, ga, None
 
 
 class _LinearNN(torch.autograd.Function):
@@ -2336,15 +2364,16 @@ class _LinearNN(torch.autograd.Function):
     with W(w*k) moved to the query side) - the (1, 0) form of the own GEMM, no transposed copy of W."""
 
     @staticmethod
-    def forward(ctx, x, w):
+    def forward(ctx, x, w, precision="f32"):
         ctx.param = w
+        ctx.precision = check_precision(precision)
         K, N = w.shape
         x2 = _rows(x.reshape(-1, K))
         w2 = _rows(w)
         _dev(x2, w2)
         M = x2.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([_prob(x2, w2, y, True, False)], True, False)
+        _gemm([_prob(x2, w2, y, True, False)], True, False, **_pk(precision))
         ctx.save_for_backward(x2, w2)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], N)
@@ -2358,26 +2387,26 @@ class _LinearNN(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[0]:                  # dx = g W^T: W [K, N] is the [J][R] operand of the (1, 1) form
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(g2, w2, gx, True, True)], True, True)
+            _gemm([_prob(g2, w2, gx, True, True)], True, True, **_pk(ctx.precision))
             gx = gx.view(ctx.xshape)
         if ctx.needs_input_grad[1]:                  # dW [K, N] = x^T g
-            gw = _tn_grad(x2, g2, ctx.param)
-        return gx, gw
+            gw = _tn_grad(x2, g2, ctx.param, precision=ctx.precision)
+        return gx, gw, None
 
 
-def linear_nn(x, w):
+def linear_nn(x, w, precision="f32"):
     if x.is_cuda and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0 and x.numel() > 0:
-        return _LinearNN.apply(x, w)
-    return linear(x, w.t())
+        return _LinearNN.apply(x, w, precision)
+    return linear(x, w.t(), precision=precision)
 
 
-def _tn_grad(g2, x2, param, bias=None):
+def _tn_grad(g2, x2, param, bias=None, precision="f32"):
     """dW[N, K] = g2^T x2 (reduction over the rows, split over workgroups): the one-problem case of _dw_grads.  Returns the
     gradient shaped like `param`, or None when it was queued into param.grad - and, with `bias`, the bias gradient (the
     per-split column sums of g ride behind the slab) as a second result.  (Tried and dropped in round 3: queueing the
     products themselves and launching them 12 at a time - one split count and one tile shape for a mixed batch cost 12 ms
     per step at config 3 and gained nothing on the 17-graph shard, tools/lab/ab_bench.py.)"""
-    (gw,), gb = _dw_grads([(g2, x2, param, bias)], _tn_splits(g2.shape[0], g2.shape[1], x2.shape[1]))
+    (gw,), gb = _dw_grads([(g2, x2, param, bias)], _tn_splits(g2.shape[0], g2.shape[1], x2.shape[1]), precision=precision)
     return (gw, gb[0]) if bias is not None else gw
 
 
@@ -2394,7 +2423,7 @@ def _pad4(x, w):
     return x, w
 
 
-def linear(x, w, b=None):
+def linear(x, w, b=None, precision="f32"):
     """y = x W^T + b (w: [out, in] or a 1x1 Conv1d weight [out, in, 1]) on the own MFMA GEMM (k7).  A reduction that is not a
     multiple of 4 floats is zero-padded, an output width that is not is computed 4-aligned and cut; there is no
     BLAS-library path."""
@@ -2404,13 +2433,13 @@ def linear(x, w, b=None):
     if x.numel() == 0:                              # nothing to multiply: zeros that still hang in the autograd graph
         return x.new_zeros(*x.shape[:-1], N) + 0.0 * w.sum() + (0.0 * b.sum() if b is not None else 0.0)
     if _own_linear_ok(x, w, b):
-        return _LinearOwn.apply(x, w, b, None)
+        return _LinearOwn.apply(x, w, b, None, precision)
     x, w = _pad4(x, w)
     padn = -N % 4
     if padn:
         w = torch.nn.functional.pad(w, (0, 0, 0, padn))
         b = torch.nn.functional.pad(b, (0, padn)) if b is not None else None
-    y = _LinearOwn.apply(x.contiguous(), w.contiguous(), b, None)
+    y = _LinearOwn.apply(x.contiguous(), w.contiguous(), b, None, precision)
     return y[..., :N] if padn else y
 
 
@@ -2422,9 +2451,10 @@ class _LinearMulti(torch.autograd.Function):
     buffer; the attention kernels read them in place and hand back their gradients in the same arrangement."""
 
     @staticmethod
-    def forward(ctx, x, *wb):
+    def forward(ctx, x, precision, *wb):
         ws, bs = wb[0::2], wb[1::2]
         ctx.params = (ws, bs)
+        ctx.precision = check_precision(precision)
         K = x.shape[-1]
         x2 = _rows(x.reshape(-1, K))
         w2 = [_rows(w.view(w.shape[0], K)) for w in ws]
@@ -2434,7 +2464,7 @@ class _LinearMulti(torch.autograd.Function):
         tot = sum(ns)
         y = torch.empty(M, tot, device=x.device, dtype=torch.float32)
         ys = y.split(ns, 1)
-        _gemm([_prob(x2, w, yb, True, True, bias=b) for w, b, yb in zip(w2, bs, ys)], True, True)
+        _gemm([_prob(x2, w, yb, True, True, bias=b) for w, b, yb in zip(w2, bs, ys)], True, True, **_pk(precision))
         ctx.save_for_backward(x2, *w2)
         ctx.xshape, ctx.ns = x.shape, ns
         return tuple(yb.view(*x.shape[:-1], n) for yb, n in zip(ys, ns))
@@ -2461,44 +2491,49 @@ class _LinearMulti(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wcat = torch.cat(w2, 0)                                  # [tot, K]: the reduction runs over all output columns
             gx = torch.empty(M, K, device=x2.device, dtype=torch.float32)
-            _gemm([_prob(G, wcat, gx, True, False)], True, False)
+            _gemm([_prob(G, wcat, gx, True, False)], True, False, **_pk(ctx.precision))
             gx = gx.view(ctx.xshape)
         # weight-gradient slabs + the bias gradients (column sums of G, same launch)
-        gws, gbs = _dw_grads([(g, x2, w, b) for g, w, b in zip(G.split(ns, 1), ws, bs)], _tn_splits(M, max(ns), K))
+        gws, gbs = _dw_grads([(g, x2, w, b) for g, w, b in zip(G.split(ns, 1), ws, bs)], _tn_splits(M, max(ns), K),
+                             precision=ctx.precision)
         gbs = iter(gbs)
-        out = [gx]
+        out = [gx, None]
         for gw, b in zip(gws, bs):
             out += [gw, next(gbs) if b is not None else None]
         return tuple(out)
 
 
-def linear_multi(x, layers):
+def linear_multi(x, layers, precision="f32"):
     """[(weight, bias), ...] applied to the same x -> tuple of outputs (views of one fused buffer).  Falls back to
     separate ops.linear calls for shapes the own GEMM cannot take."""
     if all(_own_linear_ok(x, w, b) and b is not None for w, b in layers) and len(layers) <= 8:
         flat = []
         for w, b in layers:
             flat += [w, b]
-        return _LinearMulti.apply(x, *flat)
-    return tuple(linear(x, w, b) for w, b in layers)
+        return _LinearMulti.apply(x, precision, *flat)
+    return tuple(linear(x, w, b, precision) for w, b in layers)
 
 
-def linear_add(x, w, b, addend):
+def linear_add(x, w, b, addend, precision="f32"):
     """x W^T + b + addend (addend shaped like the result) in one launch."""
     if _own_linear_ok(x, w, b):
-        return _LinearOwn.apply(x, w, b, addend)
-    return linear(x, w, b) + addend
+        return _LinearOwn.apply(x, w, b, addend, precision)
+    return linear(x, w, b, precision) + addend
 
 
 class _PosFFN(torch.autograd.Function):
     """PoswiseFeedForward(De)Net up to its residual LayerNorm (CP:161-191): Linear(256 -> 1024) + ReLU + Linear(1024 -> 256)
     as two launches forward (ReLU in the first GEMM's epilogue) and four backward: dh = (g W2) masked by h > 0 in the
     epilogue of its own GEMM, dx = dh W1, and the two split-reduction weight gradients; bias gradients ride in the step's
-    shared column-sum launch."""
+    shared column-sum launch.  The precision of its six GEMMs is the node class's - _PosFFNBf16 below is the bf16 form - and
+    not a sixth argument: tests/helpers.py wraps this `forward` with its five-argument signature.  forward keeps it on ctx for
+    backward, like the other functions."""
+    precision = "f32"
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
         ctx.params = (w1, b1, w2, b2)
+        precision = ctx.precision = ctx._forward_cls.precision
         K, H = x.shape[-1], w1.shape[0]
         x2 = _rows(x.reshape(-1, K))
         a1, a2 = _rows(w1.view(H, K)), _rows(w2.view(w2.shape[0], H))
@@ -2506,8 +2541,8 @@ class _PosFFN(torch.autograd.Function):
         M, N = x2.shape[0], a2.shape[0]
         h = torch.empty(M, H, device=x.device, dtype=torch.float32)
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([_prob(x2, a1, h, True, True, bias=b1, relu=True)], True, True)
-        _gemm([_prob(h, a2, y, True, True, bias=b2)], True, True)
+        _gemm([_prob(x2, a1, h, True, True, bias=b1, relu=True)], True, True, **_pk(precision))
+        _gemm([_prob(h, a2, y, True, True, bias=b2)], True, True, **_pk(precision))
         ctx.save_for_backward(x2, a1, a2, h)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], N)
@@ -2519,21 +2554,26 @@ class _PosFFN(torch.autograd.Function):
         H, N = a1.shape[0], a2.shape[0]
         g2 = _rows(g.reshape(-1, N))
         w1, b1, w2, b2 = ctx.params
-        gw2, gb2 = _tn_grad(g2, h, w2, b2)                 # (each weight gradient in front of the input gradient it goes with)
+        prec = ctx.precision
+        gw2, gb2 = _tn_grad(g2, h, w2, b2, prec)           # (each weight gradient in front of the input gradient it goes with)
         dh = torch.empty(M, H, device=g.device, dtype=torch.float32)
-        _gemm([_prob(g2, a2, dh, True, False, mask=h)], True, False)
-        gw1, gb1 = _tn_grad(dh, x2, w1, b1)
+        _gemm([_prob(g2, a2, dh, True, False, mask=h)], True, False, **_pk(prec))
+        gw1, gb1 = _tn_grad(dh, x2, w1, b1, prec)
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(dh, a1, gx, True, False)], True, False)
+            _gemm([_prob(dh, a1, gx, True, False)], True, False, **_pk(prec))
             gx = gx.view(ctx.xshape)
         return gx, gw1, gb1, gw2, gb2
 
 
-def pos_ffn(x, w1, b1, w2, b2):
+class _PosFFNBf16(_PosFFN):
+    precision = "bf16"
+
+
+def pos_ffn(x, w1, b1, w2, b2, precision="f32"):
     """relu(x W1^T + b1) W2^T + b2 (the position-wise feed-forward of CP:161-191 before its residual LayerNorm)."""
-    return _PosFFN.apply(x, w1, b1, w2, b2)
+    return (_PosFFNBf16 if check_precision(precision) == "bf16" else _PosFFN).apply(x, w1, b1, w2, b2)
 
 
 class _SmallVocabEmbedding(torch.autograd.Function):

@@ -82,6 +82,11 @@ def main():
                     help="rebuild the embedding's largest saved activations in the backward pass instead of holding them (both "
                          "[N, K, 512] tensors of every feed-forward block, the S2 activation of every attention block): less memory, "
                          "slightly longer steps, the same checkpoints")
+    ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
+                    help="bf16: the CProMG transformer's real GEMMs (Linears, feed-forward, grouped projections; forward, input and "
+                         "weight gradients) round their operands to bfloat16 inside the kernel and accumulate in f32 "
+                         "(include/singa_hip_bf16.h).  Tensors, master weights, gradients, Adam and checkpoints stay f32; the "
+                         "equivariant embedding and generation stay f32")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
 
@@ -140,7 +145,9 @@ def main():
             gs = [G.synthetic_graph(base + i) for i in range(lo, hi)]
         return G.collate(gs).to(dev)
 
-    model = SINGA(cfg, device=dev, recompute=args.recompute)
+    model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision)
+    log(f"precision {args.precision}: the transformer's real GEMMs take " +
+        ("bf16 operands with f32 accumulation" if args.precision == "bf16" else "f32 operands"))
     if args.no_dropout:
         model.model.decoder.pos_emb.dropout.p = 0.0
     o = cfg.train.optimizer
