@@ -219,9 +219,11 @@ _ATTN_TILES_SIGS = {
 }
 ATTN_TILES_EXPORTS = tuple(_ATTN_TILES_SIGS)
 
-# include/singa_hip_bf16.h: the real GEMM with bf16 operands (`precision="bf16"` of ops._gemm); a table of its own
+# include/singa_hip_bf16.h: the real and the complex GEMM with bf16 operands (`precision="bf16"` of ops._gemm and ops._cgemm); a
+# table of its own
 _BF16_SIGS = {
     "singa_gemm_bf16": (_SIGS["singa_gemm_f32"][0], I32),
+    "singa_cgemm_bf16": (_SIGS["singa_cgemm3m_f32"][0], I32),
 }
 BF16_EXPORTS = tuple(_BF16_SIGS)
 

@@ -5552,6 +5552,38 @@ struct CGemmBatch {
     long long r_chunk;
 };
 
+// Loads of an output-contiguous complex operand (k7c and its bf16 form k7d): `width4` float4 per reduction row and part,
+// 256 / width4 reduction rows per pass, n / 2 passes per part; register j = part j / (n / 2), pass j % (n / 2).  all_c and the
+// mask as in gemm_load_rc.
+template <class AllC>
+__device__ __forceinline__ void cgemm_load_oc(AllC, float4* reg, unsigned& mask, const float* base, long long ld, long long im, int o0,
+                                              int lim, int n, int width4, long long r0, int tid, long long r_begin,
+                                              long long r_end) {
+    const int c4 = tid % width4, rq = tid / width4, rows = 256 / width4;
+    const int i = o0 + 4 * c4;
+    if constexpr (AllC::value) {
+        const float* b = base + (r0 + rq) * ld + i;
+#pragma unroll
+        for (int j = 0; j < n; ++j) {
+            const int part = j / (n / 2), ps = j % (n / 2);
+            reg[j] = *reinterpret_cast<const float4*>(b + (long long)part * im + (long long)(rows * ps) * ld);
+        }
+        mask = ~0u;
+    } else {
+        const int ic = i < lim ? i : o0;
+        mask = 0;
+#pragma unroll
+        for (int j = 0; j < n; ++j) {
+            const int part = j / (n / 2), ps = j % (n / 2);
+            const long long r = r0 + rq + rows * ps;
+            const bool ok = r < r_end && i < lim;
+            const long long rc = r < r_end ? r : r_begin;
+            reg[j] = *reinterpret_cast<const float4*>(base + rc * ld + (long long)part * im + ic);
+            mask |= (ok ? 1u : 0u) << j;
+        }
+    }
+}
+
 template <bool A_RC, bool B_RC>
 __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
     constexpr int BM = 128, BN = 64, BK = 16, PR = BK + 4, LDA = BM + 4, LDB = BN + 4;
@@ -5593,33 +5625,6 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
         }
     }
     const bool full = i0 + BM <= P.I && j0 + BN <= P.J && r_end > r_begin && (r_end - r_begin) % BK == 0;
-    // output-contiguous: `width4` float4 per reduction row and part, 256 / width4 reduction rows per pass, n / 2 passes per part
-    auto load_oc = [&](auto all_c, float4* reg, unsigned& mask, const float* base, long long ld, long long im, int o0, int lim, int n,
-                       int width4, long long r0) {
-        const int c4 = tid % width4, rq = tid / width4, rows = 256 / width4;
-        const int i = o0 + 4 * c4;
-        if constexpr (decltype(all_c)::value) {
-            const float* b = base + (r0 + rq) * ld + i;
-#pragma unroll
-            for (int j = 0; j < n; ++j) {
-                const int part = j / (n / 2), ps = j % (n / 2);
-                reg[j] = *reinterpret_cast<const float4*>(b + (long long)part * im + (long long)(rows * ps) * ld);
-            }
-            mask = ~0u;
-        } else {
-            const int ic = i < lim ? i : o0;
-            mask = 0;
-#pragma unroll
-            for (int j = 0; j < n; ++j) {
-                const int part = j / (n / 2), ps = j % (n / 2);
-                const long long r = r0 + rq + rows * ps;
-                const bool ok = r < r_end && i < lim;
-                const long long rc = r < r_end ? r : r_begin;
-                reg[j] = *reinterpret_cast<const float4*>(base + rc * ld + (long long)part * im + ic);
-                mask |= (ok ? 1u : 0u) << j;
-            }
-        }
-    };
     auto store_rc = [&](float* S, int sz1, const float4* reg, unsigned mask, int n) {
 #pragma unroll
         for (int j = 0; j < n; ++j)
@@ -5637,9 +5642,9 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
     };
     auto load_ab = [&](auto all_c, GemmRegs<NA, NB>& s, long long r0) __attribute__((always_inline)) {
         if (A_RC) gemm_load_rc(all_c, s.a, s.ma, arow, P.A, NA, kq, r0, r_begin, r_end);
-        else load_oc(all_c, s.a, s.ma, P.A, P.lda, P.a_im, i0, P.I, NA, BM / 4, r0);
+        else cgemm_load_oc(all_c, s.a, s.ma, P.A, P.lda, P.a_im, i0, P.I, NA, BM / 4, r0, tid, r_begin, r_end);
         if (B_RC) gemm_load_rc(all_c, s.b, s.mb, brow, P.B, NB, kq, r0, r_begin, r_end);
-        else load_oc(all_c, s.b, s.mb, P.B, P.ldb, P.b_im, j0, P.J, NB, BN / 4, r0);
+        else cgemm_load_oc(all_c, s.b, s.mb, P.B, P.ldb, P.b_im, j0, P.J, NB, BN / 4, r0, tid, r_begin, r_end);
     };
     auto store_ab = [&](const GemmRegs<NA, NB>& s, int buf) __attribute__((always_inline)) {
         if (A_RC) store_rc(As0 + buf * SZA, SZA1, s.a, s.ma, NA);
@@ -5736,6 +5741,158 @@ __global__ void __launch_bounds__(256, 2) cgemm3m_f32_kernel(CGemmBatch gb) {
         }
     }
 }
+
+// ---- k7d: the complex product with bf16 operands (singa_cgemm_bf16, include/singa_hip_bf16.h).  k7c's records, tile (128 rows x
+// 64 complex columns, 2 x 2 wavefronts), tile walk, masked f32 float4 loads, K loop and staged epilogue; k7b's rounding on the
+// way to LDS, bf16 images (two parts side by side, pitches of GEMM_BF16_PR / gemm_bf16_pitch), fragment reads and MFMA.  FOUR
+// real products instead of 3M's three: 3M's operands a + b, c +- d would have to be summed in f32 and rounded a second time (a
+// third LDS plane per operand), and re = P1 - P3 would cancel terms that each carry a 2^-9 error.  Here every operand value is
+// rounded once and
+//     re += a c + b (-sigma d),   im += b c + a (sigma d)
+// with sigma d and -sigma d made from d's packed fragment by flipping sign bits (exact).  Complex K step 16, k7c's, = one MFMA
+// of 16 reduction indices per product and 32 x 32 block (8 MFMAs per wavefront and step, as many as k7b's 128 x 128 tile); two
+// accumulator sets (re, im) of two 32 x 32 tiles per wavefront: 64 registers; 196-212 VGPRs, no scratch.  (A K step of 32 was
+// built first: its two register sets of 12 float4 left the ragged-tile loop of the reduction-contiguous forms 19-39 registers
+// short - 76-156 bytes of scratch per lane - and the full-tile loop at 252-254.)  The images keep k7b's pitches, of which a
+// [row][r] image uses the first 32 bytes of each 80-byte row.  The K loop takes the fenced phases, as k7b's.
+#ifndef SINGA_EMUL
+template <bool A_RC, bool B_RC>
+__global__ void __launch_bounds__(256, 2) cgemm_bf16_kernel(CGemmBatch gb) {
+    typedef GemmBf16 BF;
+    constexpr int BM = 128, BN = 64, BK = 16;
+    constexpr int LDA = gemm_bf16_pitch(BM), LDB = gemm_bf16_pitch(BN);       // pitches of the [r][col] images (bf16)
+    constexpr int NA = 4, NB = 2;                                   // float4 loads per thread and K step (both parts)
+    // one part's image in floats (two bf16 per float)
+    constexpr int SZA1 = (A_RC ? BM * GEMM_BF16_PR : BK * LDA) / 2, SZB1 = (B_RC ? BN * GEMM_BF16_PR : BK * LDB) / 2;
+    constexpr int SZA = 2 * SZA1, SZB = 2 * SZB1;
+    constexpr int PE = 64 + 4;                                      // epilogue staging pitch: 32 real + 32 imaginary columns
+    constexpr int SMEM = 2 * SZA + 2 * SZB > 4 * 32 * PE ? 2 * SZA + 2 * SZB : 4 * 32 * PE;
+    __shared__ __attribute__((aligned(16))) float smem[SMEM];
+    float* const As0 = smem;
+    float* const Bs0 = smem + 2 * SZA;
+    GemmTile T;
+    if (!gemm_tile_walk<BM, BN, SINGA_CGEMM_MAX>(gb, T)) return;
+    const CGemmProb& P = gb.p[T.pi];
+    const int split = T.split, i0 = T.i0, j0 = T.j0;
+    const long long r_begin = T.r_begin, r_end = T.r_end;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 32;
+    const int l31 = lane & 31, half = lane >> 5;
+    // sigma d = d with these bits flipped, -sigma d = sigma d with the sign bits flipped
+    const unsigned sflip = P.sigma < 0.f ? 0x80008000u : 0u;
+
+    // ---- staging maps: k7c's.  Reduction-contiguous operand: float4 kq (of 4) of part pt of row rr + 32 j.  Output-contiguous
+    // operand: cgemm_load_oc's.
+    const int kq = tid & 3, pt = (tid >> 2) & 1, rr = tid >> 3;
+    const float* arow[NA];
+    const float* brow[NB];
+    if (A_RC) {
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const int i = i0 + rr + 32 * j;
+            arow[j] = i < P.I ? P.A + (long long)i * P.lda + (long long)pt * P.a_im + 4 * kq : nullptr;
+        }
+    }
+    if (B_RC) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int jj = j0 + rr + 32 * j;
+            brow[j] = jj < P.J ? P.B + (long long)jj * P.ldb + (long long)pt * P.b_im + 4 * kq : nullptr;
+        }
+    }
+    const bool full = i0 + BM <= P.I && j0 + BN <= P.J && r_end > r_begin && (r_end - r_begin) % BK == 0;
+    auto load_ab = [&](auto all_c, GemmRegs<NA, NB>& s, long long r0) __attribute__((always_inline)) {
+        if (A_RC) gemm_load_rc(all_c, s.a, s.ma, arow, P.A, NA, kq, r0, r_begin, r_end);
+        else cgemm_load_oc(all_c, s.a, s.ma, P.A, P.lda, P.a_im, i0, P.I, NA, BM / 4, r0, tid, r_begin, r_end);
+        if (B_RC) gemm_load_rc(all_c, s.b, s.mb, brow, P.B, NB, kq, r0, r_begin, r_end);
+        else cgemm_load_oc(all_c, s.b, s.mb, P.B, P.ldb, P.b_im, j0, P.J, NB, BN / 4, r0, tid, r_begin, r_end);
+    };
+    // a reduction-contiguous operand: all of the thread's registers belong to part pt; an output-contiguous one: registers
+    // 0 .. n / 2 - 1 are the real part's, the rest the imaginary part's - one GemmBf16 store per part
+    auto store_ab = [&](const GemmRegs<NA, NB>& s, int buf) __attribute__((always_inline)) {
+        float* Sa = As0 + buf * SZA;
+        float* Sb = Bs0 + buf * SZB;
+        if (A_RC) BF::store_rc(Sa + pt * SZA1, s.a, s.ma, NA, rr, kq);
+        else {
+            BF::store_oc(Sa, s.a, s.ma, LDA, NA / 2, BM / 4, tid);
+            BF::store_oc(Sa + SZA1, s.a + NA / 2, s.ma >> (NA / 2), LDA, NA / 2, BM / 4, tid);
+        }
+        if (B_RC) BF::store_rc(Sb + pt * SZB1, s.b, s.mb, NB, rr, kq);
+        else {
+            BF::store_oc(Sb, s.b, s.mb, LDB, NB / 2, BN / 4, tid);
+            BF::store_oc(Sb + SZB1, s.b + NB / 2, s.mb >> (NB / 2), LDB, NB / 2, BN / 4, tid);
+        }
+    };
+    const int ia = wrow + l31, jb = wcol + l31;
+    floatx16 acc_re[2], acc_im[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc_re[a][r] = acc_im[a][r] = 0.f;
+    const bool row1 = __builtin_amdgcn_readfirstlane((int)(i0 + wrow + 32 < P.I)) != 0;      // the wavefront's second 32-row block holds rows
+    const bool colv = __builtin_amdgcn_readfirstlane((int)(j0 + wcol < P.J)) != 0;           // ... its 32-column block holds columns
+    auto compute = [&](auto all_c, int buf, int) __attribute__((always_inline)) {      // (a step is one MFMA per product)
+        if constexpr (!decltype(all_c)::value) {
+            if (!colv) return;                   // (a 96-wide result: the last tile's second column block is padding only)
+        }
+        const float* Sa = As0 + buf * SZA;
+        const float* Sb = Bs0 + buf * SZB;
+        BF::Frag ar[2], ai[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            ar[a] = BF::frag(Sa, A_RC, LDA, ia + 32 * a, 0, lane);
+            ai[a] = BF::frag(Sa + SZA1, A_RC, LDA, ia + 32 * a, 0, lane);
+        }
+        const BF::Frag br = BF::frag(Sb, B_RC, LDB, jb, 0, lane);
+        uint4 d = __builtin_bit_cast(uint4, BF::frag(Sb + SZB1, B_RC, LDB, jb, 0, lane));
+        d.x ^= sflip; d.y ^= sflip; d.z ^= sflip; d.w ^= sflip;
+        const BF::Frag sd = __builtin_bit_cast(BF::Frag, d);
+        d.x ^= 0x80008000u; d.y ^= 0x80008000u; d.z ^= 0x80008000u; d.w ^= 0x80008000u;
+        const BF::Frag nsd = __builtin_bit_cast(BF::Frag, d);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            if (a == 0 || decltype(all_c)::value || row1) {
+                acc_re[a] = BF::mfma(ar[a], br, acc_re[a]);
+                acc_im[a] = BF::mfma(ai[a], br, acc_im[a]);
+                acc_re[a] = BF::mfma(ai[a], nsd, acc_re[a]);
+                acc_im[a] = BF::mfma(ar[a], sd, acc_im[a]);
+            }
+        }
+    };
+    const long long nsteps = r_end > r_begin ? (r_end - r_begin + BK - 1) / BK : 0;
+    auto pipeline = [&]() __attribute__((always_inline)) {};        // (fenced phases only)
+    auto k_loop = [&](auto all_c) __attribute__((always_inline)) {
+        gemm_k_loop<BK, NA, NB, false>(all_c, r_begin, nsteps, BK / 8, load_ab, store_ab, compute, pipeline);
+    };
+    if (full) k_loop(std::true_type{});
+    else k_loop(std::false_type{});
+    // ---- epilogue: k7c's.  Per wavefront one 32-row block at a time through LDS ([row][32 re | 32 im]), then float4 rows: 8
+    // float4 of the real half and 8 of the imaginary half (c_im elements behind) per row
+    float* Cb = P.C + (long long)split * P.c_split;
+    float* stage = smem + wave * (32 * PE);
+    const int c4 = lane & 15, rsub = lane >> 4;
+    const int part = c4 >> 3, jcol = j0 + wcol + 4 * (c4 & 7);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int rw = (q & 3) + 8 * (q >> 2) + 4 * half;
+            stage[rw * PE + l31] = acc_re[a][q];
+            stage[rw * PE + 32 + l31] = acc_im[a][q];
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int ps = 0; ps < 8; ++ps) {
+            const int rloc = rsub + 4 * ps;
+            const int i = i0 + wrow + 32 * a + rloc;
+            const float4 v = *reinterpret_cast<const float4*>(stage + rloc * PE + 4 * c4);
+            if (i < P.I && jcol < P.J)
+                *reinterpret_cast<float4*>(Cb + (long long)i * P.ldc + (long long)part * P.c_im + jcol) = v;
+        }
+    }
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------ small weight / node transforms
 // SO2_m_Convolution's Linear acts on [x_+m | x_-m] through the "complex" recombination (out_r = fc_r(x_+) - fc_i(x_-),
@@ -7678,9 +7835,11 @@ int singa_gemm_bf16(const singa_gemm_t* probs, int n, int a_r_contig, int b_r_co
 #endif
 }
 
-int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
-    if (!probs || n < 1 || n > SINGA_CGEMM_MAX) return fail(SINGA_E_SHAPE, "cgemm3m_f32: 1..SINGA_CGEMM_MAX problems per launch");
-    if (int bad = gemm_check_launch("cgemm3m_f32", a_r_contig, b_r_contig, splits)) return bad;
+// singa_cgemm3m_f32 and singa_cgemm_bf16: the same checks, tile plan and grid; `entry` names the caller in the error text.
+static int cgemm_launch(const char* entry, bool bf16, const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits,
+                        void* stream) {
+    if (!probs || n < 1 || n > SINGA_CGEMM_MAX) return fail_at(SINGA_E_SHAPE, entry, "1..SINGA_CGEMM_MAX problems per launch");
+    if (int bad = gemm_check_launch(entry, a_r_contig, b_r_contig, splits)) return bad;
     CGemmBatch gb;
     memset(&gb, 0, sizeof(gb));
     gb.n = n;
@@ -7688,14 +7847,14 @@ int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r
     for (int k = 0; k < n; ++k) {
         const singa_cgemm_t& q = probs[k];
         CGemmProb& P = gb.p[k];
-        if (int bad = gemm_check_operands("cgemm3m_f32", q)) return bad;
+        if (int bad = gemm_check_operands(entry, q)) return bad;
         const bool a_ok = a_r_contig ? (q.R % 4 == 0) : (q.I % 4 == 0);
         const bool b_ok = b_r_contig ? (q.R % 4 == 0) : (q.J % 4 == 0);
         if (!a_ok || !b_ok || q.J % 4 || q.lda % 4 || q.ldb % 4 || q.ldc % 4 || q.a_im % 4 || q.b_im % 4 || q.c_im % 4 ||
             q.c_split_stride % 4 || ((uintptr_t)q.a & 15) || ((uintptr_t)q.b & 15) || ((uintptr_t)q.c & 15))
-            return fail(SINGA_E_SHAPE, "cgemm3m_f32: contiguous axes, pitches and part offsets must be multiples of 4 floats, bases 16-byte aligned");
-        if (q.sigma != 1.0f && q.sigma != -1.0f) return fail(SINGA_E_SHAPE, "cgemm3m_f32: sigma is +1 or -1");
-        if (splits > 1 && q.c_split_stride <= 0) return fail(SINGA_E_SHAPE, "cgemm3m_f32: split reductions need c_split_stride");
+            return fail_at(SINGA_E_SHAPE, entry, "contiguous axes, pitches and part offsets must be multiples of 4 floats, bases 16-byte aligned");
+        if (q.sigma != 1.0f && q.sigma != -1.0f) return fail_at(SINGA_E_SHAPE, entry, "sigma is +1 or -1");
+        if (splits > 1 && q.c_split_stride <= 0) return fail_at(SINGA_E_SHAPE, entry, "split reductions need c_split_stride");
         P.A = q.a; P.B = q.b; P.C = q.c;
         P.lda = q.lda; P.ldb = q.ldb; P.ldc = q.ldc;
         P.a_im = q.a_im; P.b_im = q.b_im; P.c_im = q.c_im;
@@ -7704,16 +7863,36 @@ int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r
         P.sigma = q.sigma;
     }
     unsigned nwg = 0;
-    if (int bad = gemm_plan(gb, 128, 64, 16, "cgemm3m_f32", &nwg)) return bad;
+    // (split reductions are cut at multiples of 16, k7c's K step - for the bf16 form at multiples of 32, two of k7d's steps, as
+    // singa_gemm_bf16 cuts them)
+    if (int bad = gemm_plan(gb, 128, 64, bf16 ? 32 : 16, entry, &nwg)) return bad;
     if (nwg == 0) return SINGA_OK;
     const dim3 grid(nwg), block(256);
     hipStream_t st = (hipStream_t)stream;
     dispatch_gemm_form(a_r_contig, b_r_contig, [&](auto a, auto b) {
         constexpr bool A_RC = decltype(a)::value, B_RC = decltype(b)::value;
-        SINGA_LAUNCH(B_RC ? SINGA_PROF_CGEMM_NT : (A_RC ? SINGA_PROF_CGEMM_NN : SINGA_PROF_CGEMM_TN), 0, gb.tiles_total,
-                     (cgemm3m_f32_kernel<A_RC, B_RC>), grid, block, st, gb);
+        constexpr int tag = B_RC ? SINGA_PROF_CGEMM_NT : (A_RC ? SINGA_PROF_CGEMM_NN : SINGA_PROF_CGEMM_TN);
+#ifndef SINGA_EMUL
+        if (bf16) {
+            SINGA_LAUNCH(tag, 0, gb.tiles_total, (cgemm_bf16_kernel<A_RC, B_RC>), grid, block, st, gb);
+            return;
+        }
+#endif
+        SINGA_LAUNCH(tag, 0, gb.tiles_total, (cgemm3m_f32_kernel<A_RC, B_RC>), grid, block, st, gb);
     });
-    return check_launch("cgemm3m_f32");
+    return check_launch(entry);
+}
+
+int singa_cgemm3m_f32(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
+    return cgemm_launch("cgemm3m_f32", false, probs, n, a_r_contig, b_r_contig, splits, stream);
+}
+
+int singa_cgemm_bf16(const singa_cgemm_t* probs, int n, int a_r_contig, int b_r_contig, int splits, void* stream) {
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "cgemm_bf16: not part of the emulation build");
+#else
+    return cgemm_launch("cgemm_bf16", true, probs, n, a_r_contig, b_r_contig, splits, stream);
+#endif
 }
 
 int singa_alpha_logits_nslots(int E) {

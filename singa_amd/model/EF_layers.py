@@ -282,7 +282,10 @@ class SO2_m_Convolution(nn.Module):
 
 class SO2_Convolution(nn.Module):
     """SO(2) convolution over all orders (EF:732-875) on an m-primary edge matrix X [E, KR*Cin]: a real GEMM for m = 0 and a
-    complex (3M) GEMM launch for m = 1, 2."""
+    complex (3M) GEMM launch for m = 1, 2.  precision: "f32", or "bf16" - the convolution's GEMMs, real and complex, forward and
+    backward, round their operands to bfloat16 inside the kernel (ops.so2_conv3m); set by EquivariantEmbedding(precision=...)."""
+
+    precision = "f32"
 
     def __init__(self, sphere_channels: int, m_output_channels: int, lmax_list: list, mmax_list: list, mappingReduced,
                  edge_channels_list=None, extra_m0_output_channels=None, internal_weights: bool = True,
@@ -314,10 +317,10 @@ class SO2_Convolution(nn.Module):
         if len(self.so2_m_conv) == 2:
             # m = 1, 2 as complex products in three real multiplications on the fc weights themselves (k7c)
             return list(ops.so2_conv3m(X, self.fc_m0.weight, self.fc_m0.bias, self.so2_m_conv[0].fc.weight,
-                                       self.so2_m_conv[1].fc.weight, st[1] * c, (st[2] - st[1]) * c))
-        outs = [ops.linear(X[:, : st[1] * c], self.fc_m0.weight, self.fc_m0.bias)]
+                                       self.so2_m_conv[1].fc.weight, st[1] * c, (st[2] - st[1]) * c, self.precision))
+        outs = [ops.linear(X[:, : st[1] * c], self.fc_m0.weight, self.fc_m0.bias, self.precision)]
         for i, conv in enumerate(self.so2_m_conv):
-            outs.append(ops.linear(X[:, st[i + 1] * c: st[i + 2] * c], conv.block_weight()))
+            outs.append(ops.linear(X[:, st[i + 1] * c: st[i + 2] * c], conv.block_weight(), precision=self.precision))
         return outs
 
 
@@ -416,7 +419,7 @@ class SO2EquivariantGraphAttention(nn.Module):
             c2 = self.so2_conv_2
             logits, y0, y1, y2 = ops.edge_head_conv_recompute(
                 h0, h1, h2, self.alpha_norm.weight, self.alpha_norm.bias, self.alpha_dot, c2.fc_m0.weight, c2.fc_m0.bias,
-                c2.so2_m_conv[0].fc.weight, c2.so2_m_conv[1].fc.weight, heads, A, H, L, M, self.alpha_norm.eps)
+                c2.so2_m_conv[0].fc.weight, c2.so2_m_conv[1].fc.weight, heads, A, H, L, M, self.alpha_norm.eps, c2.precision)
             alpha = ops.segment_softmax(logits, es.row_ptr, 1e-16)
         else:
             logits, act = ops.edge_head(h0, h1, h2, self.alpha_norm.weight, self.alpha_norm.bias, self.alpha_dot, heads, A, H,

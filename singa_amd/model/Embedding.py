@@ -13,8 +13,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..graph import E_LL, E_LP, E_PL, E_PP, LA, PA
-from .EF_layers import (CoefficientMappingModule, EdgeDegreeEmbedding, GaussianSmearing, ModuleListInfo, SO3_Embedding,
-                        SO3_Grid, SO3_Rotation, TransBlockV2, get_normalization_layer, init_edge_rot_mat,
+from .EF_layers import (CoefficientMappingModule, EdgeDegreeEmbedding, GaussianSmearing, ModuleListInfo, SO2_Convolution,
+                        SO3_Embedding, SO3_Grid, SO3_Rotation, TransBlockV2, get_normalization_layer, init_edge_rot_mat,
                         forward_pass)
 
 _AVG_NUM_MODES = 77.81317
@@ -29,10 +29,15 @@ def barcode(x: torch.Tensor) -> torch.Tensor:
 
 
 class EquivariantEmbedding(nn.Module):
-    def __init__(self, config, device: str = "cuda", recompute: bool = False) -> None:
+    def __init__(self, config, device: str = "cuda", recompute: bool = False, precision: str = "f32") -> None:
         """recompute: the blocks rebuild their largest saved activations in the backward pass (both [N, K, 512] tensors of every
         feed-forward block, the [E, KR*128] S2 activation of every attention block) instead of holding them: less memory, a
-        little more time, the same parameters and state_dict."""
+        little more time, the same parameters and state_dict.
+        precision: "f32", or "bf16" - the SO(2) convolutions' GEMMs (m = 0 real, m > 0 complex; forward, input and weight
+        gradients) round their operands to bfloat16 inside the kernel and accumulate in f32.  It reaches the SO2_Convolution
+        modules only: the radial MLPs, SO3_LinearV2 (projection, feed-forward), the edge-degree embedding, norms and S2
+        activations stay f32, and so does every tensor in memory."""
+        ops.check_precision(precision)
         super().__init__()
         self.device = device
         self.recompute = bool(recompute)
@@ -96,6 +101,17 @@ class EquivariantEmbedding(nn.Module):
                 device=device, recompute=self.recompute))
         self.norm = get_normalization_layer(self.norm_type, lmax=max(self.lmax_list), num_channels=self.sphere_channels,
                                             device=device)
+        self.set_precision(precision)
+
+    def set_precision(self, precision):
+        """The precision of the SO(2) convolutions.  (Not CProMG.set_precision: the Linears under an SO2_Convolution - fc_m0,
+        fc, the radial function's - carry a `precision` of their own, and their weights are consumed by ops.so2_conv3m and the
+        radial kernels, not by Linear.forward.)"""
+        ops.check_precision(precision)
+        self.precision = precision
+        for m in self.modules():
+            if isinstance(m, SO2_Convolution):
+                m.precision = precision
 
     # ------------------------------------------------------------------------------------------------------------
     def _frames(self, g, key: str, vec: torch.Tensor) -> torch.Tensor:

@@ -21,17 +21,21 @@ def lap_pe(data, node_type: str):
 
 
 class SINGA(nn.Module):
-    def __init__(self, config, device="cuda", recompute=False, precision="f32"):
+    def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32"):
         """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
         depends on it, so checkpoints move freely between the two modes.
         precision: "f32", or "bf16" - the CProMG transformer's real GEMMs (forward, input and weight gradients) round their
         operands to bfloat16 inside the kernel and accumulate in f32 (ops._gemm).  It reaches the transformer only; the
-        embedding, every tensor in memory, the optimizer state and the checkpoints are f32 in both settings."""
+        embedding, every tensor in memory, the optimizer state and the checkpoints are f32 in both settings.
+        embedding_precision: "f32", or "bf16" - the same for the GEMMs, real and complex (ops._cgemm), of the embedding's SO(2)
+        convolutions, and for nothing else in the embedding.  The two switches are independent."""
         ops.check_precision(precision)
+        ops.check_precision(embedding_precision)
         super().__init__()
         self.device = device
         self.config = config
-        self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device, recompute=recompute)
+        self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device, recompute=recompute,
+                                              precision=embedding_precision)
         self.model = Transformer(config=self.config.model, protein_atom_feature_dim=self.config.model.featurizer_feat_dim,
                                  num_props=self.config.train.num_props, device=self.device, precision=precision)
 

@@ -1762,9 +1762,18 @@ def _gemm(items, a_rc, b_rc, splits=1, precision="f32"):
     _chk(getattr(_lib.lib(), name)(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), name)
 
 
-def _cgemm(items, a_rc, b_rc, splits=1):
+# precision -> entry point of the complex GEMM (the m > 0 blocks of an SO(2) convolution).  "bf16" is singa_cgemm_bf16
+# (include/singa_hip_bf16.h): rounded operands, four real products, f32 sums.  No operand-form class is sent back to f32: each
+# of the three takes less time per config-3 step in the bf16 kernel (bf16 / f32 0.40 / 0.38 / 0.30 for forward / dX / dW, 0.26 - 0.53
+# per launch, profiles/bf16_embed/README.md), and so do the convolutions' m = 0 launches in ops._gemm (0.31 - 0.52).
+_CGEMM_ENTRY = {"f32": "singa_cgemm3m_f32", "bf16": "singa_cgemm_bf16"}
+
+
+def _cgemm(items, a_rc, b_rc, splits=1, precision="f32"):
+    """The one place that picks the complex GEMM's entry point."""
+    name = _CGEMM_ENTRY[check_precision(precision)]
     arr, n = _capi.gemm_probs(items, _capi.CGemm)
-    _chk(_lib.lib().singa_cgemm3m_f32(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), "singa_cgemm3m_f32")
+    _chk(getattr(_lib.lib(), name)(arr, n, int(a_rc), int(b_rc), int(splits), _stream()), name)
 
 
 def _splits_for(rows, tiles=None):
@@ -1802,7 +1811,7 @@ def _dw_grads(probs, splits, cplx=False, precision="f32"):
     (0, 0)-form products dW = A^T B over the rows of the views A [rows, out] and B [rows, in] (grouped rows allowed), whose
     result is (a part of) the parameter in the parameter's own layout; problems in a row that name the same parameter fill it
     front to back.  A bias parameter takes the column sums of A from the same launch (asum).  cplx: A = [g_r | g_i], B =
-    [x_+ | x_-] column halves, the result an fc weight [Wr; Wi] (singa_cgemm3m_f32, no bias).  The partial slabs of all
+    [x_+ | x_-] column halves, the result an fc weight [Wr; Wi] (the complex GEMM, no bias).  precision: of either launch.  The partial slabs of all
     problems, then the asum rows, are the columns of one [splits, row] buffer that param_colsum adds up.
     -> ([gradient per distinct weight parameter, shaped like it], [gradient per bias parameter]): None where the sum was
     queued into .grad (_GradSink), zeros when there are no rows to reduce over."""
@@ -1834,7 +1843,7 @@ def _dw_grads(probs, splits, cplx=False, precision="f32"):
             else:
                 items.append(_prob(A, B, slab, False, False, asum=next(asums) if bias is not None else None))
         if cplx:
-            _cgemm(items, False, False, splits)
+            _cgemm(items, False, False, splits, **_pk(precision))
         else:
             _gemm(items, False, False, splits, **_pk(precision))
         res = param_colsum(part, targets)
@@ -1904,23 +1913,26 @@ class _SO2Conv3M(torch.autograd.Function):
     """One SO(2) convolution (EF:807-875) on the m-primary edge matrix X [E, n0 + n1 + n2], the m = 1, 2 blocks as COMPLEX
     products in three real multiplications (k7c, `singa_cgemm3m_f32`) on the modules' own fc weights [2N, K] (Wr = w[:N],
     Wi = w[N:]; no block weight is built), the m = 0 block on the real GEMM (k7): two launches forward, two for dX, two
-    split reductions + one column sum for the weight gradients, which arrive in the parameters' own layout."""
+    split reductions + one column sum for the weight gradients, which arrive in the parameters' own layout.  Under
+    precision "bf16" all six launches take the bf16 entry points (singa_gemm_bf16, singa_cgemm_bf16); the m = 0 bias gradient
+    still comes from the unrounded column sums."""
 
     @staticmethod
-    def forward(ctx, X, w0, b0, w1, w2, n0, n1):
+    def forward(ctx, X, w0, b0, w1, w2, n0, n1, precision="f32"):
         ctx.params = (w0, w1, w2, b0)
-        X, ws, ctx.ins, hs = _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1)
+        ctx.precision = check_precision(precision)
+        X, ws, ctx.ins, hs = _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision)
         ctx.save_for_backward(X, *ws)
         return hs
 
     @staticmethod
     def backward(ctx, g0, g1, g2):
         X, *ws = ctx.saved_tensors
-        gX, gw0, gb, gw1, gw2 = _so2_conv3m_bwd(X, ws, ctx.ins, ctx.params, (g0, g1, g2), ctx.needs_input_grad[0])
-        return gX, gw0, gb, gw1, gw2, None, None
+        gX, gw0, gb, gw1, gw2 = _so2_conv3m_bwd(X, ws, ctx.ins, ctx.params, (g0, g1, g2), ctx.needs_input_grad[0], ctx.precision)
+        return gX, gw0, gb, gw1, gw2, None, None, None
 
 
-def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1):
+def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision="f32"):
     """The forward launches of _SO2Conv3M -> (X and the three weights as the launches read them, the input widths, the outputs)."""
     X = _rows(X)
     ws = [_rows(w0), w1.contiguous(), w2.contiguous()]
@@ -1933,14 +1945,14 @@ def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1):
     H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
     xs, hs = X.split(ins, 1), H.split(outs, 1)
     if E > 0:
-        _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True)
+        _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True, **_pk(precision))
         # A = [x_+ | x_-], B = fc.weight [Wr; Wi], C = [out_r | out_i]
         _cgemm([_cprob(x.chunk(2, 1), w.chunk(2, 0), h.chunk(2, 1), True, True, 1.0)
-                for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True)
+                for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True, **_pk(precision))
     return X, ws, ins, hs
 
 
-def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx):
+def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx, precision="f32"):
     """The backward launches of _SO2Conv3M -> the gradients of (X, w0, b0, w1, w2); params = (w0, w1, w2, b0) as the caller was
     given them (the targets of direct accumulation, _GradSink)."""
     outs = tuple(w.shape[0] for w in ws)
@@ -1953,23 +1965,25 @@ def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx):
     S0 = _splits_few(E, -(-outs[0] // 128) * -(-ins[0] // 128))
     Sc = _splits_few(E, sum(-(-(o // 2) // 128) * -(-(k // 2) // 64) for o, k in zip(outs[1:], ins[1:])))
     pw0, pw1, pw2, pb0 = params
-    (gw0,), (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0)], S0)
-    (gw1, gw2), _ = _dw_grads([(gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], Sc, cplx=True)
+    (gw0,), (gb,) = _dw_grads([(gs[0], xs[0], pw0, pb0)], S0, precision=precision)
+    (gw1, gw2), _ = _dw_grads([(gs[1], xs[1], pw1, None), (gs[2], xs[2], pw2, None)], Sc, cplx=True, precision=precision)
     gX = None
     if need_gx:
         gX = torch.empty_like(X)
         if E > 0:
             gxs = gX.split(ins, 1)
-            _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False)
+            _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False, **_pk(precision))
             # A = [g_r | g_i], B = fc.weight [Wr; Wi] as [r = n][j = k], C = [dx_+ | dx_-]
             _cgemm([_cprob(g.chunk(2, 1), w.chunk(2, 0), gx.chunk(2, 1), True, False, -1.0)
-                    for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False)
+                    for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False, **_pk(precision))
     return gX, gw0, gb, gw1, gw2
 
 
-def so2_conv3m(X, w0, b0, w1, w2, n0, n1):
+def so2_conv3m(X, w0, b0, w1, w2, n0, n1, precision="f32"):
     """The SO(2) convolution on the fc weights themselves (w1, w2: [2N, K] = [Wr; Wi]) - see _SO2Conv3M."""
-    return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1)
+    if check_precision(precision) == "f32":
+        return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1)
+    return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1, precision)
 
 
 def so2_linear3(X, w0, b0, w1, w2, n0, n1):
@@ -2209,12 +2223,13 @@ class _EdgeHeadConvRecompute(torch.autograd.Function):
     forward launch, then runs the launches of _SO2Conv3M.backward and of _EdgeHead.backward.  -> (logits, y0, y1, y2)."""
 
     @staticmethod
-    def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, w0, b0, w1, w2, heads, A, C, L, M, eps):
+    def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, w0, b0, w1, w2, heads, A, C, L, M, eps, precision="f32"):
         ctx.head_params, ctx.conv_params = (ln_w, ln_b, dot), (w0, w1, w2, b0)
         ctx.cfg = (heads, A, C, L, M, eps)
+        ctx.precision = check_precision(precision)          # of the convolution's launches, forward and backward
         saved, logits, act = _edge_head_fwd(h0, h1, h2, ln_w, ln_b, dot, ctx.cfg)
         st = so3.layout(L, M).seg_start
-        _, ws, ctx.ins, hs = _so2_conv3m_fwd(act, w0, b0, w1, w2, st[1] * C, (st[2] - st[1]) * C)
+        _, ws, ctx.ins, hs = _so2_conv3m_fwd(act, w0, b0, w1, w2, st[1] * C, (st[2] - st[1]) * C, precision)
         ctx.save_for_backward(*saved, *ws)
         return (logits,) + tuple(hs)
 
@@ -2223,14 +2238,17 @@ class _EdgeHeadConvRecompute(torch.autograd.Function):
         *head, w0, w1, w2 = ctx.saved_tensors
         h0, h1, h2 = head[:3]
         act = _edge_act(h0, h1, h2, ctx.cfg)
-        g_act, gw0, gb0, gw1, gw2 = _so2_conv3m_bwd(act, [w0, w1, w2], ctx.ins, ctx.conv_params, (g0, g1, g2), True)
+        g_act, gw0, gb0, gw1, gw2 = _so2_conv3m_bwd(act, [w0, w1, w2], ctx.ins, ctx.conv_params, (g0, g1, g2), True,
+                                                    ctx.precision)
         del act
-        return _edge_head_bwd(head, ctx.cfg, ctx.head_params, g_logits, g_act) + (gw0, gb0, gw1, gw2) + (None,) * 6
+        return _edge_head_bwd(head, ctx.cfg, ctx.head_params, g_logits, g_act) + (gw0, gb0, gw1, gw2) + (None,) * 7
 
 
-def edge_head_conv_recompute(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M=2, eps=1e-5):
-    """edge_head(...) -> so2_conv3m(act, w0, b0, w1, w2, ...) without a saved `act` - see _EdgeHeadConvRecompute."""
-    return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps)
+def edge_head_conv_recompute(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M=2, eps=1e-5, precision="f32"):
+    """edge_head(...) -> so2_conv3m(act, w0, b0, w1, w2, ..., precision) without a saved `act` - see _EdgeHeadConvRecompute."""
+    if check_precision(precision) == "f32":
+        return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps)
+    return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps, precision)
 
 
 class _GroupedLinear3(torch.autograd.Function):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What `SINGA(..., precision="bf16")` changes in time, on the GPU only.
+"""What `SINGA(..., precision="bf16")` and `SINGA(..., embedding_precision="bf16")` change in time, on the GPU only.
 
   steps    BASELINE configs[2] (cfg3_b128_l4) built as bench.py builds it (bucketed HIP-graph replay over `--distinct-batches`
            resident batches), the flag off and on ALTERNATED (off, on, off, on, ... `--rounds` times, a fresh model / engine
@@ -9,9 +9,14 @@
            wrapped for one eager step) and timed where it is made, on its own operands: singa_gemm_f32 against singa_gemm_bf16
            per launch (a device-event pair around every launch, warm, `--launches` of them, median).  One line per distinct
            launch with its count per step, one per shape class - operand form x tile shape - with the class's time per step
-           in both kernels.  This is the figure a routing table in ops._gemm would be built from.
+           in both kernels.  This is the figure a routing table in ops._gemm would be built from.  The complex launches
+           (ops._cgemm: the m > 0 blocks of the SO(2) convolutions under --embedding-precision bf16) are recorded and timed the
+           same way through singa_cgemm3m_f32 and singa_cgemm_bf16; their tile is 128 rows x 64 complex columns.
 
-    python tools/bench_precision.py [--part steps|kernels|all] [--workload cfg3_b128_l4] [--out FILE.jsonl]
+  --embedding-precision bf16 switches the embedding's SO(2) convolutions as well (both parts); --settings P/E,P/E,... alternates
+  the steps part over (precision, embedding precision) pairs instead of over --precisions.
+
+    python tools/bench_precision.py [--part steps|kernels|all] [--workload cfg3_b128_l4] [--embedding-precision bf16] [--out FILE.jsonl]
 """
 import argparse
 import hashlib
@@ -29,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_recompute import emit, make_batches, per_launch_ms  # noqa: E402
 
 
-def run_steps(workload, precision, batches, L, args, dev):
+def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f32"):
     import gc
     import bench
     from singa_amd.config import load_config
@@ -40,7 +45,7 @@ def run_steps(workload, precision, batches, L, args, dev):
     gc.collect()
     torch.cuda.empty_cache()
     torch.manual_seed(cfg.train.seed)
-    model = SINGA(cfg, device=dev, precision=precision)
+    model = SINGA(cfg, device=dev, precision=precision, embedding_precision=embedding_precision)
     model.train()
     opt = Adam(model.parameters(), lr=cfg.train.optimizer.lr, betas=(cfg.train.optimizer.beta1, cfg.train.optimizer.beta2))
     engine = TrainStep(model, opt, None, use_graph=True, max_grad_norm=float(cfg.train.max_grad_norm), bucket=True,
@@ -49,7 +54,7 @@ def run_steps(workload, precision, batches, L, args, dev):
         engine.step(batches[i % len(batches)])
     torch.cuda.synchronize()
     elapsed, per_step, loss, _ = bench.timed_region(engine, batches, args.steps, False, dev, True)
-    rec = {"kind": "steps", "workload": workload, "precision": precision, "steps": args.steps,
+    rec = {"kind": "steps", "workload": workload, "precision": precision, "embedding_precision": embedding_precision, "steps": args.steps,
            "ms_per_step_median": round(bench.median(per_step), 3), "ms_per_step_min": round(min(per_step), 3),
            "ms_per_step_max": round(max(per_step), 3), "final_loss": round(float(loss.detach()), 6)}
     engine.release()
@@ -61,11 +66,28 @@ def run_steps(workload, precision, batches, L, args, dev):
 
 def steps_part(args, dev):
     L, batches = make_batches(args.workload, args.distinct_batches, dev)
-    runs = {p: [] for p in args.precisions}
     t0 = time.perf_counter()
+    if args.settings:                         # (precision, embedding precision) pairs, alternated
+        runs = {s: [] for s in args.settings}
+        for rnd in range(args.rounds):
+            for s in args.settings:
+                rec = run_steps(args.workload, s[0], batches, L, args, dev, s[1])
+                rec.update(round=rnd)
+                runs[s].append(rec)
+                emit(rec, args.out)
+        base = statistics.median(r["ms_per_step_median"] for r in runs[args.settings[0]])
+        for s in args.settings:
+            meds = [r["ms_per_step_median"] for r in runs[s]]
+            emit({"kind": "settings_summary", "workload": args.workload, "rounds": args.rounds, "precision": s[0],
+                  "embedding_precision": s[1], "ms": statistics.median(meds), "spread_ms": [min(meds), max(meds)],
+                  "diff_ms_against_first": round(statistics.median(meds) - base, 3),
+                  "diff_pct_against_first": round(100.0 * (statistics.median(meds) - base) / base, 2),
+                  "wall_s": round(time.perf_counter() - t0, 1)}, args.out)
+        return
+    runs = {p: [] for p in args.precisions}
     for rnd in range(args.rounds):
         for precision in args.precisions:
-            rec = run_steps(args.workload, precision, batches, L, args, dev)
+            rec = run_steps(args.workload, precision, batches, L, args, dev, args.embedding_precision)
             rec.update(round=rnd)
             runs[precision].append(rec)
             emit(rec, args.out)
@@ -107,13 +129,13 @@ def kernels_part(args, dev):
     L, batches = make_batches(args.workload, 1, dev)
     cfg = load_config(lmax=L)
     torch.manual_seed(cfg.train.seed)
-    model = SINGA(cfg, device=dev, precision="bf16")
+    model = SINGA(cfg, device=dev, precision="bf16", embedding_precision=args.embedding_precision)
     model.train()
     opt = Adam(model.parameters(), lr=cfg.train.optimizer.lr, betas=(cfg.train.optimizer.beta1, cfg.train.optimizer.beta2))
     engine = TrainStep(model, opt, None, use_graph=False, max_grad_norm=float(cfg.train.max_grad_norm))
     engine.step(batches[0])
     torch.cuda.synchronize()
-    inner, seen, other = ops._gemm, {}, [0]
+    inner, inner_c, seen, other = ops._gemm, ops._cgemm, {}, [0]
     opts = ("a_group", "b_group", "c_group", "c_split_stride", "bias", "addend", "mask", "relu", "asum")
 
     def recorded(items, a_rc, b_rc, splits=1, precision="f32"):
@@ -134,12 +156,31 @@ def kernels_part(args, dev):
         seen[key] = rec
         return inner(items, a_rc, b_rc, splits, precision)
 
-    ops._gemm = recorded
+    def recorded_c(items, a_rc, b_rc, splits=1, precision="f32"):
+        """The same for the complex launches (extents in complex units; 8 real flops per complex multiply-add)."""
+        if precision != "bf16" or not items:
+            other[0] += 1
+            return inner_c(items, a_rc, b_rc, splits, precision)
+        key = ("complex", bool(a_rc), bool(b_rc), int(splits), tuple((it["I"], it["J"], it["R"]) for it in items))
+        if key in seen:
+            seen[key]["per_step"] += 1
+            return inner_c(items, a_rc, b_rc, splits, precision)
+        rec = {"kind": "kernels", "launch": "complex " + FORMS[key[1], key[2]], "tile": "128x64c", "splits": int(splits),
+               "problems": len(items), "I": items[0]["I"], "J": items[0]["J"], "R": items[0]["R"], "options": [],
+               "equal_problems": len(set(key[4])) == 1, "all_problems": [list(k) for k in key[4]],
+               "gflop": round(8e-9 * sum(it["I"] * it["J"] * it["R"] for it in items), 3), "per_step": 1}
+        for p in ("f32", "bf16"):
+            rec[p] = per_launch_ms(lambda: inner_c(items, a_rc, b_rc, splits, p), args.launches)
+        rec["bf16_over_f32"] = round(rec["bf16"]["median_ms"] / rec["f32"]["median_ms"], 3)
+        seen[key] = rec
+        return inner_c(items, a_rc, b_rc, splits, precision)
+
+    ops._gemm, ops._cgemm = recorded, recorded_c
     try:
         engine.step(batches[0])
         torch.cuda.synchronize()
     finally:
-        ops._gemm = inner
+        ops._gemm, ops._cgemm = inner, inner_c
     classes = {}
     for rec in seen.values():
         emit(rec, args.out)
@@ -154,7 +195,7 @@ def kernels_part(args, dev):
               "f32_ms_per_step": round(c["f32_ms"], 4), "bf16_ms_per_step": round(c["bf16_ms"], 4),
               "bf16_over_f32": round(c["bf16_ms"] / c["f32_ms"], 3), "ratio_min": min(c["ratios"]), "ratio_max": max(c["ratios"])}, args.out)
     emit({"kind": "kernels_summary", "bf16_launches_per_step": sum(c["per_step"] for c in classes.values()),
-          "f32_real_gemm_launches_per_step": other[0], "f32_ms_per_step": round(sum(c["f32_ms"] for c in classes.values()), 3),
+          "f32_gemm_launches_per_step": other[0], "f32_ms_per_step": round(sum(c["f32_ms"] for c in classes.values()), 3),
           "bf16_ms_per_step": round(sum(c["bf16_ms"] for c in classes.values()), 3)}, args.out)
     engine.release()
 
@@ -177,8 +218,14 @@ def main():
     ap.add_argument("--growth", type=float, default=1.04)
     ap.add_argument("--precisions", type=lambda v: [ops_precision(p) for p in v.split(",")], default=["f32", "bf16"],
                     help="steps part: the modes to alternate; one mode alone for a run under a kernel trace")
+    ap.add_argument("--embedding-precision", type=ops_precision, default="f32",
+                    help="the embedding's SO(2) convolutions (SINGA(..., embedding_precision=...)), in both parts")
+    ap.add_argument("--settings", type=lambda v: [tuple(ops_precision(p) for p in s.split("/")) for s in v.split(",")], default=None,
+                    help="steps part: precision/embedding-precision pairs to alternate, e.g. f32/f32,bf16/f32,f32/bf16,bf16/bf16; "
+                         "differences are reported against the first")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    assert not args.settings or all(len(s) == 2 for s in args.settings), "--settings takes precision/embedding-precision pairs"
     assert args.launches >= 50, "per-launch medians over at least 50 launches"
     import __graft_entry__
     __graft_entry__.build()

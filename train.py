@@ -87,6 +87,9 @@ def main():
                          "weight gradients) round their operands to bfloat16 inside the kernel and accumulate in f32 "
                          "(include/singa_hip_bf16.h).  Tensors, master weights, gradients, Adam and checkpoints stay f32; the "
                          "equivariant embedding and generation stay f32")
+    ap.add_argument("--embedding-precision", choices=["f32", "bf16"], default="f32",
+                    help="bf16: the same for the GEMMs of the equivariant embedding's SO(2) convolutions, real (m = 0) and complex "
+                         "(m > 0), and for nothing else in the embedding; independent of --precision")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
 
@@ -145,9 +148,12 @@ def main():
             gs = [G.synthetic_graph(base + i) for i in range(lo, hi)]
         return G.collate(gs).to(dev)
 
-    model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision)
+    model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision, embedding_precision=args.embedding_precision)
     log(f"precision {args.precision}: the transformer's real GEMMs take " +
         ("bf16 operands with f32 accumulation" if args.precision == "bf16" else "f32 operands"))
+    if args.embedding_precision != "f32":
+        log(f"embedding precision {args.embedding_precision}: the SO(2) convolutions' real and complex GEMMs take bf16 operands "
+            "with f32 accumulation")
     if args.no_dropout:
         model.model.decoder.pos_emb.dropout.p = 0.0
     o = cfg.train.optimizer
