@@ -95,7 +95,11 @@ def branch_stream(device=None):
     (three branches), and an instrumented capture of such a step crashed inside hipGraphLaunch on this ROCm build."""
     dev = torch.cuda.current_device() if device is None else torch.device(device).index
     dev = torch.cuda.current_device() if dev is None else dev
-    if dev not in _branch_streams:
+    cur = torch.cuda.current_stream(dev)
+    # torch hands its streams out of a pool of 32 per device, round robin: a stream made later - a graph capture's, a warm-up's -
+    # can BE the one kept here, and a pass that forks onto its own stream runs on one stream and captures one branch (seen in a
+    # whole-suite process: the capture stream equalled this one).  The stream in use as the current one is replaced.
+    while _branch_streams.get(dev) is None or _branch_streams[dev] == cur:
         _branch_streams[dev] = torch.cuda.Stream(device=dev)
     return _branch_streams[dev]
 
