@@ -1754,11 +1754,6 @@ def check_precision(precision):
     return precision
 
 
-def _pk(precision):
-    """The keyword of _gemm for a launch in `precision`: none for "f32", whose call is the one made before the switch existed."""
-    return {} if precision == "f32" else {"precision": precision}
-
-
 def _gemm(items, a_rc, b_rc, splits=1, precision="f32"):
     """The one place that picks the real GEMM's entry point."""
     name = _GEMM_ENTRY[check_precision(precision)]
@@ -1846,24 +1841,39 @@ def _dw_grads(probs, splits, cplx=False, precision="f32"):
                 items.append(_cprob(A.chunk(2, 1), B.chunk(2, 1), slab.chunk(2, 1), False, False, -1.0))
             else:
                 items.append(_prob(A, B, slab, False, False, asum=next(asums) if bias is not None else None))
-        if cplx:
-            _cgemm(items, False, False, splits, **_pk(precision))
-        else:
-            _gemm(items, False, False, splits, **_pk(precision))
+        (_cgemm if cplx else _gemm)(items, False, False, splits, precision)
         res = param_colsum(part, targets)
     return [g.view(p.shape) if g is not None else None for g, (_, _, p) in zip(res[:nw], targets)], res[nw:]
 
 
+def _rows_gemm(x, w, b_rc, precision, bias=None, addend=None, relu=False, out=None):
+    """One launch of y = x w^T (b_rc: w is [N, K]) or y = x w (w [K, N]) over the rows of x [..., K], with the epilogue options of
+    _prob; addend: shaped like y up to the flattening of its rows; out: the [M, N] tensor to write instead of a fresh one.
+    -> (x2, w2, y): x as [M, K] rows and the weight w2, both as the launch read them (copies where _rows had to make one: what
+    a backward pass saves), and the result y [M, N]."""
+    x2, w2 = _rows(x.reshape(-1, x.shape[-1])), _rows(w)
+    _dev(x2, w2, bias)
+    M, N = x2.shape[0], w2.shape[0 if b_rc else 1]
+    y = torch.empty(M, N, device=x2.device, dtype=torch.float32) if out is None else out
+    if addend is not None:
+        addend = addend.reshape(M, N).contiguous()
+        _dev(addend)
+    _gemm([_prob(x2, w2, y, True, b_rc, bias=bias, addend=addend, relu=relu)], True, b_rc, precision=precision)
+    return x2, w2, y
+
+
+def _rows_gemm_dx(g2, w2, b_rc, precision, mask=None):
+    """The input gradient of a _rows_gemm as one launch, g2 w2 (w2 [N, K]) or g2 w2^T (b_rc: w2 [K, N]) for the output gradient's
+    rows g2 [M, N] and the weight as forward read it; mask [M, K]: the output of the ReLU that produced the forward's x - the
+    result is zeroed where it is not positive.  -> [M, K]."""
+    gx = torch.empty(g2.shape[0], w2.shape[0 if b_rc else 1], device=g2.device, dtype=torch.float32)
+    _gemm([_prob(g2, w2, gx, True, b_rc, mask=mask)], True, b_rc, precision=precision)
+    return gx
+
+
 def gemm_nt(x, w, bias=None, out=None, precision="f32"):
     """y = x w^T (+ bias) on the library's own MFMA kernel; x [M, K] (row-strided views allowed), w [N, K]."""
-    x, w = _rows(x), _rows(w)
-    _dev(x, w)
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    _gemm([_prob(x, w, out, True, True, bias=bias)], True, True, **_pk(precision))
-    return out
+    return _rows_gemm(x, w, True, precision, bias=bias, out=out)[2]
 
 
 class _SO2Linear3(torch.autograd.Function):
@@ -1922,7 +1932,7 @@ class _SO2Conv3M(torch.autograd.Function):
     still comes from the unrounded column sums."""
 
     @staticmethod
-    def forward(ctx, X, w0, b0, w1, w2, n0, n1, precision="f32"):
+    def forward(ctx, X, w0, b0, w1, w2, n0, n1, precision):
         ctx.params = (w0, w1, w2, b0)
         ctx.precision = check_precision(precision)
         X, ws, ctx.ins, hs = _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision)
@@ -1936,7 +1946,7 @@ class _SO2Conv3M(torch.autograd.Function):
         return gX, gw0, gb, gw1, gw2, None, None, None
 
 
-def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision="f32"):
+def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision):
     """The forward launches of _SO2Conv3M -> (X and the three weights as the launches read them, the input widths, the outputs)."""
     X = _rows(X)
     ws = [_rows(w0), w1.contiguous(), w2.contiguous()]
@@ -1949,14 +1959,14 @@ def _so2_conv3m_fwd(X, w0, b0, w1, w2, n0, n1, precision="f32"):
     H = torch.empty(E, sum(outs), device=X.device, dtype=torch.float32)
     xs, hs = X.split(ins, 1), H.split(outs, 1)
     if E > 0:
-        _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True, **_pk(precision))
+        _gemm([_prob(xs[0], ws[0], hs[0], True, True, bias=b0)], True, True, precision=precision)
         # A = [x_+ | x_-], B = fc.weight [Wr; Wi], C = [out_r | out_i]
         _cgemm([_cprob(x.chunk(2, 1), w.chunk(2, 0), h.chunk(2, 1), True, True, 1.0)
-                for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True, **_pk(precision))
+                for x, w, h in zip(xs[1:], ws[1:], hs[1:])], True, True, precision=precision)
     return X, ws, ins, hs
 
 
-def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx, precision="f32"):
+def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx, precision):
     """The backward launches of _SO2Conv3M -> the gradients of (X, w0, b0, w1, w2); params = (w0, w1, w2, b0) as the caller was
     given them (the targets of direct accumulation, _GradSink)."""
     outs = tuple(w.shape[0] for w in ws)
@@ -1976,18 +1986,16 @@ def _so2_conv3m_bwd(X, ws, ins, params, gs, need_gx, precision="f32"):
         gX = torch.empty_like(X)
         if E > 0:
             gxs = gX.split(ins, 1)
-            _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False, **_pk(precision))
+            _gemm([_prob(gs[0], ws[0], gxs[0], True, False)], True, False, precision=precision)
             # A = [g_r | g_i], B = fc.weight [Wr; Wi] as [r = n][j = k], C = [dx_+ | dx_-]
             _cgemm([_cprob(g.chunk(2, 1), w.chunk(2, 0), gx.chunk(2, 1), True, False, -1.0)
-                    for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False, **_pk(precision))
+                    for g, w, gx in zip(gs[1:], ws[1:], gxs[1:])], True, False, precision=precision)
     return gX, gw0, gb, gw1, gw2
 
 
 def so2_conv3m(X, w0, b0, w1, w2, n0, n1, precision="f32"):
     """The SO(2) convolution on the fc weights themselves (w1, w2: [2N, K] = [Wr; Wi]) - see _SO2Conv3M."""
-    if check_precision(precision) == "f32":
-        return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1)
-    return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1, precision)
+    return _SO2Conv3M.apply(X, w0, b0, w1, w2, n0, n1, check_precision(precision))
 
 
 def so2_linear3(X, w0, b0, w1, w2, n0, n1):
@@ -2227,7 +2235,7 @@ class _EdgeHeadConvRecompute(torch.autograd.Function):
     forward launch, then runs the launches of _SO2Conv3M.backward and of _EdgeHead.backward.  -> (logits, y0, y1, y2)."""
 
     @staticmethod
-    def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, w0, b0, w1, w2, heads, A, C, L, M, eps, precision="f32"):
+    def forward(ctx, h0, h1, h2, ln_w, ln_b, dot, w0, b0, w1, w2, heads, A, C, L, M, eps, precision):
         ctx.head_params, ctx.conv_params = (ln_w, ln_b, dot), (w0, w1, w2, b0)
         ctx.cfg = (heads, A, C, L, M, eps)
         ctx.precision = check_precision(precision)          # of the convolution's launches, forward and backward
@@ -2250,9 +2258,8 @@ class _EdgeHeadConvRecompute(torch.autograd.Function):
 
 def edge_head_conv_recompute(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M=2, eps=1e-5, precision="f32"):
     """edge_head(...) -> so2_conv3m(act, w0, b0, w1, w2, ..., precision) without a saved `act` - see _EdgeHeadConvRecompute."""
-    if check_precision(precision) == "f32":
-        return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps)
-    return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps, precision)
+    return _EdgeHeadConvRecompute.apply(h0, h1, h2, ln_w, ln_b, alpha_dot, w0, b0, w1, w2, heads, A, C, L, M, eps,
+                                        check_precision(precision))
 
 
 class _GroupedLinear3(torch.autograd.Function):
@@ -2275,7 +2282,7 @@ class _GroupedLinear3(torch.autograd.Function):
         if N > 0:
             hs = h.split(ig, 1)                                      # the heads' column blocks of h, row blocks of a weight
             _gemm([_prob(hh, wh, oh, True, True) for w, o, og in zip(ws, outs, ogs)
-                   for hh, wh, oh in zip(hs, w.split(og, 0), o.unbind(1))], True, True, **_pk(precision))
+                   for hh, wh, oh in zip(hs, w.split(og, 0), o.unbind(1))], True, True, precision=precision)
         ctx.save_for_backward(h, *ws)
         ctx.heads, ctx.ogs = heads, ogs
         return tuple(outs)
@@ -2294,7 +2301,7 @@ class _GroupedLinear3(torch.autograd.Function):
                 cur = gh.split(ig, 1)
                 _gemm([_prob(gg, wh, c, True, False, addend=ad)
                        for gg, wh, c, ad in zip(g.split(og, 1), w.split(og, 0), cur, prev)], True, False,
-                      **_pk(ctx.precision))
+                      precision=ctx.precision)
                 prev = cur
         elif ctx.needs_input_grad[0]:
             gh = torch.zeros_like(h)
@@ -2326,7 +2333,7 @@ def _tn_splits(rows, out, cin):
     return max(1, min(1024, max(-(-rows // 4096), fill), rows // 256))
 
 
-def _own_linear_ok(x, w, b):
+def _own_linear_ok(x, w):
     K = x.shape[-1]
     N = w.shape[0]
     return x.is_cuda and x.dtype == torch.float32 and K % 4 == 0 and N % 4 == 0 and x.numel() > 0
@@ -2339,20 +2346,11 @@ class _LinearOwn(torch.autograd.Function):
     column-sum launch (ops._GradSink)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, addend, precision="f32"):
+    def forward(ctx, x, w, b, addend, precision):
         ctx.params = (w, b)
         ctx.precision = check_precision(precision)
         K, N = x.shape[-1], w.shape[0]
-        x2 = _rows(x.reshape(-1, K))
-        w2 = _rows(w.view(N, K))
-        _dev(x2, w2, b)
-        M = x2.shape[0]
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        ad = None
-        if addend is not None:
-            ad = addend.reshape(M, N).contiguous()
-            _dev(ad)
-        _gemm([_prob(x2, w2, y, True, True, bias=b, addend=ad)], True, True, **_pk(precision))
+        x2, w2, y = _rows_gemm(x, w.view(N, K), True, precision, bias=b, addend=addend)
         ctx.save_for_backward(x2, w2)
         ctx.xshape, ctx.has_bias, ctx.ashape = x.shape, b is not None, (addend.shape if addend is not None else None)
         return y.view(*x.shape[:-1], N)
@@ -2360,8 +2358,7 @@ class _LinearOwn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x2, w2 = ctx.saved_tensors
-        M, K = x2.shape
-        N = w2.shape[0]
+        M, N = x2.shape[0], w2.shape[0]
         g2 = _rows(g.reshape(-1, N))
         wp, bp = ctx.params
         gx = gw = gb = None
@@ -2374,9 +2371,7 @@ class _LinearOwn(torch.autograd.Function):
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 gb = param_colsum(g2, [(0, N, bp)])[0]
         if ctx.needs_input_grad[0]:
-            gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(g2, w2, gx, True, False)], True, False, **_pk(ctx.precision))
-            gx = gx.view(ctx.xshape)
+            gx = _rows_gemm_dx(g2, w2, False, ctx.precision).view(ctx.xshape)
         ga = g.reshape(ctx.ashape) if ctx.ashape is not None and ctx.needs_input_grad[3] else None
         return gx, gw, gb, ga, None
 
@@ -2386,31 +2381,21 @@ class _LinearNN(torch.autograd.Function):
     with W(w*k) moved to the query side) - the (1, 0) form of the own GEMM, no transposed copy of W."""
 
     @staticmethod
-    def forward(ctx, x, w, precision="f32"):
+    def forward(ctx, x, w, precision):
         ctx.param = w
         ctx.precision = check_precision(precision)
-        K, N = w.shape
-        x2 = _rows(x.reshape(-1, K))
-        w2 = _rows(w)
-        _dev(x2, w2)
-        M = x2.shape[0]
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([_prob(x2, w2, y, True, False)], True, False, **_pk(precision))
+        x2, w2, y = _rows_gemm(x, w, False, precision)
         ctx.save_for_backward(x2, w2)
         ctx.xshape = x.shape
-        return y.view(*x.shape[:-1], N)
+        return y.view(*x.shape[:-1], w.shape[1])
 
     @staticmethod
     def backward(ctx, g):
         x2, w2 = ctx.saved_tensors
-        M, K = x2.shape
-        N = w2.shape[1]
-        g2 = _rows(g.reshape(-1, N))
+        g2 = _rows(g.reshape(-1, w2.shape[1]))
         gx = gw = None
         if ctx.needs_input_grad[0]:                  # dx = g W^T: W [K, N] is the [J][R] operand of the (1, 1) form
-            gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(g2, w2, gx, True, True)], True, True, **_pk(ctx.precision))
-            gx = gx.view(ctx.xshape)
+            gx = _rows_gemm_dx(g2, w2, True, ctx.precision).view(ctx.xshape)
         if ctx.needs_input_grad[1]:                  # dW [K, N] = x^T g
             gw = _tn_grad(x2, g2, ctx.param, precision=ctx.precision)
         return gx, gw, None
@@ -2454,7 +2439,7 @@ def linear(x, w, b=None, precision="f32"):
     N = w.shape[0]
     if x.numel() == 0:                              # nothing to multiply: zeros that still hang in the autograd graph
         return x.new_zeros(*x.shape[:-1], N) + 0.0 * w.sum() + (0.0 * b.sum() if b is not None else 0.0)
-    if _own_linear_ok(x, w, b):
+    if _own_linear_ok(x, w):
         return _LinearOwn.apply(x, w, b, None, precision)
     x, w = _pad4(x, w)
     padn = -N % 4
@@ -2486,7 +2471,7 @@ class _LinearMulti(torch.autograd.Function):
         tot = sum(ns)
         y = torch.empty(M, tot, device=x.device, dtype=torch.float32)
         ys = y.split(ns, 1)
-        _gemm([_prob(x2, w, yb, True, True, bias=b) for w, b, yb in zip(w2, bs, ys)], True, True, **_pk(precision))
+        _gemm([_prob(x2, w, yb, True, True, bias=b) for w, b, yb in zip(w2, bs, ys)], True, True, precision=precision)
         ctx.save_for_backward(x2, *w2)
         ctx.xshape, ctx.ns = x.shape, ns
         return tuple(yb.view(*x.shape[:-1], n) for yb, n in zip(ys, ns))
@@ -2512,9 +2497,7 @@ class _LinearMulti(torch.autograd.Function):
         gx = None
         if ctx.needs_input_grad[0]:
             wcat = torch.cat(w2, 0)                                  # [tot, K]: the reduction runs over all output columns
-            gx = torch.empty(M, K, device=x2.device, dtype=torch.float32)
-            _gemm([_prob(G, wcat, gx, True, False)], True, False, **_pk(ctx.precision))
-            gx = gx.view(ctx.xshape)
+            gx = _rows_gemm_dx(G, wcat, False, ctx.precision).view(ctx.xshape)
         # weight-gradient slabs + the bias gradients (column sums of G, same launch)
         gws, gbs = _dw_grads([(g, x2, w, b) for g, w, b in zip(G.split(ns, 1), ws, bs)], _tn_splits(M, max(ns), K),
                              precision=ctx.precision)
@@ -2528,7 +2511,7 @@ class _LinearMulti(torch.autograd.Function):
 def linear_multi(x, layers, precision="f32"):
     """[(weight, bias), ...] applied to the same x -> tuple of outputs (views of one fused buffer).  Falls back to
     separate ops.linear calls for shapes the own GEMM cannot take."""
-    if all(_own_linear_ok(x, w, b) and b is not None for w, b in layers) and len(layers) <= 8:
+    if all(_own_linear_ok(x, w) and b is not None for w, b in layers) and len(layers) <= 8:
         flat = []
         for w, b in layers:
             flat += [w, b]
@@ -2538,7 +2521,7 @@ def linear_multi(x, layers, precision="f32"):
 
 def linear_add(x, w, b, addend, precision="f32"):
     """x W^T + b + addend (addend shaped like the result) in one launch."""
-    if _own_linear_ok(x, w, b):
+    if _own_linear_ok(x, w):
         return _LinearOwn.apply(x, w, b, addend, precision)
     return linear(x, w, b, precision) + addend
 
@@ -2547,15 +2530,14 @@ class _PosFFN(torch.autograd.Function):
     """PoswiseFeedForward(De)Net up to its residual LayerNorm (CP:161-191): Linear(256 -> 1024) + ReLU + Linear(1024 -> 256)
     as two launches forward (ReLU in the first GEMM's epilogue) and four backward: dh = (g W2) masked by h > 0 in the
     epilogue of its own GEMM, dx = dh W1, and the two split-reduction weight gradients; bias gradients ride in the step's
-    shared column-sum launch.  The precision of its six GEMMs is the node class's - _PosFFNBf16 below is the bf16 form - and
-    not a sixth argument: tests/helpers.py wraps this `forward` with its five-argument signature.  forward keeps it on ctx for
-    backward, like the other functions."""
-    precision = "f32"
+    shared column-sum launch.  `precision` is that of all six GEMMs; forward keeps it on ctx for backward, like the other
+    functions.  forward allocates h and y before its first launch (the order a captured step's memory pool has seen so far),
+    so it spells its two products out where two _rows_gemm calls would allocate y between them."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2):
+    def forward(ctx, x, w1, b1, w2, b2, precision):
         ctx.params = (w1, b1, w2, b2)
-        precision = ctx.precision = ctx._forward_cls.precision
+        ctx.precision = check_precision(precision)
         K, H = x.shape[-1], w1.shape[0]
         x2 = _rows(x.reshape(-1, K))
         a1, a2 = _rows(w1.view(H, K)), _rows(w2.view(w2.shape[0], H))
@@ -2563,8 +2545,8 @@ class _PosFFN(torch.autograd.Function):
         M, N = x2.shape[0], a2.shape[0]
         h = torch.empty(M, H, device=x.device, dtype=torch.float32)
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _gemm([_prob(x2, a1, h, True, True, bias=b1, relu=True)], True, True, **_pk(precision))
-        _gemm([_prob(h, a2, y, True, True, bias=b2)], True, True, **_pk(precision))
+        _gemm([_prob(x2, a1, h, True, True, bias=b1, relu=True)], True, True, precision=precision)
+        _gemm([_prob(h, a2, y, True, True, bias=b2)], True, True, precision=precision)
         ctx.save_for_backward(x2, a1, a2, h)
         ctx.xshape = x.shape
         return y.view(*x.shape[:-1], N)
@@ -2572,30 +2554,19 @@ class _PosFFN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x2, a1, a2, h = ctx.saved_tensors
-        M, K = x2.shape
-        H, N = a1.shape[0], a2.shape[0]
-        g2 = _rows(g.reshape(-1, N))
+        g2 = _rows(g.reshape(-1, a2.shape[0]))
         w1, b1, w2, b2 = ctx.params
         prec = ctx.precision
         gw2, gb2 = _tn_grad(g2, h, w2, b2, prec)           # (each weight gradient in front of the input gradient it goes with)
-        dh = torch.empty(M, H, device=g.device, dtype=torch.float32)
-        _gemm([_prob(g2, a2, dh, True, False, mask=h)], True, False, **_pk(prec))
+        dh = _rows_gemm_dx(g2, a2, False, prec, mask=h)
         gw1, gb1 = _tn_grad(dh, x2, w1, b1, prec)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-            _gemm([_prob(dh, a1, gx, True, False)], True, False, **_pk(prec))
-            gx = gx.view(ctx.xshape)
-        return gx, gw1, gb1, gw2, gb2
-
-
-class _PosFFNBf16(_PosFFN):
-    precision = "bf16"
+        gx = _rows_gemm_dx(dh, a1, False, prec).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        return gx, gw1, gb1, gw2, gb2, None
 
 
 def pos_ffn(x, w1, b1, w2, b2, precision="f32"):
     """relu(x W1^T + b1) W2^T + b2 (the position-wise feed-forward of CP:161-191 before its residual LayerNorm)."""
-    return (_PosFFNBf16 if check_precision(precision) == "bf16" else _PosFFN).apply(x, w1, b1, w2, b2)
+    return _PosFFN.apply(x, w1, b1, w2, b2, check_precision(precision))
 
 
 class _SmallVocabEmbedding(torch.autograd.Function):

@@ -184,8 +184,8 @@ class pinned_relu_ties:
         self._orig = ops._PosFFN.forward
         orig = self._orig
 
-        def fwd(ctx, x, w1, b1, w2, b2):
-            y = orig(ctx, x, w1, b1, w2, b2)
+        def fwd(ctx, *args):
+            y = orig(ctx, *args)
             h = ctx.to_save[3]
             assert self.call < len(self.rows) and tuple(h.shape) == (self.rows[self.call], 1024), (self.call, h.shape)
             sel = self.layer == self.call
@@ -219,8 +219,8 @@ class relu_gate_log:
         self._orig = ops._PosFFN.forward
         orig = self._orig
 
-        def fwd(ctx, x, w1, b1, w2, b2):
-            y = orig(ctx, x, w1, b1, w2, b2)
+        def fwd(ctx, *args):
+            y = orig(ctx, *args)
             if torch.cuda.is_current_stream_capturing() == self.capturing:
                 self.masks.append(ctx.to_save[3] > 0)
             return y

@@ -37,8 +37,8 @@ def recorded(monkeypatch):
     """ops._dw_grads without a device: launches and column sums are recorded, not run."""
     rec = dict(launches=[], colsums=[])
     for kind in ("gemm", "cgemm"):
-        monkeypatch.setattr(ops, "_" + kind, lambda items, a_rc, b_rc, splits=1, kind=kind:
-                            rec["launches"].append((kind, items, a_rc, b_rc, splits)))
+        monkeypatch.setattr(ops, "_" + kind, lambda items, a_rc, b_rc, splits=1, precision="f32", kind=kind:
+                            rec["launches"].append((kind, items, a_rc, b_rc, splits, precision)))
 
     def colsum(src, targets):
         rec["colsums"].append((src, targets))
@@ -90,9 +90,9 @@ def test_so3_linear_per_degree_lists(L, recorded):
 
     S, sz = 3, cout * cin
     (gw,), gb = ops._dw_grads([(gl, xl, weight, None) for gl, xl in zip(ops._degrees(g, L), ops._degrees(x, L))], S)
-    (kind, items, a_rc, b_rc, splits), = recorded["launches"]
+    (kind, items, a_rc, b_rc, splits, precision), = recorded["launches"]
     (part, targets), = recorded["colsums"]
-    assert (kind, a_rc, b_rc, splits) == ("gemm", False, False, S) and tuple(part.shape) == (S, (L + 1) * sz)
+    assert (kind, a_rc, b_rc, splits, precision) == ("gemm", False, False, S, "f32") and tuple(part.shape) == (S, (L + 1) * sz)
     want = []
     for l in range(L + 1):
         n = 2 * l + 1
@@ -148,10 +148,10 @@ def test_complex_problems_in_three_forms(recorded):
     K2, N2, S = 8, 12, 5
     x2, g2, w2 = X[:, ai + 2 * K - 12:ai + 2 * K + 4], rand(E, 2 * N2), rand(2 * N2, K2)
     (gw, gw2), _ = ops._dw_grads([(g, x, w, None), (g2, x2, w2, None)], S, cplx=True)
-    (kind, items, a_rc, b_rc, splits), = recorded["launches"]
+    (kind, items, a_rc, b_rc, splits, precision), = recorded["launches"]
     (part, targets), = recorded["colsums"]
     rowc = 2 * N * K + 2 * N2 * K2
-    assert (kind, a_rc, b_rc, splits) == ("cgemm", False, False, S) and tuple(part.shape) == (S, rowc)
+    assert (kind, a_rc, b_rc, splits, precision) == ("cgemm", False, False, S, "f32") and tuple(part.shape) == (S, rowc)
     same_list(items, [dict(a=g.data_ptr(), lda=g.stride(0), a_im=N, b=X.data_ptr() + 4 * ai, ldb=X.stride(0), b_im=K,
                            c=part.data_ptr(), ldc=K, c_im=N * K, I=N, J=K, R=E, sigma=-1.0, c_split_stride=rowc),
                       dict(a=g2.data_ptr(), lda=g2.stride(0), a_im=N2, b=X.data_ptr() + 4 * (ai + 2 * K - 12), ldb=X.stride(0),
@@ -166,10 +166,10 @@ def test_weight_gradient_with_bias_sums(recorded):
     M, N, K = 300, 16, 24
     g, x, w, b = rand(M, N), rand(M, 40)[:, 8:8 + K], rand(N, K), rand(N)
     gw, gb = ops._tn_grad(g, x, w, b)
-    (kind, items, a_rc, b_rc, S), = recorded["launches"]
+    (kind, items, a_rc, b_rc, S, precision), = recorded["launches"]
     (part, targets), = recorded["colsums"]
     row = N * K + N
-    assert S == ops._tn_splits(M, N, K) and tuple(part.shape) == (S, row) and (a_rc, b_rc) == (False, False)
+    assert S == ops._tn_splits(M, N, K) and tuple(part.shape) == (S, row) and (a_rc, b_rc, precision) == (False, False, "f32")
     same_list(items, [dict(a=g.data_ptr(), lda=g.stride(0), b=x.data_ptr(), ldb=x.stride(0), c=part.data_ptr(), ldc=K,
                            I=N, J=K, R=M, c_split_stride=row, asum=part.data_ptr() + 4 * N * K, asum_stride=row)])
     assert [t[:2] for t in targets] == [(0, N * K), (N * K, N)] and targets[0][2] is w and targets[1][2] is b
