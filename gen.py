@@ -72,6 +72,9 @@ def parse_args(argv=None):
     ap.add_argument("--rows-per-pocket", type=int, default=None, metavar="R",
                     help="sample, score: decode on R rows per pocket; a row that ends its sequence starts the pocket's next one "
                          "(sample_stream: same sequences and scores for the same uniforms, whatever R)")
+    ap.add_argument("--decoder-tiles", action="store_true",
+                    help="every mode: the row-tiled decoder step kernels (16 rows per workgroup, weights read once per tile, a "
+                         "pocket of any size) instead of the one-row-per-workgroup ones")
     ap.add_argument("--prefix", type=str, default=None,
                     help="sample, distinct, beam (selected on the device): every sequence starts with this SMILES fragment")
     ap.add_argument("--molecules", type=str, default=None,
@@ -149,7 +152,7 @@ def main():
         mols = [[smi for name, smi in wanted if name == n] for n in names]
         grammar = None if args.grammar == "none" else args.grammar
         res = score(model, voc, mols, B, ex, torch.tensor([args.prop], dtype=torch.float32) if cfg.train.num_props else None,
-                    device=dev, max_length=args.max_length, grammar=grammar, rows_per_pocket=args.rows_per_pocket)
+                    device=dev, max_length=args.max_length, grammar=grammar, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles)
         print(f"# scored {len(wanted)} molecules for {B} pockets")
         seen = {n: 0 for n in names}
         lines = []
@@ -170,17 +173,18 @@ def main():
             tokens = sample_stream(model, voc, per, B, max_length, ex, None if prop is None else prop[:B], args.rows_per_pocket,
                                    device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                    suppress=("&", "^"), generator=gen, trace=tr,
-                                   grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
+                                   grammar=None if args.grammar == "none" else args.grammar, forced=forced,
+                                   tiles=args.decoder_tiles).cpu()
         else:
             tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
                             top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
-                            grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
+                            grammar=None if args.grammar == "none" else args.grammar, forced=forced, tiles=args.decoder_tiles).cpu()
         lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
         print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
     elif args.mode == "distinct":
         tokens = sample_distinct(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature,
                                  suppress=("&", "^"), grammar=None if args.grammar == "none" else args.grammar, seed=args.seed,
-                                 trace=tr, forced=forced).cpu()
+                                 trace=tr, forced=forced, tiles=args.decoder_tiles).cpu()
         keep = tr["valid"].cpu().bool()                                       # a small tree leaves trailing slots empty
         print(f"# {int(keep.sum())} distinct sequences for {B} pockets ({per} asked for each): {tr['steps']} steps")
         rows = [r for r in range(B * per) if keep[r]]
@@ -189,10 +193,11 @@ def main():
     else:
         if args.beam_select == "device" or args.grammar != "none":
             tokens = beam_search_device(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr,
-                                        grammar=None if args.grammar == "none" else args.grammar, forced=forced).cpu()
+                                        grammar=None if args.grammar == "none" else args.grammar, forced=forced,
+                                        tiles=args.decoder_tiles).cpu()
             print(f"# beam search selected on the device: {tr['steps']} steps")
         else:
-            tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr).cpu()
+            tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr, tiles=args.decoder_tiles).cpu()
         best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7
         lengths, logps = [len(h) for _, h in best], [s * len(h) ** 0.7 for s, h in best]
         per = 1

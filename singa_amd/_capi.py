@@ -227,6 +227,15 @@ _BF16_SIGS = {
 }
 BF16_EXPORTS = tuple(_BF16_SIGS)
 
+# include/singa_hip_dec_tiles.h: the decoder step of generation per tile of 16 rows (`ops.dec_layer_step(..., tiles=True)`,
+# `KVDecoder(..., tiles=True)`); a table of its own
+_DEC_TILES_SIGS = {
+    "singa_dec_tile_self_attn": ([P] * 10 + [I32, I32, I32, I32, P, F32, P], I32),
+    "singa_dec_tile_cross_attn": (_SIGS["singa_dec_cross_attn"][0], I32),
+    "singa_dec_tile_ffn": (_SIGS["singa_dec_ffn"][0], I32),
+}
+DEC_TILES_EXPORTS = tuple(_DEC_TILES_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -234,7 +243,7 @@ def bind(path):
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
-            list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()):
+            list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

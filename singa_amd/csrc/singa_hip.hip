@@ -32,6 +32,7 @@
 #include "../../include/singa_hip_prefix.h"
 #include "../../include/singa_hip_data.h"
 #include "../../include/singa_hip_bf16.h"
+#include "../../include/singa_hip_dec_tiles.h"
 #include "so3_index.h"
 
 namespace {
@@ -6986,6 +6987,417 @@ __global__ void __launch_bounds__(256) calib_copy16_kernel(const float4* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ row-tiled decoder step
+// The three sub-blocks of k17 (dec_*_kernel above) with a TILE of 16 consecutive rows of one pocket as the unit of work
+// (include/singa_hip_dec_tiles.h): the tile's input rows sit in LDS, every wavefront owns a slice of the output columns and walks
+// K with v_mfma_f32_16x16x4_f32 - A = the tile (lane i = row, g = k), B = the transposed weights, read ONCE per tile: a lane's
+// VW accumulator tiles are VW consecutive output columns n0 + VW i + t, so a B fragment is one float4 / float2 per lane and 64 VW
+// contiguous bytes per k row.  Accumulator register r of tile t = row 4 g + r, column n0 + VW i + t.  An output element is a
+// sum over its own row's data in the order of the K walk, whatever else the tile holds: rows are independent to the bit.
+// Rows a tile does not have (the pocket's last tile, a per-row position outside the cache) are fed as zeros and never read
+// or written.
+#ifndef SINGA_EMUL
+constexpr int DT_ROWS = 16;                                            // rows of a tile = rows of an MFMA tile
+constexpr int DT_LD = 260, DT_QLD = 516, DT_SLD = 132, DT_PLD = 68;    // LDS pitches of [16][256], [16][512], [16][128], [16][64]:
+                                                                       // = 4 mod 64, so that the A reads (bank 4 i + g) do not collide
+constexpr int DT_CHUNK = 64;                                           // encoder positions per step of the running softmax
+constexpr float DT_SCALE = 0.17677669529663687f;                       // 1 / sqrt(32)
+
+// acc[t] (row 4 g + r, column n0 + VW i + t) += sum over k < K of a[row][k] * w[k * N + column]
+template <int VW>
+__device__ __forceinline__ void dt_gemm(const float* a, int lda, int K, const float* __restrict__ w, int N, int n0,
+                                        floatx4 (&acc)[VW]) {
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const float* ap = a + i * lda + g;
+    const float* wp = w + (long long)g * N + n0 + VW * i;
+    // the walk is latency-bound (one workgroup per CU at best, a dependent chain per accumulator): the B fragments of the next
+    // U steps are in flight while the matrix cores work on the present U.  K is a multiple of 4 U.
+    constexpr int U = VW == 4 ? 8 : 16;
+    float cur[U][VW], nxt[U][VW];
+    auto load = [&](float (&b)[U][VW], int k0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float* p = wp + (long long)(k0 + 4 * u) * N;
+            if constexpr (VW == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(p);
+                b[u][0] = v.x, b[u][1] = v.y, b[u][2] = v.z, b[u][3] = v.w;
+            } else if constexpr (VW == 2) {
+                const float2 v = *reinterpret_cast<const float2*>(p);
+                b[u][0] = v.x, b[u][1] = v.y;
+            } else {
+                b[u][0] = *p;
+            }
+        }
+    };
+    load(nxt, 0);
+    for (int k0 = 0; k0 < K; k0 += 4 * U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < VW; ++t) cur[u][t] = nxt[u][t];
+        if (k0 + 4 * U < K) load(nxt, k0 + 4 * U);
+        __builtin_amdgcn_sched_barrier(0);                             // (the scheduler otherwise sinks every load to its use)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float av = ap[k0 + 4 * u];
+#pragma unroll
+            for (int t = 0; t < VW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, cur[u][t], acc[t], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the tile's 16 input rows -> LDS [16][DT_LD]; rows with live[row] < 0 as zeros, never read
+template <int THREADS>
+__device__ __forceinline__ void dt_load_rows(const float* __restrict__ src, long long row0, const int* live, float* dst) {
+    for (int e = threadIdx.x; e < DT_ROWS * 64; e += THREADS) {
+        const int row = e >> 6, c4 = (e & 63) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live[row] >= 0) v = *reinterpret_cast<const float4*>(src + (row0 + row) * 256 + c4);
+        *reinterpret_cast<float4*>(dst + row * DT_LD + c4) = v;
+    }
+}
+
+// projection result + bias + residual -> LayerNorm(256) -> out, live rows only.  `rs` (LDS [16][DT_LD]) holds the residual and
+// receives the sum in place (an element is read and written by the one lane that owns it); every wavefront then normalises
+// its rows, four channels per lane.
+template <int NW, int VW>
+__device__ __forceinline__ void dt_ln_store(const floatx4 (&acc)[VW], int n0, const float* __restrict__ bias, float* rs,
+                                            const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                            float* __restrict__ out, long long row0, const int* live) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4, col = n0 + VW * i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int t = 0; t < VW; ++t) {
+            float* p = rs + (4 * g + r) * DT_LD + col + t;
+            *p = (bias[col + t] + *p) + acc[t][r];
+        }
+    __syncthreads();
+    const float4 gm = *reinterpret_cast<const float4*>(gamma + lane * 4), bt = *reinterpret_cast<const float4*>(beta + lane * 4);
+    for (int row = wave; row < DT_ROWS; row += NW) {
+        const float4 o = *reinterpret_cast<const float4*>(rs + row * DT_LD + lane * 4);
+        const float mean = wave_sum64((o.x + o.y) + (o.z + o.w)) * (1.f / 256);
+        const float d0 = o.x - mean, d1 = o.y - mean, d2 = o.z - mean, d3 = o.w - mean;
+        const float var = wave_sum64((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) * (1.f / 256);
+        const float rstd = 1.f / sqrtf(var + eps);
+        if (live[row] >= 0)
+            *reinterpret_cast<float4*>(out + (row0 + row) * 256 + lane * 4) =
+                make_float4(d0 * rstd * gm.x + bt.x, d1 * rstd * gm.y + bt.y, d2 * rstd * gm.z + bt.z, d3 * rstd * gm.w + bt.w);
+    }
+}
+
+// self-attention sub-block.  512 threads: q | k | v = 8 wavefronts x 64 columns; attention per row, wavefront w rows 2 w and
+// 2 w + 1 over their own caches, masked as dec_self_attn_kernel masks them (the new position's key and value from LDS); the
+// context takes the place of the row's new value in LDS and is the A operand of the output projection.
+__global__ void __launch_bounds__(512) dec_tile_self_attn_kernel(const float* __restrict__ x, const float* __restrict__ wqkv_t,
+                                                                 const float* __restrict__ bqkv, const float* __restrict__ wo_t,
+                                                                 const float* __restrict__ bo, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float* __restrict__ kc,
+                                                                 float* __restrict__ vc, const long long* __restrict__ pos_ptr,
+                                                                 int per_row, int beams, int tiles, int P, float* __restrict__ y,
+                                                                 float eps) {
+    __shared__ float xs[DT_ROWS * DT_LD], qkv[DT_ROWS * DT_QLD], ps[8][256];
+    __shared__ int spos[DT_ROWS];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x / tiles, j0 = (blockIdx.x % tiles) * DT_ROWS;
+    const long long row0 = (long long)b * beams + j0;
+    if (t < DT_ROWS) {
+        int p = -1;
+        if (j0 + t < beams) {
+            const long long pp = pos_ptr[per_row ? row0 + t : 0];
+            if (pp >= 0 && pp < P) p = (int)pp;
+        }
+        spos[t] = p;
+    }
+    __syncthreads();
+    dt_load_rows<512>(x, row0, spos, xs);
+    __syncthreads();
+    {
+        floatx4 acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+        dt_gemm<4>(xs, DT_LD, 256, wqkv_t, 512, wave * 64, acc);
+        const int col = wave * 64 + 4 * i;                             // [0,128): q   [128,256): k   [256,512): v
+        const float4 bias = *reinterpret_cast<const float4*>(bqkv + col);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * g + r, p = spos[row];
+            const float4 v = make_float4(acc[0][r] + bias.x, acc[1][r] + bias.y, acc[2][r] + bias.z, acc[3][r] + bias.w);
+            *reinterpret_cast<float4*>(qkv + row * DT_QLD + col) = v;
+            if (p >= 0) {
+                if (col >= 256)
+                    *reinterpret_cast<float4*>(vc + (((row0 + row) * 4 + (col - 256) / 64) * P + p) * 64 + (col - 256) % 64) = v;
+                else if (col >= 128)
+                    *reinterpret_cast<float4*>(kc + (((row0 + row) * 4 + (col - 128) / 32) * P + p) * 32 + (col - 128) % 32) = v;
+            }
+        }
+    }
+    __syncthreads();
+    // attention: wavefront w serves rows 2 w and 2 w + 1, the four heads of a row together (their loads are independent)
+    float* pw = ps[wave];                                              // [head][64]: one chunk of 64 positions' probabilities
+    for (int rr = 0; rr < 2; ++rr) {
+        const int row = 2 * wave + rr, pos = spos[row];
+        if (pos < 0) continue;                                         // (uniform over the wavefront; no workgroup barrier in this loop)
+        const float* qrow = qkv + row * DT_QLD;
+        const float* krow = kc + (row0 + row) * 4 * P * 32;
+        const float* vrow = vc + (row0 + row) * 4 * P * 64 + 4 * i;
+        float sc[4][4];                                                // [head][m]: position lane + 64 m
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int tt = lane + 64 * m;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) sc[h][m] = -INFINITY;
+            if (tt < pos) {
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float4* kr = reinterpret_cast<const float4*>(krow + ((long long)h * P + tt) * 32);
+                    const float* q = qrow + h * 32;
+                    float acc = 0.f;
+#pragma unroll
+                    for (int d = 0; d < 8; ++d) {
+                        const float4 kv = kr[d];
+                        acc = fmaf(q[4 * d], kv.x, acc), acc = fmaf(q[4 * d + 1], kv.y, acc);
+                        acc = fmaf(q[4 * d + 2], kv.z, acc), acc = fmaf(q[4 * d + 3], kv.w, acc);
+                    }
+                    sc[h][m] = acc * DT_SCALE;
+                }
+            } else if (tt == pos) {                                    // the new position: its key is in LDS
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float* q = qrow + h * 32;
+                    float acc = 0.f;
+#pragma unroll
+                    for (int d = 0; d < 32; ++d) acc = fmaf(q[d], q[128 + d], acc);
+                    sc[h][m] = acc * DT_SCALE;
+                }
+            }
+        }
+        float ppos[4];                                                 // the new position's probability, per head
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const float mx = wave_max64(fmaxf(fmaxf(sc[h][0], sc[h][1]), fmaxf(sc[h][2], sc[h][3])));
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                sc[h][m] = lane + 64 * m <= pos ? __expf(sc[h][m] - mx) : 0.f;
+                sum += sc[h][m];
+            }
+            sum = 1.f / wave_sum64(sum);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) sc[h][m] *= sum;
+            const int mp = pos >> 6;
+            const float sel = mp == 0 ? sc[h][0] : (mp == 1 ? sc[h][1] : (mp == 2 ? sc[h][2] : sc[h][3]));
+            ppos[h] = __shfl(sel, pos & 63, 64);
+        }
+        // context: lane (g, i) = cached positions g, g + 4, ... of a chunk, value channels 4 i .. 4 i + 3 of every head; the four
+        // partial sums of the lane groups meet in a fixed order, the new position (value in LDS) joins group 0 last
+        float4 ca[4];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) ca[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int cnt = pos - 64 * m < 64 ? pos - 64 * m : 64;     // cached positions 64 m .. 64 m + cnt - 1 (uniform)
+            if (cnt > 0) {
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int h = 0; h < 4; ++h) pw[h * 64 + lane] = sc[h][m];
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll 2
+                for (int j = g; j < cnt; j += 4)
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) {
+                        const float4 v = *reinterpret_cast<const float4*>(vrow + ((long long)h * P + 64 * m + j) * 64);
+                        const float p = pw[h * 64 + j];
+                        ca[h].x = fmaf(p, v.x, ca[h].x), ca[h].y = fmaf(p, v.y, ca[h].y);
+                        ca[h].z = fmaf(p, v.z, ca[h].z), ca[h].w = fmaf(p, v.w, ca[h].w);
+                    }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            float4* vnew = reinterpret_cast<float4*>(qkv + row * DT_QLD + 256 + h * 64 + 4 * i);
+            float c[4] = {ca[h].x, ca[h].y, ca[h].z, ca[h].w};
+            if (g == 0) {
+                const float4 v = *vnew;
+                c[0] = fmaf(ppos[h], v.x, c[0]), c[1] = fmaf(ppos[h], v.y, c[1]);
+                c[2] = fmaf(ppos[h], v.z, c[2]), c[3] = fmaf(ppos[h], v.w, c[3]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {                              // (g0 + g1) + (g2 + g3)
+                c[e] += __shfl_xor(c[e], 16, 64);
+                c[e] += __shfl_xor(c[e], 32, 64);
+            }
+            if (g == 0) *vnew = make_float4(c[0], c[1], c[2], c[3]);
+        }
+    }
+    __syncthreads();
+    floatx4 oa[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+    dt_gemm<2>(qkv + 256, DT_QLD, 256, wo_t, 256, wave * 32, oa);
+    dt_ln_store<8, 2>(oa, wave * 32, bo, xs, gamma, beta, eps, y, row0, spos);
+}
+
+// encoder-decoder attention sub-block.  256 threads, wavefront = head.  The pocket's keys and values are walked in chunks of 64
+// positions: scores = q_h [16][32] x ck_h [32][64] and context += p [16][64] x cv_h [64][64] as matrix products (p goes through LDS
+// to become an A operand), per (row, head) a running maximum m, sum l and context, rescaled chunk by chunk in ascending order.  No
+// array is sized by S.  Padded positions score -1e9 (a fully padded pocket averages its value rows); positions behind S in the
+// last chunk score -inf, i.e. weigh exactly 0, and their loads are clamped to position S - 1.
+__global__ void __launch_bounds__(256) dec_tile_cross_attn_kernel(const float* __restrict__ y, const float* __restrict__ wq_t,
+                                                                  const float* __restrict__ bq, const float* __restrict__ ck,
+                                                                  const float* __restrict__ cv, const unsigned char* __restrict__ pad,
+                                                                  const float* __restrict__ wo_t, const float* __restrict__ bo,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  int beams, int tiles, int S, float* __restrict__ z, float eps) {
+    __shared__ float ys[DT_ROWS * DT_LD], qs[DT_ROWS * DT_SLD], ctx[DT_ROWS * DT_LD], pb[4][DT_ROWS * DT_PLD];
+    __shared__ int live[DT_ROWS];
+    const int t = threadIdx.x, h = t >> 6, lane = t & 63, i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x / tiles, j0 = (blockIdx.x % tiles) * DT_ROWS;
+    const long long row0 = (long long)b * beams + j0;
+    if (t < DT_ROWS) live[t] = j0 + t < beams ? 0 : -1;
+    __syncthreads();
+    dt_load_rows<256>(y, row0, live, ys);
+    __syncthreads();
+    {
+        floatx4 qa[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+        dt_gemm<2>(ys, DT_LD, 256, wq_t, 128, h * 32, qa);
+        const int col = h * 32 + 2 * i;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) qs[(4 * g + r) * DT_SLD + col + u] = qa[u][r] + bq[col + u];
+    }
+    __syncthreads();
+    const float* kh = ck + ((long long)b * 4 + h) * 32 * (long long)S;
+    const float* vh = cv + ((long long)b * 4 + h) * (long long)S * 64 + 4 * i;
+    const unsigned char* padb = pad + (long long)b * S;
+    float qf[8];
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) qf[kk] = qs[i * DT_SLD + h * 32 + 4 * kk + g];
+    float m[4], l[4];
+    floatx4 ca[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m[r] = -INFINITY, l[r] = 0.f, ca[r] = floatx4{0.f, 0.f, 0.f, 0.f};
+    float* pw = pb[h];
+    for (int s0 = 0; s0 < S; s0 += DT_CHUNK) {
+        // the chunk's keys and values are requested together: one memory latency per chunk, not one per product
+        float kf[8][4];
+        float4 vf[DT_CHUNK / 4];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int s = s0 + 16 * u + i;
+                kf[kk][u] = kh[(long long)(4 * kk + g) * S + (s < S ? s : S - 1)];
+            }
+#pragma unroll
+        for (int kk = 0; kk < DT_CHUNK / 4; ++kk) {
+            const int s = s0 + 4 * kk + g;
+            vf[kk] = *reinterpret_cast<const float4*>(vh + (long long)(s < S ? s : S - 1) * 64);
+        }
+        __builtin_amdgcn_sched_barrier(0);                             // (as in dt_gemm: keep the requests together, ahead of their use)
+        floatx4 sa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sa[u] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) sa[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[kk], kf[kk][u], sa[u], 0, 0, 0);
+        // sa[u][r]: row 4 g + r, position s0 + 16 u + i
+        float cm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int s = s0 + 16 * u + i;
+            const bool in = s < S;
+            const bool pd = in && padb[s] != 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = in ? (pd ? -1e9f : sa[u][r] * DT_SCALE) : -INFINITY;
+                sa[u][r] = v;
+                cm[r] = fmaxf(cm[r], v);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float c = cm[r];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) c = fmaxf(c, __shfl_xor(c, o, 64));       // over the 16 lanes of the row's group
+            const float mn = fmaxf(m[r], c), alpha = __expf(m[r] - mn);
+            float rs = 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float p = __expf(sa[u][r] - mn);
+                pw[(4 * g + r) * DT_PLD + 16 * u + i] = p;
+                rs += p;
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
+            l[r] = fmaf(l[r], alpha, rs);
+            m[r] = mn;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ca[u][r] *= alpha;
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int kk = 0; kk < DT_CHUNK / 4; ++kk) {
+            const float4 v = vf[kk];
+            const float p = pw[i * DT_PLD + 4 * kk + g];
+            ca[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(p, v.x, ca[0], 0, 0, 0);
+            ca[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(p, v.y, ca[1], 0, 0, 0);
+            ca[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(p, v.z, ca[2], 0, 0, 0);
+            ca[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(p, v.w, ca[3], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float inv = 1.f / l[r];
+        *reinterpret_cast<float4*>(ctx + (4 * g + r) * DT_LD + h * 64 + 4 * i) =
+            make_float4(ca[0][r] * inv, ca[1][r] * inv, ca[2][r] * inv, ca[3][r] * inv);
+    }
+    __syncthreads();
+    floatx4 oa[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) oa[u] = floatx4{0.f, 0.f, 0.f, 0.f};
+    dt_gemm<4>(ctx, DT_LD, 256, wo_t, 256, h * 64, oa);
+    dt_ln_store<4, 4>(oa, h * 64, bo, ys, gamma, beta, eps, z, row0, live);
+}
+
+// feed-forward sub-block.  512 threads, tiles of 16 consecutive rows of the whole batch (no operand belongs to a pocket).  The
+// hidden row is made and consumed in two halves of 512 channels, [16][512] in LDS at a time; the second product's accumulators
+// run through both halves, so an output is one sum over k = 0 .. 1023 in ascending order.
+__global__ void __launch_bounds__(512) dec_tile_ffn_kernel(const float* __restrict__ z, const float* __restrict__ w1_t,
+                                                           const float* __restrict__ b1, const float* __restrict__ w2_t,
+                                                           const float* __restrict__ b2, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int R, float* __restrict__ out, float eps) {
+    __shared__ float zs[DT_ROWS * DT_LD], hs[DT_ROWS * DT_QLD];
+    __shared__ int live[DT_ROWS];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i = lane & 15, g = lane >> 4;
+    const long long row0 = (long long)blockIdx.x * DT_ROWS;
+    if (t < DT_ROWS) live[t] = row0 + t < R ? 0 : -1;
+    __syncthreads();
+    dt_load_rows<512>(z, row0, live, zs);
+    __syncthreads();
+    floatx4 oa[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+    for (int half = 0; half < 2; ++half) {
+        floatx4 ha[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ha[u] = floatx4{0.f, 0.f, 0.f, 0.f};
+        dt_gemm<4>(zs, DT_LD, 256, w1_t + half * 512, 1024, wave * 64, ha);
+        const int col = wave * 64 + 4 * i;
+        const float4 bias = *reinterpret_cast<const float4*>(b1 + half * 512 + col);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<float4*>(hs + (4 * g + r) * DT_QLD + col) =
+                make_float4(fmaxf(ha[0][r] + bias.x, 0.f), fmaxf(ha[1][r] + bias.y, 0.f), fmaxf(ha[2][r] + bias.z, 0.f),
+                            fmaxf(ha[3][r] + bias.w, 0.f));
+        __syncthreads();
+        dt_gemm<2>(hs, DT_QLD, 512, w2_t + (long long)half * 512 * 256, 256, wave * 32, oa);
+        __syncthreads();
+    }
+    dt_ln_store<8, 2>(oa, wave * 32, b2, zs, gamma, beta, eps, out, row0, live);
+}
+#endif  // SINGA_EMUL
+
 }  // namespace
 
 // ================================================================================================= C ABI
@@ -8045,6 +8457,57 @@ int singa_dec_ffn(const float* z, const float* w1_t, const float* b1, const floa
     if (R <= 0) return SINGA_OK;
     hipLaunchKernelGGL(dec_ffn_kernel, dim3(R), dim3(1024), 0, (hipStream_t)stream, z, w1_t, b1, w2_t, b2, gamma, beta, out, eps);
     return check_launch("dec_ffn");
+}
+
+// include/singa_hip_dec_tiles.h: the same three sub-blocks, one workgroup per tile of 16 rows
+int singa_dec_tile_self_attn(const float* x, const float* wqkv_t, const float* bqkv, const float* wo_t, const float* bo,
+                             const float* gamma, const float* beta, float* k_cache, float* v_cache, const long long* pos,
+                             int per_row, int R, int beams, int P, float* y, float eps, void* stream) {
+    if (!x || !wqkv_t || !bqkv || !wo_t || !bo || !gamma || !beta || !k_cache || !v_cache || !pos || !y)
+        return fail_at(SINGA_E_NULL, "dec_tile_self_attn", "null pointer");
+    if (P <= 0 || P > 256) return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn", "built for at most 256 cached positions");
+    if (R < 0 || beams <= 0 || R % beams) return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn", "rows must be proteins x beams");
+    if (R == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn", "not part of the emulation build");
+#else
+    const int tiles = (beams + DT_ROWS - 1) / DT_ROWS;
+    hipLaunchKernelGGL(dec_tile_self_attn_kernel, dim3((unsigned)(R / beams * tiles)), dim3(512), 0, (hipStream_t)stream, x, wqkv_t,
+                       bqkv, wo_t, bo, gamma, beta, k_cache, v_cache, pos, per_row ? 1 : 0, beams, tiles, P, y, eps);
+    return check_launch("dec_tile_self_attn");
+#endif
+}
+
+int singa_dec_tile_cross_attn(const float* y, const float* wq_t, const float* bq, const float* ck, const float* cv,
+                              const unsigned char* pad, const float* wo_t, const float* bo, const float* gamma, const float* beta,
+                              int R, int beams, int S, float* z, float eps, void* stream) {
+    if (!y || !wq_t || !bq || !ck || !cv || !pad || !wo_t || !bo || !gamma || !beta || !z)
+        return fail_at(SINGA_E_NULL, "dec_tile_cross_attn", "null pointer");
+    if (S <= 0) return fail_at(SINGA_E_SHAPE, "dec_tile_cross_attn", "at least one encoder position");
+    if (R < 0 || beams <= 0 || R % beams) return fail_at(SINGA_E_SHAPE, "dec_tile_cross_attn", "rows must be proteins x beams");
+    if (R == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "dec_tile_cross_attn", "not part of the emulation build");
+#else
+    const int tiles = (beams + DT_ROWS - 1) / DT_ROWS;
+    hipLaunchKernelGGL(dec_tile_cross_attn_kernel, dim3((unsigned)(R / beams * tiles)), dim3(256), 0, (hipStream_t)stream, y, wq_t, bq,
+                       ck, cv, pad, wo_t, bo, gamma, beta, beams, tiles, S, z, eps);
+    return check_launch("dec_tile_cross_attn");
+#endif
+}
+
+int singa_dec_tile_ffn(const float* z, const float* w1_t, const float* b1, const float* w2_t, const float* b2, const float* gamma,
+                       const float* beta, int R, float* out, float eps, void* stream) {
+    if (!z || !w1_t || !b1 || !w2_t || !b2 || !gamma || !beta || !out) return fail_at(SINGA_E_NULL, "dec_tile_ffn", "null pointer");
+    if (R < 0) return fail_at(SINGA_E_SHAPE, "dec_tile_ffn", "rows must not be negative");
+    if (R == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "dec_tile_ffn", "not part of the emulation build");
+#else
+    hipLaunchKernelGGL(dec_tile_ffn_kernel, dim3((unsigned)((R + DT_ROWS - 1) / DT_ROWS)), dim3(512), 0, (hipStream_t)stream, z, w1_t,
+                       b1, w2_t, b2, gamma, beta, R, out, eps);
+    return check_launch("dec_tile_ffn");
+#endif
 }
 
 namespace {

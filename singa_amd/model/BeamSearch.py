@@ -75,14 +75,21 @@ class KVDecoder:
     graph, captured once per search and replayed per token."""
 
     def __init__(self, decoder, projection, enc_outputs, enc_pad_mask, beams, max_positions, vocab_size, fused=True,
-                 search_buffers=True):
+                 search_buffers=True, tiles=False):
         """search_buffers=False leaves out the beam step's own input / output buffers (`step_in`, `step_out`, `logp`): the
-        sampling loop (model/Sampling.py) only uses `token_input` / `prop_input` / `advance`."""
+        sampling loop (model/Sampling.py) only uses `token_input` / `prop_input` / `advance`.  `tiles=True`: the fused step is the
+        row-tiled one (include/singa_hip_dec_tiles.h), which has no limit on the pocket's size; ValueError, before any launch,
+        with `fused=False` or a decoder the step kernels are not built for."""
         self.dec, self.proj, self.beams, self.V = decoder, projection, beams, vocab_size
         a0, f0 = decoder.layers[0].dec_self_attn, decoder.layers[0].pos_ffn
         # the step kernels are built for the shipped decoder geometry; anything else takes the library path
-        self.fused = bool(fused and a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4
-                          and f0.conv1.out_channels == 1024 and max_positions <= 256 and enc_outputs.shape[1] <= 1024)
+        geometry = bool(a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4
+                        and f0.conv1.out_channels == 1024 and max_positions <= 256)
+        self.tiles = bool(tiles)
+        if self.tiles and not (fused and geometry):
+            raise ValueError("KVDecoder: tiles=True is a form of the fused step: fused=True, the shipped decoder geometry and at most "
+                             "256 positions")
+        self.fused = bool(fused and geometry and (self.tiles or enc_outputs.shape[1] <= 1024))
         B, S, _ = enc_outputs.shape
         a0 = decoder.layers[0].dec_self_attn
         self.heads = a0.num_heads
@@ -155,14 +162,14 @@ class KVDecoder:
                 raise ValueError("KVDecoder.advance: one position per row needs the k17 step kernels (fused)")
             for l in range(len(self.dec.layers)):
                 x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], row_pos, self.cross_k[l], self.cross_v[l],
-                                       self.pad_u8, self.beams, per_row=True)
+                                       self.pad_u8, self.beams, per_row=True, tiles=self.tiles)
             return x
         if self.fused:
             # three hand-written launches per layer (singa_dec_*): q/k/v + cache append + attention + projection + LayerNorm,
             # encoder-decoder attention, feed-forward - instead of ~33 library / elementwise launches on 20-row operands
             for l in range(len(self.dec.layers)):
                 x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], self.pos, self.cross_k[l],
-                                       self.cross_v[l], self.pad_u8, self.beams)
+                                       self.cross_v[l], self.pad_u8, self.beams, tiles=self.tiles)
             self.pos += 1
             return x
         R, B, H = self.R, self.B, self.heads
@@ -287,22 +294,26 @@ def _select(cand_score, cand_flat, prefixes, hyps, done, num_beams, vocab_size, 
 
 @torch.no_grad()
 def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", trace=None,
-                graph=True, fused=True):
+                graph=True, fused=True, tiles=False):
     """BS:38-175.  `model`: SINGA (uses model.model.encoder / decoder / projection); `example`: attribute bag with
     protein_element_batch, protein_atom_feature, protein_pos, protein_atom_laplacian (gen.py:176-181) and, optionally,
     protein_knn (a precomputed [2,E] kNN list; otherwise drawn on the GPU); `prop` [batch_size*num_beams, num_props].
     `graph=False` launches the step's kernels one by one instead of replaying the captured HIP graph (same numbers);
-    `fused=False` evaluates the decoder layers with library GEMMs / elementwise ops instead of the k17 step kernels.
+    `fused=False` evaluates the decoder layers with library GEMMs / elementwise ops instead of the k17 step kernels;
+    `tiles=True` evaluates them with the row-tiled step kernels (`KVDecoder`), and `trace["path"]` says which path ran.
     Returns the decoded int64 token matrix [batch_size*topk, T] on `device`."""
     tf = model.model
     vocab_size = len(smiVoc)
     voc = list(smiVoc)
     sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
     dev = torch.device(device)
+    num = 1 if tf.decoder.num_props else 0
+    if tiles:
+        from .Sampling import check_tiles
+        check_tiles("beam_search", tf.decoder, max_length + num, fused)
     enc_outputs, enc_pad_mask = encode_pockets(tf, example, batch_size)
     rows = batch_size * num_beams
-    num = 1 if tf.decoder.num_props else 0
-    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_beams, max_length + num, vocab_size, fused)
+    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_beams, max_length + num, vocab_size, fused, tiles=tiles)
     if graph:
         kv.capture()
     if num:
@@ -329,6 +340,7 @@ def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example,
         cur_len += 1
     if trace is not None:
         trace["last_beams"], trace["hyps"] = prefixes.copy(), hyps
+        trace["path"] = "tiles" if kv.tiles else "k17" if kv.fused else "library"
 
     final = beam_scores
     for b in range(batch_size):
@@ -357,7 +369,7 @@ BEAM_MAX_K = 1024       # slots per pocket singa_beam_select is built for
 
 @torch.no_grad()
 def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", grammar=None,
-                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None):
+                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None, tiles=False):
     """`beam_search` with the selection on the device (include/singa_hip_beam.h states the rule: `_select` and `BeamHypotheses`
     as kernels, ties ranked by slot, then token), which can therefore be constrained: `grammar` None, "smiles" or "valence"
     and `suppress` as in `Sampling.sample`.  Under a grammar every stored hypothesis is a string the rule accepts, ended by its
@@ -369,7 +381,8 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     returned rows are equally long (BS:164-166 returns such rows bare).  `length_penalty`: the exponent of
     `BeamHypotheses`.  `graph=False` launches the step's kernels one by one (same result).  The loop is `sample_distinct`'s:
     two cache buffers taken in turn, the step captured once per parity, one read of the pockets' live counters every
-    `Sampling.LIVE_POLL` tokens and nothing else per token.  Only the k17 step kernels serve this mode.  The end of the search
+    `Sampling.LIVE_POLL` tokens and nothing else per token.  Only the fused step kernels serve this mode: k17, or with
+    `tiles=True` the row-tiled ones, which take a pocket of any size (`trace["path"]` says "k17" or "tiles").  The end of the search
     stays on the host: a pocket that is not done adds its live beams as hypotheses (BS:141-149), the `topk` best are returned.
 
     `forced`: int64 [batch_size, max_length], ONE prefix per pocket (`smiles.encode` builds it, `smiles.check_prefix` validates
@@ -393,7 +406,7 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
     atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
     if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
-            and positions <= 256 and atoms <= 1024 and V <= 1024):
+            and positions <= 256 and (tiles or atoms <= 1024) and V <= 1024):
         raise ValueError("beam_search_device: the k17 step kernels are the only path: the shipped decoder geometry, at most 256 "
                          "positions, 1024 pocket atoms and 1024 tokens")
     need = 2 * S.cache_bytes(tf.decoder, rows, positions) + rows * V * 4 + 3 * rows * T * 8
@@ -405,7 +418,8 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
         forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
-    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
+                   tiles=tiles)
     bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     state = {"score": new(rows, torch.float32), "length": new(rows, torch.int32), "tokens": new((rows, T), torch.int64),
@@ -494,5 +508,6 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
                     decoded[i, len(x)] = eos
     if trace is not None:
         trace.update(hyps=hyps, hyp_sum_logp=[[sums[id(x)] for _, x in h.beams] for h in hyps],
-                     hyp_tokens=[[x for _, x in h.beams] for h in hyps], steps=steps, valid=torch.from_numpy(valid))
+                     hyp_tokens=[[x for _, x in h.beams] for h in hyps], steps=steps, valid=torch.from_numpy(valid),
+                     path="tiles" if kv.tiles else "k17")
     return torch.from_numpy(decoded).to(dev)

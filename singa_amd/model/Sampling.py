@@ -80,6 +80,17 @@ def cache_bytes(decoder, rows, positions):
     return len(decoder.layers) * rows * positions * (a.key_channels + a.hidden_channels) * 4
 
 
+def check_tiles(fn, decoder, positions, fused):
+    """`tiles=True` of `fn` before any device work: the row-tiled step kernels are a form of the fused step and are built for the
+    shipped decoder geometry and at most 256 positions (`KVDecoder` checks the same, but only once the encoder has run)."""
+    a0, f0 = decoder.layers[0].dec_self_attn, decoder.layers[0].pos_ffn
+    if fused is not None and not fused:
+        raise ValueError(f"{fn}: tiles=True is a form of the fused step, fused=False contradicts it")
+    if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
+            and positions <= 256):
+        raise ValueError(f"{fn}: tiles=True needs the shipped decoder geometry and at most 256 positions")
+
+
 def _prologue(fn, model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress):
     """What `sample` and `sample_distinct` (`fn`: the caller's name, for the messages) check and work out alike before they
     differ -> (device, transformer, vocabulary, (sos, eos, pad), rows, 1 with a property prompt else 0, cache positions, free
@@ -128,7 +139,8 @@ def _decode(replays, max_steps, live, each=None):
 
 @torch.no_grad()
 def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0, top_k=0,
-           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None, forced=None):
+           top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None, forced=None,
+           tiles=False):
     """`num_samples` sequences for each of the `batch_size` pockets of `example`, drawn token by token from the model's own
     distribution reshaped by `temperature` (0 = greedy), `top_k` (0 = off) and `top_p` (1 = off).
 
@@ -136,13 +148,15 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     as in `beam_search`.  `suppress`: tokens never to be drawn.  `generator`: torch.Generator for the uniforms (CPU or device);
     `uniforms` [max_length, rows] f32 in [0, 1) replaces the draw (row t is read by the step that writes column t + 1).
     `graph=False` launches the step's kernels one by one (same tokens).  `fused`: True = k17 step kernels, False = library
-    GEMMs, None = k17 wherever the k17 kernels' limits allow (it is the faster one at every row count measured).
+    GEMMs, None = k17 wherever the k17 kernels' limits allow (it is the faster one at every row count measured).  `tiles=True`:
+    the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17 - no limit on the pocket's atoms; a ValueError with
+    `fused=False` or another decoder geometry.
 
     Returns the int64 token matrix [batch_size * num_samples, max_length], pocket-major: a row starts with '&', ends with
     '$' if the model ended it before `max_length`, and is padded with '^'.  `trace`, if a dict, receives `lengths` (int32:
     tokens drawn per row, the '$' included, '&' not), `sum_logp` (f32: the model's own log-likelihood of the drawn tokens,
     temperature 1 and nothing filtered), `token_logp` [rows, max_length] (per drawn token), `uniforms`, `path`
-    ('k17' / 'library') and `steps` (tokens decoded before every row had ended).
+    ('k17' / 'tiles' / 'library') and `steps` (tokens decoded before every row had ended).
 
     `grammar="smiles"`: only tokens that keep the row a prefix of a syntactically complete SMILES string which still fits
     into `max_length` (>= 3) are drawn, so every row ends with '$'.  `token_logp` / `sum_logp` stay the unconstrained model's;
@@ -172,6 +186,8 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         if forced.shape[0] != batch_size * num_samples:
             raise ValueError(f"sample: forced has {forced.shape[0]} rows, expected {batch_size * num_samples} (or one per pocket: "
                              f"{batch_size})")
+    if tiles:
+        check_tiles("sample", tf.decoder, positions, fused)
     need = cache_bytes(tf.decoder, rows, positions)
     if need + (64 << 10) * rows > free:                  # + the step's activations: a few [rows, 1024] f32 operands
         raise ValueError(f"sample: the key / value caches of {rows} rows x {positions} positions take {need} bytes, "
@@ -186,7 +202,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     uniforms = uniforms.to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), num_samples, positions, len(voc),
-                   fused is None or bool(fused), search_buffers=False)
+                   fused is None or bool(fused), search_buffers=False, tiles=tiles)
     if fused and not kv.fused:
         raise ValueError("sample: fused=True needs the shipped decoder geometry, at most 256 positions and 1024 pocket atoms")
     state = {"tokens": torch.empty(rows, max_length, dtype=torch.int64, device=dev),
@@ -234,7 +250,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     steps = _decode(replays, max_length - 1, lambda: int(state["live"].item()))
     if trace is not None:
         trace.update(lengths=state["length"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"], uniforms=uniforms,
-                     path="k17" if kv.fused else "library", steps=steps)
+                     path="tiles" if kv.tiles else "k17" if kv.fused else "library", steps=steps)
         if grammar is not None:
             trace.update(allowed_logp=state["allowed_logp"])
         if forced is not None:
@@ -243,7 +259,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
 
 
 def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda", max_length=None, grammar=None, fused=None,
-          rows_per_pocket=None):
+          rows_per_pocket=None, tiles=False):
     """The model's own log-likelihood of given molecules: `molecules[b]` is the list of SMILES strings (or token lists, as
     `smiles.encode` takes them) to score for pocket b of `example`; the lists may differ in length.  Every molecule is one row
     of `sample` with all its columns forced up to and including '$', so a score comes from the same kernels, in the same
@@ -261,7 +277,7 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     the rows, not of the library, and a row that has ended a short molecule starts the pocket's next one.  The same dict comes
     back, bit for bit.  `prop` is then one prompt per pocket ([num_props] or [batch_size, num_props]); a prompt per molecule is
     a ValueError (a row keeps its cache position 0 across molecules), and `fused` is not consulted (the k17 step kernels are
-    that mode's only path)."""
+    that mode's only path).  `tiles`: handed to `sample` / `sample_stream`; with it the returned dict also holds `path`: "tiles"."""
     dev = torch.device(device)
     if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
         raise RuntimeError("score runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
@@ -292,10 +308,10 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     uniforms = torch.zeros(max_length, batch_size * per)
     if rows_per_pocket is not None:
         sample_stream(model, smiVoc, per, batch_size, max_length, example, prop, rows_per_pocket, device=device, uniforms=uniforms,
-                      trace=tr, grammar=grammar, forced=forced)
+                      trace=tr, grammar=grammar, forced=forced, tiles=tiles)
     else:
         sample(model, smiVoc, per, batch_size, max_length, example, prop, device=device, uniforms=uniforms, fused=fused, trace=tr,
-               grammar=grammar, forced=forced)
+               grammar=grammar, forced=forced, tiles=tiles)
     keys = {"token_logp": "token_logp", "rank": "rank"}
     if grammar is not None:
         keys["allowed_logp"] = "allowed_logp"
@@ -308,6 +324,8 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
         out["length"].append([int(lengths[r]) for r in rows])
         for k in keys:
             out[k].append([host[k][r, 1:1 + lengths[r]].copy() for r in rows])
+    if tiles:
+        out["path"] = tr["path"]
     return out
 
 
@@ -317,7 +335,7 @@ STREAM_MAX_ROWS = 2048  # rows per pocket singa_stream_refill is built for
 @torch.no_grad()
 def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, rows_per_pocket=64, device="cuda",
                   temperature=1.0, top_k=0, top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, trace=None,
-                  grammar=None, forced=None):
+                  grammar=None, forced=None, tiles=False):
     """`sample` on a fixed budget of rows: `num_samples` molecules for each of the `batch_size` pockets of `example`, decoded on
     batch_size * `rows_per_pocket` rows; a row that has ended its molecule ('$', or the last column) starts the pocket's next
     one in the following step, until the pocket has none left (include/singa_hip_stream.h states the rule).  Rows that have
@@ -344,7 +362,10 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
 
     ValueError before any device work for a `prop` of another shape, `rows_per_pocket` outside 1..2048, a decoder geometry,
     length or pocket size the k17 step kernels are not built for (they are the only path), and a run whose caches and
-    per-molecule buffers (`forced` and `rank` included) do not fit the free memory."""
+    per-molecule buffers (`forced` and `rank` included) do not fit the free memory.
+
+    `tiles=True`: the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17; the limit on the pocket's atoms does
+    not apply to them, and `trace["path"]` says "tiles"."""
     dev, tf, voc, (sos, eos, pad), mols, num, positions, free, cls, allowed = _prologue(
         "sample_stream", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
     R, V = int(rows_per_pocket), len(voc)
@@ -358,7 +379,7 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
     a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
     atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
     if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
-            and positions <= 256 and atoms <= 1024 and V <= 1024):
+            and positions <= 256 and (tiles or atoms <= 1024) and V <= 1024):
         raise ValueError("sample_stream: unsupported decoder geometry - the k17 step kernels are the only path: the shipped "
                          "decoder geometry, at most 256 positions, 1024 pocket atoms and 1024 tokens")
     if forced is not None:
@@ -385,7 +406,8 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
                          f"{uniforms.dtype} {tuple(uniforms.shape)}")
     uniforms = uniforms.to(dev).contiguous()
 
-    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), R, positions, V, True, search_buffers=False)
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), R, positions, V, True, search_buffers=False,
+                   tiles=tiles)
     if not kv.fused:
         raise ValueError("sample_stream: unsupported decoder geometry for the k17 step kernels")
     i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
@@ -441,7 +463,7 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
         raise RuntimeError(f"sample_stream: {live()} rows still hold a molecule after {steps} steps")
     if trace is not None:
         trace.update(lengths=state["length"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"], uniforms=uniforms,
-                     path="k17", steps=steps, row_of=state["row_of"], start_step=state["start_step"])
+                     path="tiles" if kv.tiles else "k17", steps=steps, row_of=state["row_of"], start_step=state["start_step"])
         if grammar is not None:
             trace.update(allowed_logp=state["allowed_logp"])
         if forced is not None:
@@ -454,7 +476,7 @@ SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
 
 @torch.no_grad()
 def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
-                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None):
+                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None, tiles=False):
     """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
     replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` ("smiles", as in `sample`;
     "valence" is a ValueError here), by
@@ -482,7 +504,10 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     the completions of the prefix, not over all sequences.  A matrix without a forced column gives the bits of `forced=None`.
 
     ValueError before any launch for temperature <= 0, num_samples > 2048, a decoder geometry,
-    length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory."""
+    length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory.
+
+    `tiles=True`: the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17; the limit on the pocket's atoms does
+    not apply to them, and `trace` also receives `path`: "tiles"."""
     if grammar == "valence":
         raise ValueError("sample_distinct: grammar='valence' is unsupported (the selection gathers one state word per row); use "
                          "grammar='smiles' here, or `sample` / `sample_stream` for the valence rule")
@@ -496,7 +521,7 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     a0, f0 = tf.decoder.layers[0].dec_self_attn, tf.decoder.layers[0].pos_ffn
     atoms = int(torch.bincount(example.protein_element_batch.cpu().long()).max())
     if not (a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4 and f0.conv1.out_channels == 1024
-            and positions <= 256 and atoms <= 1024 and V <= 1024):
+            and positions <= 256 and (tiles or atoms <= 1024) and V <= 1024):
         raise ValueError("sample_distinct: the k17 step kernels are the only path: the shipped decoder geometry, at most 256 "
                          "positions, 1024 pocket atoms and 1024 tokens")
     if streams is None:
@@ -513,7 +538,8 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         forced = forced.cpu().numpy() if torch.is_tensor(forced) else forced
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
-    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False)
+    kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
+                   tiles=tiles)
     bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     f32 = dict(dtype=torch.float32, device=dev)
     state = {"gumbel": torch.empty(rows, **f32), "prop_logp": torch.empty(rows, **f32), "sum_logp": torch.empty(rows, **f32),
@@ -566,6 +592,8 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     if trace is not None:
         trace.update(gumbel=state["gumbel"], prop_logp=state["prop_logp"], sum_logp=state["sum_logp"], token_logp=state["tok_logp"],
                      lengths=state["length"], valid=(state["gumbel"] > float("-inf")).to(torch.uint8), steps=steps)
+        if tiles:
+            trace.update(path="tiles")
     return state["tokens"]
 
 

@@ -3,7 +3,7 @@
 num_beams=20, topk=1, max_length = tgt_len + 1 = 201, property prompt - on synthetic pockets with random-init weights.
 
     python tools/bench_beam.py [--proteins 4] [--max-length 201] [--beams 20] [--no-graph] [--prefix-baseline]
-                               [--select host|device] [--batch 1]
+                               [--select host|device] [--batch 1] [--tiles]
 
 Prints one JSON line: new tokens per second (beams x steps / time), pockets per second, and the per-step time.
 `--select device` times `beam_search_device` (the selection as kernels inside the captured step, nothing copied per token)
@@ -11,6 +11,9 @@ instead of `beam_search` (2 x beams candidates per pocket to the host and the ch
 pockets per call, so that the two can be compared at 1 and at several pockets, back to back on one device.
 `--prefix-baseline` also times the reference's schedule (the whole decoder re-run on the growing prefix for every
 token, BeamSearch.py:82) built from the same product modules on the same GPU, so the two differ by the algorithm only.
+`--tiles` times the chosen search on both decoder paths instead - the k17 step kernels and the row-tiled ones
+(include/singa_hip_dec_tiles.h) - on the first pocket: one warm-up each, then three whole searches each, interleaved, every run
+listed in ms per step (`tiles_table`).
 """
 import argparse
 import json
@@ -59,6 +62,7 @@ def main():
     ap.add_argument("--prefix-baseline", action="store_true")
     ap.add_argument("--select", choices=["host", "device"], default="host")
     ap.add_argument("--batch", type=int, default=1, help="pockets per call")
+    ap.add_argument("--tiles", action="store_true", help="time the search on the k17 and on the row-tiled decoder step, interleaved")
     args = ap.parse_args()
     assert not args.prefix_baseline or args.batch == 1, "--prefix-baseline re-runs one pocket: --batch 1"
     import __graft_entry__
@@ -97,6 +101,25 @@ def main():
     pockets = [pocket(i) for i in range(args.proteins)]
     search = beam_search_device if args.select == "device" else beam_search
     run = lambda ex: search(model, voc, args.beams, args.batch, args.max_length, 1, ex, prop, device=dev, graph=not args.no_graph)
+    if args.tiles:
+        def timed(tiles):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = search(model, voc, args.beams, args.batch, args.max_length, 1, pockets[0], prop, device=dev, graph=not args.no_graph,
+                       tiles=tiles).shape[1]
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (n - 1)
+        timed(False), timed(True)
+        k17, til = [], []
+        for _ in range(3):
+            k17.append(timed(False))
+            til.append(timed(True))
+        print(json.dumps({"select": args.select, "num_beams": args.beams, "pockets_per_call": args.batch, "max_length": args.max_length,
+                          "tiles_table": [{"rows": args.beams * args.batch, "k17_ms_per_step": round(float(np.median(k17)), 4),
+                                           "tiles_ms_per_step": round(float(np.median(til)), 4),
+                                           "k17_runs_ms": [round(x, 4) for x in k17], "tiles_runs_ms": [round(x, 4) for x in til],
+                                           "tiles_faster": max(til) < min(k17), "k17_faster": max(k17) < min(til)}]}))
+        return
     out = run(pockets[0])                                               # warm-up (library initialisation)
     torch.cuda.synchronize()
     t0 = time.perf_counter()

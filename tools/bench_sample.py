@@ -4,7 +4,7 @@ atoms, property prompt, max_length = tgt_len + 1 = 201 - on a synthetic pocket w
 step of `tools/bench_beam.py` measured in the same process on the same pocket.
 
     python tools/bench_sample.py [--rows 128] [--max-length 201] [--reps 5] [--fused auto|k17|library] [--table] [--grammar] [--forced]
-                                  [--distinct] [--rows-per-pocket R] [--valence] [--score-stream]
+                                  [--distinct] [--rows-per-pocket R] [--valence] [--score-stream] [--tiles]
 
 Prints one JSON line: rows, steps, ms per step, new tokens / s, sequences / s and the decoder path of the sampled run; the
 20-row comparison (`at_20_rows`: medians of `--reps` full generations each, sampled and beam runs interleaved, both in ms
@@ -30,6 +30,10 @@ molecules per pocket of ragged length, drawn once by `sample` from the `beam_b2_
 of 256 molecules per pocket against `score(rows_per_pocket=256)`, whole calls timed, alternately, twice each, with the ratio of
 step counts that predicts the gain - and `prefix_table`: `sample_distinct` and `beam_search_device` on the synthetic pocket with
 a forced prefix of 5 tokens next to the same run without one, ms per step of whole generations, interleaved.
+With `--tiles` nothing but the row-tiled decoder step (include/singa_hip_dec_tiles.h) next to k17: `tiles_table` - `sample` on
+both paths at rows = 20, 128, 512, 2048 (5 / 5 / 3 / 3 whole generations each, as `--table` takes them), interleaved - and
+`tiles_distinct` - `sample_distinct` at 2,048 rows on both paths, 3 generations each, interleaved.  Every run is listed.  With
+`--tiles-only ROWS` nothing but two `sample(tiles=True)` generations of ROWS rows: the run to take a kernel trace of.
 """
 import argparse
 import json
@@ -63,6 +67,11 @@ def main():
                     help="nothing but the k17 step under grammar='valence' next to grammar='smiles' at rows = 128, 512, 2048 (valence_table)")
     ap.add_argument("--rows-per-pocket", type=int, default=0, metavar="R",
                     help="nothing but sample_stream: the streaming step next to the plain one, and molecules / s at R rows per pocket")
+    ap.add_argument("--tiles", action="store_true",
+                    help="nothing but the row-tiled decoder step next to k17: sample at rows = 20, 128, 512, 2048 and sample_distinct at "
+                         "2048 (tiles_table, tiles_distinct)")
+    ap.add_argument("--tiles-only", type=int, default=0, metavar="ROWS",
+                    help="nothing but two sample(tiles=True) generations of ROWS rows: the run to take a kernel trace of")
     ap.add_argument("--score-stream", action="store_true",
                     help="nothing but score on a row budget against score in chunks, and the forced step of the two slot searches")
     args = ap.parse_args()
@@ -105,11 +114,11 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 
-    def run_sample(rows, fused, grammar=None, forced=None):
+    def run_sample(rows, fused, grammar=None, forced=None, tiles=False):
         tr = {}
         prop = torch.ones(rows, 3, device=dev)
         sample(model, voc, rows, 1, T, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar, forced=forced)
+               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar, forced=forced, tiles=tiles)
         run_sample.path = tr["path"]
         return tr["steps"]
 
@@ -120,6 +129,34 @@ def main():
         return {"rows": rows, "ms_per_step": round(ms, 4), "new_tokens_per_s": round(rows / ms * 1e3, 1),
                 "sequences_per_s": round(rows / (ms * (T - 1)) * 1e3, 2)}
 
+    if args.tiles_only:
+        ms = [timed(lambda: run_sample(args.tiles_only, True, tiles=True)) for _ in range(2)]
+        print(json.dumps({"tiles_only_rows": args.tiles_only, "path": run_sample.path, "ms_per_step": [round(x, 4) for x in ms]}))
+        return
+    if args.tiles:
+        def both(fn, reps):
+            """fn(tiles) -> steps: one warm-up each, then `reps` whole generations each, interleaved -> (k17 runs, tile runs) in ms per step"""
+            fn(False), fn(True)
+            k17, til = [], []
+            for _ in range(reps):
+                k17.append(timed(lambda: fn(False)))
+                til.append(timed(lambda: fn(True)))
+            return k17, til
+
+        def row(rows, k17, til):
+            return {"rows": rows, "k17_ms_per_step": round(statistics.median(k17), 4), "tiles_ms_per_step": round(statistics.median(til), 4),
+                    "k17_runs_ms": [round(x, 4) for x in k17], "tiles_runs_ms": [round(x, 4) for x in til],
+                    "tiles_faster": max(til) < min(k17), "k17_faster": max(k17) < min(til)}       # faster = the runs do not overlap
+
+        def run_distinct(rows, tiles):
+            tr = {}
+            sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev, temperature=args.temperature,
+                            suppress=("$",), seed=rows, trace=tr, tiles=tiles)
+            return tr["steps"]
+        ttable = [row(rows, *both(lambda t: run_sample(rows, True, tiles=t), 3 if rows >= 512 else args.reps)) for rows in (20, 128, 512, 2048)]
+        print(json.dumps({"max_length": T, "tiles_table": ttable,
+                          "tiles_distinct": [row(2048, *both(lambda t: run_distinct(2048, t), 3))]}))
+        return
     if args.score_stream:
         import numpy as np
         from singa_amd.model.BeamSearch import beam_search_device
