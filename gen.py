@@ -57,7 +57,7 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--data", choices=["golden", "synthetic"], default="golden")
     ap.add_argument("--pockets", type=int, default=3, help="number of pockets (synthetic data)")
-    ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 4 or 6)")
+    ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 3, 4 or 6)")
     ap.add_argument("--mode", choices=["beam", "sample", "score", "distinct"], default="sample")
     ap.add_argument("--num-samples", type=int, default=100, help="sequences per pocket (sample, distinct)")
     ap.add_argument("--num-beams", type=int, default=20, help="beams per pocket (beam); the best hypothesis is written")

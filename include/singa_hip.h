@@ -22,8 +22,8 @@
  * Coefficient orderings: node tensors are [N, K=(L+1)^2, C] l-primary; edge tensors between the
  * two rotations are "m-primary": [(l,0) l=0..L] ++ for m=1..M: [(l,+m) l=m..L] ++ [(l,-m) l=m..L], KR rows.
  * Reduced Wigner rows Wr[E, WSZ]: for l=0..L the rows |m|<=min(l,M) of the l-th Wigner block, row-major
- * [2*min(l,M)+1][2l+1]: 35 / 115 / 235 coefficients for L = 2 / 4 / 6 at M = 2, padded with zeros to a record of
- * WSZ = 36 / 116 / 236 floats (a multiple of 4: 16-byte aligned records; singa_dims reports WSZ).
+ * [2*min(l,M)+1][2l+1]: 35 / 70 / 115 / 235 coefficients for L = 2 / 3 / 4 / 6 at M = 2, padded with zeros to a
+ * record of WSZ = 36 / 72 / 116 / 236 floats (a multiple of 4: 16-byte aligned records; singa_dims reports WSZ).
  */
 #ifndef SINGA_HIP_H
 #define SINGA_HIP_H
@@ -37,7 +37,7 @@ extern "C" {
 
 #define SINGA_OK 0
 #define SINGA_E_NULL (-1)        /* required pointer is null */
-#define SINGA_E_LMAX (-2)        /* unsupported (lmax, mmax): built for lmax in {2,4,6}, mmax = 2; EF:2208-2209 */
+#define SINGA_E_LMAX (-2)        /* unsupported (lmax, mmax): built for lmax in {2,3,4,6}, mmax = 2; EF:2208-2209 */
 #define SINGA_E_SHAPE (-3)       /* inconsistent or unsupported dimension */
 #define SINGA_E_NOINIT (-4)      /* singa_init() has not been called on this device */
 

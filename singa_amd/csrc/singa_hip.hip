@@ -4659,7 +4659,7 @@ __global__ void __launch_bounds__(SkinnyCfg<C>::BLOCK) so3_skinny_expand_mfma_ke
 template <int L>
 struct SkinnyChunk {
     static constexpr int K = (L + 1) * (L + 1);
-    static constexpr int D = L == 2 ? 3 : (L == 4 ? 5 : 7);        // coefficient rows per prefetch chunk (K = D * D)
+    static constexpr int D = L + 1;                                // coefficient rows per prefetch chunk (K = D * D)
 };
 
 template <int L, int C>
@@ -4759,6 +4759,7 @@ static int so3_skinny_reduce_runs(int lmax) {
     hipError_t e = hipErrorInvalidValue;
     constexpr int BL = SkinnyCfg<C>::BLOCK;
     if (lmax == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, so3_skinny_reduce_kernel<2, C>, BL, 0);
+    if (lmax == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, so3_skinny_reduce_kernel<3, C>, BL, 0);
     if (lmax == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, so3_skinny_reduce_kernel<4, C>, BL, 0);
     if (lmax == 6) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, so3_skinny_reduce_kernel<6, C>, BL, 0);
     if (e != hipSuccess || per_cu < 1) per_cu = 2;
@@ -6793,14 +6794,17 @@ bool pack_mut(const singa_seg_mut_t* s, int nseg, SegsMut* out) {
     return true;
 }
 
+// the one text behind every SINGA_E_LMAX
+#define SINGA_LMAX_TEXT "built for lmax in {2, 3, 4, 6} at mmax = 2"
 #define SINGA_DISPATCH_L(lmax, mmax, ...)                                             \
     do {                                                                                \
-        if ((mmax) != 2) return fail(SINGA_E_LMAX, "only mmax = 2 is built");           \
+        if ((mmax) != 2) return fail(SINGA_E_LMAX, SINGA_LMAX_TEXT);                    \
         switch (lmax) {                                                                 \
             case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                              \
+            case 3: { constexpr int L_ = 3; __VA_ARGS__; } break;                              \
             case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                              \
             case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                              \
-            default: return fail(SINGA_E_LMAX, "lmax must be 2, 4 or 6");               \
+            default: return fail(SINGA_E_LMAX, SINGA_LMAX_TEXT);                        \
         }                                                                               \
     } while (0)
 
@@ -7735,24 +7739,27 @@ int singa_segment_wsum_bwd(const float* g_out, const float* w, const float* v, c
 }
 
 // (KIN, C, edge?) combinations that are built: attention grids [L][2] on 128 hidden channels over the three per-m
-// segments (KIN = 9, 19, 29), FFN grids [L][L] on 512 hidden channels over one [KIN, C] record (KIN = 9, 25, 49).
+// segments (KIN = 5L - 1: 9, 14, 19, 29), FFN grids [L][L] on 512 hidden channels over one [KIN, C] record
+// (KIN = (L + 1)^2: 9, 16, 25, 49).
 #define SINGA_DISPATCH_S2(kin, ch, nseg, ...)                                                            \
     do {                                                                                                 \
         if ((nseg) == 3 && (ch) == 128) {                                                                \
             constexpr int C_ = 128; constexpr bool EDGE_ = true;                                         \
             switch (kin) {                                                                               \
                 case 9: { constexpr int KIN_ = 9; __VA_ARGS__; } break;                                  \
+                case 14: { constexpr int KIN_ = 14; __VA_ARGS__; } break;                                \
                 case 19: { constexpr int KIN_ = 19; __VA_ARGS__; } break;                                \
                 case 29: { constexpr int KIN_ = 29; __VA_ARGS__; } break;                                \
-                default: return fail(SINGA_E_SHAPE, "s2act(edge): KIN must be 9, 19 or 29");             \
+                default: return fail(SINGA_E_SHAPE, "s2act(edge): KIN must be 9, 14, 19 or 29");         \
             }                                                                                            \
         } else if ((nseg) == 1 && (ch) == 512) {                                                         \
             constexpr int C_ = 512; constexpr bool EDGE_ = false;                                        \
             switch (kin) {                                                                               \
                 case 9: { constexpr int KIN_ = 9; __VA_ARGS__; } break;                                  \
+                case 16: { constexpr int KIN_ = 16; __VA_ARGS__; } break;                                \
                 case 25: { constexpr int KIN_ = 25; __VA_ARGS__; } break;                                \
                 case 49: { constexpr int KIN_ = 49; __VA_ARGS__; } break;                                \
-                default: return fail(SINGA_E_SHAPE, "s2act(node): KIN must be 9, 25 or 49");             \
+                default: return fail(SINGA_E_SHAPE, "s2act(node): KIN must be 9, 16, 25 or 49");         \
             }                                                                                            \
         } else {                                                                                         \
             return fail(SINGA_E_SHAPE, "s2act: built for (3 segments, C = 128) and (1 segment, C = 512)"); \
@@ -7851,13 +7858,19 @@ int singa_gather_wsum_bwd(const float* g, const float* alpha, const float* wv, c
             constexpr int C_ = EDGE_ ? 128 : 512;                                                        \
             switch (lmax) {                                                                              \
                 case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                                    \
+                case 3: { constexpr int L_ = 3; __VA_ARGS__; } break;                                    \
                 case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                                    \
                 case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                                    \
-                default: rc_ = fail(SINGA_E_LMAX, "s2act_sep: lmax must be 2, 4 or 6");                  \
+                default: rc_ = fail(SINGA_E_LMAX, SINGA_LMAX_TEXT);                                      \
             }                                                                                            \
         });                                                                                              \
         if (rc_ != SINGA_OK) return rc_;                                                                 \
     } while (0)
+
+// The largest degree whose node-grid forward is built in the two-channel form (see singa_s2act_sep_fwd)
+#ifndef SINGA_S2_NODE_PAIR_LMAX
+#define SINGA_S2_NODE_PAIR_LMAX 4
+#endif
 
 // The checks singa_s2act_sep_fwd and singa_s2act_sep_bwd_seg share: form against C, segment rows against lmax.  *EC: the
 // threads of a one-channel launch, 0 where there are no rows (the caller returns SINGA_OK behind its own checks).
@@ -7883,12 +7896,12 @@ int singa_s2act_sep_fwd(const singa_seg_t* x, int nseg, const float* gate, int64
     const int tag = edge ? SINGA_PROF_S2_EDGE_FWD : SINGA_PROF_S2_NODE_FWD;
     // two channels per thread (packed f32) where every row start is 8-byte aligned and the registers allow it (not the
     // L = 6 node grid: 167 registers per channel; 256 VGPRs + 24 AGPRs as a pair, so that instantiation is not built)
-    bool pair = (((uintptr_t)gate | (uintptr_t)out) & 7) == 0 && ldg % 2 == 0 && (edge || lmax <= 4);
+    bool pair = (((uintptr_t)gate | (uintptr_t)out) & 7) == 0 && ldg % 2 == 0 && (edge || lmax <= SINGA_S2_NODE_PAIR_LMAX);
     for (int i = 0; i < nseg; ++i) pair = pair && ((uintptr_t)s.p[i] & 7) == 0 && s.ld[i] % 2 == 0;
     const long long NT = pair ? EC / 2 : EC;
     const int blocks = (int)((NT + 255) / 256);
     SINGA_DISPATCH_S2SEP(lmax, edge, {
-        using T2_ = std::conditional_t<EDGE_ || L_ <= 4, v2f, float>;
+        using T2_ = std::conditional_t<EDGE_ || L_ <= SINGA_S2_NODE_PAIR_LMAX, v2f, float>;
         if (pair) SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd_kernel<L_, EDGE_, C_, T2_>), dim3(blocks), dim3(256), (hipStream_t)stream, s,
                                gate, (long long)ldg, P, Q, out, NT);
         else SINGA_LAUNCH(tag, E, 0, (s2act_sep_fwd_kernel<L_, EDGE_, C_, float>), dim3(blocks), dim3(256), (hipStream_t)stream, s,
@@ -7972,17 +7985,19 @@ int singa_so3_skinny_nparts(int N, int lmax, int C) {
             constexpr int C_ = 512;                                                        \
             switch (lmax) {                                                                \
                 case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                      \
+                case 3: { constexpr int L_ = 3; __VA_ARGS__; } break;                      \
                 case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                      \
                 case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                      \
-                default: return fail(SINGA_E_LMAX, "so3_skinny: lmax must be 2, 4 or 6");  \
+                default: return fail(SINGA_E_LMAX, SINGA_LMAX_TEXT);                       \
             }                                                                              \
         } else {                                                                           \
             constexpr int C_ = 112;                                                        \
             switch (lmax) {                                                                \
                 case 2: { constexpr int L_ = 2; __VA_ARGS__; } break;                      \
+                case 3: { constexpr int L_ = 3; __VA_ARGS__; } break;                      \
                 case 4: { constexpr int L_ = 4; __VA_ARGS__; } break;                      \
                 case 6: { constexpr int L_ = 6; __VA_ARGS__; } break;                      \
-                default: return fail(SINGA_E_LMAX, "so3_skinny: lmax must be 2, 4 or 6");  \
+                default: return fail(SINGA_E_LMAX, SINGA_LMAX_TEXT);                       \
             }                                                                              \
         }                                                                                  \
     } while (0)

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..config import validate_embedding_config
 from ..graph import E_LL, E_LP, E_PL, E_PP, LA, PA
 from .EF_layers import (CoefficientMappingModule, EdgeDegreeEmbedding, GaussianSmearing, ModuleListInfo, SO2_Convolution,
                         SO3_Embedding, SO3_Grid, SO3_Rotation, TransBlockV2, get_normalization_layer, init_edge_rot_mat,
@@ -38,6 +39,7 @@ class EquivariantEmbedding(nn.Module):
         modules only: the radial MLPs, SO3_LinearV2 (projection, feed-forward), the edge-degree embedding, norms and S2
         activations stay f32, and so does every tensor in memory."""
         ops.check_precision(precision)
+        validate_embedding_config(config)
         super().__init__()
         self.device = device
         self.recompute = bool(recompute)
@@ -50,7 +52,6 @@ class EquivariantEmbedding(nn.Module):
         self.lmax_list = [int(i) for i in config.lmax_list]
         self.mmax_list = [int(i) for i in config.mmax_list]
         self.num_resolutions = len(self.lmax_list)
-        assert self.num_resolutions == 1
         self.sphere_channels_all = self.num_resolutions * self.sphere_channels
         self.max_num_elements = config.max_num_elements
         self.num_heads = config.num_heads
@@ -60,8 +61,6 @@ class EquivariantEmbedding(nn.Module):
         self.norm_type = config.norm_type
         self.share_atom_edge_embedding = config.share_atom_edge_embedding
         self.use_atom_edge_embedding = config.use_atom_edge_embedding
-        assert self.share_atom_edge_embedding and self.use_atom_edge_embedding, "shipped config (config/train.yml:44-45)"
-        assert config.alpha_drop == 0.0 and config.proj_drop == 0.0 and config.drop_path_rate == 0.0
         self.block_use_atom_edge_embedding = False
         # when True, hetero layers whose outputs the reference discards only apply their norm_1 side effect (Q4)
         self.skip_dead_hetero_layers = True

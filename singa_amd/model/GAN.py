@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..config import validate_embedding_config
 from ..graph import LA, PA
 from .CProMG import Transformer
 from .Embedding import EquivariantEmbedding
@@ -31,6 +32,7 @@ class SINGA(nn.Module):
         convolutions, and for nothing else in the embedding.  The two switches are independent."""
         ops.check_precision(precision)
         ops.check_precision(embedding_precision)
+        validate_embedding_config(config.embedding)
         super().__init__()
         self.device = device
         self.config = config

@@ -64,7 +64,7 @@ def main():
     ap.add_argument("--host-dataset", action="store_true",
                     help="--data packed: keep the pack on the host (batches gathered on the host and copied per step) - for a "
                          "pack that does not fit on the device")
-    ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 4 or 6)")
+    ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 3, 4 or 6)")
     ap.add_argument("--max-iters", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None, help="graphs per step over all ranks")
     ap.add_argument("--graph", action="store_true",
