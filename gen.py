@@ -6,8 +6,14 @@ temperature / top-k / top-p; singa_amd/model/Sampling.py).  `--mode distinct` sa
 pairwise distinct sequences per pocket (stochastic beam search; `--temperature`, `--grammar` and `--seed` apply, top-k / top-p
 do not), best perturbed score first.
 
-The reference's PDB / docking front end is out of scope, so pockets come from `--data golden` (the three
-example graphs the reference bundles) or `--data synthetic`.  No chemistry toolkit is required: the sequences are written as
+The reference's PDB / docking front end is out of scope, so pockets are graphs that are featurised already:
+`--data golden` (the three example graphs the reference bundles), `--data synthetic`, or `--data packed --dataset DIR`, the
+packed dataset train.py trains on (singa_amd/dataset.py, made by tools/pack_dataset.py).  A pack is run over split by split
+(`--split`, default test; `--first N` pockets of it) in passes of `--pockets-per-pass` pockets, each pass one collate, one
+encoding and one decoder call (singa_amd/generate.py); lines are written pass by pass in split order, named as the pack names
+its graphs; `--prop-from-dataset` prompts every pocket with its own graph's property bits, and `--mode score --molecules
+dataset` scores every graph's own ligand.  A pocket's random numbers are a function of `--seed` and its graph id, not of the
+pass it falls into.  No chemistry toolkit is required: the sequences are written as
 they were decoded, without a validity filter.  `--grammar smiles` (sample, distinct and beam mode) removes the syntactic rejects
 where the token is chosen: every sequence then ends with '$' before `--max-length` and has balanced branches, paired
 ring-closure digits and no dangling bond symbol (include/singa_hip_gen.h states the rule).  Under `--grammar smiles` chemical
@@ -33,6 +39,9 @@ log-likelihood under the model for its pocket is written, in the same four colum
     python gen.py --data golden --mode distinct --num-samples 100 --grammar smiles --prefix "c1ccc("
     python gen.py --data golden --mode score --molecules library.tsv --rows-per-pocket 256
     python gen.py --data golden --mode beam --num-beams 20 --grammar valence
+    python gen.py --ckpt 100.pt --data packed --dataset packs/crossdocked --split test --mode sample --num-samples 100 \\
+                  --grammar smiles --prop-from-dataset --out test_samples.tsv
+    python gen.py --ckpt 100.pt --data packed --dataset packs/crossdocked --mode score --molecules dataset
 
 One line per sequence on stdout (or in `--out`), tab-separated: pocket name, the SMILES string between '&' and '$', the
 number of tokens decoded ('$' included), the summed log-probability of the sequence under the model.  Everything else that
@@ -55,8 +64,16 @@ def parse_args(argv=None):
     ap.add_argument("--config", type=str, default=os.path.join(ROOT, "config", "train.yml"))
     ap.add_argument("--ckpt", type=str, default=None, help="a train.py checkpoint; without it the weights are random")
     ap.add_argument("--device", type=str, default="cuda")
-    ap.add_argument("--data", choices=["golden", "synthetic"], default="golden")
-    ap.add_argument("--pockets", type=int, default=3, help="number of pockets (synthetic data)")
+    ap.add_argument("--data", choices=["golden", "synthetic", "packed"], default="golden")
+    ap.add_argument("--pockets", type=int, default=None, help="number of pockets (synthetic data; default 3)")
+    ap.add_argument("--dataset", type=str, default=None, help="--data packed: directory of a packed dataset (tools/pack_dataset.py)")
+    ap.add_argument("--split", choices=["train", "val", "test"], default=None, help="--data packed: the split to run over (default test)")
+    ap.add_argument("--first", type=int, default=None, metavar="N", help="--data packed: only the first N pockets of the split")
+    ap.add_argument("--pockets-per-pass", type=int, default=None, metavar="P",
+                    help="--data packed: pockets encoded and decoded together; default: the largest P with P x rows per pocket "
+                         "<= 2048 (rows per pocket: --rows-per-pocket, else --num-samples or --num-beams, 1 in score mode)")
+    ap.add_argument("--prop-from-dataset", action="store_true",
+                    help="--data packed: every pocket's property prompt is the one training gives its graph, instead of --prop")
     ap.add_argument("--lmax", type=int, default=None, help="override embedding.lmax_list (2, 3, 4 or 6)")
     ap.add_argument("--mode", choices=["beam", "sample", "score", "distinct"], default="sample")
     ap.add_argument("--num-samples", type=int, default=100, help="sequences per pocket (sample, distinct)")
@@ -78,7 +95,8 @@ def parse_args(argv=None):
     ap.add_argument("--prefix", type=str, default=None,
                     help="sample, distinct, beam (selected on the device): every sequence starts with this SMILES fragment")
     ap.add_argument("--molecules", type=str, default=None,
-                    help="score: a file of lines `pocket name<TAB>SMILES` (further columns are ignored)")
+                    help="score: a file of lines `pocket name<TAB>SMILES` (further columns are ignored); with --data packed the "
+                         "word `dataset`: every graph's own ligand is scored for its pocket")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--prop", type=float, nargs=3, default=[1.0, 1.0, 1.0], metavar=("V", "Q", "S"),
                     help="the property prompt: vina score below -7.5, QED above 0.6, SAS below 4 (1 = wanted)")
@@ -98,6 +116,29 @@ def parse_args(argv=None):
     if args.rows_per_pocket is not None and args.mode not in ("sample", "score"):
         ap.error("--rows-per-pocket is continuous sampling: sample and score mode only")
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
+    if args.data == "packed":
+        if args.dataset is None:
+            ap.error("--data packed reads its pockets from a pack: add --dataset DIR")
+        if args.pockets is not None:
+            ap.error("--pockets counts synthetic pockets; with --data packed use --split and --first")
+        if args.first is not None and args.first < 1:
+            ap.error("--first N: at least 1")
+        if args.pockets_per_pass is not None and args.pockets_per_pass < 1:
+            ap.error("--pockets-per-pass P: at least 1")
+        if args.mode == "score" and args.molecules != "dataset":
+            ap.error("--data packed scores every graph's own ligand: --molecules dataset (a file names the bundled pockets only)")
+        args.split = args.split or "test"
+        if args.pockets_per_pass is None:
+            rows = args.rows_per_pocket or (1 if args.mode == "score" else args.num_beams if args.mode == "beam" else args.num_samples)
+            args.pockets_per_pass = max(1, 2048 // max(1, rows))
+    else:
+        given = [flag for flag, on in (("--dataset", args.dataset is not None), ("--split", args.split is not None),
+                                       ("--first", args.first is not None), ("--pockets-per-pass", args.pockets_per_pass is not None),
+                                       ("--prop-from-dataset", args.prop_from_dataset),
+                                       ("--molecules dataset", args.molecules == "dataset")) if on]
+        if given:
+            ap.error(f"{', '.join(given)}: only with --data packed")
+        args.pockets = 3 if args.pockets is None else args.pockets
     return args
 
 
@@ -108,13 +149,10 @@ def main():
 
     import __graft_entry__
     __graft_entry__.build()
+    from singa_amd import generate as GEN
     from singa_amd import graph as G
-    from singa_amd.config import Config, load_config
-    from singa_amd.model.BeamSearch import beam_search, beam_search_device
-    from singa_amd.model.CProMG import DenseMap, knn_graph
+    from singa_amd.config import load_config
     from singa_amd.model.GAN import SINGA
-    from singa_amd import smiles
-    from singa_amd.model.Sampling import sample, sample_distinct, sample_stream, score
 
     cfg = load_config(args.config, lmax=args.lmax)
     torch.manual_seed(args.seed)
@@ -126,102 +164,77 @@ def main():
         print("# no --ckpt: random initial weights")
     model.eval()
     voc = list(cfg.model.decoder.smiVoc)
-    eos, pad = voc.index("$"), voc.index("^")
     max_length = args.max_length or cfg.model.decoder.tgt_len + 1
+    per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
+    decoder = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, grammar=None if args.grammar == "none" else args.grammar,
+                   prefix=args.prefix, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles, beam_select=args.beam_select)
+    out = Output(args.out)
+
+    if args.data == "packed":
+        from singa_amd.dataset import PackedDataset
+        store = PackedDataset.load(args.dataset).to(dev)
+        print(f"# packed dataset {args.dataset}: {store.G} graphs, split {args.split}")
+        for k, rec in enumerate(GEN.generate_split(model, cfg, voc, store, args.split, args.mode, per, args.pockets_per_pass,
+                                                   first=args.first, prop="dataset" if args.prop_from_dataset else args.prop,
+                                                   molecules=args.molecules, max_length=args.max_length, seed=args.seed, **decoder)):
+            print(f"# pass {k}: {len(rec['names'])} pockets ({rec['names'][0]} .. {rec['names'][-1]}), {args.mode} mode, "
+                  + (f"{rec['steps']} steps" if rec["steps"] is not None else f"{len(rec['molecules'])} molecules scored"))
+            out.write(GEN.format_lines(rec, voc))
+        out.close()
+        return
 
     if args.data == "golden":
         names, graphs = list(G.EXAMPLE_NAMES), [G.example_graph(i) for i in range(len(G.EXAMPLE_NAMES))]
     else:
         names, graphs = [f"synthetic_{i}" for i in range(args.pockets)], [G.synthetic_graph(i) for i in range(args.pockets)]
-    B = len(graphs)
-    batch = G.collate(graphs).to(dev)
-    model.prepare(batch)
-    with torch.no_grad():                                                     # gen.py:157-160: the protein pass alone
-        feat = model.embedding(batch, gen_mode=True)[G.PA].embedding.reshape(batch[G.PA]["x"].shape[0], -1)
-    ex = Config()
-    ids = batch[G.PA]["batch"]
-    ex.protein_element_batch, ex.protein_atom_feature, ex.protein_pos = ids, feat, batch[G.PA]["pos"]
-    ex.protein_atom_laplacian = batch[G.PA]["lap_pe"]
-    knn = knn_graph(batch[G.PA]["pos"], cfg.model.encoder.knn, ids, B, DenseMap(ids, B))
-    ex.protein_knn = knn[:, knn[0] >= 0]
+    ex, B = GEN.pocket_example(model, cfg, G.collate(graphs).to(dev))
+    prop = torch.tensor([args.prop] * B, dtype=torch.float32, device=dev) if cfg.train.num_props else None
 
     if args.mode == "score":
         wanted = [ln.rstrip("\n").split("\t")[:2] for ln in open(args.molecules) if ln.strip() and not ln.startswith("#")]
         assert wanted and all(len(w) == 2 and w[0] in names for w in wanted), \
             f"--molecules: every line is `pocket name<TAB>SMILES`, the pockets are {names}"
         mols = [[smi for name, smi in wanted if name == n] for n in names]
-        grammar = None if args.grammar == "none" else args.grammar
-        res = score(model, voc, mols, B, ex, torch.tensor([args.prop], dtype=torch.float32) if cfg.train.num_props else None,
-                    device=dev, max_length=args.max_length, grammar=grammar, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles)
+        rec = GEN.decode(model, voc, ex, B, "score", 1, prop, args.max_length, device=dev, molecules=mols, **decoder)
         print(f"# scored {len(wanted)} molecules for {B} pockets")
-        seen = {n: 0 for n in names}
+        by_row = GEN.format_lines(rec, voc, names)                            # pocket-major; written in the order of the input
+        first_row, seen = [sum(len(m) for m in mols[:b]) for b in range(B)], {n: 0 for n in names}
         lines = []
-        for name, smi in wanted:
-            b, i = names.index(name), seen[name]
+        for name, _ in wanted:
+            lines.append(by_row[first_row[names.index(name)] + seen[name]])
             seen[name] += 1
-            lines.append(f"{name}\t{smi}\t{res['length'][b][i]}\t{res['sum_logp'][b][i]:.6f}")
-        emit(args, lines)
+        out.write(lines)
+        out.close()
         return
 
-    per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
-    prop = torch.tensor([args.prop] * (B * per), dtype=torch.float32, device=dev) if cfg.train.num_props else None
-    tr = {}
-    forced = None if args.prefix is None else smiles.encode([args.prefix] * B, voc, max_length)
+    rec = GEN.decode(model, voc, ex, B, args.mode, per, prop, max_length, device=dev, seed=args.seed,
+                     generator=torch.Generator(device=dev).manual_seed(args.seed) if args.mode == "sample" else None, **decoder)
     if args.mode == "sample":
-        gen = torch.Generator(device=dev).manual_seed(args.seed)
-        if args.rows_per_pocket is not None:
-            tokens = sample_stream(model, voc, per, B, max_length, ex, None if prop is None else prop[:B], args.rows_per_pocket,
-                                   device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                                   suppress=("&", "^"), generator=gen, trace=tr,
-                                   grammar=None if args.grammar == "none" else args.grammar, forced=forced,
-                                   tiles=args.decoder_tiles).cpu()
-        else:
-            tokens = sample(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k,
-                            top_p=args.top_p, suppress=("&", "^"), generator=gen, trace=tr,
-                            grammar=None if args.grammar == "none" else args.grammar, forced=forced, tiles=args.decoder_tiles).cpu()
-        lengths, logps = tr["lengths"].cpu().tolist(), tr["sum_logp"].cpu().tolist()
-        print(f"# sampled {per} sequences for each of {B} pockets: {tr['steps']} steps on the {tr['path']} path")
+        print(f"# sampled {per} sequences for each of {B} pockets: {rec['steps']} steps on the {rec['path']} path")
     elif args.mode == "distinct":
-        tokens = sample_distinct(model, voc, per, B, max_length, ex, prop, device=dev, temperature=args.temperature,
-                                 suppress=("&", "^"), grammar=None if args.grammar == "none" else args.grammar, seed=args.seed,
-                                 trace=tr, forced=forced, tiles=args.decoder_tiles).cpu()
-        keep = tr["valid"].cpu().bool()                                       # a small tree leaves trailing slots empty
-        print(f"# {int(keep.sum())} distinct sequences for {B} pockets ({per} asked for each): {tr['steps']} steps")
-        rows = [r for r in range(B * per) if keep[r]]
-        tokens, names_of = tokens[keep], [names[r // per] for r in rows]
-        lengths, logps = tr["lengths"].cpu()[keep].tolist(), tr["sum_logp"].cpu()[keep].tolist()
-    else:
-        if args.beam_select == "device" or args.grammar != "none":
-            tokens = beam_search_device(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr,
-                                        grammar=None if args.grammar == "none" else args.grammar, forced=forced,
-                                        tiles=args.decoder_tiles).cpu()
-            print(f"# beam search selected on the device: {tr['steps']} steps")
-        else:
-            tokens = beam_search(model, voc, per, B, max_length, 1, ex, prop, device=dev, trace=tr, tiles=args.decoder_tiles).cpu()
-        best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7
-        lengths, logps = [len(h) for _, h in best], [s * len(h) ** 0.7 for s, h in best]
-        per = 1
-
-    if args.mode != "distinct":
-        names_of = [names[r // per] for r in range(tokens.shape[0])]
-    lines = []
-    for r, row in enumerate(tokens.tolist()):
-        body = []
-        for t in (row[1:1 + lengths[r]] if args.mode != "beam" else row[1:]):     # a sampled row is `lengths[r]` tokens long
-            if t == eos or (t == pad and args.mode == "beam"):
-                break
-            body.append(voc[t])
-        lines.append(f"{names_of[r]}\t{''.join(body)}\t{lengths[r]}\t{logps[r]:.6f}")
-    emit(args, lines)
+        print(f"# {int(rec['valid'].sum())} distinct sequences for {B} pockets ({per} asked for each): {rec['steps']} steps")
+    elif rec["on_device"]:
+        print(f"# beam search selected on the device: {rec['steps']} steps")
+    out.write(GEN.format_lines(rec, voc, names))
+    out.close()
 
 
-def emit(args, lines):
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        print(f"# {len(lines)} sequences written to {args.out}")
-    else:
-        print("\n".join(lines))
+class Output:
+    """The sequence lines: on stdout, or in `path`, opened once and written pass by pass."""
+
+    def __init__(self, path):
+        self.path, self.n = path, 0
+        self.f = open(path, "w") if path else None
+
+    def write(self, lines):
+        self.n += len(lines)
+        if lines:
+            print("\n".join(lines), file=self.f or sys.stdout)
+
+    def close(self):
+        if self.f:
+            self.f.close()
+            print(f"# {self.n} sequences written to {self.path}")
 
 
 if __name__ == "__main__":

@@ -21,6 +21,16 @@ def lap_pe(data, node_type: str):
     return data[node_type]["lap_pe"]
 
 
+def property_prompt(ligand_data, names):
+    """[B, len(names)] f32: the property prompt of each graph of a batch, one column per entry of `names`
+    (`config.train.prop`) - the threshold bits of GAN:38-40 for vina_score / qed / sas, the stored value for any other name.
+    The training forward and `singa_amd.generate.dataset_props` both take it from here."""
+    ld = ligand_data
+    cols = {"vina_score": torch.lt(ld["vina_score"], -7.5), "qed": torch.gt(ld["qed"], 0.6),
+            "sas": torch.lt(ld["sas"], 4.0)}                                                 # GAN:38-40
+    return torch.stack([(cols[p] if p in cols else ld[p]).to(torch.float32) for p in names], 1)
+
+
 class SINGA(nn.Module):
     def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32"):
         """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
@@ -52,12 +62,7 @@ class SINGA(nn.Module):
         them, and the list receives (output, detached twin) pairs: backward() of the loss fills the twins' .grad, and
         torch.autograd.backward(outputs, twin gradients) continues through the embedding."""
         ld = g["ligand_data"]
-        if self.config.train.num_props:
-            cols = {"vina_score": torch.lt(ld["vina_score"], -7.5), "qed": torch.gt(ld["qed"], 0.6),
-                    "sas": torch.lt(ld["sas"], 4.0)}                                         # GAN:38-40
-            prop = torch.stack([(cols[p] if p in cols else ld[p]).to(torch.float32) for p in self.config.train.prop], 1)
-        else:
-            prop = None
+        prop = property_prompt(ld, self.config.train.prop) if self.config.train.num_props else None
         batch, batch_aa = g[PA]["batch"], g[LA]["batch"]
         embed = self.embedding(g)
         xa, xl = embed[PA].embedding, embed[LA].embedding
