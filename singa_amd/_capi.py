@@ -236,6 +236,14 @@ _DEC_TILES_SIGS = {
 }
 DEC_TILES_EXPORTS = tuple(_DEC_TILES_SIGS)
 
+# include/singa_hip_lap_large.h: n2 for graphs of up to 2,048 atoms (`ops.lap_pe_large`, the per-graph routing of
+# graph.laplacian_pe_batched); a table of its own
+_LAP_LARGE_SIGS = {
+    "singa_lap_pe_large_work": ([I32, I32], I32),
+    "singa_lap_pe_large": ([P] * 8 + [I32, I32, I32, P], I32),
+}
+LAP_LARGE_EXPORTS = tuple(_LAP_LARGE_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -243,7 +251,8 @@ def bind(path):
     for name, (args, res) in list(_SIGS.items()) + list(_LAB_SIGS.items()) + list(_GEN_SIGS.items()) + \
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
-            list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()):
+            list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
+            list(_LAP_LARGE_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -33,6 +33,7 @@
 #include "../../include/singa_hip_data.h"
 #include "../../include/singa_hip_bf16.h"
 #include "../../include/singa_hip_dec_tiles.h"
+#include "../../include/singa_hip_lap_large.h"
 #include "so3_index.h"
 
 namespace {
@@ -6747,6 +6748,538 @@ __global__ void __launch_bounds__(1024) lap_pe_kernel(double* __restrict__ Aall,
         __syncthreads();
     }
 }
+
+// ---- n2 for graphs of up to 2,048 atoms (singa_lap_pe_large): the same encoding with NO per-atom state in LDS.  One workgroup of
+// 1024 threads (16 wavefronts) per graph; everything of size O(n) lives in the graph's slice of `work` (L2 resident: 3 blocks of
+// 16 vectors = 768 KB at 2,048 atoms, ELL rows 768 KB), LDS holds the bounded pieces only (16 x 16 / 32 x 32 matrices, reduction
+// rows: 17 KB whatever n is).  Everything is indexed by ATOM: the Laplacian is block diagonal over the connected components in
+// any ordering, so no positions are needed.
+//   0. ELL rows (<= 32 off-diagonal neighbours, sorted by atom, + the diagonal) straight from the edge list: every edge drops a
+//      tagged entry into both end points' raw rows (<= 64 each, one atomic counter per atom), then one thread per atom merges its
+//      raw row (repeats count once, direction bits OR-ed), counts its in-degree, and the values follow from the two degrees.
+//   1. component labels by minimum-label propagation with pointer jumping, as in lap_pe_kernel, in global memory.
+//   2. graphs of <= 32 atoms: the dense 32 x 32 Laplacian in LDS, cyclic Jacobi (16 disjoint rotations per step), done.
+//   3. the zero eigenvalue is WRITTEN, not solved for: a component with an edge (or a self loop) carries the null vector
+//      sqrt(d_i) / sqrt(sum d) on its atoms - checked against the component's own rows (|L z| <= 1e-12; it fails only for edge lists
+//      that are not symmetric, which give up).  An atom without any edge is an eigenvector of eigenvalue 1.  With c such
+//      components and m = min(n, kout + 1) wanted pairs: c >= m -> the answer is m of the null vectors and nothing is solved.
+//   4. otherwise (c <= 8) the m - c lowest NON-zero pairs of the whole graph come from the Chebyshev-filtered subspace iteration of
+//      lap_fsi (block of 16, degree 24, CholQR2, residual 2e-10, <= 40 outer iterations) with its three blocks in global memory
+//      and the block kept orthogonal to the c null vectors (one [8][16] projection before each Cholesky pass: supports are
+//      disjoint, so the null vectors are orthonormal as they stand).  Rayleigh-Ritz over the whole block-diagonal operator IS the
+//      merge of the components' spectra by eigenvalue; the zeros sort first.
+// A graph that does not go by the book sets status[g] and writes NOTHING to `out` (every write of `out` is behind the last
+// check): 1 a row with more than 32 neighbours (or more than 64 raw entries), 2 a vanishing Cholesky pivot, 3 no convergence,
+// 4 a component whose null vector fails its check, 5 an edge index outside the graph, 6 more atoms than ld / 2,048.
+constexpr int LAPL_MAXN = 2048, LAPL_W = 32, LAPL_RAW = 64, LAPL_PB = 16;
+constexpr int LAPL_PER_LD = 3 * LAPL_PB + LAPL_W + 4 + (LAPL_W + 8) / 2;      // doubles of `work` per atom of ld (ints count half)
+__global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restrict__ esrc, const int* __restrict__ edst,
+                                                            const int* __restrict__ eptr, const int* __restrict__ nnodes,
+                                                            const int* __restrict__ first, double* work, float* out, int* status,
+                                                            int ld, int kout) {
+    constexpr int PB = LAPL_PB, W = LAPL_W, RAW = LAPL_RAW, NW = 16;
+    __shared__ double Hs[1024];            // Jacobi: H [32][32]; subspace iteration: H [16][16] | Q [16][16] | Q sorted | coef [8][16]
+    __shared__ double Vs[1024];            // Jacobi: V [32][32]; subspace iteration: reduction scratch
+    __shared__ double theta[16], resn[16], redd[NW];
+    __shared__ int redi[NW], ordv[32], fl[4];
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = nnodes[g];
+    if (n <= 0 || n > ld || n > LAPL_MAXN) {
+        if (tid == 0) status[g] = n <= 0 ? 0 : 6;
+        return;
+    }
+    double* base = work + (long long)g * LAPL_PER_LD * ld;
+    double* Xc = base;                                   // [n][PB] current block
+    double* Yp = base + (long long)PB * ld;              // [n][PB] previous block of the recurrence
+    double* Nx = base + (long long)2 * PB * ld;          // [n][PB] next block / L X
+    double* ell_v = base + (long long)3 * PB * ld;       // [n][W] off-diagonal values
+    double* diag = ell_v + (long long)W * ld;            // [n]
+    double* dinv = diag + ld;                            // [n] 1 / sqrt(clipped in-degree)
+    double* zn = dinv + ld;                              // [n] the atom's entry of its component's null vector (0: none)
+    int* ell_i = reinterpret_cast<int*>(zn + 2 * (long long)ld);     // [n][W] neighbour atoms, ascending
+    int* ell_n = ell_i + (long long)W * ld;              // [n]
+    int* cnt = ell_n + ld;                               // [n] raw entries
+    int* label = cnt + ld;                               // [n] component = its smallest atom
+    int* zr = label + ld;                                // [n] rank of the atom's component among the null-carrying ones (-1: none)
+    int* degsum = zr + ld;                               // [root] sum of the clipped in-degrees of the component
+    int* dclip = degsum + ld;                            // [n]
+    int* selfl = dclip + ld;                             // [n] self loop
+    int* raw = reinterpret_cast<int*>(Yp);               // [n][RAW] atom | direction << 12 (dead before the blocks are used)
+    const int e0 = eptr[g], e1 = eptr[g + 1];
+    const int m = n < kout + 1 ? n : kout + 1;           // pairs wanted: the smallest + up to kout more
+    float* o = out + (long long)first[g] * kout;
+
+    // what atomics wrote (counters, labels, degree sums) is read back at device scope, past the vector cache
+    auto aload = [](const int* p) -> int { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto block_sum = [&](double x) -> double {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+        __syncthreads();
+        if (lane == 0) redd[wave] = x;
+        __syncthreads();
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += redd[w];
+        return s;
+    };
+    // column `col` of the result from x(atom): entry of largest magnitude (lowest atom on ties) made positive
+    auto emit = [&](int col, auto x) {
+        double best = -1.0;
+        int bi = 1 << 30;
+        for (int i = tid; i < n; i += 1024) {
+            const double v = fabs(x(i));
+            if (v > best) best = v, bi = i;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ob = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (ob > best || (ob == best && oi < bi)) best = ob, bi = oi;
+        }
+        __syncthreads();
+        if (lane == 0) redd[wave] = best, redi[wave] = bi;
+        __syncthreads();
+        best = redd[0], bi = redi[0];
+        for (int w = 1; w < NW; ++w)
+            if (redd[w] > best || (redd[w] == best && redi[w] < bi)) best = redd[w], bi = redi[w];
+        const double sg = x(bi) < 0.0 ? -1.0 : 1.0;
+        for (int i = tid; i < n; i += 1024) o[(long long)i * kout + col] = (float)(sg * x(i));
+        __syncthreads();
+    };
+    auto zero_cols = [&](int from) {                     // columns the graph is too small for
+        for (int i = tid; i < n; i += 1024)
+            for (int k = from; k < kout; ++k) o[(long long)i * kout + k] = 0.f;
+    };
+
+    // ---- 0. ELL rows
+    if (tid < 4) fl[tid] = 0;
+    for (int i = tid; i < n; i += 1024) cnt[i] = 0, label[i] = i, degsum[i] = 0;
+    __syncthreads();
+    for (int e = e0 + tid; e < e1; e += 1024) {
+        const int a = esrc[e], b = edst[e];
+        if ((unsigned)a >= (unsigned)n || (unsigned)b >= (unsigned)n) { fl[1] = 5; continue; }
+        const int sa = atomicAdd(&cnt[a], 1);
+        if (sa < RAW) raw[(long long)a * RAW + sa] = b | (1 << 12);          // a -> b seen from a
+        const int sb = atomicAdd(&cnt[b], 1);
+        if (sb < RAW) raw[(long long)b * RAW + sb] = a | (2 << 12);          // a -> b seen from b: counts into b's in-degree
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) {
+        int* row = ell_i + (long long)i * W;
+        const int c = aload(&cnt[i]);
+        int nn = 0, self = 0, over = c > RAW;
+        for (int s = 0; s < c && s < RAW; ++s) {
+            const int ent = raw[(long long)i * RAW + s], j = ent & 0xFFF, f = ent >> 12;
+            if (j == i) { self |= f; continue; }
+            int p = 0;
+            while (p < nn && (row[p] & 0xFFF) < j) ++p;
+            if (p < nn && (row[p] & 0xFFF) == j) row[p] |= f << 12;
+            else if (nn < W) {
+                for (int q = nn; q > p; --q) row[q] = row[q - 1];
+                row[p] = ent;
+                ++nn;
+            } else over = 1;
+        }
+        int indeg = (self >> 1) & 1;
+        for (int p = 0; p < nn; ++p) indeg += (row[p] >> 13) & 1;
+        const int d = indeg < 1 ? 1 : indeg;
+        ell_n[i] = nn, selfl[i] = self != 0, dclip[i] = d;
+        dinv[i] = 1.0 / sqrt((double)d);
+        if (over) fl[1] = 1;
+    }
+    __syncthreads();
+    if (fl[1]) {
+        if (tid == 0) status[g] = fl[1];
+        return;
+    }
+    for (int i = tid; i < n; i += 1024) {
+        int* row = ell_i + (long long)i * W;
+        const double di = dinv[i];
+        const int nn = ell_n[i];
+        for (int p = 0; p < nn; ++p) {
+            const int ent = row[p], j = ent & 0xFFF;
+            ell_v[(long long)i * W + p] = -0.5 * di * dinv[j] * (double)(((ent >> 12) & 1) + ((ent >> 13) & 1));
+            row[p] = j;
+        }
+        diag[i] = 1.0 - (selfl[i] ? di * di : 0.0);
+    }
+    // ---- 1. connected components
+    for (int round = 0; round < n + 2; ++round) {
+        __syncthreads();
+        if (tid == 0) fl[0] = 0;
+        __syncthreads();
+        for (int e = e0 + tid; e < e1; e += 1024) {
+            const int a = esrc[e], b = edst[e];
+            const int la = aload(&label[a]), lb = aload(&label[b]);
+            if (la < lb) { atomicMin(&label[b], la); fl[0] = 1; }
+            else if (lb < la) { atomicMin(&label[a], lb); fl[0] = 1; }
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 1024) {            // pointer jumping: labels are atoms
+            int l = aload(&label[i]);
+            const int l0 = l;
+            for (int h = 0; h < 4; ++h) {
+                const int l2 = aload(&label[l]);
+                if (l2 >= l) break;
+                l = l2;
+            }
+            if (l < l0) { atomicMin(&label[i], l); fl[0] = 1; }
+        }
+        __syncthreads();
+        if (!fl[0]) break;
+    }
+    __syncthreads();
+
+    // ---- 2. small graphs: dense Jacobi in LDS
+    if (n <= 32) {
+        {
+            const int i = tid >> 5, j = tid & 31;
+            Hs[tid] = i != j ? 0.0 : i < n ? diag[i] : 4.0 + i;      // padding: decoupled, above every real eigenvalue (<= 2)
+            Vs[tid] = i == j ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        if (tid < n)
+            for (int p = 0; p < ell_n[tid]; ++p) Hs[tid * 32 + ell_i[(long long)tid * W + p]] = ell_v[(long long)tid * W + p];
+        __syncthreads();
+        bool conv = false;
+        for (int sweep = 0; sweep < 30 && !conv; ++sweep) {
+            const double h = Hs[tid];
+            const bool dg = (tid >> 5) == (tid & 31);
+            const double off2 = block_sum(dg ? 0.0 : h * h), dg2 = block_sum(dg && (tid >> 5) < n ? h * h : 0.0);
+            if (off2 <= 1e-30 * (dg2 + 1e-300)) { conv = true; break; }
+            for (int st = 0; st < 31; ++st) {            // round robin: 16 disjoint pairs, 32 lanes per pair
+                const int pr = tid >> 5, i = tid & 31;
+                const int p = pr == 0 ? 31 : (st + pr) % 31, q = pr == 0 ? st : (st + 31 - pr) % 31;
+                double c = 1.0, sn = 0.0;
+                if (tid < 512) {
+                    const double hpp = Hs[p * 32 + p], hqq = Hs[q * 32 + q], hpq = Hs[p * 32 + q];
+                    if (fabs(hpq) > 1e-300) {
+                        const double tau = (hqq - hpp) / (2.0 * hpq);
+                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                        c = 1.0 / sqrt(1.0 + t * t);
+                        sn = t * c;
+                    }
+                }
+                __syncthreads();
+                if (tid < 512) {
+                    const double aip = Hs[i * 32 + p], aiq = Hs[i * 32 + q];
+                    Hs[i * 32 + p] = c * aip - sn * aiq;
+                    Hs[i * 32 + q] = sn * aip + c * aiq;
+                    const double vip = Vs[i * 32 + p], viq = Vs[i * 32 + q];
+                    Vs[i * 32 + p] = c * vip - sn * viq;
+                    Vs[i * 32 + q] = sn * vip + c * viq;
+                }
+                __syncthreads();
+                if (tid < 512) {
+                    const double api = Hs[p * 32 + i], aqi = Hs[q * 32 + i];
+                    Hs[p * 32 + i] = c * api - sn * aqi;
+                    Hs[q * 32 + i] = sn * api + c * aqi;
+                }
+                __syncthreads();
+            }
+        }
+        if (!conv) {
+            if (tid == 0) status[g] = 3;
+            return;
+        }
+        if (tid == 0) {                                  // ascending eigenvalues, stable
+            for (int a = 0; a < 32; ++a) {
+                int b = a;
+                while (b > 0 && Hs[ordv[b - 1] * 33] > Hs[a * 33]) { ordv[b] = ordv[b - 1]; --b; }
+                ordv[b] = a;
+            }
+        }
+        __syncthreads();
+        for (int k = 1; k < m; ++k) {
+            const int col = ordv[k];
+            emit(k - 1, [&](int i) { return Vs[i * 32 + col]; });
+        }
+        zero_cols(m - 1);
+        if (tid == 0) status[g] = 0;
+        return;
+    }
+
+    // ---- 3. the null vectors
+    for (int i = tid; i < n; i += 1024) {
+        const int nn = ell_n[i];
+        double r = diag[i] * sqrt((double)dclip[i]);
+        for (int p = 0; p < nn; ++p) r += ell_v[(long long)i * W + p] * sqrt((double)dclip[ell_i[(long long)i * W + p]]);
+        const bool lone = nn == 0 && !selfl[i];          // an atom without any edge: eigenvalue 1, no null vector
+        if (!lone) {
+            if (!(fabs(r) <= 1e-12)) fl[1] = 4;
+            atomicAdd(&degsum[aload(&label[i])], dclip[i]);
+        }
+    }
+    __syncthreads();
+    if (fl[1]) {
+        if (tid == 0) status[g] = fl[1];
+        return;
+    }
+    if (wave == 0) {                                     // rank of every null-carrying component, in order of its smallest atom
+        int seen = 0;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool root = i < n && aload(&label[i]) == i && aload(&degsum[i]) > 0;
+            const unsigned long long mask = __ballot(root);
+            if (i < n) zr[i] = root ? seen + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+            seen += __popcll(mask);
+        }
+        if (lane == 0) fl[2] = seen;
+    }
+    __syncthreads();
+    const int c = fl[2];
+    for (int i = tid; i < n; i += 1024) {
+        const int l = aload(&label[i]), s = aload(&degsum[l]);
+        zn[i] = s > 0 ? sqrt((double)dclip[i] / (double)s) : 0.0;
+        if (l != i) zr[i] = zr[l];                       // (roots hold their own rank: no atom reads a slot another one writes)
+    }
+    __syncthreads();
+    if (c >= m) {                                        // zero is (at least) m-fold: null vectors 1 .. m - 1, nothing to solve
+        for (int k = 1; k < m; ++k) emit(k - 1, [&](int i) { return zr[i] == k ? zn[i] : 0.0; });
+        zero_cols(m - 1);
+        if (tid == 0) status[g] = 0;
+        return;
+    }
+
+    // ---- 4. the m - c lowest non-zero pairs: filtered subspace iteration, blocks in global memory
+    double* H = Hs;                                      // [16][16] projected / Gram matrix
+    double* Q = Hs + 256;                                // [16][16] rotations / Cholesky factor
+    double* Qs = Hs + 512;                               // [16][16] rotations, columns by ascending Ritz value
+    double* coef = Hs + 768;                             // [8][16] null vectors . block
+    double* part = Vs;
+    const int total = n * PB, want = m - c;
+    auto lx = [&](const double* X, int idx) -> double {  // (L X)[r][j]
+        const int r = idx >> 4, j = idx & 15;
+        const int nn = ell_n[r];
+        const double* ev = ell_v + (long long)r * W;
+        const int* ei = ell_i + (long long)r * W;
+        double acc = diag[r] * X[idx];
+        for (int p = 0; p < nn; ++p) acc += ev[p] * X[ei[p] * PB + j];
+        return acc;
+    };
+    auto gram = [&](const double* A, const double* B) {  // H = sym(A^T B): 4 row chunks x 256 entries
+        {
+            const int p = tid & 255, ch = tid >> 8, a = p >> 4, b = p & 15;
+            double acc = 0.0;
+            for (int r = ch; r < n; r += 4) acc += A[r * PB + a] * B[r * PB + b];
+            part[tid] = acc;
+        }
+        __syncthreads();
+        if (tid < 256) Q[tid] = (part[tid] + part[256 + tid]) + (part[512 + tid] + part[768 + tid]);
+        __syncthreads();
+        if (tid < 256) H[tid] = 0.5 * (Q[tid] + Q[(tid & 15) * 16 + (tid >> 4)]);
+        __syncthreads();
+    };
+    auto project = [&]() {                               // X <- X - Z (Z^T X) over the c null vectors
+        if (c == 0) return;
+        {
+            const int j = tid & 15, a = (tid >> 4) & 7, ch = tid >> 7;
+            double acc = 0.0;
+            for (int r = ch; r < n; r += 8)
+                if (zr[r] == a) acc += zn[r] * Xc[r * PB + j];
+            part[tid] = acc;
+        }
+        __syncthreads();
+        if (tid < 128) {
+            double s = 0.0;
+            for (int ch = 0; ch < 8; ++ch) s += part[ch * 128 + tid];
+            coef[tid] = s;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < total; idx += 1024) {
+            const int r = idx >> 4, a = zr[r];
+            if (a >= 0) Xc[idx] -= zn[r] * coef[a * 16 + (idx & 15)];
+        }
+        __syncthreads();
+    };
+    auto orthonormalise = [&]() -> bool {                // X <- X R^-1, X^T X = R^T R, twice (CholQR2)
+        for (int pass = 0; pass < 2; ++pass) {
+            project();
+            gram(Xc, Xc);
+            if (tid == 0) {
+                fl[3] = 0;
+                double tr = 0.0;
+                for (int j = 0; j < PB; ++j) tr += H[j * 16 + j];
+                for (int j = 0; j < PB; ++j) {
+                    double d = H[j * 16 + j];
+                    for (int k = 0; k < j; ++k) d -= Q[k * 16 + j] * Q[k * 16 + j];
+                    if (!(d > 1e-26 * tr)) { fl[3] = 1; d = 1.0; }
+                    const double rj = sqrt(d);
+                    Q[j * 16 + j] = rj;
+                    for (int i = j + 1; i < PB; ++i) {
+                        double v = H[j * 16 + i];
+                        for (int k = 0; k < j; ++k) v -= Q[k * 16 + j] * Q[k * 16 + i];
+                        Q[j * 16 + i] = v / rj;
+                    }
+                }
+            }
+            __syncthreads();
+            if (fl[3]) return false;
+            for (int r = tid; r < n; r += 1024) {        // the thread's own rows, solved in place (y R = x): no register arrays
+                double* xr = Xc + r * PB;
+#pragma unroll 1
+                for (int j = 0; j < PB; ++j) {
+                    double v = xr[j];
+#pragma unroll 1
+                    for (int i = 0; i < j; ++i) v -= xr[i] * Q[i * 16 + j];
+                    xr[j] = v / Q[j * 16 + j];
+                }
+            }
+            __syncthreads();
+        }
+        return true;
+    };
+    auto ritz = [&]() {                                  // Nx = L X, Jacobi on X^T L X, X <- X Q, Nx <- Nx Q, residual norms
+        double* Wg = Nx;
+        for (int idx = tid; idx < total; idx += 1024) Wg[idx] = lx(Xc, idx);
+        __syncthreads();
+        gram(Xc, Wg);
+        if (tid < 256) Q[tid] = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;
+        __syncthreads();
+        for (int sweep = 0; sweep < 10; ++sweep) {
+            const double h = tid < 256 ? H[tid] : 0.0;
+            const bool dg = tid < 256 && (tid >> 4) == (tid & 15);
+            const double off2 = block_sum(dg ? 0.0 : h * h), dg2 = block_sum(dg ? h * h : 0.0);
+            if (off2 <= 1e-30 * (dg2 + 1e-300)) break;
+            for (int st = 0; st < 15; ++st) {
+                const int pr = tid >> 3, sub = tid & 7;
+                const int p = pr == 0 ? 15 : (st + pr) % 15, q = pr == 0 ? st : (st + 15 - pr) % 15;
+                double cs = 1.0, sn = 0.0;
+                if (tid < 64) {
+                    const double hpp = H[p * 16 + p], hqq = H[q * 16 + q], hpq = H[p * 16 + q];
+                    if (fabs(hpq) > 1e-300) {
+                        const double tau = (hqq - hpp) / (2.0 * hpq);
+                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                        cs = 1.0 / sqrt(1.0 + t * t);
+                        sn = t * cs;
+                    }
+                }
+                __syncthreads();
+                if (tid < 64) {
+#pragma unroll
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const int i = sub + 8 * h2;
+                        const double aip = H[i * 16 + p], aiq = H[i * 16 + q];
+                        H[i * 16 + p] = cs * aip - sn * aiq;
+                        H[i * 16 + q] = sn * aip + cs * aiq;
+                        const double qip = Q[i * 16 + p], qiq = Q[i * 16 + q];
+                        Q[i * 16 + p] = cs * qip - sn * qiq;
+                        Q[i * 16 + q] = sn * qip + cs * qiq;
+                    }
+                }
+                __syncthreads();
+                if (tid < 64) {
+#pragma unroll
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const int i = sub + 8 * h2;
+                        const double api = H[p * 16 + i], aqi = H[q * 16 + i];
+                        H[p * 16 + i] = cs * api - sn * aqi;
+                        H[q * 16 + i] = sn * api + cs * aqi;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (tid == 0) {                                  // ascending Ritz values
+            for (int a = 0; a < PB; ++a) {
+                int b = a;
+                while (b > 0 && H[ordv[b - 1] * 17] > H[a * 17]) { ordv[b] = ordv[b - 1]; --b; }
+                ordv[b] = a;
+            }
+            for (int j = 0; j < PB; ++j) {
+                theta[j] = H[ordv[j] * 17];
+                for (int i = 0; i < PB; ++i) Qs[i * 16 + j] = Q[i * 16 + ordv[j]];
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < n; r += 1024) {
+            for (int which = 0; which < 2; ++which) {
+                double* rowp = (which == 0 ? Xc : Wg) + r * PB;
+                double x[PB];
+#pragma unroll
+                for (int i = 0; i < PB; ++i) x[i] = rowp[i];
+#pragma unroll 1
+                for (int j = 0; j < PB; ++j) {
+                    double xs = 0.0;
+#pragma unroll
+                    for (int i = 0; i < PB; ++i) xs += x[i] * Qs[i * 16 + j];
+                    rowp[j] = xs;
+                }
+            }
+        }
+        __syncthreads();
+        {   // residual norms |L x_j - theta_j x_j|: 64 row chunks x 16 columns
+            const int j = tid & 15, ch = tid >> 4;
+            const double th = theta[j];
+            double acc = 0.0;
+            for (int r = ch; r < n; r += 64) {
+                const double d = Wg[r * PB + j] - th * Xc[r * PB + j];
+                acc += d * d;
+            }
+            acc += __shfl_xor(acc, 16, 64);
+            acc += __shfl_xor(acc, 32, 64);
+            if (lane < 16) part[wave * 16 + lane] = acc;
+            __syncthreads();
+            if (tid < PB) {
+                double t = 0.0;
+                for (int w2 = 0; w2 < NW; ++w2) t += part[w2 * 16 + tid];
+                resn[tid] = sqrt(t);
+            }
+            __syncthreads();
+        }
+    };
+    // start block: deterministic pseudo-random entries tied to the atom
+    for (int idx = tid; idx < total; idx += 1024) {
+        const int r = idx >> 4, j = idx & 15;
+        unsigned h = (unsigned)(r * 2654435761u) ^ (unsigned)((j + 11) * 40503u * 2246822519u);
+        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+        Xc[idx] = (double)(h & 0xFFFFFF) / 8388608.0 - 1.0;
+    }
+    __syncthreads();
+    int code = 3;
+    double prev = 0.0;
+    if (!orthonormalise()) code = 2;
+    for (int it = 0; it < LAP_FSI_MAXIT && code == 3; ++it) {
+        ritz();
+        double worst = 0.0;
+        for (int j = 0; j < want; ++j) worst = fmax(worst, resn[j]);
+        if (worst <= 2e-10) { code = 0; break; }
+        // a residual that falls too slowly to get there in the iterations left (a long chain: eigenvalues 1e-5 apart) gives up
+        // now, not after the 40th filter: the caller's dense route answers such a graph either way
+        if (it >= 3 && (worst >= prev || log(2e-10 / worst) / log(worst / prev) > (double)(LAP_FSI_MAXIT - 1 - it))) break;
+        prev = worst;
+        // Chebyshev filter of degree LAP_FSI_DEG: damp [a, 2], scaled at a0 (Zhou & Saad's recurrence); the three blocks rotate
+        const double a0 = theta[0], b = 2.0 + 1e-9;
+        const double a = fmax(theta[PB - 1], a0 + 1e-4);
+        if (!(a < b - 1e-3)) break;
+        const double e = 0.5 * (b - a), cc = 0.5 * (b + a);
+        double sigma = e / (a0 - cc);
+        const double sigma1 = sigma;
+        for (int idx = tid; idx < total; idx += 1024) Nx[idx] = (lx(Xc, idx) - cc * Xc[idx]) * (sigma1 / e);
+        __syncthreads();
+        { double* t = Yp; Yp = Xc; Xc = Nx; Nx = t; }
+        for (int i = 2; i <= LAP_FSI_DEG; ++i) {
+            const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
+            const double f1 = 2.0 * sigma2 / e, f2 = sigma * sigma2;
+            for (int idx = tid; idx < total; idx += 1024) Nx[idx] = (lx(Xc, idx) - cc * Xc[idx]) * f1 - f2 * Yp[idx];
+            __syncthreads();
+            { double* t = Yp; Yp = Xc; Xc = Nx; Nx = t; }
+            sigma = sigma2;
+        }
+        if (!orthonormalise()) code = 2;
+    }
+    if (code) {
+        if (tid == 0) status[g] = code;
+        return;
+    }
+    // merged by eigenvalue: the c zeros, then the Ritz values in ascending order
+    for (int k = 1; k < m; ++k) {
+        if (k < c) emit(k - 1, [&](int i) { return zr[i] == k ? zn[i] : 0.0; });
+        else emit(k - 1, [&](int i) { return Xc[i * PB + k - c]; });
+    }
+    zero_cols(m - 1);
+    if (tid == 0) status[g] = 0;
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------ host helpers
@@ -8128,6 +8661,31 @@ int singa_lap_pe(double* A, const int32_t* esrc, const int32_t* edst, const int3
         hipLaunchKernelGGL(lap_pe_kernel<16>, dim3(B), dim3(1024), lds, st, A, esrc, edst, eptr, nnodes, first, work, out, ld, kout, g_lap_fsi_min);
     }
     return check_launch("lap_pe");
+#endif
+}
+
+int singa_lap_pe_large_work(int B, int ld) {
+#ifdef SINGA_EMUL
+    return 0;
+#else
+    const long long w = (long long)B * LAPL_PER_LD * ld;
+    return (B < 0 || ld < 0 || w > 0x7fffffffLL) ? 0 : (int)w;
+#endif
+}
+
+int singa_lap_pe_large(const int32_t* esrc, const int32_t* edst, const int32_t* eptr, const int32_t* nnodes, const int32_t* first,
+                       double* work, float* out, int32_t* status, int B, int ld, int kout, void* stream) {
+    if (!esrc || !edst || !eptr || !nnodes || !first || !work || !out || !status) return fail(SINGA_E_NULL, "lap_pe_large: null pointer");
+    if (kout < 1 || kout > 8) return fail(SINGA_E_SHAPE, "lap_pe_large: 1..8 eigenvectors");
+    if (ld < 1 || ld > 2048) return fail(SINGA_E_SHAPE, "lap_pe_large: graphs of up to 2,048 atoms");
+    if (B <= 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail(SINGA_E_SHAPE, "lap_pe_large: not part of the emulation build");
+#else
+    if (singa_lap_pe_large_work(B, ld) <= 0) return fail(SINGA_E_SHAPE, "lap_pe_large: B * ld beyond the work array's int32 size");
+    hipLaunchKernelGGL(lap_pe_large_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, esrc, edst, eptr, nnodes, first, work, out, status,
+                       ld, kout);
+    return check_launch("lap_pe_large");
 #endif
 }
 

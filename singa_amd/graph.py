@@ -446,23 +446,65 @@ def laplacian_pe_batched(edge_index, batch, num_graphs, k=8):
     diagonalises it per connected component - Householder tridiagonalisation + Sturm multi-section + inverse iteration,
     fp64), same sign convention as `laplacian_pe`.  Eigenvectors of a repeated eigenvalue (a bonded pocket graph has dozens
     of connected components, i.e. a many-fold zero eigenvalue) are ANY orthonormal basis of that invariant subspace, as in
-    the reference (dgl adds random signs on top).  CPU tensors / graphs of more than 896 atoms: dense Laplacians and one
-    batched torch.linalg.eigh (padding rows get a unit diagonal above every real eigenvalue (<= 2), so they sort last)."""
+    the reference (dgl adds random signs on top).
+
+    The route is chosen PER GRAPH (k <= 8 on the GPU): graphs of up to 896 atoms go to ops.lap_pe - a batch of such graphs
+    alone is one launch, as ever, and a small graph's rows do not depend on what else the batch holds; graphs of 897 .. 2,048
+    atoms go to ops.lap_pe_large in one launch over just those graphs (no dense matrix: sparse rows, the zero eigenvalue's
+    vectors written per connected component, filtered subspace iteration for the rest); only a graph that kernel gives up on
+    (its status entry: an atom with more than 32 neighbours, no convergence, ...) or one above 2,048 atoms takes the dense
+    route below, in a sub-batch of its own.  A batch with a large graph costs two read-backs more than one without: the
+    sizes of the two launches, and "did any graph give up".  CPU tensors / k > 8: dense Laplacians and one batched
+    torch.linalg.eigh (padding rows get a unit diagonal above every real eigenvalue (<= 2), so they sort last)."""
     dev = edge_index.device
     n = batch.numel()
     num = torch.zeros(num_graphs, dtype=torch.long, device=dev).index_add_(0, batch, torch.ones_like(batch))
     mx = int(num.max())
     start = num.cumsum(0) - num
     gb = batch[edge_index[0]]
-    if edge_index.is_cuda and mx <= 896 and k <= 8:
-        from . import ops
-        # edges grouped by graph (a collated batch already has them so; the stable sort makes no assumption)
-        order = torch.argsort(gb, stable=True)
-        gs = gb[order]
-        src = (edge_index[0][order] - start[gs]).to(torch.int32)
-        dst = (edge_index[1][order] - start[gs]).to(torch.int32)
-        eptr = torch.searchsorted(gs, torch.arange(num_graphs + 1, device=dev)).to(torch.int32)
+    if not (edge_index.is_cuda and k <= 8):
+        return _laplacian_pe_dense(edge_index, batch, num, mx, start, gb, k)
+    from . import ops
+    # edges grouped by graph (a collated batch already has them so; the stable sort makes no assumption)
+    order = torch.argsort(gb, stable=True)
+    gs = gb[order]
+    src = (edge_index[0][order] - start[gs]).to(torch.int32)
+    dst = (edge_index[1][order] - start[gs]).to(torch.int32)
+    eptr = torch.searchsorted(gs, torch.arange(num_graphs + 1, device=dev)).to(torch.int32)
+    if mx <= 896:
         return ops.lap_pe(src, dst, eptr, num, start, n, mx, k)
+    small = num <= 896
+    large = ~small & (num <= 2048)
+    mx_s, mx_l, n_l, e_l = torch.stack([(num * small).max(), (num * large).max(), large.sum(), large[gs].sum()]).tolist()
+    # the small graphs: the same launch with the other graphs' sizes set to 0 (a workgroup without atoms returns at once)
+    out = ops.lap_pe(src, dst, eptr, num * small, start, n, mx_s, k) if mx_s else torch.empty(n, k, device=dev, dtype=torch.float32)
+    bad = num > 2048
+    if n_l:
+        sel = torch.argsort(~large, stable=True)[:n_l]                             # the large graphs, in batch order
+        esel = torch.argsort(~large[gs], stable=True)[:e_l]                        # their edges, still grouped by graph
+        ecount = (eptr[1:] - eptr[:-1])[sel]
+        eptr_l = torch.cat([ecount.new_zeros(1), ecount.cumsum(0)]).to(torch.int32)
+        _, status = ops.lap_pe_large(src[esel], dst[esel], eptr_l, num[sel], start[sel], n, mx_l, k, out=out)
+        bad[sel] = status != 0
+    if bool(bad.any()):
+        # the graphs left over, as a batch of their own through the dense route
+        rows = torch.nonzero(bad[batch]).squeeze(1)
+        new_row = torch.zeros(n, dtype=torch.long, device=dev)
+        new_row[rows] = torch.arange(rows.numel(), device=dev)
+        new_graph = bad.long().cumsum(0) - 1
+        sub_batch = new_graph[batch[rows]]
+        sub_num = num[bad]
+        sub_ei = new_row[edge_index[:, bad[gb]]]
+        out[rows] = _laplacian_pe_dense(sub_ei, sub_batch, sub_num, int(sub_num.max()), sub_num.cumsum(0) - sub_num,
+                                        sub_batch[sub_ei[0]], k)
+    return out
+
+
+def _laplacian_pe_dense(edge_index, batch, num, mx, start, gb, k):
+    """laplacian_pe_batched's dense route: [B, mx, mx] fp64 Laplacians, one batched torch.linalg.eigh."""
+    dev = edge_index.device
+    n = batch.numel()
+    num_graphs = num.numel()
     local = torch.arange(n, device=dev) - start[batch]
     a = torch.zeros(num_graphs, mx, mx, dtype=torch.float64, device=dev)
     a[gb, local[edge_index[0]], local[edge_index[1]]] = 1.0
