@@ -25,7 +25,9 @@ reference does, unless `--beam-select device` or a `--grammar` is given: then th
 the two select the same hypotheses up to the order of exactly tied candidates.  `--prefix TEXT` starts every sequence with
 that fragment - a scaffold to continue - in sample mode (with or without `--rows-per-pocket`), in distinct mode and in beam
 mode with the selection on the device (include/singa_hip_prefix.h states the rule; host-selected beam search refuses it); under
-a `--grammar` a fragment the rule refuses is an error before anything runs.
+a `--grammar` a fragment the rule refuses is an error before anything runs.  `--kv-cache ancestry` (distinct mode, beam mode
+selected on the device) leaves the key / value caches where they were written and re-ranks a table of slots instead
+(include/singa_hip_ancestry.h states the rule): the same sequences, one cache buffer instead of two.
 `--mode score --molecules FILE` draws nothing: FILE holds lines of `pocket name<TAB>SMILES`, and every molecule's
 log-likelihood under the model for its pocket is written, in the same four columns and in the order of the input;
 `--rows-per-pocket R` scores them on R rows per pocket (same numbers, the caches of R rows whatever the length of FILE).
@@ -92,6 +94,9 @@ def parse_args(argv=None):
     ap.add_argument("--decoder-tiles", action="store_true",
                     help="every mode: the row-tiled decoder step kernels (16 rows per workgroup, weights read once per tile, a "
                          "pocket of any size) instead of the one-row-per-workgroup ones")
+    ap.add_argument("--kv-cache", choices=["copy", "ancestry"], default=None,
+                    help="distinct, beam selected on the device: how the key / value caches follow the re-ranked rows - copied "
+                         "between two buffers (the default), or one buffer read through an ancestry table (same sequences)")
     ap.add_argument("--prefix", type=str, default=None,
                     help="sample, distinct, beam (selected on the device): every sequence starts with this SMILES fragment")
     ap.add_argument("--molecules", type=str, default=None,
@@ -113,6 +118,11 @@ def parse_args(argv=None):
     if args.prefix is not None and args.mode == "beam" and args.beam_select == "host" and args.grammar == "none":
         ap.error("--prefix in beam mode needs the selection on the device: add --beam-select device (or a --grammar); the "
                  "host-selected beam search takes no forced tokens")
+    if args.kv_cache is not None and not (args.mode == "distinct" or (
+            args.mode == "beam" and (args.beam_select == "device" or args.grammar != "none"))):
+        ap.error("--kv-cache is about the rows re-ranked on the device: --mode distinct, or --mode beam with --beam-select device "
+                 "(or a --grammar)")
+    args.kv_cache = args.kv_cache or "copy"
     if args.rows_per_pocket is not None and args.mode not in ("sample", "score"):
         ap.error("--rows-per-pocket is continuous sampling: sample and score mode only")
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
@@ -167,7 +177,8 @@ def main():
     max_length = args.max_length or cfg.model.decoder.tgt_len + 1
     per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
     decoder = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, grammar=None if args.grammar == "none" else args.grammar,
-                   prefix=args.prefix, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles, beam_select=args.beam_select)
+                   prefix=args.prefix, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles, beam_select=args.beam_select,
+                   kv_cache=args.kv_cache)
     out = Output(args.out)
 
     if args.data == "packed":

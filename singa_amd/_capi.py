@@ -244,6 +244,15 @@ _LAP_LARGE_SIGS = {
 }
 LAP_LARGE_EXPORTS = tuple(_LAP_LARGE_SIGS)
 
+# include/singa_hip_ancestry.h: self-attention through an ancestry table instead of moved caches (`ops.dec_layer_step(..., anc=...)`,
+# `ops.anc_follow`, `KVDecoder(..., ancestry=True)`); a table of its own
+_ANCESTRY_SIGS = {
+    "singa_dec_self_attn_anc": ([P] * 10 + [I32, I32, P, F32, P, P], I32),
+    "singa_dec_tile_self_attn_anc": ([P] * 10 + [I32, I32, I32, I32, P, F32, P, P], I32),
+    "singa_anc_follow": ([P, P, P, I32, I32, I32, P], I32),
+}
+ANCESTRY_EXPORTS = tuple(_ANCESTRY_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -252,7 +261,7 @@ def bind(path):
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
-            list(_LAP_LARGE_SIGS.items()):
+            list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

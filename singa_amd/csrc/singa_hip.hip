@@ -34,6 +34,7 @@
 #include "../../include/singa_hip_bf16.h"
 #include "../../include/singa_hip_dec_tiles.h"
 #include "../../include/singa_hip_lap_large.h"
+#include "../../include/singa_hip_ancestry.h"
 #include "so3_index.h"
 
 namespace {
@@ -1374,18 +1375,34 @@ __device__ __forceinline__ float sum4(const float* partial, int N, int c) {
 // each head (wavefront h of the first four) over positions 0..pos, output projection + residual + LayerNorm.
 // ROWS (singa_dec_self_attn_rows, include/singa_hip_stream.h): one position per row instead of one for all; append, mask and
 // context sum depend on nothing but the row's own pos.  A row whose position lies outside the cache is left alone.
-template <bool ROWS>
+// ANC (singa_dec_self_attn_anc, include/singa_hip_ancestry.h): the cached position tt < pos is read from slot anc[tt][r] instead of
+// r.  The row's table column is staged in LDS ahead of the first barrier (1 KB, clamped to the R rows): in the score loop a lane
+// picks the slot of its own position - its key stays one run of 128 bytes -, in the value loop all 64 lanes of a head read one
+// word (an LDS broadcast) and the value row stays one run of 256 bytes.  Nothing else differs from the plain instantiation.
+// (`anc` is the last argument, so that the plain instantiations keep their argument layout and instruction streams.)
+template <bool ROWS, bool ANC = false>
 __global__ void __launch_bounds__(1024) dec_self_attn_kernel(const float* __restrict__ x, const float* __restrict__ wqkv_t,
                                                              const float* __restrict__ bqkv, const float* __restrict__ wo_t,
                                                              const float* __restrict__ bo, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ kc,
                                                              float* __restrict__ vc, const long long* __restrict__ pos_ptr, int P,
-                                                             float* __restrict__ y, float eps) {
+                                                             float* __restrict__ y, float eps,
+                                                             const int32_t* __restrict__ anc = nullptr) {
     __shared__ float xs[256], qkv[512], ps[4][256], ctx[256], partial[4 * 512], red[4];
+    __shared__ int slot[ANC ? 256 : 1];
     const int r = blockIdx.x, t = threadIdx.x, c = t & 255, part = t >> 8, h = c >> 6, lane = c & 63;
     const int pos = (int)pos_ptr[ROWS ? r : 0];
     if constexpr (ROWS) {
         if (pos < 0 || pos >= P) return;                               // (uniform over the workgroup)
+    }
+    if constexpr (ANC) {
+        if (pos < 0 || pos >= P) return;                               // (the table has P rows; uniform over the workgroup)
+        const int R = (int)gridDim.x;
+        if (t < 256) {
+            int s = t < pos ? anc[(long long)t * R + r] : r;
+            s = s < 0 ? 0 : (s >= R ? R - 1 : s);
+            slot[t] = s;
+        }
     }
     if (t < 256) xs[t] = x[(long long)r * 256 + t];
     __syncthreads();
@@ -1408,6 +1425,9 @@ __global__ void __launch_bounds__(1024) dec_self_attn_kernel(const float* __rest
             float sv = -INFINITY;
             if (tt <= pos) {
                 const float* kr = tt == pos ? qkv + 128 + h * 32 : krow + (long long)tt * 32;
+                if constexpr (ANC) {
+                    if (tt < pos) kr = kc + (((long long)slot[tt] * 4 + h) * P + tt) * 32;
+                }
                 float acc = 0.f;
 #pragma unroll
                 for (int d = 0; d < 32; ++d) acc = fmaf(q[d], kr[d], acc);
@@ -1432,7 +1452,10 @@ __global__ void __launch_bounds__(1024) dec_self_attn_kernel(const float* __rest
         const float* vrow = vc + ((long long)r * 4 + h) * P * 64;
         float a = part == 0 ? ps[h][pos] * qkv[256 + c] : 0.f;
 #pragma unroll 4
-        for (int tt = part; tt < pos; tt += 4) a = fmaf(ps[h][tt], vrow[(long long)tt * 64 + lane], a);
+        for (int tt = part; tt < pos; tt += 4) {
+            if constexpr (ANC) a = fmaf(ps[h][tt], vc[(((long long)slot[tt] * 4 + h) * P + tt) * 64 + lane], a);
+            else a = fmaf(ps[h][tt], vrow[(long long)tt * 64 + lane], a);
+        }
         partial[part * 256 + c] = a;
     }
     __syncthreads();
@@ -2434,6 +2457,33 @@ __global__ void __launch_bounds__(256) swor_follow_kernel(const float* __restric
     for (int e = threadIdx.x; e < heads * vq; e += 256) {
         const int h = e / vq, o = e - h * vq;
         vd[h * vh + o] = vs[h * vh + o];
+    }
+}
+
+// singa_anc_follow (include/singa_hip_ancestry.h states the rule): workgroup (pocket, position).  The launch stands behind the
+// step's increment of the position: t = *pos - 1 is the position just appended.  In place - the pocket's k entries of the position
+// rest in LDS while the gathered column is written over them; a position's entries are touched by this workgroup alone.
+constexpr int ANC_MAX_K = 2048;
+
+__global__ void __launch_bounds__(256) anc_follow_kernel(int32_t* __restrict__ anc, const long long* __restrict__ src,
+                                                         const long long* __restrict__ pos, int rows, int k, int P) {
+    __shared__ int32_t col[ANC_MAX_K];
+    const long long t = *pos - 1, base = (long long)blockIdx.x * k;
+    const int p = blockIdx.y;
+    if (t < 0 || t >= P || p > t) return;                              // workgroup-uniform
+    int32_t* a = anc + (long long)p * rows + base;
+    if (p == t) {
+        for (int j = threadIdx.x; j < k; j += 256) {
+            const long long s = src[base + j] - base;
+            if (s >= 0 && s < k) a[j] = (int32_t)(base + s);
+        }
+        return;
+    }
+    for (int j = threadIdx.x; j < k; j += 256) col[j] = a[j];
+    __syncthreads();
+    for (int j = threadIdx.x; j < k; j += 256) {
+        const long long s = src[base + j] - base;
+        if (s >= 0 && s < k) a[j] = col[s];
     }
 }
 #endif
@@ -7627,15 +7677,22 @@ __device__ __forceinline__ void dt_ln_store(const floatx4 (&acc)[VW], int n0, co
 // self-attention sub-block.  512 threads: q | k | v = 8 wavefronts x 64 columns; attention per row, wavefront w rows 2 w and
 // 2 w + 1 over their own caches, masked as dec_self_attn_kernel masks them (the new position's key and value from LDS); the
 // context takes the place of the row's new value in LDS and is the A operand of the output projection.
+// ANC (singa_dec_tile_self_attn_anc, include/singa_hip_ancestry.h): cached position tt of a row is read from slot anc[tt][row],
+// clamped to the row's pocket.  A lane fetches the table entries of its own four positions (lane + 64 m) into registers next to
+// the score loop - the 16 rows of a tile share the table's cache lines - and its key stays one run of 128 bytes; for the value
+// loop the chunk's 64 slots go through LDS with the chunk's probabilities (256 bytes per wavefront), so that the lanes of a group
+// read the slot of position j as they read its probability, and a value row stays one run of 256 bytes per head.
+template <bool ANC>
 __global__ void __launch_bounds__(512) dec_tile_self_attn_kernel(const float* __restrict__ x, const float* __restrict__ wqkv_t,
                                                                  const float* __restrict__ bqkv, const float* __restrict__ wo_t,
                                                                  const float* __restrict__ bo, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float* __restrict__ kc,
                                                                  float* __restrict__ vc, const long long* __restrict__ pos_ptr,
                                                                  int per_row, int beams, int tiles, int P, float* __restrict__ y,
-                                                                 float eps) {
+                                                                 float eps, const int32_t* __restrict__ anc, int R) {
     __shared__ float xs[DT_ROWS * DT_LD], qkv[DT_ROWS * DT_QLD], ps[8][256];
     __shared__ int spos[DT_ROWS];
+    __shared__ int sslot[ANC ? 8 : 1][64];                             // [wavefront]: one chunk of 64 positions' slots
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i = lane & 15, g = lane >> 4;
     const int b = blockIdx.x / tiles, j0 = (blockIdx.x % tiles) * DT_ROWS;
     const long long row0 = (long long)b * beams + j0;
@@ -7680,12 +7737,23 @@ __global__ void __launch_bounds__(512) dec_tile_self_attn_kernel(const float* __
         const float* krow = kc + (row0 + row) * 4 * P * 32;
         const float* vrow = vc + (row0 + row) * 4 * P * 64 + 4 * i;
         float sc[4][4];                                                // [head][m]: position lane + 64 m
+        int sl[ANC ? 4 : 1];                                           // ANC: the slot that holds position lane + 64 m
+        if constexpr (ANC) {
+            const int lo = b * beams, hi = lo + beams - 1;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int tt = lane + 64 * m;
+                int s = tt < pos ? anc[(long long)tt * R + row0 + row] : lo;
+                sl[m] = s < lo ? lo : (s > hi ? hi : s);
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int tt = lane + 64 * m;
 #pragma unroll
             for (int h = 0; h < 4; ++h) sc[h][m] = -INFINITY;
             if (tt < pos) {
+                if constexpr (ANC) krow = kc + (long long)sl[m] * 4 * P * 32;
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     const float4* kr = reinterpret_cast<const float4*>(krow + ((long long)h * P + tt) * 32);
@@ -7739,9 +7807,11 @@ __global__ void __launch_bounds__(512) dec_tile_self_attn_kernel(const float* __
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int h = 0; h < 4; ++h) pw[h * 64 + lane] = sc[h][m];
+                if constexpr (ANC) sslot[wave][lane] = sl[m];
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll 2
-                for (int j = g; j < cnt; j += 4)
+                for (int j = g; j < cnt; j += 4) {
+                    if constexpr (ANC) vrow = vc + (long long)sslot[wave][j] * 4 * P * 64 + 4 * i;
 #pragma unroll
                     for (int h = 0; h < 4; ++h) {
                         const float4 v = *reinterpret_cast<const float4*>(vrow + ((long long)h * P + 64 * m + j) * 64);
@@ -7749,6 +7819,7 @@ __global__ void __launch_bounds__(512) dec_tile_self_attn_kernel(const float* __
                         ca[h].x = fmaf(p, v.x, ca[h].x), ca[h].y = fmaf(p, v.y, ca[h].y);
                         ca[h].z = fmaf(p, v.z, ca[h].z), ca[h].w = fmaf(p, v.w, ca[h].w);
                     }
+                }
             }
         }
 #pragma unroll
@@ -9045,9 +9116,60 @@ int singa_dec_tile_self_attn(const float* x, const float* wqkv_t, const float* b
     return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn", "not part of the emulation build");
 #else
     const int tiles = (beams + DT_ROWS - 1) / DT_ROWS;
-    hipLaunchKernelGGL(dec_tile_self_attn_kernel, dim3((unsigned)(R / beams * tiles)), dim3(512), 0, (hipStream_t)stream, x, wqkv_t,
-                       bqkv, wo_t, bo, gamma, beta, k_cache, v_cache, pos, per_row ? 1 : 0, beams, tiles, P, y, eps);
+    hipLaunchKernelGGL(dec_tile_self_attn_kernel<false>, dim3((unsigned)(R / beams * tiles)), dim3(512), 0, (hipStream_t)stream, x,
+                       wqkv_t, bqkv, wo_t, bo, gamma, beta, k_cache, v_cache, pos, per_row ? 1 : 0, beams, tiles, P, y, eps, nullptr, R);
     return check_launch("dec_tile_self_attn");
+#endif
+}
+
+// include/singa_hip_ancestry.h: the two self-attention step kernels reading cached positions through the ancestry table, and the
+// table's update
+int singa_dec_self_attn_anc(const float* x, const float* wqkv_t, const float* bqkv, const float* wo_t, const float* bo,
+                            const float* gamma, const float* beta, float* k_cache, float* v_cache, const long long* pos, int R,
+                            int P, float* y, float eps, const int32_t* anc, void* stream) {
+    if (!x || !wqkv_t || !bqkv || !wo_t || !bo || !gamma || !beta || !k_cache || !v_cache || !pos || !y || !anc)
+        return fail_at(SINGA_E_NULL, "dec_self_attn_anc", "null pointer");
+    if (P <= 0 || P > 256) return fail_at(SINGA_E_SHAPE, "dec_self_attn_anc", "built for at most 256 cached positions");
+    if (R <= 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "dec_self_attn_anc", "not part of the emulation build");
+#else
+    hipLaunchKernelGGL((dec_self_attn_kernel<false, true>), dim3(R), dim3(1024), 0, (hipStream_t)stream, x, wqkv_t, bqkv, wo_t, bo,
+                       gamma, beta, k_cache, v_cache, pos, P, y, eps, anc);
+    return check_launch("dec_self_attn_anc");
+#endif
+}
+
+int singa_dec_tile_self_attn_anc(const float* x, const float* wqkv_t, const float* bqkv, const float* wo_t, const float* bo,
+                                 const float* gamma, const float* beta, float* k_cache, float* v_cache, const long long* pos,
+                                 int per_row, int R, int beams, int P, float* y, float eps, const int32_t* anc, void* stream) {
+    if (!x || !wqkv_t || !bqkv || !wo_t || !bo || !gamma || !beta || !k_cache || !v_cache || !pos || !y || !anc)
+        return fail_at(SINGA_E_NULL, "dec_tile_self_attn_anc", "null pointer");
+    if (P <= 0 || P > 256) return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn_anc", "built for at most 256 cached positions");
+    if (R < 0 || beams <= 0 || R % beams) return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn_anc", "rows must be proteins x beams");
+    if (per_row) return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn_anc", "one position for all rows only (per_row = 0)");
+    if (R == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "dec_tile_self_attn_anc", "not part of the emulation build");
+#else
+    const int tiles = (beams + DT_ROWS - 1) / DT_ROWS;
+    hipLaunchKernelGGL(dec_tile_self_attn_kernel<true>, dim3((unsigned)(R / beams * tiles)), dim3(512), 0, (hipStream_t)stream, x,
+                       wqkv_t, bqkv, wo_t, bo, gamma, beta, k_cache, v_cache, pos, 0, beams, tiles, P, y, eps, anc, R);
+    return check_launch("dec_tile_self_attn_anc");
+#endif
+}
+
+int singa_anc_follow(int32_t* anc, const long long* src, const long long* pos, int rows, int k, int P, void* stream) {
+    if (!anc || !src || !pos) return fail_at(SINGA_E_NULL, "anc_follow", "null pointer");
+    if (P <= 0 || P > 256) return fail_at(SINGA_E_SHAPE, "anc_follow", "built for at most 256 cached positions");
+    if (k <= 0 || k > 2048 || rows < 0 || rows % k) return fail_at(SINGA_E_SHAPE, "anc_follow", "rows = pockets x k, 1 <= k <= 2048");
+    if (rows == 0) return SINGA_OK;
+#ifdef SINGA_EMUL
+    return fail_at(SINGA_E_SHAPE, "anc_follow", "not part of the emulation build");
+#else
+    hipLaunchKernelGGL(anc_follow_kernel, dim3((unsigned)(rows / k), (unsigned)P), dim3(256), 0, (hipStream_t)stream, anc, src, pos,
+                       rows, k, P);
+    return check_launch("anc_follow");
 #endif
 }
 

@@ -115,14 +115,15 @@ def pocket_uniforms(seed, graph_ids, per, max_length, device):
 # ---------------------------------------------------------------------------------------------------- one decoder call
 def decode(model, voc, example, B, mode, per, prop, max_length, *, device, temperature=1.0, top_k=0, top_p=1.0, grammar=None,
            prefix=None, rows_per_pocket=None, tiles=False, beam_select="host", seed=0, generator=None, uniforms=None, streams=None,
-           molecules=None):
+           molecules=None, kv_cache="copy"):
     """One decoder call for the `B` pockets of `example`, as gen.py makes it, and its result as a record of host tensors.
 
     mode "sample": `sample`, or `sample_stream` with `rows_per_pocket`; `per` molecules per pocket from `uniforms`, else
     `generator`.  "distinct": `sample_distinct` with `seed` and `streams`.  "beam": `beam_search`, or `beam_search_device` with
     beam_select="device" or under a `grammar`; `per` beams, the best hypothesis of each pocket.  "score": `score` of
     `molecules[b]`, the strings of pocket b.  `prop`: [B, num_props], one prompt per pocket, or None.  `prefix`: a SMILES
-    fragment every sequence starts with.  `max_length` may be None in score mode only (the longest molecule + 2).
+    fragment every sequence starts with.  `kv_cache`: "copy" or "ancestry", the `cache` of `sample_distinct` and
+    `beam_search_device`; ValueError with "ancestry" where no rows are re-ranked on the device.  `max_length` may be None in score mode only (the longest molecule + 2).
 
     The record: `mode`, `per` (rows per pocket: 1 in beam mode, the longest list in score mode), `pocket_of` (the pocket of every
     row), `tokens` int64 [rows, L], `lengths`, `sum_logp`, `steps`, `path` where the call reports one, `valid` (uint8, distinct
@@ -134,6 +135,9 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
     if mode not in MODES:
         raise ValueError(f"decode: mode is one of {MODES} (got {mode!r})")
     dev, tr = device, {}
+    if kv_cache != "copy" and not (mode == "distinct" or (mode == "beam" and (beam_select == "device" or grammar is not None))):
+        raise ValueError(f"decode: kv_cache={kv_cache!r} is about the rows re-ranked on the device: distinct mode, or beam mode "
+                         "selected on the device")
     if mode == "score":
         res = score(model, voc, molecules, B, example, prop, device=dev, max_length=max_length, grammar=grammar,
                     rows_per_pocket=rows_per_pocket, tiles=tiles)
@@ -159,14 +163,15 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
         rec.update(tokens=tokens.cpu(), lengths=tr["lengths"].cpu(), sum_logp=tr["sum_logp"].cpu(), steps=tr["steps"], path=tr["path"])
     elif mode == "distinct":
         tokens = sample_distinct(model, voc, per, B, max_length, example, rows_prop, device=dev, temperature=temperature,
-                                 suppress=("&", "^"), grammar=grammar, seed=seed, streams=streams, trace=tr, forced=forced, tiles=tiles)
+                                 suppress=("&", "^"), grammar=grammar, seed=seed, streams=streams, trace=tr, forced=forced, tiles=tiles,
+                                 cache=kv_cache)
         rec.update(tokens=tokens.cpu(), lengths=tr["lengths"].cpu(), sum_logp=tr["sum_logp"].cpu(), valid=tr["valid"].cpu(),
                    steps=tr["steps"])
     else:
         on_device = beam_select == "device" or grammar is not None
         if on_device:
             tokens = beam_search_device(model, voc, per, B, max_length, 1, example, rows_prop, device=dev, trace=tr, grammar=grammar,
-                                        forced=forced, tiles=tiles)
+                                        forced=forced, tiles=tiles, cache=kv_cache)
         else:
             tokens = beam_search(model, voc, per, B, max_length, 1, example, rows_prop, device=dev, trace=tr, tiles=tiles)
         best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7

@@ -75,11 +75,14 @@ class KVDecoder:
     graph, captured once per search and replayed per token."""
 
     def __init__(self, decoder, projection, enc_outputs, enc_pad_mask, beams, max_positions, vocab_size, fused=True,
-                 search_buffers=True, tiles=False):
+                 search_buffers=True, tiles=False, ancestry=False):
         """search_buffers=False leaves out the beam step's own input / output buffers (`step_in`, `step_out`, `logp`): the
         sampling loop (model/Sampling.py) only uses `token_input` / `prop_input` / `advance`.  `tiles=True`: the fused step is the
         row-tiled one (include/singa_hip_dec_tiles.h), which has no limit on the pocket's size; ValueError, before any launch,
-        with `fused=False` or a decoder the step kernels are not built for."""
+        with `fused=False` or a decoder the step kernels are not built for.  `ancestry=True` (include/singa_hip_ancestry.h): the
+        decoder owns an ancestry table `anc` [max_positions, rows] int32 - the identity after `reset` -, `advance` hands it to every
+        layer's self-attention, and `follow_ancestry(src)` re-ranks the rows by updating the table: the caches are never moved
+        and no second cache buffer is needed.  The fused step only (ValueError otherwise), one position for all rows."""
         self.dec, self.proj, self.beams, self.V = decoder, projection, beams, vocab_size
         a0, f0 = decoder.layers[0].dec_self_attn, decoder.layers[0].pos_ffn
         # the step kernels are built for the shipped decoder geometry; anything else takes the library path
@@ -90,6 +93,9 @@ class KVDecoder:
             raise ValueError("KVDecoder: tiles=True is a form of the fused step: fused=True, the shipped decoder geometry and at most "
                              "256 positions")
         self.fused = bool(fused and geometry and (self.tiles or enc_outputs.shape[1] <= 1024))
+        if ancestry and not self.fused:
+            raise ValueError("KVDecoder: ancestry=True is a form of the fused step: fused=True, the shipped decoder geometry, at most "
+                             "256 positions and, without tiles=True, at most 1024 encoder positions")
         B, S, _ = enc_outputs.shape
         a0 = decoder.layers[0].dec_self_attn
         self.heads = a0.num_heads
@@ -125,6 +131,9 @@ class KVDecoder:
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)            # next position to be written
         self.slots = torch.arange(max_positions, device=dev)
         self.replay = None                                                 # the captured step's replay, once `capture` has run
+        self.anc = None
+        if ancestry:
+            self.anc = torch.arange(self.R, dtype=torch.int32, device=dev).repeat(max_positions, 1)
         if not search_buffers:
             return
         # the step's inputs (scores, tokens, source rows - one row each, as doubles: exact for fp32 and for indices) and
@@ -135,6 +144,13 @@ class KVDecoder:
 
     def reset(self):
         self.pos.zero_()
+        if self.anc is not None:
+            self.anc.copy_(torch.arange(self.R, dtype=torch.int32, device=self.dev))
+
+    def follow_ancestry(self, src_rows):
+        """Row r continues the prefix that row src_rows[r] (int64 [rows], within r's pocket) held: the ancestry table is updated in
+        place (`ops.anc_follow`), behind the `advance` whose position the parents wrote.  `ancestry=True` only."""
+        ops.anc_follow(self.anc, src_rows, self.pos, self.beams)
 
     def follow(self, src_rows):
         """Row r continues the prefix that row src_rows[r] held (BS:134-136)."""
@@ -157,6 +173,8 @@ class KVDecoder:
         two pairs of buffers).  `row_pos` [rows] int64: row r is at position row_pos[r] instead, and nothing is advanced - the
         positions are the caller's to move (`Sampling.sample_stream`; the k17 step kernels only)."""
         k, v = self.k if k is None else k, self.v if v is None else v
+        if row_pos is not None and self.anc is not None:
+            raise ValueError("KVDecoder.advance: ancestry=True goes with one position for all rows, not with row_pos")
         if row_pos is not None:
             if not self.fused:
                 raise ValueError("KVDecoder.advance: one position per row needs the k17 step kernels (fused)")
@@ -169,7 +187,7 @@ class KVDecoder:
             # encoder-decoder attention, feed-forward - instead of ~33 library / elementwise launches on 20-row operands
             for l in range(len(self.dec.layers)):
                 x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], self.pos, self.cross_k[l],
-                                       self.cross_v[l], self.pad_u8, self.beams, tiles=self.tiles)
+                                       self.cross_v[l], self.pad_u8, self.beams, tiles=self.tiles, anc=self.anc)
             self.pos += 1
             return x
         R, B, H = self.R, self.B, self.heads
@@ -369,7 +387,7 @@ BEAM_MAX_K = 1024       # slots per pocket singa_beam_select is built for
 
 @torch.no_grad()
 def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", grammar=None,
-                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None, tiles=False):
+                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None, tiles=False, cache="copy"):
     """`beam_search` with the selection on the device (include/singa_hip_beam.h states the rule: `_select` and `BeamHypotheses`
     as kernels, ties ranked by slot, then token), which can therefore be constrained: `grammar` None, "smiles" or "valence"
     and `suppress` as in `Sampling.sample`.  Under a grammar every stored hypothesis is a string the rule accepts, ended by its
@@ -395,9 +413,16 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
     '$' included where the search ended the string, and the tokens without '$'), `steps` and `valid` (uint8 per returned row: 0
     where the pocket stored fewer than `topk` hypotheses - such rows are all '^').  ValueError before any launch unless
     1 <= topk <= num_beams <= 1024, for what `smiles.check_arguments` refuses, for a decoder geometry, length or pocket size
-    the k17 kernels are not built for, and for caches (two buffers) that do not fit the free memory."""
+    the k17 kernels are not built for, and for caches (two buffers) that do not fit the free memory.
+
+    `cache`: "copy" (the default) or "ancestry", as in `Sampling.sample_distinct`: with "ancestry" the caches are one buffer that
+    is never moved, the self-attention kernels read a row's past through a table (include/singa_hip_ancestry.h) that
+    `ops.anc_follow` updates, and the step is captured once.  Same result, bit for bit.  Anything else is a ValueError."""
     from . import Sampling as S
     from .. import smiles
+    if cache not in ("copy", "ancestry"):
+        raise ValueError(f"beam_search_device: cache is 'copy' or 'ancestry', got {cache!r}")
+    ancestry = cache == "ancestry"
     if not 1 <= topk <= num_beams <= BEAM_MAX_K:
         raise ValueError(f"beam_search_device: 1 <= topk <= num_beams <= {BEAM_MAX_K} (got topk {topk}, num_beams {num_beams})")
     dev, tf, voc, (sos, eos, pad), rows, num, positions, free, cls, allowed = S._prologue(
@@ -410,8 +435,10 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
         raise ValueError("beam_search_device: the k17 step kernels are the only path: the shipped decoder geometry, at most 256 "
                          "positions, 1024 pocket atoms and 1024 tokens")
     need = 2 * S.cache_bytes(tf.decoder, rows, positions) + rows * V * 4 + 3 * rows * T * 8
+    if ancestry:                                         # one buffer and the table
+        need -= S.cache_bytes(tf.decoder, rows, positions) - 4 * rows * positions
     if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
-        raise ValueError(f"beam_search_device: the two key / value cache buffers of {rows} rows x {positions} positions and the "
+        raise ValueError(f"beam_search_device: the {'' if ancestry else 'two '}key / value cache buffers of {rows} rows x {positions} positions and the "
                          f"candidates take {need} bytes, {free} bytes are free on {dev}: use fewer beams or pockets per call")
 
     if forced is not None:
@@ -419,8 +446,8 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
-                   tiles=tiles)
-    bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
+                   tiles=tiles, ancestry=ancestry)
+    bufs = ((kv.k, kv.v), (kv.k, kv.v) if ancestry else (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     state = {"score": new(rows, torch.float32), "length": new(rows, torch.int32), "tokens": new((rows, T), torch.int64),
              "next": new(rows, torch.int64), "src": new(rows, torch.int64), "cand": new((rows, V), torch.float32),
@@ -457,13 +484,17 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
         out = kv.advance(kv.token_input(state["next"]), ck, cv)
         ops.beam_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, allowed, cls, cap, forced=forced)
         ops.beam_select(kv.pos, num + 1, state, k, work, len_pow, eos, pad, cls, cap)
-        ops.swor_follow(ck, cv, ok, ov, state["src"], state["score"], never, kv.pos)
+        if ancestry:
+            kv.follow_ancestry(state["src"])
+        else:
+            ops.swor_follow(ck, cv, ok, ov, state["src"], state["score"], never, kv.pos)
 
     def prime():
         start()
         kv.pos += num
 
-    replays = [lambda: step(0), lambda: step(1)]                       # the step on each pair of cache buffers, taken in turn
+    # the step on each pair of cache buffers, taken in turn; with the ancestry table there is one buffer and one step
+    replays = [lambda: step(0)] if ancestry else [lambda: step(0), lambda: step(1)]
     if graph:
         replays = capture_steps(prime, replays, 1)
     start()

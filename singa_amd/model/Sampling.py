@@ -476,7 +476,7 @@ SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
 
 @torch.no_grad()
 def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
-                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None, tiles=False):
+                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None, tiles=False, cache="copy"):
     """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
     replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` ("smiles", as in `sample`;
     "valence" is a ValueError here), by
@@ -507,7 +507,16 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     length or pocket size the k17 kernels are not built for, and caches (two buffers) that do not fit the free memory.
 
     `tiles=True`: the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17; the limit on the pocket's atoms does
-    not apply to them, and `trace` also receives `path`: "tiles"."""
+    not apply to them, and `trace` also receives `path`: "tiles".
+
+    `cache`: how the key / value caches follow the re-ranked rows.  "copy" (the default): two cache buffers, the surviving
+    prefixes move from one to the other after every token (`ops.swor_follow`), the step is captured once per direction.
+    "ancestry" (include/singa_hip_ancestry.h): one buffer that is never moved, a table [positions, rows] int32 names the slot that
+    holds each position of a row's prefix, the self-attention kernels gather through it and `ops.anc_follow` updates it - 4 bytes
+    per row and position instead of about 9 KB; one captured step.  Same result, bit for bit.  Anything else is a ValueError."""
+    if cache not in ("copy", "ancestry"):
+        raise ValueError(f"sample_distinct: cache is 'copy' or 'ancestry', got {cache!r}")
+    ancestry = cache == "ancestry"
     if grammar == "valence":
         raise ValueError("sample_distinct: grammar='valence' is unsupported (the selection gathers one state word per row); use "
                          "grammar='smiles' here, or `sample` / `sample_stream` for the valence rule")
@@ -530,8 +539,10 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     if streams.shape != (batch_size,) or (streams < 0).any() or (streams >= 2 ** 32).any():
         raise ValueError(f"sample_distinct: streams holds one 32-bit integer per pocket, got shape {streams.shape}")
     need = 2 * cache_bytes(tf.decoder, rows, positions) + 3 * rows * V * 4 + 2 * rows * max_length * 12
+    if ancestry:                                         # one buffer and the table
+        need -= cache_bytes(tf.decoder, rows, positions) - 4 * rows * positions
     if need + (64 << 10) * rows > free:                  # + the step's activations, as in `sample`
-        raise ValueError(f"sample_distinct: the two key / value cache buffers of {rows} rows x {positions} positions and the "
+        raise ValueError(f"sample_distinct: the {'' if ancestry else 'two '}key / value cache buffers of {rows} rows x {positions} positions and the "
                          f"candidates take {need} bytes, {free} bytes are free on {dev}: draw fewer samples per call")
     streams = torch.as_tensor(streams.astype(np.uint32).view(np.int32)).to(dev)
     if forced is not None:
@@ -539,8 +550,8 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
-                   tiles=tiles)
-    bufs = ((kv.k, kv.v), (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
+                   tiles=tiles, ancestry=ancestry)
+    bufs = ((kv.k, kv.v), (kv.k, kv.v) if ancestry else (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     f32 = dict(dtype=torch.float32, device=dev)
     state = {"gumbel": torch.empty(rows, **f32), "prop_logp": torch.empty(rows, **f32), "sum_logp": torch.empty(rows, **f32),
              "hash": torch.empty(rows, dtype=torch.int64, device=dev), "finished": torch.empty(rows, dtype=torch.uint8, device=dev),
@@ -574,13 +585,17 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         ops.swor_expand(tf.projection(out).contiguous(), kv.pos, num + 1, state, k, streams, float(temperature), int(seed), pad,
                         allowed, cls, forced=forced)
         ops.swor_select(kv.pos, num + 1, state, k, work, eos, pad, cls)
-        ops.swor_follow(ck, cv, ok, ov, state["src"], state["gumbel"], state["finished"], kv.pos)
+        if ancestry:
+            kv.follow_ancestry(state["src"])
+        else:
+            ops.swor_follow(ck, cv, ok, ov, state["src"], state["gumbel"], state["finished"], kv.pos)
 
     def prime():
         start()
         kv.pos += num
 
-    replays = [lambda: step(0), lambda: step(1)]                       # the step on each pair of cache buffers, taken in turn
+    # the step on each pair of cache buffers, taken in turn; with the ancestry table there is one buffer and one step
+    replays = [lambda: step(0)] if ancestry else [lambda: step(0), lambda: step(1)]
     if graph:
         replays = capture_steps(prime, replays, 1)
     start()

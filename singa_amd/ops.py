@@ -850,13 +850,17 @@ def ln_silu(x, gamma, beta, eps=1e-5):
     return _LnSilu.apply(x, gamma, beta, eps)
 
 
-def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, per_row=False, tiles=False):
+def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, per_row=False, tiles=False, anc=None):
     """One decoder layer for one new position of every beam-search row (k17; inference only, no autograd): three launches.
     `w`: dict of the layer's transposed weights as built by BeamSearch.KVDecoder; k_cache [R,4,P,32], v_cache [R,4,P,64];
     pos: int64 device scalar; cross_k [B,4,32,S], cross_v [B,4,S,64], pad [B,S] uint8.  `pos` of shape [R] (more than one
     dimension-0 entry, or `per_row=True`) is one position per row: the self-attention launch is `singa_dec_self_attn_rows` of
     include/singa_hip_stream.h, the other two launches do not depend on the position.  `tiles=True`: the three launches are the
-    row-tiled ones of include/singa_hip_dec_tiles.h (one workgroup per 16 rows of a pocket, any number of encoder positions)."""
+    row-tiled ones of include/singa_hip_dec_tiles.h (one workgroup per 16 rows of a pocket, any number of encoder positions).
+    `anc`: int32 [P, R] ancestry table (include/singa_hip_ancestry.h states the rule): the self-attention launch of the chosen path
+    is its `_anc` form, which reads cached position p of row r from slot anc[p, r]; ValueError together with `per_row`."""
+    if anc is not None and per_row:
+        raise ValueError("dec_layer_step: an ancestry table goes with one position for all rows, not with per_row=True")
     _dev(x, k_cache, v_cache, cross_k, cross_v)
     lib, st = _lib.lib(), _stream()
     R, P, S = x.shape[0], k_cache.shape[2], cross_v.shape[2]
@@ -864,20 +868,28 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, pe
     a, c, f = w["self"], w["cross"], w["ffn"]
     if per_row:
         _check_views("dec_layer_step", ((pos, torch.int64, (R,)),))
+    _check_views("dec_layer_step", ((anc, torch.int32, (P, R)),))
+    self_args = (_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]), _p(a["beta"]), _p(k_cache),
+                 _p(v_cache), _p(pos))
     if tiles:
-        _chk(lib.singa_dec_tile_self_attn(_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]),
-                                          _p(a["beta"]), _p(k_cache), _p(v_cache), _p(pos), 1 if per_row else 0, R, beams, P, _p(y),
-                                          a["eps"], st), "singa_dec_tile_self_attn")
+        if anc is not None:
+            _chk(lib.singa_dec_tile_self_attn_anc(*self_args, 0, R, beams, P, _p(y), a["eps"], _p(anc), st),
+                 "singa_dec_tile_self_attn_anc")
+        else:
+            _chk(lib.singa_dec_tile_self_attn(*self_args, 1 if per_row else 0, R, beams, P, _p(y), a["eps"], st),
+                 "singa_dec_tile_self_attn")
         _chk(lib.singa_dec_tile_cross_attn(_p(y), _p(c["wq_t"]), _p(c["bq"]), _p(cross_k), _p(cross_v), _p(pad), _p(c["wo_t"]),
                                            _p(c["bo"]), _p(c["gamma"]), _p(c["beta"]), R, beams, S, _p(z), c["eps"], st),
              "singa_dec_tile_cross_attn")
         _chk(lib.singa_dec_tile_ffn(_p(z), _p(f["w1_t"]), _p(f["b1"]), _p(f["w2_t"]), _p(f["b2"]), _p(f["gamma"]), _p(f["beta"]), R,
                                     _p(out), f["eps"], st), "singa_dec_tile_ffn")
         return out
-    self_attn, name = (lib.singa_dec_self_attn_rows, "singa_dec_self_attn_rows") if per_row else \
-        (lib.singa_dec_self_attn, "singa_dec_self_attn")
-    _chk(self_attn(_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]), _p(a["beta"]), _p(k_cache),
-                   _p(v_cache), _p(pos), R, P, _p(y), a["eps"], st), name)
+    if anc is not None:
+        _chk(lib.singa_dec_self_attn_anc(*self_args, R, P, _p(y), a["eps"], _p(anc), st), "singa_dec_self_attn_anc")
+    else:
+        self_attn, name = (lib.singa_dec_self_attn_rows, "singa_dec_self_attn_rows") if per_row else \
+            (lib.singa_dec_self_attn, "singa_dec_self_attn")
+        _chk(self_attn(*self_args, R, P, _p(y), a["eps"], st), name)
     _chk(lib.singa_dec_cross_attn(_p(y), _p(c["wq_t"]), _p(c["bq"]), _p(cross_k), _p(cross_v), _p(pad), _p(c["wo_t"]), _p(c["bo"]),
                                   _p(c["gamma"]), _p(c["beta"]), R, beams, S, _p(z), c["eps"], st), "singa_dec_cross_attn")
     _chk(lib.singa_dec_ffn(_p(z), _p(f["w1_t"]), _p(f["b1"]), _p(f["w2_t"]), _p(f["b2"]), _p(f["gamma"]), _p(f["beta"]), R, _p(out),
@@ -1139,6 +1151,17 @@ def swor_follow(k_src, v_src, k_dst, v_dst, src, gumbel, finished, pos):
     _chk(_lib.lib().singa_swor_follow(_p(k_src), _p(v_src), _p(k_dst), _p(v_dst), _p(src), _p(gumbel), _p(finished), _p(pos), n, R,
                                       H, P, dk, dv, k_src.stride(1), k_src.stride(0), v_src.stride(1), v_src.stride(0), _stream()),
          "singa_swor_follow")
+
+
+def anc_follow(anc, src, pos, k):
+    """The ancestry table follows a re-ranking (`singa_anc_follow`, include/singa_hip_ancestry.h states the rule) in place of
+    the caches: one launch behind the step's increment of `pos`, t = pos - 1 the position just appended.  Row r takes its parent
+    src[r]'s entries of the positions below t, and position t names the parent's slot.  anc [P, R] int32, src [R] int64 (parents
+    within the row's pocket of `k` slots; any other entry leaves the row alone), pos: int64 device scalar."""
+    P, R = anc.shape
+    _check_views("anc_follow", ((anc, torch.int32, (P, R)), (src, torch.int64, (R,)), (pos, torch.int64, None)))
+    _lib.ensure_init(anc.device.index if anc.device.index is not None else torch.cuda.current_device())
+    _chk(_lib.lib().singa_anc_follow(_p(anc), _p(src), _p(pos), R, k, P, _stream()), "singa_anc_follow")
 
 
 def beam_work(rows, T, device):

@@ -3,7 +3,7 @@
 num_beams=20, topk=1, max_length = tgt_len + 1 = 201, property prompt - on synthetic pockets with random-init weights.
 
     python tools/bench_beam.py [--proteins 4] [--max-length 201] [--beams 20] [--no-graph] [--prefix-baseline]
-                               [--select host|device] [--batch 1] [--tiles]
+                               [--select host|device] [--batch 1] [--tiles] [--ancestry]
 
 Prints one JSON line: new tokens per second (beams x steps / time), pockets per second, and the per-step time.
 `--select device` times `beam_search_device` (the selection as kernels inside the captured step, nothing copied per token)
@@ -13,7 +13,8 @@ pockets per call, so that the two can be compared at 1 and at several pockets, b
 token, BeamSearch.py:82) built from the same product modules on the same GPU, so the two differ by the algorithm only.
 `--tiles` times the chosen search on both decoder paths instead - the k17 step kernels and the row-tiled ones
 (include/singa_hip_dec_tiles.h) - on the first pocket: one warm-up each, then three whole searches each, interleaved, every run
-listed in ms per step (`tiles_table`).
+listed in ms per step (`tiles_table`).  `--ancestry` (with `--select device`) times `cache="copy"` against `cache="ancestry"`
+(include/singa_hip_ancestry.h) the same way, on the k17 path or with `--tiles` on the row-tiled one (`ancestry_table`).
 """
 import argparse
 import json
@@ -63,7 +64,10 @@ def main():
     ap.add_argument("--select", choices=["host", "device"], default="host")
     ap.add_argument("--batch", type=int, default=1, help="pockets per call")
     ap.add_argument("--tiles", action="store_true", help="time the search on the k17 and on the row-tiled decoder step, interleaved")
+    ap.add_argument("--ancestry", action="store_true",
+                    help="--select device: time the search with copied caches and with the ancestry table, interleaved")
     args = ap.parse_args()
+    assert not args.ancestry or args.select == "device", "--ancestry is about the rows re-ranked on the device: --select device"
     assert not args.prefix_baseline or args.batch == 1, "--prefix-baseline re-runs one pocket: --batch 1"
     import __graft_entry__
     __graft_entry__.build()
@@ -101,6 +105,26 @@ def main():
     pockets = [pocket(i) for i in range(args.proteins)]
     search = beam_search_device if args.select == "device" else beam_search
     run = lambda ex: search(model, voc, args.beams, args.batch, args.max_length, 1, ex, prop, device=dev, graph=not args.no_graph)
+    if args.ancestry:
+        def timed(cache):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = search(model, voc, args.beams, args.batch, args.max_length, 1, pockets[0], prop, device=dev, graph=not args.no_graph,
+                       tiles=args.tiles, cache=cache).shape[1]
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (n - 1)
+        timed("copy"), timed("ancestry")
+        cp, an = [], []
+        for _ in range(3):
+            cp.append(timed("copy"))
+            an.append(timed("ancestry"))
+        print(json.dumps({"select": args.select, "num_beams": args.beams, "pockets_per_call": args.batch, "max_length": args.max_length,
+                          "ancestry_table": [{"rows": args.beams * args.batch, "path": "tiles" if args.tiles else "k17",
+                                              "copy_ms_per_step": round(float(np.median(cp)), 4),
+                                              "ancestry_ms_per_step": round(float(np.median(an)), 4),
+                                              "copy_runs_ms": [round(x, 4) for x in cp], "ancestry_runs_ms": [round(x, 4) for x in an],
+                                              "ancestry_faster": max(an) < min(cp), "copy_faster": max(cp) < min(an)}]}))
+        return
     if args.tiles:
         def timed(tiles):
             torch.cuda.synchronize()

@@ -63,6 +63,9 @@ def main():
     ap.add_argument("--distinct", action="store_true", help="also time sample_distinct next to the plain step (distinct_table)")
     ap.add_argument("--distinct-only", type=int, default=0, metavar="ROWS",
                     help="nothing but two sample_distinct generations of ROWS slots: the run to take a kernel trace of")
+    ap.add_argument("--kv-cache", choices=["copy", "ancestry"], default="copy",
+                    help="--distinct-only: how the caches follow the re-ranked rows (the trace of one path)")
+    ap.add_argument("--decoder-tiles", action="store_true", help="--distinct-only: on the row-tiled step kernels instead of k17")
     ap.add_argument("--valence", action="store_true",
                     help="nothing but the k17 step under grammar='valence' next to grammar='smiles' at rows = 128, 512, 2048 (valence_table)")
     ap.add_argument("--rows-per-pocket", type=int, default=0, metavar="R",
@@ -148,14 +151,26 @@ def main():
                     "k17_runs_ms": [round(x, 4) for x in k17], "tiles_runs_ms": [round(x, 4) for x in til],
                     "tiles_faster": max(til) < min(k17), "k17_faster": max(k17) < min(til)}       # faster = the runs do not overlap
 
-        def run_distinct(rows, tiles):
+        def run_distinct(rows, tiles, cache="copy"):
             tr = {}
             sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev, temperature=args.temperature,
-                            suppress=("$",), seed=rows, trace=tr, tiles=tiles)
+                            suppress=("$",), seed=rows, trace=tr, tiles=tiles, cache=cache)
             return tr["steps"]
+
+        def anc_row(rows):
+            """tiles=True, cache "copy" against "ancestry": one warm-up each, then 3 whole generations each, interleaved"""
+            run_distinct(rows, True), run_distinct(rows, True, "ancestry")
+            cp, an = [], []
+            for _ in range(3):
+                cp.append(timed(lambda: run_distinct(rows, True)))
+                an.append(timed(lambda: run_distinct(rows, True, "ancestry")))
+            return {"rows": rows, "path": "tiles", "copy_ms_per_step": round(statistics.median(cp), 4),
+                    "ancestry_ms_per_step": round(statistics.median(an), 4), "copy_runs_ms": [round(x, 4) for x in cp],
+                    "ancestry_runs_ms": [round(x, 4) for x in an], "ancestry_faster": max(an) < min(cp), "copy_faster": max(cp) < min(an)}
         ttable = [row(rows, *both(lambda t: run_sample(rows, True, tiles=t), 3 if rows >= 512 else args.reps)) for rows in (20, 128, 512, 2048)]
         print(json.dumps({"max_length": T, "tiles_table": ttable,
-                          "tiles_distinct": [row(2048, *both(lambda t: run_distinct(2048, t), 3))]}))
+                          "tiles_distinct": [row(2048, *both(lambda t: run_distinct(2048, t), 3))],
+                          "tiles_distinct_ancestry": [anc_row(rows) for rows in (128, 512, 2048)]}))
         return
     if args.score_stream:
         import numpy as np
@@ -241,9 +256,10 @@ def main():
         for _ in range(2):
             tr = {}
             ms.append(timed(lambda: sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev,
-                                                    temperature=args.temperature, suppress=("$",), seed=rows, trace=tr) is None
+                                                    temperature=args.temperature, suppress=("$",), seed=rows, trace=tr,
+                                                    cache=args.kv_cache, tiles=args.decoder_tiles) is None
                             or tr["steps"]))
-        print(json.dumps({"distinct_only_rows": rows, "ms_per_step": [round(x, 4) for x in ms]}))
+        print(json.dumps({"distinct_only_rows": rows, "kv_cache": args.kv_cache, "path": "tiles" if args.decoder_tiles else "k17", "ms_per_step": [round(x, 4) for x in ms]}))
         return
     if args.valence:
         vtable = []
@@ -381,21 +397,25 @@ def main():
         res["score_2048"] = {"molecules": 2048, "tokens_each": 40, "seconds": [round(x, 4) for x in secs],
                              "molecules_per_s": round(2048 / statistics.median(secs), 1)}
     if args.distinct:
-        def run_distinct(rows):
+        def run_distinct(rows, cache="copy"):
             tr = {}
             sample_distinct(model, voc, rows, 1, T, ex, torch.ones(rows, 3, device=dev), device=dev, temperature=args.temperature,
-                            suppress=("$",), seed=rows, trace=tr)
+                            suppress=("$",), seed=rows, trace=tr, cache=cache)
             return tr["steps"]
         dtable = []
         for rows in (128, 512, 2048):
-            run_sample(rows, True), run_distinct(rows)
-            plain, dist = [], []
+            run_sample(rows, True), run_distinct(rows), run_distinct(rows, "ancestry")
+            plain, dist, anc = [], [], []
             for _ in range(3 if rows >= 512 else args.reps):
                 plain.append(timed(lambda: run_sample(rows, True)))
                 dist.append(timed(lambda: run_distinct(rows)))
+                anc.append(timed(lambda: run_distinct(rows, "ancestry")))
             dtable.append({"rows": rows, "path": "k17", "plain_ms_per_step": round(statistics.median(plain), 4),
                            "distinct_ms_per_step": round(statistics.median(dist), 4),
-                           "plain_runs_ms": [round(x, 4) for x in plain], "distinct_runs_ms": [round(x, 4) for x in dist]})
+                           "distinct_ancestry_ms_per_step": round(statistics.median(anc), 4),
+                           "plain_runs_ms": [round(x, 4) for x in plain], "distinct_runs_ms": [round(x, 4) for x in dist],
+                           "distinct_ancestry_runs_ms": [round(x, 4) for x in anc],
+                           "ancestry_faster": max(anc) < min(dist), "copy_faster": max(dist) < min(anc)})
         res["distinct_table"] = dtable
     print(json.dumps(res))
 
