@@ -6039,10 +6039,256 @@ __global__ void __launch_bounds__(256) rowdot32_bwd_kernel(const float* __restri
 //      good as the reference's (dgl draws random signs on top) -
 //   5. back-transformation through the reflectors, sign convention (entry of largest magnitude positive), fp32 output.
 #ifndef SINGA_EMUL      // (workgroup-cooperative: not part of the sequential CPU emulation build of tests/emul)
-// ---- the sparse route of lap_pe_kernel (see "1b." there): Chebyshev-filtered subspace iteration, block of 16 vectors
+// ---- Chebyshev-filtered subspace iteration for the lowest eigenpairs of a sparse Laplacian, block of 16 vectors: ONE body,
+// lap_fsi_iterate, under lap_fsi (the sparse route of lap_pe_kernel, "1b." there) and step 4 of lap_pe_large_kernel.  Every
+// tolerance, pivot rule and convergence test of the iteration is stated here, once.  What the callers differ in comes in as an
+// argument: where the three blocks live and how a filter step advances them (LapFsiCopied / LapFsiRotated), the LDS scratch
+// (LapFsiLds), the row chunks of a Gram matrix (CH), and callables for the atom behind a row of the start block, the product
+// with the Laplacian, the projection in front of a Cholesky pass, the Jacobi stop test and giving up early.
 constexpr int LAP_FSI_PB = 16, LAP_FSI_ELLW = 32, LAP_FSI_DEG = 24, LAP_FSI_MAXIT = 40;
 constexpr int LAP_FSI_PER_LD = 3 * LAP_FSI_PB + LAP_FSI_ELLW + LAP_FSI_ELLW / 2;     // doubles of global scratch per atom
 constexpr int LAP_WORK_PER_LD = 3 + 4 * 9 + LAP_FSI_PER_LD;
+static_assert(LAP_FSI_PER_LD == 96 && LAP_WORK_PER_LD == 135, "singa_lap_pe_work sizes the callers' buffers by these");
+
+// the three blocks [n][16].  Current block in LDS, the other two in global memory: a filter step copies previous <- current <-
+// next (a thread moves the elements it computed, so the only cross-thread hazard is the gather from the current block)
+struct LapFsiCopied {
+    double *X, *Y, *N, *Wg;
+    __device__ __forceinline__ double* W() const { return Wg; }         // L X has a block of its own
+    __device__ __forceinline__ void advance(int total, int tid) {
+        for (int idx = tid; idx < total; idx += 1024) { Y[idx] = X[idx]; X[idx] = N[idx]; }
+        __syncthreads();
+    }
+};
+// all three in global memory: a filter step rotates the pointers
+struct LapFsiRotated {
+    double *X, *Y, *N;
+    __device__ __forceinline__ double* W() const { return N; }          // L X borrows the next block
+    __device__ __forceinline__ void advance(int, int) { double* t = Y; Y = X; X = N; N = t; }
+};
+struct LapFsiLds {
+    double* H;          // [16][16] projected / Gram matrix
+    double* Q;          // [16][16] rotations / Cholesky factor
+    double* Qs;         // [16][16] rotations, columns by ascending Ritz value (may be the head of `part`)
+    double* part;       // [CH * 256] reduction scratch
+    double* theta;      // [16] Ritz values, ascending
+    double* resn;       // [16] residual norms
+    int* ord;           // [16] the sort's scratch (may lie in `part` behind Qs)
+    int* bad;           // a Cholesky pivot vanished
+};
+
+// H = sym(A^T B) (B = A: Gram matrix; B = L A: projected matrix) from CH row chunks of 256 threads each
+template <int CH>
+__device__ __forceinline__ void lap_fsi_gram(const double* A, const double* B, int n, const LapFsiLds& s, int tid) {
+    static_assert(CH == 2 || CH == 4, "the chunk sums are written out for 2 and 4");
+    if (tid < CH * 256) {
+        const int p = tid & 255, ch = tid >> 8, a = p >> 4, b = p & 15;
+        double acc = 0.0;
+        for (int r = ch; r < n; r += CH) acc += A[r * LAP_FSI_PB + a] * B[r * LAP_FSI_PB + b];
+        s.part[ch * 256 + p] = acc;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        if constexpr (CH == 2) s.Q[tid] = s.part[tid] + s.part[256 + tid];
+        else s.Q[tid] = (s.part[tid] + s.part[256 + tid]) + (s.part[512 + tid] + s.part[768 + tid]);
+    }
+    __syncthreads();
+    if (tid < 256) s.H[tid] = 0.5 * (s.Q[tid] + s.Q[(tid & 15) * 16 + (tid >> 4)]);
+    __syncthreads();
+}
+
+// the Jacobi rotation that annihilates h_pq
+__device__ __forceinline__ void lap_jacobi_rotation(double hpp, double hqq, double hpq, double& c, double& sn) {
+    c = 1.0, sn = 0.0;
+    if (fabs(hpq) > 1e-300) {
+        const double tau = (hqq - hpp) / (2.0 * hpq);
+        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+        c = 1.0 / sqrt(1.0 + t * t);
+        sn = t * c;
+    }
+}
+
+// On 1024 threads; bk.X ends as the Ritz vectors, s.theta ascending.  0: the lowest `want` pairs have residuals <= 2e-10,
+// 2: a Cholesky pivot vanished, 3: no convergence.  atom(r): what the start block's row r is tied to; lx(X, idx) = (L X)[idx];
+// project(): in front of each Cholesky pass; square_sums(off, dg): the sums of H's squared off-diagonal and diagonal entries
+// in front of a Jacobi sweep; give_up(it, worst): after the residual check of outer iteration `it` - the last two with the same
+// answer on every thread
+template <int CH, int NW, class Blocks, class Atom, class Lx, class Project, class Sums, class GiveUp>
+__device__ __forceinline__ int lap_fsi_iterate(Blocks& bk, const LapFsiLds& s, int n, int want, int tid, int lane, int wave,
+                                               Atom atom, Lx lx, Project project, Sums square_sums, GiveUp give_up) {
+    constexpr int PB = LAP_FSI_PB;
+    double *H = s.H, *Q = s.Q, *Qs = s.Qs;
+    const int total = n * PB;
+    // start block: deterministic pseudo-random entries
+    for (int idx = tid; idx < total; idx += 1024) {
+        const int r = idx >> 4, j = idx & 15;
+        unsigned h = (unsigned)(atom(r) * 2654435761u) ^ (unsigned)((j + 11) * 40503u * 2246822519u);
+        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+        bk.X[idx] = (double)(h & 0xFFFFFF) / 8388608.0 - 1.0;
+    }
+    __syncthreads();
+    // X <- X R^-1 with G = X^T X = R^T R (twice: CholQR2); false if a pivot vanishes
+    auto orthonormalise = [&]() -> bool {
+        for (int pass = 0; pass < 2; ++pass) {
+            project();
+            lap_fsi_gram<CH>(bk.X, bk.X, n, s, tid);
+            if (tid == 0) {
+                int bad = 0;
+                double tr = 0.0;
+                for (int j = 0; j < PB; ++j) tr += H[j * 16 + j];
+                for (int j = 0; j < PB; ++j) {
+                    double d = H[j * 16 + j];
+                    for (int k = 0; k < j; ++k) d -= Q[k * 16 + j] * Q[k * 16 + j];
+                    if (!(d > 1e-26 * tr)) { bad = 1; d = 1.0; }
+                    const double rj = sqrt(d);
+                    Q[j * 16 + j] = rj;
+                    for (int i = j + 1; i < PB; ++i) {
+                        double v = H[j * 16 + i];
+                        for (int k = 0; k < j; ++k) v -= Q[k * 16 + j] * Q[k * 16 + i];
+                        Q[j * 16 + i] = v / rj;
+                    }
+                }
+                *s.bad = bad;
+            }
+            __syncthreads();
+            if (*s.bad) return false;
+            for (int r = tid; r < n; r += 1024) {       // the thread's own rows, solved in place (y R = x): no register arrays
+                double* xr = bk.X + r * PB;
+#pragma unroll 1
+                for (int j = 0; j < PB; ++j) {
+                    double v = xr[j];
+#pragma unroll 1
+                    for (int i = 0; i < j; ++i) v -= xr[i] * Q[i * 16 + j];
+                    xr[j] = v / Q[j * 16 + j];
+                }
+            }
+            __syncthreads();
+        }
+        return true;
+    };
+    if (!orthonormalise()) return 2;
+    for (int it = 0; it < LAP_FSI_MAXIT; ++it) {
+        // Rayleigh-Ritz: Wg = L X, H = X^T L X, Jacobi, X <- X Q, Wg <- Wg Q (Ritz values ascending), residual norms
+        double *X = bk.X, *Wg = bk.W();
+        for (int idx = tid; idx < total; idx += 1024) Wg[idx] = lx(X, idx);
+        __syncthreads();
+        lap_fsi_gram<CH>(X, Wg, n, s, tid);
+        if (tid < 256) Q[tid] = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;
+        __syncthreads();
+        // cyclic Jacobi with the round-robin ordering: 8 disjoint pairs per step, 8 lanes per pair (two rows each)
+        for (int sweep = 0; sweep < 10; ++sweep) {
+            double off2, dg2;
+            square_sums(off2, dg2);
+            if (off2 <= 1e-30 * (dg2 + 1e-300)) break;
+            for (int st = 0; st < 15; ++st) {
+                const int pr = tid >> 3, sub = tid & 7;
+                const int p = pr == 0 ? 15 : (st + pr) % 15, q = pr == 0 ? st : (st + 15 - pr) % 15;
+                double c = 1.0, sn = 0.0;
+                if (tid < 64) lap_jacobi_rotation(H[p * 16 + p], H[q * 16 + q], H[p * 16 + q], c, sn);
+                __syncthreads();
+                if (tid < 64) {
+#pragma unroll
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const int i = sub + 8 * h2;
+                        const double aip = H[i * 16 + p], aiq = H[i * 16 + q];
+                        H[i * 16 + p] = c * aip - sn * aiq;
+                        H[i * 16 + q] = sn * aip + c * aiq;
+                        const double qip = Q[i * 16 + p], qiq = Q[i * 16 + q];
+                        Q[i * 16 + p] = c * qip - sn * qiq;
+                        Q[i * 16 + q] = sn * qip + c * qiq;
+                    }
+                }
+                __syncthreads();
+                if (tid < 64) {
+#pragma unroll
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const int i = sub + 8 * h2;
+                        const double api = H[p * 16 + i], aqi = H[q * 16 + i];
+                        H[p * 16 + i] = c * api - sn * aqi;
+                        H[q * 16 + i] = sn * api + c * aqi;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (tid == 0) {                     // ascending Ritz values, stable; Qs = Q with its columns in that order
+            int* ord = s.ord;
+            for (int a = 0; a < PB; ++a) {
+                int b = a;
+                while (b > 0 && H[ord[b - 1] * 17] > H[a * 17]) { ord[b] = ord[b - 1]; --b; }
+                ord[b] = a;
+            }
+            for (int j = 0; j < PB; ++j) {
+                s.theta[j] = H[ord[j] * 17];
+                for (int i = 0; i < PB; ++i) Qs[i * 16 + j] = Q[i * 16 + ord[j]];
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < n; r += 1024) {   // a row of X, then the same row of L X (one at a time: 16 doubles of registers each)
+            for (int which = 0; which < 2; ++which) {
+                double* rowp = (which == 0 ? X : Wg) + r * PB;
+                double x[PB];
+#pragma unroll
+                for (int i = 0; i < PB; ++i) x[i] = rowp[i];
+#pragma unroll 1
+                for (int j = 0; j < PB; ++j) {
+                    double xs = 0.0;
+#pragma unroll
+                    for (int i = 0; i < PB; ++i) xs += x[i] * Qs[i * 16 + j];
+                    rowp[j] = xs;
+                }
+            }
+        }
+        __syncthreads();
+        {   // residual norms |L x_j - theta_j x_j|: 64 row chunks x 16 columns
+            const int j = tid & 15, ch = tid >> 4;
+            const double th = s.theta[j];
+            double acc = 0.0;
+            for (int r = ch; r < n; r += 64) {
+                const double d = Wg[r * PB + j] - th * X[r * PB + j];
+                acc += d * d;
+            }
+            acc += __shfl_xor(acc, 16, 64);
+            acc += __shfl_xor(acc, 32, 64);
+            __syncthreads();                // (where Qs is the head of part, every row thread has read it above)
+            if (lane < 16) s.part[wave * 16 + lane] = acc;
+            __syncthreads();
+            if (tid < PB) {
+                double t = 0.0;
+                for (int w2 = 0; w2 < NW; ++w2) t += s.part[w2 * 16 + tid];
+                s.resn[tid] = sqrt(t);
+            }
+            __syncthreads();
+        }
+        double worst = 0.0;
+        for (int j = 0; j < want; ++j) worst = fmax(worst, s.resn[j]);
+        if (worst <= 2e-10) return 0;
+        if (give_up(it, worst)) break;
+        // Chebyshev filter of degree LAP_FSI_DEG: damp [a, 2], scaled at a0 (Zhou & Saad's recurrence)
+        const double a0 = s.theta[0], b = 2.0 + 1e-9;
+        const double a = fmax(s.theta[PB - 1], a0 + 1e-4);
+        if (!(a < b - 1e-3)) break;
+        const double e = 0.5 * (b - a), c = 0.5 * (b + a);
+        double sigma = e / (a0 - c);
+        const double sigma1 = sigma;
+        for (int idx = tid; idx < total; idx += 1024) bk.N[idx] = (lx(bk.X, idx) - c * bk.X[idx]) * (sigma1 / e);
+        __syncthreads();
+        bk.advance(total, tid);
+        for (int i = 2; i <= LAP_FSI_DEG; ++i) {
+            const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
+            const double f1 = 2.0 * sigma2 / e, f2 = sigma * sigma2;
+            for (int idx = tid; idx < total; idx += 1024) bk.N[idx] = (lx(bk.X, idx) - c * bk.X[idx]) * f1 - f2 * bk.Y[idx];
+            __syncthreads();
+            bk.advance(total, tid);
+            sigma = sigma2;
+        }
+        if (!orthonormalise()) return 2;
+    }
+    return 3;
+}
+
+// ---- the sparse route of lap_pe_kernel: ELL rows from the dense component blocks, the iteration above with its current block in
+// LDS, the m lowest pairs staged into Z[k][position].  false: the dense route answers
 template <int NW, int KV>
 __device__ __forceinline__ bool lap_fsi(const double* __restrict__ A, int ld, int n, int sl, const int* perm, const int* cbeg,
                                         const int* cend, int* ell_n, int* flag, double* Xl, double* sc, double* wk, int m, int tid,
@@ -6055,10 +6301,10 @@ __device__ __forceinline__ bool lap_fsi(const double* __restrict__ A, int ld, in
     int* ell_i = reinterpret_cast<int*>(ell_v + (long long)ld * W);     // ... and column POSITIONS
     double* H = sc;                                     // [16][16] projected matrix / Gram matrix
     double* Q = sc + 256;                               // [16][16] rotations / Cholesky factor
-    double* part = sc + 512;                            // [512] reduction scratch
-    double* theta = sc + 1024;                          // [16] Ritz values (ascending after `ritz`)
+    double* part = sc + 512;                            // [512] reduction scratch; the sorted rotations, the sort's scratch behind
+    double* theta = sc + 1024;                          // [16] Ritz values, ascending
     double* resn = theta + 16;                          // [16] residual norms
-    double* misc = resn + 16;                           // [8]
+    double* misc = resn + 16;                           // [8] pivot flag (an int) | the two sums of the Jacobi stop test
     const int total = n * PB;
     (void)sl;
     // ---- rows of the Laplacian in ELL form, from the component blocks phase 1 has built (entries outside them are undefined)
@@ -6087,217 +6333,34 @@ __device__ __forceinline__ bool lap_fsi(const double* __restrict__ A, int ld, in
     }
     __syncthreads();
     if (flag[1]) return false;
-    // ---- start block: deterministic pseudo-random entries tied to the ATOM
-    for (int idx = tid; idx < total; idx += 1024) {
-        const int r = idx >> 4, j = idx & 15;
-        unsigned h = (unsigned)(perm[r] * 2654435761u) ^ (unsigned)((j + 11) * 40503u * 2246822519u);
-        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
-        Xl[idx] = (double)(h & 0xFFFFFF) / 8388608.0 - 1.0;
-    }
-    __syncthreads();
-    auto lx = [&](int idx) -> double {                  // (L X)[r][j] from the block in LDS
-        const int r = idx >> 4, j = idx & 15;
-        const int cnt = ell_n[r];
-        const double* ev = ell_v + (long long)r * W;
-        const int* ei = ell_i + (long long)r * W;
-        double acc = 0.0;
-        for (int e = 0; e < cnt; ++e) acc += ev[e] * Xl[ei[e] * PB + j];
-        return acc;
-    };
-    // G = X^T B (B = X in LDS: Gram matrix; B = Wg: projected matrix), symmetrised, -> H
-    auto gram = [&](const double* B) {
-        if (tid < 512) {
-            const int p = tid & 255, ch = tid >> 8, a = p >> 4, b = p & 15;
+    // ---- the iteration: zeros are solved for like every other eigenvalue, 40 iterations or nothing
+    LapFsiCopied bk{Xl, Yg, Ng, Wg};
+    const LapFsiLds lds{H, Q, part, part, theta, resn, reinterpret_cast<int*>(part + 256), reinterpret_cast<int*>(misc)};
+    const int code = lap_fsi_iterate<2, NW>(
+        bk, lds, n, m, tid, lane, wave, [&](int r) { return perm[r]; },
+        [&](const double* X, int idx) -> double {       // (L X)[r][j]: the diagonal is an ELL entry
+            const int r = idx >> 4, j = idx & 15;
+            const int cnt = ell_n[r];
+            const double* ev = ell_v + (long long)r * W;
+            const int* ei = ell_i + (long long)r * W;
             double acc = 0.0;
-            for (int r = ch; r < n; r += 2) acc += Xl[r * PB + a] * B[r * PB + b];
-            part[ch * 256 + p] = acc;
-        }
-        __syncthreads();
-        if (tid < 256) Q[tid] = part[tid] + part[256 + tid];
-        __syncthreads();
-        if (tid < 256) H[tid] = 0.5 * (Q[tid] + Q[(tid & 15) * 16 + (tid >> 4)]);
-        __syncthreads();
-    };
-    // X <- X R^-1 with G = X^T X = R^T R (twice: CholQR2); false if a pivot vanishes
-    auto orthonormalise = [&]() -> bool {
-        for (int pass = 0; pass < 2; ++pass) {
-            gram(Xl);
-            if (tid == 0) {
-                misc[0] = 0.0;
-                double tr = 0.0;
-                for (int j = 0; j < PB; ++j) tr += H[j * 16 + j];
-                for (int j = 0; j < PB; ++j) {
-                    double d = H[j * 16 + j];
-                    for (int k = 0; k < j; ++k) d -= Q[k * 16 + j] * Q[k * 16 + j];
-                    if (!(d > 1e-26 * tr)) { misc[0] = 1.0; d = 1.0; }
-                    const double rj = sqrt(d);
-                    Q[j * 16 + j] = rj;
-                    for (int i = j + 1; i < PB; ++i) {
-                        double v = H[j * 16 + i];
-                        for (int k = 0; k < j; ++k) v -= Q[k * 16 + j] * Q[k * 16 + i];
-                        Q[j * 16 + i] = v / rj;
-                    }
-                }
-            }
-            __syncthreads();
-            if (misc[0] != 0.0) return false;
-            if (tid < n) {                  // the thread's own row, solved in place (y R = x): no register arrays
-                double* xr = Xl + tid * PB;
-#pragma unroll 1
-                for (int j = 0; j < PB; ++j) {
-                    double v = xr[j];
-#pragma unroll 1
-                    for (int i = 0; i < j; ++i) v -= xr[i] * Q[i * 16 + j];
-                    xr[j] = v / Q[j * 16 + j];
-                }
-            }
-            __syncthreads();
-        }
-        return true;
-    };
-    // Rayleigh-Ritz: Wg = L X, H = X^T L X, Jacobi, X <- X Q, Wg <- Wg Q (Ritz values ascending), residual norms
-    auto ritz = [&]() {
-        for (int idx = tid; idx < total; idx += 1024) Wg[idx] = lx(idx);
-        __syncthreads();
-        gram(Wg);
-        if (tid < 256) Q[tid] = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;
-        __syncthreads();
-        // cyclic Jacobi with the round-robin ordering: 8 disjoint pairs per step, 8 lanes per pair (two rows each)
-        for (int sweep = 0; sweep < 10; ++sweep) {
+            for (int e = 0; e < cnt; ++e) acc += ev[e] * X[ei[e] * PB + j];
+            return acc;
+        },
+        [] {},
+        [&](double& off2, double& dg2) {                // serial sums on thread 0
             if (tid == 0) {
                 double off = 0.0, dg = 0.0;
                 for (int i = 0; i < PB; ++i)
                     for (int j = 0; j < PB; ++j) (i == j ? dg : off) += H[i * 16 + j] * H[i * 16 + j];
-                misc[1] = off <= 1e-30 * (dg + 1e-300) ? 1.0 : 0.0;
+                misc[1] = off, misc[2] = dg;
             }
             __syncthreads();
-            const bool done = misc[1] != 0.0;
+            off2 = misc[1], dg2 = misc[2];
             __syncthreads();
-            if (done) break;
-            for (int st = 0; st < 15; ++st) {
-                const int pr = tid >> 3, sub = tid & 7;
-                const int p = pr == 0 ? 15 : (st + pr) % 15, q = pr == 0 ? st : (st + 15 - pr) % 15;
-                double c = 1.0, sn = 0.0;
-                if (tid < 64) {
-                    const double hpp = H[p * 16 + p], hqq = H[q * 16 + q], hpq = H[p * 16 + q];
-                    if (fabs(hpq) > 1e-300) {
-                        const double tau = (hqq - hpp) / (2.0 * hpq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        c = 1.0 / sqrt(1.0 + t * t);
-                        sn = t * c;
-                    }
-                }
-                __syncthreads();
-                if (tid < 64) {
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int i = sub + 8 * h2;
-                        const double aip = H[i * 16 + p], aiq = H[i * 16 + q];
-                        H[i * 16 + p] = c * aip - sn * aiq;
-                        H[i * 16 + q] = sn * aip + c * aiq;
-                        const double qip = Q[i * 16 + p], qiq = Q[i * 16 + q];
-                        Q[i * 16 + p] = c * qip - sn * qiq;
-                        Q[i * 16 + q] = sn * qip + c * qiq;
-                    }
-                }
-                __syncthreads();
-                if (tid < 64) {
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int i = sub + 8 * h2;
-                        const double api = H[p * 16 + i], aqi = H[q * 16 + i];
-                        H[p * 16 + i] = c * api - sn * aqi;
-                        H[q * 16 + i] = sn * api + c * aqi;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // ascending order of the Ritz values; part[0..255] = Q with its columns in that order
-        if (tid == 0) {
-            int ord[PB];
-            for (int j = 0; j < PB; ++j) ord[j] = j;
-            for (int a = 1; a < PB; ++a) {
-                const int oa = ord[a];
-                int b = a;
-                while (b > 0 && H[ord[b - 1] * 16 + ord[b - 1]] > H[oa * 16 + oa]) { ord[b] = ord[b - 1]; --b; }
-                ord[b] = oa;
-            }
-            for (int j = 0; j < PB; ++j) {
-                theta[j] = H[ord[j] * 16 + ord[j]];
-                for (int i = 0; i < PB; ++i) part[i * 16 + j] = Q[i * 16 + ord[j]];
-            }
-        }
-        __syncthreads();
-        if (tid < n) {                      // one row of X, then the same row of L X (one at a time: 16 doubles of registers each)
-            for (int which = 0; which < 2; ++which) {
-                double* rowp = which == 0 ? Xl + tid * PB : Wg + tid * PB;
-                double x[PB];
-#pragma unroll
-                for (int i = 0; i < PB; ++i) x[i] = rowp[i];
-#pragma unroll 1
-                for (int j = 0; j < PB; ++j) {
-                    double xs = 0.0;
-#pragma unroll
-                    for (int i = 0; i < PB; ++i) xs += x[i] * part[i * 16 + j];
-                    rowp[j] = xs;
-                }
-            }
-        }
-        __syncthreads();
-        {   // residual norms |L x_j - theta_j x_j|
-            const int j = tid & 15, ch = tid >> 4;
-            const double th = theta[j];
-            double acc = 0.0;
-            for (int r = ch; r < n; r += 64) {
-                const double d = Wg[r * PB + j] - th * Xl[r * PB + j];
-                acc += d * d;
-            }
-            acc += __shfl_xor(acc, 16, 64);
-            acc += __shfl_xor(acc, 32, 64);
-            __syncthreads();                 // (part is read above by every row thread)
-            if (lane < 16) part[wave * 16 + lane] = acc;
-            __syncthreads();
-            if (tid < PB) {
-                double t = 0.0;
-                for (int w2 = 0; w2 < NW; ++w2) t += part[w2 * 16 + tid];
-                resn[tid] = sqrt(t);
-            }
-            __syncthreads();
-        }
-    };
-    if (!orthonormalise()) return false;
-    bool ok = false;
-    for (int it = 0; it < LAP_FSI_MAXIT; ++it) {
-        ritz();
-        double worst = 0.0;
-        for (int j = 0; j < m; ++j) worst = fmax(worst, resn[j]);
-        if (worst <= 2e-10) { ok = true; break; }
-        // Chebyshev filter of degree LAP_FSI_DEG: damp [a, 2], scaled at a0 (Zhou & Saad's recurrence)
-        const double a0 = theta[0], b = 2.0 + 1e-9;
-        const double a = fmax(theta[PB - 1], a0 + 1e-4);
-        if (!(a < b - 1e-3)) break;
-        const double e = 0.5 * (b - a), c = 0.5 * (b + a);
-        double sigma = e / (a0 - c);
-        const double sigma1 = sigma;
-        // (every step: next block -> global, barrier, then previous <- current, current <- next: a thread moves the elements it
-        // computed, so the only cross-thread hazard is the gather from the current block in LDS)
-        for (int idx = tid; idx < total; idx += 1024) Ng[idx] = (lx(idx) - c * Xl[idx]) * (sigma1 / e);
-        __syncthreads();
-        for (int idx = tid; idx < total; idx += 1024) { Yg[idx] = Xl[idx]; Xl[idx] = Ng[idx]; }
-        __syncthreads();
-        for (int i = 2; i <= LAP_FSI_DEG; ++i) {
-            const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
-            const double f1 = 2.0 * sigma2 / e, f2 = sigma * sigma2;
-            for (int idx = tid; idx < total; idx += 1024) Ng[idx] = (lx(idx) - c * Xl[idx]) * f1 - f2 * Yg[idx];
-            __syncthreads();
-            for (int idx = tid; idx < total; idx += 1024) { Yg[idx] = Xl[idx]; Xl[idx] = Ng[idx]; }
-            __syncthreads();
-            sigma = sigma2;
-        }
-        if (!orthonormalise()) return false;
-    }
-    if (!ok) return false;
+        },
+        [](int, double) { return false; });
+    if (code) return false;
     // ---- the m lowest pairs -> Z[k][position] (the same LDS region: staged through global memory)
     for (int idx = tid; idx < total; idx += 1024) Yg[idx] = Xl[idx];
     __syncthreads();
@@ -6813,21 +6876,25 @@ __global__ void __launch_bounds__(1024) lap_pe_kernel(double* __restrict__ Aall,
 //      sqrt(d_i) / sqrt(sum d) on its atoms - checked against the component's own rows (|L z| <= 1e-12; it fails only for edge lists
 //      that are not symmetric, which give up).  An atom without any edge is an eigenvector of eigenvalue 1.  With c such
 //      components and m = min(n, kout + 1) wanted pairs: c >= m -> the answer is m of the null vectors and nothing is solved.
-//   4. otherwise (c <= 8) the m - c lowest NON-zero pairs of the whole graph come from the Chebyshev-filtered subspace iteration of
-//      lap_fsi (block of 16, degree 24, CholQR2, residual 2e-10, <= 40 outer iterations) with its three blocks in global memory
-//      and the block kept orthogonal to the c null vectors (one [8][16] projection before each Cholesky pass: supports are
-//      disjoint, so the null vectors are orthonormal as they stand).  Rayleigh-Ritz over the whole block-diagonal operator IS the
-//      merge of the components' spectra by eigenvalue; the zeros sort first.
+//   4. otherwise (c <= 8) the m - c lowest NON-zero pairs of the whole graph come from the Chebyshev-filtered subspace iteration
+//      that lap_fsi runs: lap_fsi_iterate<4, 16> (block of 16, degree 24, CholQR2, residual 2e-10, <= 40 outer iterations) over
+//      LapFsiRotated, its three blocks in global memory.  This kernel's own arguments to it: the diagonal kept apart from the
+//      ELL row, the block kept orthogonal to the c null vectors (one [8][16] projection before each Cholesky pass: supports are
+//      disjoint, so the null vectors are orthonormal as they stand), block sums for the Jacobi stop test, and giving up early on
+//      a residual that falls too slowly.  Rayleigh-Ritz over the whole block-diagonal operator IS the merge of the components'
+//      spectra by eigenvalue; the zeros sort first.
 // A graph that does not go by the book sets status[g] and writes NOTHING to `out` (every write of `out` is behind the last
 // check): 1 a row with more than 32 neighbours (or more than 64 raw entries), 2 a vanishing Cholesky pivot, 3 no convergence,
 // 4 a component whose null vector fails its check, 5 an edge index outside the graph, 6 more atoms than ld / 2,048.
-constexpr int LAPL_MAXN = 2048, LAPL_W = 32, LAPL_RAW = 64, LAPL_PB = 16;
-constexpr int LAPL_PER_LD = 3 * LAPL_PB + LAPL_W + 4 + (LAPL_W + 8) / 2;      // doubles of `work` per atom of ld (ints count half)
+constexpr int LAPL_MAXN = 2048, LAPL_RAW = 64;
+// doubles of `work` per atom of ld (ints count half)
+constexpr int LAPL_PER_LD = 3 * LAP_FSI_PB + LAP_FSI_ELLW + 4 + (LAP_FSI_ELLW + 8) / 2;
+static_assert(LAPL_PER_LD == 104, "singa_lap_pe_large_work sizes the caller's buffer by this");
 __global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restrict__ esrc, const int* __restrict__ edst,
                                                             const int* __restrict__ eptr, const int* __restrict__ nnodes,
                                                             const int* __restrict__ first, double* work, float* out, int* status,
                                                             int ld, int kout) {
-    constexpr int PB = LAPL_PB, W = LAPL_W, RAW = LAPL_RAW, NW = 16;
+    constexpr int PB = LAP_FSI_PB, W = LAP_FSI_ELLW, RAW = LAPL_RAW, NW = 16;
     __shared__ double Hs[1024];            // Jacobi: H [32][32]; subspace iteration: H [16][16] | Q [16][16] | Q sorted | coef [8][16]
     __shared__ double Vs[1024];            // Jacobi: V [32][32]; subspace iteration: reduction scratch
     __shared__ double theta[16], resn[16], redd[NW];
@@ -6839,9 +6906,8 @@ __global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restric
         return;
     }
     double* base = work + (long long)g * LAPL_PER_LD * ld;
-    double* Xc = base;                                   // [n][PB] current block
-    double* Yp = base + (long long)PB * ld;              // [n][PB] previous block of the recurrence
-    double* Nx = base + (long long)2 * PB * ld;          // [n][PB] next block / L X
+    // X [n][PB] current block | Y [n][PB] previous block of the recurrence | N [n][PB] next block / L X
+    LapFsiRotated bk{base, base + (long long)PB * ld, base + (long long)2 * PB * ld};
     double* ell_v = base + (long long)3 * PB * ld;       // [n][W] off-diagonal values
     double* diag = ell_v + (long long)W * ld;            // [n]
     double* dinv = diag + ld;                            // [n] 1 / sqrt(clipped in-degree)
@@ -6854,7 +6920,7 @@ __global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restric
     int* degsum = zr + ld;                               // [root] sum of the clipped in-degrees of the component
     int* dclip = degsum + ld;                            // [n]
     int* selfl = dclip + ld;                             // [n] self loop
-    int* raw = reinterpret_cast<int*>(Yp);               // [n][RAW] atom | direction << 12 (dead before the blocks are used)
+    int* raw = reinterpret_cast<int*>(bk.Y);              // [n][RAW] atom | direction << 12 (dead before the blocks are used)
     const int e0 = eptr[g], e1 = eptr[g + 1];
     const int m = n < kout + 1 ? n : kout + 1;           // pairs wanted: the smallest + up to kout more
     float* o = out + (long long)first[g] * kout;
@@ -7001,15 +7067,7 @@ __global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restric
                 const int pr = tid >> 5, i = tid & 31;
                 const int p = pr == 0 ? 31 : (st + pr) % 31, q = pr == 0 ? st : (st + 31 - pr) % 31;
                 double c = 1.0, sn = 0.0;
-                if (tid < 512) {
-                    const double hpp = Hs[p * 32 + p], hqq = Hs[q * 32 + q], hpq = Hs[p * 32 + q];
-                    if (fabs(hpq) > 1e-300) {
-                        const double tau = (hqq - hpp) / (2.0 * hpq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        c = 1.0 / sqrt(1.0 + t * t);
-                        sn = t * c;
-                    }
-                }
+                if (tid < 512) lap_jacobi_rotation(Hs[p * 32 + p], Hs[q * 32 + q], Hs[p * 32 + q], c, sn);
                 __syncthreads();
                 if (tid < 512) {
                     const double aip = Hs[i * 32 + p], aiq = Hs[i * 32 + q];
@@ -7092,237 +7150,66 @@ __global__ void __launch_bounds__(1024) lap_pe_large_kernel(const int* __restric
     }
 
     // ---- 4. the m - c lowest non-zero pairs: filtered subspace iteration, blocks in global memory
-    double* H = Hs;                                      // [16][16] projected / Gram matrix
-    double* Q = Hs + 256;                                // [16][16] rotations / Cholesky factor
-    double* Qs = Hs + 512;                               // [16][16] rotations, columns by ascending Ritz value
+    // (lap_fsi_iterate; here with the diagonal kept apart from the ELL row, the block kept orthogonal to the c null vectors, and
+    // giving up early)
+    double* H = Hs;                                      // H | Q | Q sorted, [16][16] each
     double* coef = Hs + 768;                             // [8][16] null vectors . block
     double* part = Vs;
-    const int total = n * PB, want = m - c;
-    auto lx = [&](const double* X, int idx) -> double {  // (L X)[r][j]
-        const int r = idx >> 4, j = idx & 15;
-        const int nn = ell_n[r];
-        const double* ev = ell_v + (long long)r * W;
-        const int* ei = ell_i + (long long)r * W;
-        double acc = diag[r] * X[idx];
-        for (int p = 0; p < nn; ++p) acc += ev[p] * X[ei[p] * PB + j];
-        return acc;
-    };
-    auto gram = [&](const double* A, const double* B) {  // H = sym(A^T B): 4 row chunks x 256 entries
-        {
-            const int p = tid & 255, ch = tid >> 8, a = p >> 4, b = p & 15;
-            double acc = 0.0;
-            for (int r = ch; r < n; r += 4) acc += A[r * PB + a] * B[r * PB + b];
-            part[tid] = acc;
-        }
-        __syncthreads();
-        if (tid < 256) Q[tid] = (part[tid] + part[256 + tid]) + (part[512 + tid] + part[768 + tid]);
-        __syncthreads();
-        if (tid < 256) H[tid] = 0.5 * (Q[tid] + Q[(tid & 15) * 16 + (tid >> 4)]);
-        __syncthreads();
-    };
-    auto project = [&]() {                               // X <- X - Z (Z^T X) over the c null vectors
-        if (c == 0) return;
-        {
-            const int j = tid & 15, a = (tid >> 4) & 7, ch = tid >> 7;
-            double acc = 0.0;
-            for (int r = ch; r < n; r += 8)
-                if (zr[r] == a) acc += zn[r] * Xc[r * PB + j];
-            part[tid] = acc;
-        }
-        __syncthreads();
-        if (tid < 128) {
-            double s = 0.0;
-            for (int ch = 0; ch < 8; ++ch) s += part[ch * 128 + tid];
-            coef[tid] = s;
-        }
-        __syncthreads();
-        for (int idx = tid; idx < total; idx += 1024) {
-            const int r = idx >> 4, a = zr[r];
-            if (a >= 0) Xc[idx] -= zn[r] * coef[a * 16 + (idx & 15)];
-        }
-        __syncthreads();
-    };
-    auto orthonormalise = [&]() -> bool {                // X <- X R^-1, X^T X = R^T R, twice (CholQR2)
-        for (int pass = 0; pass < 2; ++pass) {
-            project();
-            gram(Xc, Xc);
-            if (tid == 0) {
-                fl[3] = 0;
-                double tr = 0.0;
-                for (int j = 0; j < PB; ++j) tr += H[j * 16 + j];
-                for (int j = 0; j < PB; ++j) {
-                    double d = H[j * 16 + j];
-                    for (int k = 0; k < j; ++k) d -= Q[k * 16 + j] * Q[k * 16 + j];
-                    if (!(d > 1e-26 * tr)) { fl[3] = 1; d = 1.0; }
-                    const double rj = sqrt(d);
-                    Q[j * 16 + j] = rj;
-                    for (int i = j + 1; i < PB; ++i) {
-                        double v = H[j * 16 + i];
-                        for (int k = 0; k < j; ++k) v -= Q[k * 16 + j] * Q[k * 16 + i];
-                        Q[j * 16 + i] = v / rj;
-                    }
-                }
+    const LapFsiLds lds{H, Hs + 256, Hs + 512, part, theta, resn, ordv, &fl[3]};
+    const int total = n * PB;
+    double prev = 0.0;
+    const int code = lap_fsi_iterate<4, NW>(
+        bk, lds, n, m - c, tid, lane, wave, [](int r) { return r; },
+        [&](const double* X, int idx) -> double {        // (L X)[r][j]
+            const int r = idx >> 4, j = idx & 15;
+            const int nn = ell_n[r];
+            const double* ev = ell_v + (long long)r * W;
+            const int* ei = ell_i + (long long)r * W;
+            double acc = diag[r] * X[idx];
+            for (int p = 0; p < nn; ++p) acc += ev[p] * X[ei[p] * PB + j];
+            return acc;
+        },
+        [&]() {                                          // X <- X - Z (Z^T X) over the c null vectors
+            if (c == 0) return;
+            double* Xc = bk.X;
+            {
+                const int j = tid & 15, a = (tid >> 4) & 7, ch = tid >> 7;
+                double acc = 0.0;
+                for (int r = ch; r < n; r += 8)
+                    if (zr[r] == a) acc += zn[r] * Xc[r * PB + j];
+                part[tid] = acc;
             }
             __syncthreads();
-            if (fl[3]) return false;
-            for (int r = tid; r < n; r += 1024) {        // the thread's own rows, solved in place (y R = x): no register arrays
-                double* xr = Xc + r * PB;
-#pragma unroll 1
-                for (int j = 0; j < PB; ++j) {
-                    double v = xr[j];
-#pragma unroll 1
-                    for (int i = 0; i < j; ++i) v -= xr[i] * Q[i * 16 + j];
-                    xr[j] = v / Q[j * 16 + j];
-                }
+            if (tid < 128) {
+                double s = 0.0;
+                for (int ch = 0; ch < 8; ++ch) s += part[ch * 128 + tid];
+                coef[tid] = s;
             }
             __syncthreads();
-        }
-        return true;
-    };
-    auto ritz = [&]() {                                  // Nx = L X, Jacobi on X^T L X, X <- X Q, Nx <- Nx Q, residual norms
-        double* Wg = Nx;
-        for (int idx = tid; idx < total; idx += 1024) Wg[idx] = lx(Xc, idx);
-        __syncthreads();
-        gram(Xc, Wg);
-        if (tid < 256) Q[tid] = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;
-        __syncthreads();
-        for (int sweep = 0; sweep < 10; ++sweep) {
+            for (int idx = tid; idx < total; idx += 1024) {
+                const int r = idx >> 4, a = zr[r];
+                if (a >= 0) Xc[idx] -= zn[r] * coef[a * 16 + (idx & 15)];
+            }
+            __syncthreads();
+        },
+        [&](double& off2, double& dg2) {                 // two block sums
             const double h = tid < 256 ? H[tid] : 0.0;
             const bool dg = tid < 256 && (tid >> 4) == (tid & 15);
-            const double off2 = block_sum(dg ? 0.0 : h * h), dg2 = block_sum(dg ? h * h : 0.0);
-            if (off2 <= 1e-30 * (dg2 + 1e-300)) break;
-            for (int st = 0; st < 15; ++st) {
-                const int pr = tid >> 3, sub = tid & 7;
-                const int p = pr == 0 ? 15 : (st + pr) % 15, q = pr == 0 ? st : (st + 15 - pr) % 15;
-                double cs = 1.0, sn = 0.0;
-                if (tid < 64) {
-                    const double hpp = H[p * 16 + p], hqq = H[q * 16 + q], hpq = H[p * 16 + q];
-                    if (fabs(hpq) > 1e-300) {
-                        const double tau = (hqq - hpp) / (2.0 * hpq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        cs = 1.0 / sqrt(1.0 + t * t);
-                        sn = t * cs;
-                    }
-                }
-                __syncthreads();
-                if (tid < 64) {
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int i = sub + 8 * h2;
-                        const double aip = H[i * 16 + p], aiq = H[i * 16 + q];
-                        H[i * 16 + p] = cs * aip - sn * aiq;
-                        H[i * 16 + q] = sn * aip + cs * aiq;
-                        const double qip = Q[i * 16 + p], qiq = Q[i * 16 + q];
-                        Q[i * 16 + p] = cs * qip - sn * qiq;
-                        Q[i * 16 + q] = sn * qip + cs * qiq;
-                    }
-                }
-                __syncthreads();
-                if (tid < 64) {
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int i = sub + 8 * h2;
-                        const double api = H[p * 16 + i], aqi = H[q * 16 + i];
-                        H[p * 16 + i] = cs * api - sn * aqi;
-                        H[q * 16 + i] = sn * api + cs * aqi;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        if (tid == 0) {                                  // ascending Ritz values
-            for (int a = 0; a < PB; ++a) {
-                int b = a;
-                while (b > 0 && H[ordv[b - 1] * 17] > H[a * 17]) { ordv[b] = ordv[b - 1]; --b; }
-                ordv[b] = a;
-            }
-            for (int j = 0; j < PB; ++j) {
-                theta[j] = H[ordv[j] * 17];
-                for (int i = 0; i < PB; ++i) Qs[i * 16 + j] = Q[i * 16 + ordv[j]];
-            }
-        }
-        __syncthreads();
-        for (int r = tid; r < n; r += 1024) {
-            for (int which = 0; which < 2; ++which) {
-                double* rowp = (which == 0 ? Xc : Wg) + r * PB;
-                double x[PB];
-#pragma unroll
-                for (int i = 0; i < PB; ++i) x[i] = rowp[i];
-#pragma unroll 1
-                for (int j = 0; j < PB; ++j) {
-                    double xs = 0.0;
-#pragma unroll
-                    for (int i = 0; i < PB; ++i) xs += x[i] * Qs[i * 16 + j];
-                    rowp[j] = xs;
-                }
-            }
-        }
-        __syncthreads();
-        {   // residual norms |L x_j - theta_j x_j|: 64 row chunks x 16 columns
-            const int j = tid & 15, ch = tid >> 4;
-            const double th = theta[j];
-            double acc = 0.0;
-            for (int r = ch; r < n; r += 64) {
-                const double d = Wg[r * PB + j] - th * Xc[r * PB + j];
-                acc += d * d;
-            }
-            acc += __shfl_xor(acc, 16, 64);
-            acc += __shfl_xor(acc, 32, 64);
-            if (lane < 16) part[wave * 16 + lane] = acc;
-            __syncthreads();
-            if (tid < PB) {
-                double t = 0.0;
-                for (int w2 = 0; w2 < NW; ++w2) t += part[w2 * 16 + tid];
-                resn[tid] = sqrt(t);
-            }
-            __syncthreads();
-        }
-    };
-    // start block: deterministic pseudo-random entries tied to the atom
-    for (int idx = tid; idx < total; idx += 1024) {
-        const int r = idx >> 4, j = idx & 15;
-        unsigned h = (unsigned)(r * 2654435761u) ^ (unsigned)((j + 11) * 40503u * 2246822519u);
-        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
-        Xc[idx] = (double)(h & 0xFFFFFF) / 8388608.0 - 1.0;
-    }
-    __syncthreads();
-    int code = 3;
-    double prev = 0.0;
-    if (!orthonormalise()) code = 2;
-    for (int it = 0; it < LAP_FSI_MAXIT && code == 3; ++it) {
-        ritz();
-        double worst = 0.0;
-        for (int j = 0; j < want; ++j) worst = fmax(worst, resn[j]);
-        if (worst <= 2e-10) { code = 0; break; }
+            off2 = block_sum(dg ? 0.0 : h * h), dg2 = block_sum(dg ? h * h : 0.0);
+        },
         // a residual that falls too slowly to get there in the iterations left (a long chain: eigenvalues 1e-5 apart) gives up
         // now, not after the 40th filter: the caller's dense route answers such a graph either way
-        if (it >= 3 && (worst >= prev || log(2e-10 / worst) / log(worst / prev) > (double)(LAP_FSI_MAXIT - 1 - it))) break;
-        prev = worst;
-        // Chebyshev filter of degree LAP_FSI_DEG: damp [a, 2], scaled at a0 (Zhou & Saad's recurrence); the three blocks rotate
-        const double a0 = theta[0], b = 2.0 + 1e-9;
-        const double a = fmax(theta[PB - 1], a0 + 1e-4);
-        if (!(a < b - 1e-3)) break;
-        const double e = 0.5 * (b - a), cc = 0.5 * (b + a);
-        double sigma = e / (a0 - cc);
-        const double sigma1 = sigma;
-        for (int idx = tid; idx < total; idx += 1024) Nx[idx] = (lx(Xc, idx) - cc * Xc[idx]) * (sigma1 / e);
-        __syncthreads();
-        { double* t = Yp; Yp = Xc; Xc = Nx; Nx = t; }
-        for (int i = 2; i <= LAP_FSI_DEG; ++i) {
-            const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
-            const double f1 = 2.0 * sigma2 / e, f2 = sigma * sigma2;
-            for (int idx = tid; idx < total; idx += 1024) Nx[idx] = (lx(Xc, idx) - cc * Xc[idx]) * f1 - f2 * Yp[idx];
-            __syncthreads();
-            { double* t = Yp; Yp = Xc; Xc = Nx; Nx = t; }
-            sigma = sigma2;
-        }
-        if (!orthonormalise()) code = 2;
-    }
+        [&](int it, double worst) -> bool {
+            if (it >= 3 && (worst >= prev || log(2e-10 / worst) / log(worst / prev) > (double)(LAP_FSI_MAXIT - 1 - it))) return true;
+            prev = worst;
+            return false;
+        });
     if (code) {
         if (tid == 0) status[g] = code;
         return;
     }
     // merged by eigenvalue: the c zeros, then the Ritz values in ascending order
+    const double* Xc = bk.X;
     for (int k = 1; k < m; ++k) {
         if (k < c) emit(k - 1, [&](int i) { return zr[i] == k ? zn[i] : 0.0; });
         else emit(k - 1, [&](int i) { return Xc[i * PB + k - c]; });

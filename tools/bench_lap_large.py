@@ -5,6 +5,8 @@
   small    the same 128 graphs with the protein left out of the batch (what `mixed` should cost)
   frag2048 16 graphs of 2,048 atoms as fragments of 20 .. 60 atoms
   chain2048 16 graphs of 2,048 atoms as ONE chain each (a backbone path with a two-atom side chain at every third atom)
+  fsi800   16 graphs of 800 atoms, a path and 400 random chords each: the small kernel's sparse route, where it converges
+  fsi2048  16 graphs of 2,048 atoms, a path and 900 random chords each: the large kernel's iteration, where it converges
 
 One JSON line per workload: median / min / max ms over --reps calls after --warmup calls (device synchronise around each call)
 and the peak device memory of one call.  Runs on any commit that has graph.laplacian_pe_batched; --tag names the code under
@@ -39,6 +41,13 @@ def chain(n):
     return np.stack([np.concatenate([a, b]), np.concatenate([b, a])])
 
 
+def chords(rs, n, k):
+    """One path over all n atoms and k random chords: a single component, the iteration converges."""
+    pairs = [(i, i + 1) for i in range(n - 1)] + [(int(a), int(b)) for a, b in rs.randint(0, n, (k, 2)) if a != b]
+    a, b = np.asarray(pairs, np.int64).T
+    return np.stack([np.concatenate([a, b]), np.concatenate([b, a])])
+
+
 def collate(graphs, dev):
     off = np.cumsum([0] + [n for n, _ in graphs])
     ei = torch.tensor(np.concatenate([e + o for (_, e), o in zip(graphs, off)], 1), device=dev)
@@ -66,6 +75,8 @@ def main():
         "mixed": pockets[:-1] + [(1200, fragments(rs, 1200, 20, 60))],
         "frag2048": [(2048, fragments(rs, 2048, 20, 60)) for _ in range(16)],
         "chain2048": [(2048, chain(2048)) for _ in range(16)],
+        "fsi800": [(800, chords(rs, 800, 400)) for _ in range(16)],
+        "fsi2048": [(2048, chords(rs, 2048, 900)) for _ in range(16)],
     }
     lines = []
     for name, graphs in work.items():
