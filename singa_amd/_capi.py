@@ -253,6 +253,12 @@ _ANCESTRY_SIGS = {
 }
 ANCESTRY_EXPORTS = tuple(_ANCESTRY_SIGS)
 
+# include/singa_hip_knn_large.h: n1 for molecules of any size (`ops.knn_graph(..., route=...)`); a table of its own
+_KNN_LARGE_SIGS = {
+    "singa_knn_graph_large": ([P, P, P, I32, I32, I32, P, P, P], I32),
+}
+KNN_LARGE_EXPORTS = tuple(_KNN_LARGE_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -261,7 +267,7 @@ def bind(path):
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
-            list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()):
+            list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -25,7 +25,7 @@ from .graph import E_LL, E_LP, E_PL, E_PP, LA, PA
 
 VERSION = 1
 FEAT = 59                                  # atom feature width of the reference's featuriser
-MAX_ATOMS = 2048                           # per graph and node type: the limit of singa_knn_graph
+MAX_ATOMS = 2048                           # per graph and node type: the pack's own limit (its collate kernel); the kNN graph has none
 AXES = ("n_p", "n_l", "e_pp", "e_ll", "e_lp", "e_pl")
 PROPS = ("vina_score", "qed", "sas", "logP", "weight", "tpsa")
 _NODE = ((PA, "p", 0), (LA, "l", 1))                                   # node type, suffix, axis
@@ -130,7 +130,7 @@ class PackedDataset:
     def from_graphs(cls, graphs, names=None, skip_invalid=False, splits=None):
         """Pack an iterable of HeteroGraph.  `names` (default: '0', '1', ...) appear in every refusal.  Refused: a feature
         width other than 59, a token row whose length is not T (the first graph's), an edge index outside its graph's
-        range, more than 2048 atoms of one type (singa_knn_graph refuses those later anyway), an integer that does not
+        range, more than 2048 atoms of one type (the pack is the remaining place with this limit), an integer that does not
         fit 32 bits.  skip_invalid=True drops such graphs and counts them in `.skipped` instead (ids in `splits`, which
         index the INPUT sequence, are renumbered and the dropped ones removed)."""
         per, kept_names, kept = [], [], []

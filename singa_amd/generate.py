@@ -18,7 +18,8 @@ every launch, so equal molecules across different `pockets_per_pass` are measure
 whose graphs carry no edge-frame draws (`rot_rand`) has them drawn per pass from torch's global generator.
 
 Out of scope: pockets without a ligand in the pack (the packer refuses such graphs), overlapping the next pass's encoding with
-the current pass's decoding, and graphs above the existing atom limits.
+the current pass's decoding, and graphs above the pack's limit of 2,048 atoms of one type (the kNN graph itself takes any size:
+ops.knn_graph routes molecules above 2,048 atoms to singa_knn_graph_large).
 """
 import time
 

@@ -90,8 +90,9 @@ def to_dense_batch(x, batch, batch_size):
 
 def knn_graph(pos, k, batch, batch_size, dm=None):
     """For every node its k nearest other nodes of the same graph, row = centre (torch_cluster.knn_graph with
-    flow='target_to_source', CP:293,330): the library's kernel singa_knn_graph (one wavefront per centre atom, exact fp32
-    coordinate differences as torch_cluster forms them, ties to the lower index).  Returns a fixed-size [2, N * k] list in
+    flow='target_to_source', CP:293,330): the library's kernels - singa_knn_graph (one wavefront per centre atom, candidates in
+    registers) while no graph has more than 2,048 nodes, singa_knn_graph_large (candidates streamed, k <= 64) above; exact fp32
+    coordinate differences as torch_cluster forms them, ties to the lower index, graphs of any size.  Returns a fixed-size [2, N * k] list in
     which slots that do not exist (graphs with fewer than k+1 nodes, atoms of no graph) hold -1: no data-dependent
     compaction (and no host synchronisation) happens here."""
     dm = dm or DenseMap(batch, batch_size)

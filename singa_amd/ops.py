@@ -428,17 +428,33 @@ def knn_edge_attr(ln, seg_ptr, E0, n_real, offset, coeff):
     return out
 
 
-def knn_graph(pos, k, batch, ptr, max_nodes):
+KNN_SMALL_MAX = 2048                       # atoms per molecule up to which singa_knn_graph holds the candidates in registers
+KNN_LARGE_MAX_K = 64                       # singa_knn_graph_large: the k-best list is one key per lane
+
+
+def knn_graph(pos, k, batch, ptr, max_nodes, route=None):
     """n1: torch_cluster.knn_graph(pos, k, batch, flow='target_to_source') (CP:293,330) -> [2, N * k] int64, row = centre,
-    -1 where a slot does not exist (singa_knn_graph).  batch ids outside [0, len(ptr) - 1) = atoms of no molecule."""
+    -1 where a slot does not exist.  batch ids outside [0, len(ptr) - 1) = atoms of no molecule.  route: None = singa_knn_graph
+    for molecules of up to 2,048 atoms (max_nodes) and singa_knn_graph_large, which streams the candidates and takes any size
+    with k <= 64, above that; "small" / "large" force one of the two (the same integers wherever both accept the batch)."""
+    if route not in (None, "small", "large"):
+        raise ValueError(f"knn_graph: route must be None, 'small' or 'large', not {route!r}")
+    large = route == "large" or (route is None and int(max_nodes) > KNN_SMALL_MAX)
+    if large and not 1 <= int(k) <= KNN_LARGE_MAX_K:
+        raise ValueError(f"knn_graph: k = {int(k)}, but molecules of more than {KNN_SMALL_MAX} atoms (here up to {int(max_nodes)}) "
+                         f"take the streaming kernel, whose limit is 1 <= k <= {KNN_LARGE_MAX_K}")
     pos = pos.detach().to(torch.float32).contiguous()
     b32 = batch.to(torch.int32).contiguous()
     _dev(pos, b32)
     p64 = ptr.to(device=pos.device, dtype=torch.int64).contiguous()
     N = pos.shape[0]
     out = torch.empty(2, N * k, dtype=torch.int64, device=pos.device)
-    _chk(_lib.lib().singa_knn_graph(_p(pos), _p(b32), _p(p64), p64.numel() - 1, N, int(k), int(max_nodes), _p(out[0]), _p(out[1]),
-                                    _stream()), "singa_knn_graph")
+    if large:
+        _chk(_lib.lib().singa_knn_graph_large(_p(pos), _p(b32), _p(p64), p64.numel() - 1, N, int(k), _p(out[0]), _p(out[1]),
+                                              _stream()), "singa_knn_graph_large")
+    else:
+        _chk(_lib.lib().singa_knn_graph(_p(pos), _p(b32), _p(p64), p64.numel() - 1, N, int(k), int(max_nodes), _p(out[0]),
+                                        _p(out[1]), _stream()), "singa_knn_graph")
     return out
 
 
