@@ -259,6 +259,14 @@ _KNN_LARGE_SIGS = {
 }
 KNN_LARGE_EXPORTS = tuple(_KNN_LARGE_SIGS)
 
+# include/singa_hip_lap_xl.h: n2 for graphs of 2,049 .. 32,768 atoms, many workgroups per graph (`ops.lap_pe_xl`, the per-graph
+# routing of graph.laplacian_pe_batched); a table of its own
+_LAP_XL_SIGS = {
+    "singa_lap_pe_xl_work": ([I32, I32], I64),
+    "singa_lap_pe_xl": ([P] * 8 + [I32, I32, I32, P], I32),
+}
+LAP_XL_EXPORTS = tuple(_LAP_XL_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -267,7 +275,8 @@ def bind(path):
             list(_FORCE_SIGS.items()) + list(_SWOR_SIGS.items()) + list(_STREAM_SIGS.items()) + list(_VALENCE_SIGS.items()) + \
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
-            list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()):
+            list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()) + \
+            list(_LAP_XL_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -7895,7 +7895,7 @@ __global__ void __launch_bounds__(512) dec_tile_ffn_kernel(const float* __restri
 
 }  // namespace
 
-// The library's other translation units (singa_knn_large.hip) report through the same thread's last-error text; hidden, no ABI.
+// The library's other translation units (singa_knn_large.hip, singa_lap_xl.hip) report through the same thread's last-error text; hidden, no ABI.
 __attribute__((visibility("hidden"))) int singa_detail_fail(int code, const char* msg) { return fail(code, msg); }
 __attribute__((visibility("hidden"))) int singa_detail_check_launch(const char* what) { return check_launch(what); }
 
@@ -10045,6 +10045,7 @@ int singa_collate_batch(const int32_t* ids, int B, int G, const int64_t* offsets
 
 }  // extern "C"
 
-#ifdef SINGA_EMUL       // one translation unit there; the gfx950 build compiles this file on its own (__graft_entry__.build)
+#ifdef SINGA_EMUL       // one translation unit there; the gfx950 build compiles these files on their own (__graft_entry__.build)
 #include "singa_knn_large.hip"
+#include "singa_lap_xl.hip"     // (its entry points only: they answer "not part of the emulation build")
 #endif

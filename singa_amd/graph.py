@@ -452,9 +452,12 @@ def laplacian_pe_batched(edge_index, batch, num_graphs, k=8):
     alone is one launch, as ever, and a small graph's rows do not depend on what else the batch holds; graphs of 897 .. 2,048
     atoms go to ops.lap_pe_large in one launch over just those graphs (no dense matrix: sparse rows, the zero eigenvalue's
     vectors written per connected component, filtered subspace iteration for the rest); only a graph that kernel gives up on
-    (its status entry: an atom with more than 32 neighbours, no convergence, ...) or one above 2,048 atoms takes the dense
-    route below, in a sub-batch of its own.  A batch with a large graph costs two read-backs more than one without: the
-    sizes of the two launches, and "did any graph give up".  CPU tensors / k > 8: dense Laplacians and one batched
+    (its status entry: an atom with more than 32 neighbours, no convergence, ...) takes the dense route below, in a sub-batch
+    of its own.  Graphs of 2,049 .. 32,768 atoms go to ops.lap_pe_xl in one call over just those graphs (many workgroups per
+    graph, the same sparse rows and null vectors, a filter whose degree follows the Ritz values, so that a single long chain
+    converges); a graph that route gives up on, or one above 32,768 atoms, takes the dense route too.  A batch with a large
+    graph costs two read-backs more than one without: the sizes of the launches, and "did any graph give up"; one with a graph
+    above 2,048 atoms also the read-backs of ops.lap_pe_xl.  CPU tensors / k > 8: dense Laplacians and one batched
     torch.linalg.eigh (padding rows get a unit diagonal above every real eigenvalue (<= 2), so they sort last)."""
     dev = edge_index.device
     n = batch.numel()
@@ -475,17 +478,23 @@ def laplacian_pe_batched(edge_index, batch, num_graphs, k=8):
         return ops.lap_pe(src, dst, eptr, num, start, n, mx, k)
     small = num <= 896
     large = ~small & (num <= 2048)
-    mx_s, mx_l, n_l, e_l = torch.stack([(num * small).max(), (num * large).max(), large.sum(), large[gs].sum()]).tolist()
+    stats = [(num * small).max(), (num * large).max(), large.sum(), large[gs].sum()]
+    xl = None
+    if mx >= ops.LAP_XL_MIN_ATOMS:                       # (a batch without such a graph runs what it always ran)
+        xl = (num >= ops.LAP_XL_MIN_ATOMS) & (num <= ops.LAP_XL_MAX_ATOMS)
+        stats += [(num * xl).max(), xl.sum(), xl[gs].sum()]
+    mx_s, mx_l, n_l, e_l, mx_x, n_x, e_x = (torch.stack(stats).tolist() + [0, 0, 0])[:7]
     # the small graphs: the same launch with the other graphs' sizes set to 0 (a workgroup without atoms returns at once)
     out = ops.lap_pe(src, dst, eptr, num * small, start, n, mx_s, k) if mx_s else torch.empty(n, k, device=dev, dtype=torch.float32)
-    bad = num > 2048
-    if n_l:
-        sel = torch.argsort(~large, stable=True)[:n_l]                             # the large graphs, in batch order
-        esel = torch.argsort(~large[gs], stable=True)[:e_l]                        # their edges, still grouped by graph
-        ecount = (eptr[1:] - eptr[:-1])[sel]
-        eptr_l = torch.cat([ecount.new_zeros(1), ecount.cumsum(0)]).to(torch.int32)
-        _, status = ops.lap_pe_large(src[esel], dst[esel], eptr_l, num[sel], start[sel], n, mx_l, k, out=out)
-        bad[sel] = status != 0
+    bad = num > ops.LAP_XL_MAX_ATOMS
+    for op, which, mx_w, n_w, e_w in ((ops.lap_pe_large, large, mx_l, n_l, e_l), (ops.lap_pe_xl, xl, mx_x, n_x, e_x)):
+        if n_w:
+            sel = torch.argsort(~which, stable=True)[:n_w]                         # this route's graphs, in batch order
+            esel = torch.argsort(~which[gs], stable=True)[:e_w]                    # their edges, still grouped by graph
+            ecount = (eptr[1:] - eptr[:-1])[sel]
+            eptr_w = torch.cat([ecount.new_zeros(1), ecount.cumsum(0)]).to(torch.int32)
+            _, status = op(src[esel], dst[esel], eptr_w, num[sel], start[sel], n, mx_w, k, out=out)
+            bad[sel] = status != 0
     if bool(bad.any()):
         # the graphs left over, as a batch of their own through the dense route
         rows = torch.nonzero(bad[batch]).squeeze(1)

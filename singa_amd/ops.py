@@ -205,6 +205,34 @@ def lap_pe_large(src, dst, eptr, num, start, n_total, mx, k=8, out=None):
     return out, status
 
 
+LAP_XL_MIN_ATOMS, LAP_XL_MAX_ATOMS = 2049, 32768     # singa_lap_pe_xl's range of graph sizes
+
+
+def lap_pe_xl(src, dst, eptr, num, start, n_total, mx, k=8, out=None):
+    """n2 for graphs of 2,049 .. 32,768 atoms (singa_lap_pe_xl: many workgroups per graph, a filter whose degree follows the Ritz
+    values - long single chains converge): the arguments, the encoding and the returns of `lap_pe_large`.  -> (fp32 [n_total, k],
+    int32 status [B]): a graph with status != 0 did not go by the book (include/singa_hip_lap_xl.h lists the reasons; 6 for a graph
+    outside this range of sizes) and NONE of its rows is written.  The call synchronises the stream once per round of component
+    labelling and once per outer iteration (it belongs to preparation, like its caller's read-backs)."""
+    for t in (src, dst, eptr):
+        if not t.is_cuda or t.dtype != torch.int32:
+            raise RuntimeError("lap_pe_xl: CUDA int32 edge arrays (no CPU path)")
+    B = num.numel()
+    dev = src.device
+    _lib.ensure_init(dev.index if dev.index is not None else torch.cuda.current_device())
+    lib = _lib.lib()
+    src, dst, eptr = src.contiguous(), dst.contiguous(), eptr.contiguous()
+    nn, st = num.to(torch.int32).contiguous(), start.to(torch.int32).contiguous()
+    work = torch.empty(max(lib.singa_lap_pe_xl_work(B, mx), 1), device=dev, dtype=torch.float64)
+    if out is None:
+        out = torch.empty(n_total, k, device=dev, dtype=torch.float32)
+    assert out.shape == (n_total, k) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+    status = torch.empty(B, device=dev, dtype=torch.int32)            # the library writes every graph's entry
+    _chk(lib.singa_lap_pe_xl(_p(src), _p(dst), _p(eptr), _p(nn), _p(st), _p(work), _p(out), _p(status), B, mx, k, _stream()),
+         "singa_lap_pe_xl")
+    return out, status
+
+
 def wigner_rows(rot, L, M=2):
     """k2: rot [E,3,3] -> reduced Wigner rows [E, WSZ] (no gradient, EF:485-528)."""
     rot = rot.detach().contiguous().float()

@@ -7,6 +7,9 @@
   chain2048 16 graphs of 2,048 atoms as ONE chain each (a backbone path with a two-atom side chain at every third atom)
   fsi800   16 graphs of 800 atoms, a path and 400 random chords each: the small kernel's sparse route, where it converges
   fsi2048  16 graphs of 2,048 atoms, a path and 900 random chords each: the large kernel's iteration, where it converges
+  chain4096 4 graphs of 4,096 atoms as ONE chain each: above 2,048 atoms (singa_lap_pe_xl, where the code under test has it)
+  chain8192 2 graphs of 8,192 atoms as ONE chain each
+  frag8192 2 graphs of 8,192 atoms as fragments of 20 .. 60 atoms
 
 One JSON line per workload: median / min / max ms over --reps calls after --warmup calls (device synchronise around each call)
 and the peak device memory of one call.  Runs on any commit that has graph.laplacian_pe_batched; --tag names the code under
@@ -61,6 +64,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--only", default=None, help="comma-separated workloads (default: all)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lap_large needs a GPU"
     from singa_amd import graph as G
@@ -77,7 +81,12 @@ def main():
         "chain2048": [(2048, chain(2048)) for _ in range(16)],
         "fsi800": [(800, chords(rs, 800, 400)) for _ in range(16)],
         "fsi2048": [(2048, chords(rs, 2048, 900)) for _ in range(16)],
+        "chain4096": [(4096, chain(4096)) for _ in range(4)],
+        "chain8192": [(8192, chain(8192)) for _ in range(2)],
+        "frag8192": [(8192, fragments(rs, 8192, 20, 60)) for _ in range(2)],
     }
+    if args.only:
+        work = {name: work[name] for name in args.only.split(",")}
     lines = []
     for name, graphs in work.items():
         ei, bt, B = collate(graphs, dev)
