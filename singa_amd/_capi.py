@@ -267,6 +267,14 @@ _LAP_XL_SIGS = {
 }
 LAP_XL_EXPORTS = tuple(_LAP_XL_SIGS)
 
+# include/singa_hip_emlp_bf16.h: the unit forms of the kNN edge MLPs with bf16 operands (`ops.edge_mlp_pair(..., units=...,
+# precision="bf16")`); a table of its own
+_EMLP_BF16_SIGS = {
+    "singa_edge_mlp_bf16_units_fwd": (_UNITS_SIGS["singa_edge_mlp_units_fwd"][0], I32),
+    "singa_edge_mlp_bf16_units_bwd": (_UNITS_SIGS["singa_edge_mlp_units_bwd"][0], I32),
+}
+EMLP_BF16_EXPORTS = tuple(_EMLP_BF16_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -276,7 +284,7 @@ def bind(path):
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
             list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()) + \
-            list(_LAP_XL_SIGS.items()):
+            list(_LAP_XL_SIGS.items()) + list(_EMLP_BF16_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -10048,4 +10048,5 @@ int singa_collate_batch(const int32_t* ids, int B, int G, const int64_t* offsets
 #ifdef SINGA_EMUL       // one translation unit there; the gfx950 build compiles these files on their own (__graft_entry__.build)
 #include "singa_knn_large.hip"
 #include "singa_lap_xl.hip"     // (its entry points only: they answer "not part of the emulation build")
+#include "singa_emlp_bf16.hip"  // (likewise)
 #endif

@@ -236,9 +236,20 @@ def set_precision(module, precision):
             m.precision = precision
 
 
+def set_edge_mlp_precision(module, precision):
+    """The precision of the kNN edge MLPs `weight_k_net` / `weight_v_net` on their kernel path (ops.edge_mlp_pair: "bf16" takes
+    k15e) of every module under `module` that declares `edge_mlp_precision`.  Independent of `set_precision`, which does not
+    touch it; the module path `_edge_mlp` of other geometries follows `precision` as before."""
+    ops.check_precision(precision)
+    for m in module.modules():
+        if hasattr(type(m), "edge_mlp_precision"):
+            m.edge_mlp_precision = precision
+
+
 class MultiHeadAttention(nn.Module):
     """Graph attention over the kNN edges (CP:19-78)."""
     precision = "f32"
+    edge_mlp_precision = "f32"
 
     def __init__(self, hidden_channels, edge_channels, key_channels, num_heads=1, device="cuda"):
         super().__init__()
@@ -273,7 +284,8 @@ class MultiHeadAttention(nn.Module):
         if edges.attr.shape[1] == 64 and self.weight_k_net[0].out_features == 32 and self.weight_v_net[0].out_features == 64:
             W_k, W_v = ops.edge_mlp_pair(edges.attr, (self.weight_k_net[0], self.weight_k_net[2]),
                                          (self.weight_v_net[0], self.weight_v_net[2]),
-                                         units=(edges.unit_a, edges.unit_b))                  # [E, 32], [E, 64]: k15c
+                                         units=(edges.unit_a, edges.unit_b),
+                                         precision=self.edge_mlp_precision)                   # [E, 32], [E, 64]: k15c / k15e
         else:                                    # other widths: the same two MLPs as library GEMMs + the k15d kernel
             W_k = self._edge_mlp(self.weight_k_net, edges.attr)
             W_v = self._edge_mlp(self.weight_v_net, edges.attr)
@@ -580,8 +592,9 @@ class Decoder(nn.Module):
 
 
 class Transformer(nn.Module):
-    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda", precision="f32"):
+    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda", precision="f32", edge_mlp_precision="f32"):
         ops.check_precision(precision)
+        ops.check_precision(edge_mlp_precision)
         super().__init__()
         self.config, self.num_props, self.device = config, num_props, device
         self.encoder = Encoder(config.encoder, protein_atom_feature_dim, device=device)
@@ -589,6 +602,7 @@ class Transformer(nn.Module):
         self.decoder = Decoder(config.decoder, self.num_props, device=device)
         self.projection = Linear(config.hidden_channels, len(config.decoder.smiVoc), bias=False, device=device)
         set_precision(self, precision)
+        set_edge_mlp_precision(self, edge_mlp_precision)
 
     overlap_encoders = os.environ.get("SINGA_OVERLAP_ENCODERS", "1") == "1"      # (0: one stream, lab)
 

@@ -32,15 +32,19 @@ def property_prompt(ligand_data, names):
 
 
 class SINGA(nn.Module):
-    def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32"):
+    def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32", edge_mlp_precision="f32"):
         """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
         depends on it, so checkpoints move freely between the two modes.
         precision: "f32", or "bf16" - the CProMG transformer's real GEMMs (forward, input and weight gradients) round their
         operands to bfloat16 inside the kernel and accumulate in f32 (ops._gemm).  It reaches the transformer only; the
         embedding, every tensor in memory, the optimizer state and the checkpoints are f32 in both settings.
         embedding_precision: "f32", or "bf16" - the same for the GEMMs, real and complex (ops._cgemm), of the embedding's SO(2)
-        convolutions, and for nothing else in the embedding.  The two switches are independent."""
+        convolutions, and for nothing else in the embedding.
+        edge_mlp_precision: "f32", or "bf16" - the transformer's kNN edge MLPs (`weight_k_net` / `weight_v_net`, k15e) round the
+        operands of their matrix products to bfloat16 inside the kernels; bias gradients come from the unrounded values.
+        The three switches are independent."""
         ops.check_precision(precision)
+        ops.check_precision(edge_mlp_precision)
         ops.check_precision(embedding_precision)
         validate_embedding_config(config.embedding)
         super().__init__()
@@ -49,7 +53,8 @@ class SINGA(nn.Module):
         self.embedding = EquivariantEmbedding(config=self.config.embedding, device=self.device, recompute=recompute,
                                               precision=embedding_precision)
         self.model = Transformer(config=self.config.model, protein_atom_feature_dim=self.config.model.featurizer_feat_dim,
-                                 num_props=self.config.train.num_props, device=self.device, precision=precision)
+                                 num_props=self.config.train.num_props, device=self.device, precision=precision,
+                                 edge_mlp_precision=edge_mlp_precision)
 
     def backward_phases(self):
         """Parameter groups in the order their gradients become final in a backward pass: the transformer (it consumes the

@@ -1510,7 +1510,8 @@ class _EdgeMLPPair(torch.autograd.Function):
     backward pass, which recomputes the hidden units and reduces all four parameter gradients itself."""
 
     @staticmethod
-    def forward(ctx, attr, unit_a, unit_b, w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v):
+    def forward(ctx, attr, unit_a, unit_b, bf16, w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v):
+        ctx.bf16 = bf16             # the unit kernels with bf16 operands (k15e, include/singa_hip_emlp_bf16.h); backward follows
         ctx.params = (w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v)
         attr = attr.contiguous()
         fw = [t.contiguous() for t in (w1k, b1k, w2k, b2k, w1v, b1v, w2v, b2v)]      # nn.Linear's own layouts, no copies
@@ -1524,8 +1525,9 @@ class _EdgeMLPPair(torch.autograd.Function):
             unit_a, unit_b = unit_a.contiguous(), unit_b.contiguous()
             _dev(unit_a, unit_b)
             assert unit_a.dtype == unit_b.dtype == torch.int32 and unit_a.shape == unit_b.shape == (E,)
-            _chk(_lib.lib().singa_edge_mlp_units_fwd(_p(attr), _p(unit_a), _p(unit_b), *[_p(t) for t in fw], _p(wk), _p(wv), E, CIN,
-                                                     HK, HV, _stream()), "singa_edge_mlp_units_fwd")
+            what = "singa_edge_mlp_bf16_units_fwd" if bf16 else "singa_edge_mlp_units_fwd"
+            _chk(getattr(_lib.lib(), what)(_p(attr), _p(unit_a), _p(unit_b), *[_p(t) for t in fw], _p(wk), _p(wv), E, CIN, HK, HV,
+                                           _stream()), what)
             ctx.save_for_backward(attr, fw[0], fw[1], fw[2], fw[4], fw[5], fw[6], unit_a, unit_b)
             return wk, wv
         _chk(_lib.lib().singa_edge_mlp_fwd(_p(attr), *[_p(t) for t in fw], _p(wk), _p(wv), E, CIN, HK, HV, _stream()),
@@ -1539,8 +1541,8 @@ class _EdgeMLPPair(torch.autograd.Function):
         units = [_p(t) for t in ctx.saved_tensors[7:]]
         E, CIN = attr.shape
         lib = _lib.lib()
-        bwd, what = (lib.singa_edge_mlp_units_bwd, "singa_edge_mlp_units_bwd") if ctx.units else \
-            (lib.singa_edge_mlp_bwd, "singa_edge_mlp_bwd")
+        what = ("singa_edge_mlp_bf16_units_bwd" if ctx.bf16 else "singa_edge_mlp_units_bwd") if ctx.units else "singa_edge_mlp_bwd"
+        bwd = getattr(lib, what)
         grads = []
         for g, w1t, b1, w2, params in ((gk, w1tk, b1k, w2k, ctx.params[:4]), (gv, w1tv, b1v, w2v, ctx.params[4:])):
             g = g.contiguous()
@@ -1551,7 +1553,7 @@ class _EdgeMLPPair(torch.autograd.Function):
             o1, o2, o3 = H * CIN, H * CIN + H, H * CIN + H + H * H
             gs = param_colsum(part, [(0, o1, params[0]), (o1, H, params[1]), (o2, H * H, params[2]), (o3, H, params[3])])
             grads += [gs[0].view(H, CIN) if gs[0] is not None else None, gs[1], gs[2].view(H, H) if gs[2] is not None else None, gs[3]]
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
 # k15c once per undirected edge when the caller names the units (`KnnEdges.unit_a / unit_b`); False: every directed row, as
@@ -1559,11 +1561,16 @@ class _EdgeMLPPair(torch.autograd.Function):
 USE_EDGE_UNITS = True
 
 
-def edge_mlp_pair(attr, k_net, v_net, units=None):
+def edge_mlp_pair(attr, k_net, v_net, units=None, precision="f32"):
     """k_net / v_net: (first Linear, second Linear) of `weight_k_net` / `weight_v_net`.  units: (unit_a, unit_b) int32 [E] of
-    include/singa_hip_units.h - every row of attr is named once, and a unit's two rows hold the same attributes."""
-    unit_a, unit_b = units if units is not None and USE_EDGE_UNITS else (None, None)
-    return _EdgeMLPPair.apply(attr, unit_a, unit_b, k_net[0].weight, k_net[0].bias, k_net[1].weight, k_net[1].bias,
+    include/singa_hip_units.h - every row of attr is named once, and a unit's two rows hold the same attributes.
+    precision: "bf16" - every operand of the nets' matrix products is rounded to bf16 inside the kernels (k15e), forward and
+    both backward launches; only the unit form is built, so it needs `units`."""
+    check_precision(precision)
+    if precision == "bf16" and units is None:
+        raise ValueError('edge_mlp_pair: precision="bf16" is built for the unit form only - pass units=(unit_a, unit_b)')
+    unit_a, unit_b = units if units is not None and (USE_EDGE_UNITS or precision == "bf16") else (None, None)
+    return _EdgeMLPPair.apply(attr, unit_a, unit_b, precision == "bf16", k_net[0].weight, k_net[0].bias, k_net[1].weight, k_net[1].bias,
                               v_net[0].weight, v_net[0].bias, v_net[1].weight, v_net[1].bias)
 
 

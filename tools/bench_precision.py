@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""What `SINGA(..., precision="bf16")` and `SINGA(..., embedding_precision="bf16")` change in time, on the GPU only.
+"""What `SINGA(..., precision="bf16")`, `SINGA(..., embedding_precision="bf16")` and `SINGA(..., edge_mlp_precision="bf16")` change
+in time, on the GPU only.
 
   steps    BASELINE configs[2] (cfg3_b128_l4) built as bench.py builds it (bucketed HIP-graph replay over `--distinct-batches`
            resident batches), the flag off and on ALTERNATED (off, on, off, on, ... `--rounds` times, a fresh model / engine
@@ -14,7 +15,10 @@
            same way through singa_cgemm3m_f32 and singa_cgemm_bf16; their tile is 128 rows x 64 complex columns.
 
   --embedding-precision bf16 switches the embedding's SO(2) convolutions as well (both parts); --settings P/E,P/E,... alternates
-  the steps part over (precision, embedding precision) pairs instead of over --precisions.
+  the steps part over (precision, embedding precision[, edge-MLP precision]) settings instead of over --precisions;
+  --edge-mlp-precision bf16 switches the kNN edge MLPs (k15e) in the steps part without --settings.
+  emlp     the three edge-MLP launches (forward, backward of the key and of the value net) in f32-units and bf16-units form on a
+           synthetic unit list of `--emlp-rows` rows of which every two are mates, ALTERNATED `--rounds` times: median per launch.
 
     python tools/bench_precision.py [--part steps|kernels|all] [--workload cfg3_b128_l4] [--embedding-precision bf16] [--out FILE.jsonl]
 """
@@ -34,7 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_recompute import emit, make_batches, per_launch_ms  # noqa: E402
 
 
-def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f32"):
+def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f32", edge_mlp_precision="f32"):
     import gc
     import bench
     from singa_amd.config import load_config
@@ -45,7 +49,7 @@ def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f
     gc.collect()
     torch.cuda.empty_cache()
     torch.manual_seed(cfg.train.seed)
-    model = SINGA(cfg, device=dev, precision=precision, embedding_precision=embedding_precision)
+    model = SINGA(cfg, device=dev, precision=precision, embedding_precision=embedding_precision, edge_mlp_precision=edge_mlp_precision)
     model.train()
     opt = Adam(model.parameters(), lr=cfg.train.optimizer.lr, betas=(cfg.train.optimizer.beta1, cfg.train.optimizer.beta2))
     engine = TrainStep(model, opt, None, use_graph=True, max_grad_norm=float(cfg.train.max_grad_norm), bucket=True,
@@ -54,7 +58,8 @@ def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f
         engine.step(batches[i % len(batches)])
     torch.cuda.synchronize()
     elapsed, per_step, loss, _ = bench.timed_region(engine, batches, args.steps, False, dev, True)
-    rec = {"kind": "steps", "workload": workload, "precision": precision, "embedding_precision": embedding_precision, "steps": args.steps,
+    rec = {"kind": "steps", "workload": workload, "precision": precision, "embedding_precision": embedding_precision,
+           "edge_mlp_precision": edge_mlp_precision, "steps": args.steps,
            "ms_per_step_median": round(bench.median(per_step), 3), "ms_per_step_min": round(min(per_step), 3),
            "ms_per_step_max": round(max(per_step), 3), "final_loss": round(float(loss.detach()), 6)}
     engine.release()
@@ -71,7 +76,7 @@ def steps_part(args, dev):
         runs = {s: [] for s in args.settings}
         for rnd in range(args.rounds):
             for s in args.settings:
-                rec = run_steps(args.workload, s[0], batches, L, args, dev, s[1])
+                rec = run_steps(args.workload, s[0], batches, L, args, dev, s[1], s[2] if len(s) > 2 else "f32")
                 rec.update(round=rnd)
                 runs[s].append(rec)
                 emit(rec, args.out)
@@ -79,7 +84,7 @@ def steps_part(args, dev):
         for s in args.settings:
             meds = [r["ms_per_step_median"] for r in runs[s]]
             emit({"kind": "settings_summary", "workload": args.workload, "rounds": args.rounds, "precision": s[0],
-                  "embedding_precision": s[1], "ms": statistics.median(meds), "spread_ms": [min(meds), max(meds)],
+                  "embedding_precision": s[1], "edge_mlp_precision": s[2] if len(s) > 2 else "f32", "ms": statistics.median(meds), "spread_ms": [min(meds), max(meds)],
                   "diff_ms_against_first": round(statistics.median(meds) - base, 3),
                   "diff_pct_against_first": round(100.0 * (statistics.median(meds) - base) / base, 2),
                   "wall_s": round(time.perf_counter() - t0, 1)}, args.out)
@@ -87,7 +92,7 @@ def steps_part(args, dev):
     runs = {p: [] for p in args.precisions}
     for rnd in range(args.rounds):
         for precision in args.precisions:
-            rec = run_steps(args.workload, precision, batches, L, args, dev, args.embedding_precision)
+            rec = run_steps(args.workload, precision, batches, L, args, dev, args.embedding_precision, args.edge_mlp_precision)
             rec.update(round=rnd)
             runs[precision].append(rec)
             emit(rec, args.out)
@@ -200,6 +205,42 @@ def kernels_part(args, dev):
     engine.release()
 
 
+def emlp_part(args, dev):
+    """The three k15c / k15e launches on their own: E rows, units (2 u, 2 u + 1), attributes and gradients drawn once."""
+    from singa_amd import ops
+    E = args.emlp_rows
+    g = torch.Generator(device="cpu").manual_seed(0)
+    attr = torch.randn(E // 2, 64, generator=g).repeat_interleave(2, 0).contiguous().to(dev)
+    ua = torch.full((E,), -1, dtype=torch.int32)
+    ub = ua.clone()
+    ua[:E // 2], ub[:E // 2] = torch.arange(0, E, 2, dtype=torch.int32), torch.arange(1, E, 2, dtype=torch.int32)
+    ua, ub = ua.to(dev), ub.to(dev)
+    nets = [[torch.nn.Linear(64, H).to(dev), torch.nn.Linear(H, H).to(dev)] for H in (32, 64)]
+    gk, gv = torch.randn(E, 32, generator=g).to(dev), torch.randn(E, 64, generator=g).to(dev)
+    lib, p, st = ops._lib.lib(), ops._p, ops._stream
+    wk, wv = torch.empty(E, 32, device=dev), torch.empty(E, 64, device=dev)
+    fw = [t.detach() for n in nets for t in (n[0].weight, n[0].bias, n[1].weight, n[1].bias)]
+    parts = [torch.empty(lib.singa_edge_mlp_bwd_nparts(E, H), H * 64 + H + H * H + H, device=dev) for H in (32, 64)]
+
+    def launches(tag):
+        fwd, bwd = getattr(lib, f"singa_edge_mlp{tag}_units_fwd"), getattr(lib, f"singa_edge_mlp{tag}_units_bwd")
+        return {"fwd": lambda: ops._chk(fwd(p(attr), p(ua), p(ub), *[p(t) for t in fw], p(wk), p(wv), E, 64, 32, 64, st()), "fwd"),
+                "bwd_k": lambda: ops._chk(bwd(p(attr), p(ua), p(ub), p(gk), p(fw[0]), p(fw[1]), p(fw[2]), p(parts[0]), E, 64, 32, st()), "bwd"),
+                "bwd_v": lambda: ops._chk(bwd(p(attr), p(ua), p(ub), p(gv), p(fw[4]), p(fw[5]), p(fw[6]), p(parts[1]), E, 64, 64, st()), "bwd")}
+    forms = {"f32": launches(""), "bf16": launches("_bf16")}
+    meds = {(f, k): [] for f in forms for k in forms[f]}
+    for rnd in range(args.rounds):
+        for f in forms:
+            for k, fn in forms[f].items():
+                rec = per_launch_ms(fn, args.launches)
+                meds[f, k].append(rec["median_ms"])
+                emit({"kind": "emlp", "round": rnd, "form": f, "launch": k, "rows": E, "units": E // 2, **rec}, args.out)
+    for k in forms["f32"]:
+        a, b = statistics.median(meds["f32", k]), statistics.median(meds["bf16", k])
+        emit({"kind": "emlp_summary", "launch": k, "rows": E, "f32_ms": a, "f32_spread_ms": [min(meds["f32", k]), max(meds["f32", k])],
+              "bf16_ms": b, "bf16_spread_ms": [min(meds["bf16", k]), max(meds["bf16", k])], "bf16_over_f32": round(b / a, 3)}, args.out)
+
+
 def ops_precision(p):
     if p not in ("f32", "bf16"):
         raise argparse.ArgumentTypeError(p)
@@ -208,7 +249,7 @@ def ops_precision(p):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["steps", "kernels", "all"], default="all")
+    ap.add_argument("--part", choices=["steps", "kernels", "all", "emlp"], default="all")
     ap.add_argument("--workload", default="cfg3_b128_l4")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
@@ -220,12 +261,15 @@ def main():
                     help="steps part: the modes to alternate; one mode alone for a run under a kernel trace")
     ap.add_argument("--embedding-precision", type=ops_precision, default="f32",
                     help="the embedding's SO(2) convolutions (SINGA(..., embedding_precision=...)), in both parts")
+    ap.add_argument("--edge-mlp-precision", type=ops_precision, default="f32",
+                    help="the kNN edge MLPs (SINGA(..., edge_mlp_precision=...)), in the steps part")
+    ap.add_argument("--emlp-rows", type=int, default=3_800_000, help="emlp part: rows of the edge list (config 3's protein encoder)")
     ap.add_argument("--settings", type=lambda v: [tuple(ops_precision(p) for p in s.split("/")) for s in v.split(",")], default=None,
-                    help="steps part: precision/embedding-precision pairs to alternate, e.g. f32/f32,bf16/f32,f32/bf16,bf16/bf16; "
-                         "differences are reported against the first")
+                    help="steps part: precision/embedding-precision[/edge-MLP-precision] settings to alternate, e.g. "
+                         "f32/f32,bf16/f32,f32/bf16,bf16/bf16 or f32/f32/f32,f32/f32/bf16; differences are reported against the first")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert not args.settings or all(len(s) == 2 for s in args.settings), "--settings takes precision/embedding-precision pairs"
+    assert not args.settings or all(len(s) in (2, 3) for s in args.settings), "--settings takes two or three precisions per setting"
     assert args.launches >= 50, "per-launch medians over at least 50 launches"
     import __graft_entry__
     __graft_entry__.build()
@@ -235,6 +279,8 @@ def main():
         sha = hashlib.sha256(f.read()).hexdigest()[:16]
     emit({"kind": "run", "device": torch.cuda.get_device_name(0), "lib_sha256": sha, "part": args.part, "workload": args.workload,
           "distinct_batches": args.distinct_batches, "growth": args.growth}, args.out)
+    if args.part == "emlp":
+        emlp_part(args, dev)
     if args.part in ("kernels", "all"):
         kernels_part(args, dev)
     if args.part in ("steps", "all"):

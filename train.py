@@ -90,6 +90,10 @@ def main():
     ap.add_argument("--embedding-precision", choices=["f32", "bf16"], default="f32",
                     help="bf16: the same for the GEMMs of the equivariant embedding's SO(2) convolutions, real (m = 0) and complex "
                          "(m > 0), and for nothing else in the embedding; independent of --precision")
+    ap.add_argument("--edge-mlp-precision", choices=["f32", "bf16"], default="f32",
+                    help="bf16: the transformer's kNN edge MLPs (weight_k_net / weight_v_net, once per undirected edge) round the "
+                         "operands of their matrix products to bfloat16 inside the kernels (include/singa_hip_emlp_bf16.h); their "
+                         "outputs, bias gradients and everything in memory stay f32; independent of the other two switches")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
 
@@ -148,12 +152,15 @@ def main():
             gs = [G.synthetic_graph(base + i) for i in range(lo, hi)]
         return G.collate(gs).to(dev)
 
-    model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision, embedding_precision=args.embedding_precision)
+    model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision, embedding_precision=args.embedding_precision,
+                  edge_mlp_precision=args.edge_mlp_precision)
     log(f"precision {args.precision}: the transformer's real GEMMs take " +
         ("bf16 operands with f32 accumulation" if args.precision == "bf16" else "f32 operands"))
     if args.embedding_precision != "f32":
         log(f"embedding precision {args.embedding_precision}: the SO(2) convolutions' real and complex GEMMs take bf16 operands "
             "with f32 accumulation")
+    if args.edge_mlp_precision != "f32":
+        log(f"edge MLPs in {args.edge_mlp_precision}: the kNN edge MLPs' matrix products take bf16 operands with f32 accumulation")
     if args.no_dropout:
         model.model.decoder.pos_emb.dropout.p = 0.0
     o = cfg.train.optimizer
