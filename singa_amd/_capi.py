@@ -275,6 +275,14 @@ _EMLP_BF16_SIGS = {
 }
 EMLP_BF16_EXPORTS = tuple(_EMLP_BF16_SIGS)
 
+# include/singa_hip_attn_bf16.h: the dense attention core with bf16 operands (`ops.attention(..., precision="bf16")`), with or
+# without a tile map; a table of its own
+_ATTN_BF16_SIGS = {
+    "singa_attn_bf16_fwd": (_ATTN_TILES_SIGS["singa_attn_tiled_fwd"][0], I32),
+    "singa_attn_bf16_bwd": (_ATTN_TILES_SIGS["singa_attn_tiled_bwd"][0], I32),
+}
+ATTN_BF16_EXPORTS = tuple(_ATTN_BF16_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -284,7 +292,7 @@ def bind(path):
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
             list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()) + \
-            list(_LAP_XL_SIGS.items()) + list(_EMLP_BF16_SIGS.items()):
+            list(_LAP_XL_SIGS.items()) + list(_EMLP_BF16_SIGS.items()) + list(_ATTN_BF16_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

@@ -246,6 +246,17 @@ def set_edge_mlp_precision(module, precision):
             m.edge_mlp_precision = precision
 
 
+def set_attention_precision(module, precision):
+    """The precision of the dense attention core (ops.attention: "bf16" takes k19b, forward and backward, under the same masks and
+    tile maps) of every module under `module` that declares `attention_precision`: the decoder's self- and cross-attention and
+    the ligand -> protein attention.  Independent of the other switches; the generic branch of other head geometries and the
+    decoder step kernels of generation do not look at it."""
+    ops.check_precision(precision)
+    for m in module.modules():
+        if hasattr(type(m), "attention_precision"):
+            m.attention_precision = precision
+
+
 class MultiHeadAttention(nn.Module):
     """Graph attention over the kNN edges (CP:19-78)."""
     precision = "f32"
@@ -326,7 +337,7 @@ def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels, 
         else:
             q_s, k_s, v_s = module.W_Q(Q), module.W_K(K), module.W_V(V)
         context = ops.attention(q_s.view(B, -1, heads, dk), k_s.view(B, -1, heads, dk), v_s.view(B, -1, heads, dv), attn_mask,
-                                scale, heads, token_major=True, tiles=tiles)
+                                scale, heads, token_major=True, tiles=tiles, precision=module.attention_precision)
         return ops.layer_norm_residual(module.linear(context.view(B, -1, hidden_channels)), Q, module.layer_norm)
     q_s = module.W_Q(Q).view(B, -1, heads, dk).transpose(1, 2)
     k_s = module.W_K(K).view(B, -1, heads, dk).transpose(1, 2)
@@ -342,6 +353,7 @@ def _dense_attention(module, Q, K, V, attn_mask, key_channels, hidden_channels, 
 class MultiHeadAttention2(nn.Module):
     """Dense cross-attention ligand atoms -> protein atoms (CP:81-105)."""
     precision = "f32"
+    attention_precision = "f32"
 
     def __init__(self, hidden_channels, key_channels, num_heads, device="cuda"):
         super().__init__()
@@ -362,6 +374,7 @@ class MultiHeadAttention2(nn.Module):
 class MultiHeadDeAttention(nn.Module):
     """Decoder self / encoder-decoder attention (CP:134-158)."""
     precision = "f32"
+    attention_precision = "f32"
 
     def __init__(self, hidden_channels, key_channels, num_heads, device="cuda"):
         super().__init__()
@@ -592,9 +605,11 @@ class Decoder(nn.Module):
 
 
 class Transformer(nn.Module):
-    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda", precision="f32", edge_mlp_precision="f32"):
+    def __init__(self, config, protein_atom_feature_dim, num_props=None, device="cuda", precision="f32", edge_mlp_precision="f32",
+                 attention_precision="f32"):
         ops.check_precision(precision)
         ops.check_precision(edge_mlp_precision)
+        ops.check_precision(attention_precision)
         super().__init__()
         self.config, self.num_props, self.device = config, num_props, device
         self.encoder = Encoder(config.encoder, protein_atom_feature_dim, device=device)
@@ -603,6 +618,7 @@ class Transformer(nn.Module):
         self.projection = Linear(config.hidden_channels, len(config.decoder.smiVoc), bias=False, device=device)
         set_precision(self, precision)
         set_edge_mlp_precision(self, edge_mlp_precision)
+        set_attention_precision(self, attention_precision)
 
     overlap_encoders = os.environ.get("SINGA_OVERLAP_ENCODERS", "1") == "1"      # (0: one stream, lab)
 

@@ -32,7 +32,8 @@ def property_prompt(ligand_data, names):
 
 
 class SINGA(nn.Module):
-    def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32", edge_mlp_precision="f32"):
+    def __init__(self, config, device="cuda", recompute=False, precision="f32", embedding_precision="f32", edge_mlp_precision="f32",
+                 attention_precision="f32"):
         """recompute: trade time for memory in the embedding's backward pass (EquivariantEmbedding); no parameter or buffer
         depends on it, so checkpoints move freely between the two modes.
         precision: "f32", or "bf16" - the CProMG transformer's real GEMMs (forward, input and weight gradients) round their
@@ -42,8 +43,12 @@ class SINGA(nn.Module):
         convolutions, and for nothing else in the embedding.
         edge_mlp_precision: "f32", or "bf16" - the transformer's kNN edge MLPs (`weight_k_net` / `weight_v_net`, k15e) round the
         operands of their matrix products to bfloat16 inside the kernels; bias gradients come from the unrounded values.
-        The three switches are independent."""
+        attention_precision: "f32", or "bf16" - the transformer's dense attention core (decoder self- and cross-attention, ligand ->
+        protein attention; k19b) rounds q, k, v, the context gradient, the probabilities and dS to bfloat16 on the way into the
+        matrix cores; softmax, row sums and every tensor in memory stay f32.
+        The four switches are independent."""
         ops.check_precision(precision)
+        ops.check_precision(attention_precision)
         ops.check_precision(edge_mlp_precision)
         ops.check_precision(embedding_precision)
         validate_embedding_config(config.embedding)
@@ -54,7 +59,7 @@ class SINGA(nn.Module):
                                               precision=embedding_precision)
         self.model = Transformer(config=self.config.model, protein_atom_feature_dim=self.config.model.featurizer_feat_dim,
                                  num_props=self.config.train.num_props, device=self.device, precision=precision,
-                                 edge_mlp_precision=edge_mlp_precision)
+                                 edge_mlp_precision=edge_mlp_precision, attention_precision=attention_precision)
 
     def backward_phases(self):
         """Parameter groups in the order their gradients become final in a backward pass: the transformer (it consumes the

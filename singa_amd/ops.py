@@ -1328,7 +1328,8 @@ class _Attention(torch.autograd.Function):
     projection's backward takes them without a copy."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, scale, heads, token_major, tile_rows=None, tile_cols=None):
+    def forward(ctx, q, k, v, mask, scale, heads, token_major, tile_rows=None, tile_cols=None, bf16=False):
+        ctx.bf16 = bf16             # k19b (include/singa_hip_attn_bf16.h): bf16 operands, with or without a tile map; backward follows
         assert mask.dtype == torch.bool and mask.dim() == 3 and mask.stride(2) == 1 and mask.is_cuda
         if token_major:
             B, T, _, DK = q.shape
@@ -1347,7 +1348,14 @@ class _Attention(torch.autograd.Function):
         assert mask.shape[0] * heads == BH and mask.shape[2] == S and mask.shape[1] in (1, T)
         ctx.mst = 0 if mask.shape[1] == 1 else mask.stride(1)
         lse = torch.empty(BH, T, 2, device=q.device, dtype=torch.float32)       # (row maximum, 1 / row sum)
-        if tile_rows is None:
+        if bf16:
+            if tile_rows is not None:
+                _check_tiles(tile_rows, tile_cols, mask.shape[0], T, S)
+            _chk(_lib.lib().singa_attn_bf16_fwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), BH, T, S,
+                                                heads, DK, DV, int(token_major), lq, lk, lv, scale,
+                                                _p(tile_rows) if tile_rows is not None else None, _stream()), "singa_attn_bf16_fwd")
+            ctx.save_for_backward(q, k, v, mask, out, lse, *([] if tile_rows is None else [tile_rows, tile_cols]))
+        elif tile_rows is None:
             _chk(_lib.lib().singa_attn_fwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), BH, T, S, heads,
                                            DK, DV, int(token_major), lq, lk, lv, scale, _stream()), "singa_attn_fwd")
             ctx.save_for_backward(q, k, v, mask, out, lse)
@@ -1389,11 +1397,16 @@ class _Attention(torch.autograd.Function):
         else:
             (gq,), (gk,), (gv,) = like([q]), like([k]), like([v])
         if ctx.tm:
-            lq, lk, lv = gq.stride(1), gk.stride(1), gv.stride(1)
-            # the kernels address the gradients with the operands' pitches: they agree by construction
-            assert (lq, lk, lv) == (q.stride(1), k.stride(1), v.stride(1))
+            # the kernels address the gradients with the pitches the forward read the operands with: they agree by construction
+            # (not q.stride(1): the stride torch reports for a one-token operand is arbitrary, and _tok_view did not use it)
+            assert (gq.stride(1), gk.stride(1), gv.stride(1)) == (lq, lk, lv)
         dsum = torch.empty(BH, T, device=q.device, dtype=torch.float32)
-        if tiles:
+        if ctx.bf16:
+            _chk(_lib.lib().singa_attn_bf16_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g),
+                                                _p(gq), _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk,
+                                                lv, ctx.scale, _p(tiles[0]) if tiles else None, _p(tiles[1]) if tiles else None,
+                                                _stream()), "singa_attn_bf16_bwd")
+        elif tiles:
             _chk(_lib.lib().singa_attn_tiled_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g),
                                                  _p(gq), _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk,
                                                  lv, ctx.scale, _p(tiles[0]), _p(tiles[1]), _stream()), "singa_attn_tiled_bwd")
@@ -1401,7 +1414,7 @@ class _Attention(torch.autograd.Function):
             _chk(_lib.lib().singa_attn_bwd(_p(q), _p(k), _p(v), _p(mask), mask.stride(0), ctx.mst, _p(out), _p(lse), _p(g), _p(gq),
                                            _p(gk), _p(gv), _p(dsum), BH, T, S, ctx.heads, DK, DV, int(ctx.tm), lq, lk, lv, ctx.scale,
                                            _stream()), "singa_attn_bwd")
-        return gq, gk, gv, None, None, None, None, None, None
+        return gq, gk, gv, None, None, None, None, None, None, None
 
 
 def _tile_shapes(B, T, S):
@@ -1429,14 +1442,19 @@ def attn_tiles(mask, T, S):
     return rows, cols
 
 
-def attention(q, k, v, mask, scale, heads, token_major=False, tiles=None):
+def attention(q, k, v, mask, scale, heads, token_major=False, tiles=None, precision="f32"):
     """Dense attention core (k19) for q[B*heads,T,32], k[B*heads,S,32], v[B*heads,S,64] - or, token_major, q[B,T,heads,32],
     k[B,S,heads,32], v[B,S,heads,64] (dense, or column blocks of a fused projection output) -> context in the same layout
     - and a boolean mask [B, T|1, S].  tiles: `attn_tiles(mask, T, S)` of the same mask - the kernels then skip the score
-    tiles that are masked in every element; the result is the same."""
-    if tiles is None:
+    tiles that are masked in every element; the result is the same.
+    precision: "bf16" - every operand of the five matrix products (q, k, v, dO, the probabilities, dS) is rounded to bf16 inside
+    the kernels (k19b, include/singa_hip_attn_bf16.h), forward and both backward passes, with or without `tiles`; softmax,
+    sums and every tensor in memory stay f32."""
+    check_precision(precision)
+    tile_rows, tile_cols = tiles if tiles is not None else (None, None)
+    if precision == "f32" and tiles is None:
         return _Attention.apply(q, k, v, mask, scale, heads, token_major)
-    return _Attention.apply(q, k, v, mask, scale, heads, token_major, tiles[0], tiles[1])
+    return _Attention.apply(q, k, v, mask, scale, heads, token_major, tile_rows, tile_cols, precision == "bf16")
 
 
 class _LayerNorm256(torch.autograd.Function):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""What `SINGA(..., precision="bf16")`, `SINGA(..., embedding_precision="bf16")` and `SINGA(..., edge_mlp_precision="bf16")` change
-in time, on the GPU only.
+"""What `SINGA(..., precision="bf16")`, `SINGA(..., embedding_precision="bf16")`, `SINGA(..., edge_mlp_precision="bf16")` and
+`SINGA(..., attention_precision="bf16")` change in time, on the GPU only.
 
   steps    BASELINE configs[2] (cfg3_b128_l4) built as bench.py builds it (bucketed HIP-graph replay over `--distinct-batches`
            resident batches), the flag off and on ALTERNATED (off, on, off, on, ... `--rounds` times, a fresh model / engine
@@ -15,10 +15,18 @@ in time, on the GPU only.
            same way through singa_cgemm3m_f32 and singa_cgemm_bf16; their tile is 128 rows x 64 complex columns.
 
   --embedding-precision bf16 switches the embedding's SO(2) convolutions as well (both parts); --settings P/E,P/E,... alternates
-  the steps part over (precision, embedding precision[, edge-MLP precision]) settings instead of over --precisions;
+  the steps part over (precision, embedding precision[, edge-MLP precision[, attention precision]]) settings instead of over
+  --precisions;
   --edge-mlp-precision bf16 switches the kNN edge MLPs (k15e) in the steps part without --settings.
   emlp     the three edge-MLP launches (forward, backward of the key and of the value net) in f32-units and bf16-units form on a
            synthetic unit list of `--emlp-rows` rows of which every two are mates, ALTERNATED `--rounds` times: median per launch.
+  attn     every dense attention launch one step of the workload makes (14 at config 3), recorded from the model itself (the entry
+           points of the f32 core wrapped for one eager step) and timed where it is made, on its own operands, mask and tile map:
+           the f32 entry point against singa_attn_bf16_fwd / _bwd, ALTERNATED `--rounds` times, median per launch.  A backward
+           entry point is its two passes (dQ, then dK / dV) together; run the part under a kernel trace to see them apart
+           (the kernels' names and grids tell the passes and the classes).  One summary line per class and direction; the class
+           is the calling module's: MultiHeadAttention2 is the ligand -> protein attention, MultiHeadDeAttention the decoder's
+           self-attention where its queries are its keys and its cross-attention otherwise.
 
     python tools/bench_precision.py [--part steps|kernels|all] [--workload cfg3_b128_l4] [--embedding-precision bf16] [--out FILE.jsonl]
 """
@@ -38,7 +46,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_recompute import emit, make_batches, per_launch_ms  # noqa: E402
 
 
-def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f32", edge_mlp_precision="f32"):
+def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f32", edge_mlp_precision="f32",
+              attention_precision="f32"):
     import gc
     import bench
     from singa_amd.config import load_config
@@ -49,7 +58,8 @@ def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f
     gc.collect()
     torch.cuda.empty_cache()
     torch.manual_seed(cfg.train.seed)
-    model = SINGA(cfg, device=dev, precision=precision, embedding_precision=embedding_precision, edge_mlp_precision=edge_mlp_precision)
+    model = SINGA(cfg, device=dev, precision=precision, embedding_precision=embedding_precision, edge_mlp_precision=edge_mlp_precision,
+                  attention_precision=attention_precision)
     model.train()
     opt = Adam(model.parameters(), lr=cfg.train.optimizer.lr, betas=(cfg.train.optimizer.beta1, cfg.train.optimizer.beta2))
     engine = TrainStep(model, opt, None, use_graph=True, max_grad_norm=float(cfg.train.max_grad_norm), bucket=True,
@@ -59,7 +69,7 @@ def run_steps(workload, precision, batches, L, args, dev, embedding_precision="f
     torch.cuda.synchronize()
     elapsed, per_step, loss, _ = bench.timed_region(engine, batches, args.steps, False, dev, True)
     rec = {"kind": "steps", "workload": workload, "precision": precision, "embedding_precision": embedding_precision,
-           "edge_mlp_precision": edge_mlp_precision, "steps": args.steps,
+           "edge_mlp_precision": edge_mlp_precision, "attention_precision": attention_precision, "steps": args.steps,
            "ms_per_step_median": round(bench.median(per_step), 3), "ms_per_step_min": round(min(per_step), 3),
            "ms_per_step_max": round(max(per_step), 3), "final_loss": round(float(loss.detach()), 6)}
     engine.release()
@@ -76,7 +86,8 @@ def steps_part(args, dev):
         runs = {s: [] for s in args.settings}
         for rnd in range(args.rounds):
             for s in args.settings:
-                rec = run_steps(args.workload, s[0], batches, L, args, dev, s[1], s[2] if len(s) > 2 else "f32")
+                rec = run_steps(args.workload, s[0], batches, L, args, dev, s[1], s[2] if len(s) > 2 else "f32",
+                                s[3] if len(s) > 3 else "f32")
                 rec.update(round=rnd)
                 runs[s].append(rec)
                 emit(rec, args.out)
@@ -84,7 +95,8 @@ def steps_part(args, dev):
         for s in args.settings:
             meds = [r["ms_per_step_median"] for r in runs[s]]
             emit({"kind": "settings_summary", "workload": args.workload, "rounds": args.rounds, "precision": s[0],
-                  "embedding_precision": s[1], "edge_mlp_precision": s[2] if len(s) > 2 else "f32", "ms": statistics.median(meds), "spread_ms": [min(meds), max(meds)],
+                  "embedding_precision": s[1], "edge_mlp_precision": s[2] if len(s) > 2 else "f32",
+                  "attention_precision": s[3] if len(s) > 3 else "f32", "ms": statistics.median(meds), "spread_ms": [min(meds), max(meds)],
                   "diff_ms_against_first": round(statistics.median(meds) - base, 3),
                   "diff_pct_against_first": round(100.0 * (statistics.median(meds) - base) / base, 2),
                   "wall_s": round(time.perf_counter() - t0, 1)}, args.out)
@@ -241,6 +253,74 @@ def emlp_part(args, dev):
               "bf16_ms": b, "bf16_spread_ms": [min(meds["bf16", k]), max(meds["bf16", k])], "bf16_over_f32": round(b / a, 3)}, args.out)
 
 
+def attn_part(args, dev):
+    """The dense attention launches of one eager step, each timed in place through the f32 entry point it takes and through the
+    bf16 one on the same arguments (a null tile map where the step passes none)."""
+    from singa_amd import ops
+    from singa_amd.config import load_config
+    from singa_amd.engine import TrainStep
+    from singa_amd.model.GAN import SINGA
+    from singa_amd.optim import Adam
+    L, batches = make_batches(args.workload, 1, dev)
+    cfg = load_config(lmax=L)
+    torch.manual_seed(cfg.train.seed)
+    model = SINGA(cfg, device=dev)
+    model.train()
+    opt = Adam(model.parameters(), lr=cfg.train.optimizer.lr, betas=(cfg.train.optimizer.beta1, cfg.train.optimizer.beta2))
+    engine = TrainStep(model, opt, None, use_graph=False, max_grad_norm=float(cfg.train.max_grad_norm))
+    engine.step(batches[0])
+    torch.cuda.synchronize()
+    from singa_amd.model.CProMG import MultiHeadAttention2, MultiHeadDeAttention
+    lib, recs, current, by_q = ops._lib.lib(), [], [None], {}
+
+    def entering(module, inputs):                     # the class of the launches this module's forward makes
+        current[0] = "ligand_protein" if isinstance(module, MultiHeadAttention2) else "self" if inputs[0] is inputs[1] else "cross"
+    hooks = [m.register_forward_pre_hook(entering) for m in model.modules() if isinstance(m, (MultiHeadAttention2, MultiHeadDeAttention))]
+    names = {"singa_attn_fwd": ("fwd", 0), "singa_attn_tiled_fwd": ("fwd", 1), "singa_attn_bwd": ("bwd", 0), "singa_attn_tiled_bwd": ("bwd", 2)}
+    inner = {n: getattr(lib, n) for n in names}
+
+    def wrap(name):
+        direction, ntile = names[name]
+        bf = getattr(lib, f"singa_attn_bf16_{direction}")
+
+        def call(*a):
+            stream, core = a[-1], a[:len(a) - 1 - ntile]
+            maps = list(a[len(a) - 1 - ntile:-1]) + [None] * ((1 if direction == "fwd" else 2) - ntile)
+            BH, T, S = (a[8:11] if direction == "fwd" else a[13:16])
+            qp = a[0].value                           # the backward is handed the q its forward saved: same pointer, same class
+            if direction == "fwd":
+                by_q[qp] = current[0]
+            cls = by_q[qp]
+            forms = {"f32": lambda: ops._chk(inner[name](*a), name), "bf16": lambda: ops._chk(bf(*core, *maps, stream), "bf16")}
+            for rnd in range(args.rounds):
+                for f, fn in forms.items():
+                    rec = per_launch_ms(fn, args.launches)
+                    recs.append((cls, direction, f, rec["median_ms"]))
+                    emit({"kind": "attn", "round": rnd, "class": cls, "launch": direction, "form": f, "BH": BH, "T": T, "S": S,
+                          "tiled": ntile > 0, **rec}, args.out)
+            return inner[name](*a)                    # last: the step goes on with the f32 results
+        return call
+
+    for n in names:
+        setattr(lib, n, wrap(n))
+    try:
+        engine.step(batches[0])
+        torch.cuda.synchronize()
+    finally:
+        for n in names:
+            setattr(lib, n, inner[n])
+        for h in hooks:
+            h.remove()
+    for cls, direction in sorted({(r[0], r[1]) for r in recs}):
+        per = {f: [r[3] for r in recs if r[:3] == (cls, direction, f)] for f in ("f32", "bf16")}
+        n = len(per["f32"]) // args.rounds
+        a, b = statistics.median(per["f32"]), statistics.median(per["bf16"])
+        emit({"kind": "attn_summary", "class": cls, "launch": direction, "launches_per_step": n, "f32_ms": a,
+              "f32_spread_ms": [min(per["f32"]), max(per["f32"])], "bf16_ms": b, "bf16_spread_ms": [min(per["bf16"]), max(per["bf16"])],
+              "bf16_over_f32": round(b / a, 3)}, args.out)
+    engine.release()
+
+
 def ops_precision(p):
     if p not in ("f32", "bf16"):
         raise argparse.ArgumentTypeError(p)
@@ -249,7 +329,7 @@ def ops_precision(p):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["steps", "kernels", "all", "emlp"], default="all")
+    ap.add_argument("--part", choices=["steps", "kernels", "all", "emlp", "attn"], default="all")
     ap.add_argument("--workload", default="cfg3_b128_l4")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
@@ -265,11 +345,11 @@ def main():
                     help="the kNN edge MLPs (SINGA(..., edge_mlp_precision=...)), in the steps part")
     ap.add_argument("--emlp-rows", type=int, default=3_800_000, help="emlp part: rows of the edge list (config 3's protein encoder)")
     ap.add_argument("--settings", type=lambda v: [tuple(ops_precision(p) for p in s.split("/")) for s in v.split(",")], default=None,
-                    help="steps part: precision/embedding-precision[/edge-MLP-precision] settings to alternate, e.g. "
+                    help="steps part: precision/embedding-precision[/edge-MLP-precision[/attention-precision]] settings to alternate, e.g. "
                          "f32/f32,bf16/f32,f32/bf16,bf16/bf16 or f32/f32/f32,f32/f32/bf16; differences are reported against the first")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert not args.settings or all(len(s) in (2, 3) for s in args.settings), "--settings takes two or three precisions per setting"
+    assert not args.settings or all(len(s) in (2, 3, 4) for s in args.settings), "--settings takes two to four precisions per setting"
     assert args.launches >= 50, "per-launch medians over at least 50 launches"
     import __graft_entry__
     __graft_entry__.build()
@@ -281,6 +361,8 @@ def main():
           "distinct_batches": args.distinct_batches, "growth": args.growth}, args.out)
     if args.part == "emlp":
         emlp_part(args, dev)
+    if args.part == "attn":
+        attn_part(args, dev)
     if args.part in ("kernels", "all"):
         kernels_part(args, dev)
     if args.part in ("steps", "all"):

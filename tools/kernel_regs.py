@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Register / LDS / spill figures of the gfx950 kernels (compiles the device side to assembly and reads the kernel
-metadata):  python tools/kernel_regs.py [name filter]"""
+metadata):  python tools/kernel_regs.py [name filter [translation units]]
+The translation units are file names under singa_amd/csrc/, comma-separated; singa_hip.hip alone when none is given, e.g.
+    python tools/kernel_regs.py attn singa_hip.hip,singa_attn_bf16.hip"""
 import os
 import re
 import subprocess
@@ -8,10 +10,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = "/tmp/singa_hip_gfx950.s"
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out,
-                       os.path.join(ROOT, "singa_amd", "csrc", "singa_hip.hip")], stderr=subprocess.DEVNULL)
-s = open(out).read()
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
+units = sys.argv[2].split(",") if len(sys.argv) > 2 else ["singa_hip.hip"]
+s = ""
+for src in units:
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out,
+                           os.path.join(ROOT, "singa_amd", "csrc", src)], stderr=subprocess.DEVNULL)
+    s += open(out).read()
 rows = []
 for m in re.finditer(r"- \.agpr_count:\s+(\d+)(.*?)\.wavefront_size", s, re.S):
     body = m.group(0)

@@ -94,6 +94,11 @@ def main():
                     help="bf16: the transformer's kNN edge MLPs (weight_k_net / weight_v_net, once per undirected edge) round the "
                          "operands of their matrix products to bfloat16 inside the kernels (include/singa_hip_emlp_bf16.h); their "
                          "outputs, bias gradients and everything in memory stay f32; independent of the other two switches")
+    ap.add_argument("--attention-precision", choices=["f32", "bf16"], default="f32",
+                    help="bf16: the transformer's dense attention core (decoder self- and cross-attention, ligand -> protein attention) "
+                         "rounds the operands of its matrix products to bfloat16 inside the kernels "
+                         "(include/singa_hip_attn_bf16.h); softmax, sums, outputs and everything in memory stay f32; independent of "
+                         "the other three switches")
     args = ap.parse_args()
     assert args.device.startswith("cuda"), "the hot path is the HIP path: there is no CPU fallback"
 
@@ -153,7 +158,7 @@ def main():
         return G.collate(gs).to(dev)
 
     model = SINGA(cfg, device=dev, recompute=args.recompute, precision=args.precision, embedding_precision=args.embedding_precision,
-                  edge_mlp_precision=args.edge_mlp_precision)
+                  edge_mlp_precision=args.edge_mlp_precision, attention_precision=args.attention_precision)
     log(f"precision {args.precision}: the transformer's real GEMMs take " +
         ("bf16 operands with f32 accumulation" if args.precision == "bf16" else "f32 operands"))
     if args.embedding_precision != "f32":
@@ -161,6 +166,8 @@ def main():
             "with f32 accumulation")
     if args.edge_mlp_precision != "f32":
         log(f"edge MLPs in {args.edge_mlp_precision}: the kNN edge MLPs' matrix products take bf16 operands with f32 accumulation")
+    if args.attention_precision != "f32":
+        log(f"attention in {args.attention_precision}: the dense attention core's matrix products take bf16 operands with f32 accumulation")
     if args.no_dropout:
         model.model.decoder.pos_emb.dropout.p = 0.0
     o = cfg.train.optimizer
