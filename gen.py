@@ -94,6 +94,9 @@ def parse_args(argv=None):
     ap.add_argument("--decoder-tiles", action="store_true",
                     help="every mode: the row-tiled decoder step kernels (16 rows per workgroup, weights read once per tile, a "
                          "pocket of any size) instead of the one-row-per-workgroup ones")
+    ap.add_argument("--decoder-precision", choices=["f32", "bf16"], default="f32",
+                    help="with --decoder-tiles: bf16 multiplies the row-tiled step's weight matrices on the bf16 matrix cores (f32 "
+                         "caches, sums and logits); it implies nothing and is never chosen for you")
     ap.add_argument("--kv-cache", choices=["copy", "ancestry"], default=None,
                     help="distinct, beam selected on the device: how the key / value caches follow the re-ranked rows - copied "
                          "between two buffers (the default), or one buffer read through an ancestry table (same sequences)")
@@ -123,6 +126,8 @@ def parse_args(argv=None):
         ap.error("--kv-cache is about the rows re-ranked on the device: --mode distinct, or --mode beam with --beam-select device "
                  "(or a --grammar)")
     args.kv_cache = args.kv_cache or "copy"
+    if args.decoder_precision == "bf16" and not args.decoder_tiles:
+        ap.error("--decoder-precision bf16 is a form of the row-tiled step: add --decoder-tiles")
     if args.rows_per_pocket is not None and args.mode not in ("sample", "score"):
         ap.error("--rows-per-pocket is continuous sampling: sample and score mode only")
     assert (args.mode == "score") == (args.molecules is not None), "--mode score reads its molecules from --molecules FILE"
@@ -178,7 +183,7 @@ def main():
     per = args.num_samples if args.mode in ("sample", "distinct") else args.num_beams
     decoder = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, grammar=None if args.grammar == "none" else args.grammar,
                    prefix=args.prefix, rows_per_pocket=args.rows_per_pocket, tiles=args.decoder_tiles, beam_select=args.beam_select,
-                   kv_cache=args.kv_cache)
+                   kv_cache=args.kv_cache, decoder_precision=args.decoder_precision)
     out = Output(args.out)
 
     if args.data == "packed":

@@ -283,6 +283,16 @@ _ATTN_BF16_SIGS = {
 }
 ATTN_BF16_EXPORTS = tuple(_ATTN_BF16_SIGS)
 
+# include/singa_hip_dec_bf16.h: the row-tiled decoder step with its weight products on the bf16 matrix cores
+# (`ops.dec_layer_step(..., tiles=True, precision="bf16")`, `KVDecoder(..., precision="bf16")`); a table of its own
+_DEC_BF16_SIGS = {
+    "singa_dec_bf16_pack": ([P, I32, I32, P, P], I32),
+    "singa_dec_bf16_tile_self_attn": ([P] * 10 + [I32, I32, I32, I32, P, F32, P, P], I32),
+    "singa_dec_bf16_tile_cross_attn": (_SIGS["singa_dec_cross_attn"][0], I32),
+    "singa_dec_bf16_tile_ffn": (_SIGS["singa_dec_ffn"][0], I32),
+}
+DEC_BF16_EXPORTS = tuple(_DEC_BF16_SIGS)
+
 
 def bind(path):
     import torch  # noqa: F401  - the HIP runtime bundled with PyTorch must be the one this library resolves against
@@ -292,7 +302,8 @@ def bind(path):
             list(_BEAM_SIGS.items()) + list(_UNITS_SIGS.items()) + list(_PREFIX_SIGS.items()) + list(_DATA_SIGS.items()) + \
             list(_ATTN_TILES_SIGS.items()) + list(_BF16_SIGS.items()) + list(_DEC_TILES_SIGS.items()) + \
             list(_LAP_LARGE_SIGS.items()) + list(_ANCESTRY_SIGS.items()) + list(_KNN_LARGE_SIGS.items()) + \
-            list(_LAP_XL_SIGS.items()) + list(_EMLP_BF16_SIGS.items()) + list(_ATTN_BF16_SIGS.items()):
+            list(_LAP_XL_SIGS.items()) + list(_EMLP_BF16_SIGS.items()) + list(_ATTN_BF16_SIGS.items()) + \
+            list(_DEC_BF16_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         fn.restype = res

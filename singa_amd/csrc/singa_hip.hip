@@ -10050,4 +10050,5 @@ int singa_collate_batch(const int32_t* ids, int B, int G, const int64_t* offsets
 #include "singa_lap_xl.hip"     // (its entry points only: they answer "not part of the emulation build")
 #include "singa_emlp_bf16.hip"  // (likewise)
 #include "singa_attn_bf16.hip"  // (likewise)
+#include "singa_dec_bf16.hip"   // (likewise)
 #endif

@@ -116,7 +116,7 @@ def pocket_uniforms(seed, graph_ids, per, max_length, device):
 # ---------------------------------------------------------------------------------------------------- one decoder call
 def decode(model, voc, example, B, mode, per, prop, max_length, *, device, temperature=1.0, top_k=0, top_p=1.0, grammar=None,
            prefix=None, rows_per_pocket=None, tiles=False, beam_select="host", seed=0, generator=None, uniforms=None, streams=None,
-           molecules=None, kv_cache="copy"):
+           molecules=None, kv_cache="copy", decoder_precision="f32"):
     """One decoder call for the `B` pockets of `example`, as gen.py makes it, and its result as a record of host tensors.
 
     mode "sample": `sample`, or `sample_stream` with `rows_per_pocket`; `per` molecules per pocket from `uniforms`, else
@@ -124,7 +124,8 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
     beam_select="device" or under a `grammar`; `per` beams, the best hypothesis of each pocket.  "score": `score` of
     `molecules[b]`, the strings of pocket b.  `prop`: [B, num_props], one prompt per pocket, or None.  `prefix`: a SMILES
     fragment every sequence starts with.  `kv_cache`: "copy" or "ancestry", the `cache` of `sample_distinct` and
-    `beam_search_device`; ValueError with "ancestry" where no rows are re-ranked on the device.  `max_length` may be None in score mode only (the longest molecule + 2).
+    `beam_search_device`; ValueError with "ancestry" where no rows are re-ranked on the device.  `decoder_precision`: handed to
+    whichever call is made ("bf16" with `tiles=True` only, a ValueError otherwise).  `max_length` may be None in score mode only (the longest molecule + 2).
 
     The record: `mode`, `per` (rows per pocket: 1 in beam mode, the longest list in score mode), `pocket_of` (the pocket of every
     row), `tokens` int64 [rows, L], `lengths`, `sum_logp`, `steps`, `path` where the call reports one, `valid` (uint8, distinct
@@ -141,7 +142,7 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
                          "selected on the device")
     if mode == "score":
         res = score(model, voc, molecules, B, example, prop, device=dev, max_length=max_length, grammar=grammar,
-                    rows_per_pocket=rows_per_pocket, tiles=tiles)
+                    rows_per_pocket=rows_per_pocket, tiles=tiles, decoder_precision=decoder_precision)
         flat = [m for ms in molecules for m in ms]
         L = max_length or max(len(smiles.tokenize(m, voc)) for m in flat) + 2
         tokens = torch.from_numpy(smiles.encode(flat, voc, L, end=True))
@@ -155,7 +156,8 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
     rec = dict(mode=mode, per=per)
     if mode == "sample":
         common = dict(device=dev, temperature=temperature, top_k=top_k, top_p=top_p, suppress=("&", "^"), generator=generator,
-                      uniforms=uniforms, trace=tr, grammar=grammar, forced=forced, tiles=tiles)
+                      uniforms=uniforms, trace=tr, grammar=grammar, forced=forced, tiles=tiles,
+                      decoder_precision=decoder_precision)
         if rows_per_pocket is not None:
             tokens = sample_stream(model, voc, per, B, max_length, example, None if prop is None else prop.to(dev).float(),
                                    rows_per_pocket, **common)
@@ -165,16 +167,17 @@ def decode(model, voc, example, B, mode, per, prop, max_length, *, device, tempe
     elif mode == "distinct":
         tokens = sample_distinct(model, voc, per, B, max_length, example, rows_prop, device=dev, temperature=temperature,
                                  suppress=("&", "^"), grammar=grammar, seed=seed, streams=streams, trace=tr, forced=forced, tiles=tiles,
-                                 cache=kv_cache)
+                                 cache=kv_cache, decoder_precision=decoder_precision)
         rec.update(tokens=tokens.cpu(), lengths=tr["lengths"].cpu(), sum_logp=tr["sum_logp"].cpu(), valid=tr["valid"].cpu(),
                    steps=tr["steps"])
     else:
         on_device = beam_select == "device" or grammar is not None
         if on_device:
             tokens = beam_search_device(model, voc, per, B, max_length, 1, example, rows_prop, device=dev, trace=tr, grammar=grammar,
-                                        forced=forced, tiles=tiles, cache=kv_cache)
+                                        forced=forced, tiles=tiles, cache=kv_cache, decoder_precision=decoder_precision)
         else:
-            tokens = beam_search(model, voc, per, B, max_length, 1, example, rows_prop, device=dev, trace=tr, tiles=tiles)
+            tokens = beam_search(model, voc, per, B, max_length, 1, example, rows_prop, device=dev, trace=tr, tiles=tiles,
+                                 decoder_precision=decoder_precision)
         best = [max(h.beams, key=lambda x: x[0]) for h in tr["hyps"]]         # score = summed log-probability / len ** 0.7
         rec.update(per=1, tokens=tokens.cpu(), lengths=torch.tensor([len(h) for _, h in best], dtype=torch.int64),
                    sum_logp=torch.tensor([s * len(h) ** 0.7 for s, h in best], dtype=torch.float64),

@@ -75,15 +75,21 @@ class KVDecoder:
     graph, captured once per search and replayed per token."""
 
     def __init__(self, decoder, projection, enc_outputs, enc_pad_mask, beams, max_positions, vocab_size, fused=True,
-                 search_buffers=True, tiles=False, ancestry=False):
+                 search_buffers=True, tiles=False, ancestry=False, precision="f32"):
         """search_buffers=False leaves out the beam step's own input / output buffers (`step_in`, `step_out`, `logp`): the
         sampling loop (model/Sampling.py) only uses `token_input` / `prop_input` / `advance`.  `tiles=True`: the fused step is the
         row-tiled one (include/singa_hip_dec_tiles.h), which has no limit on the pocket's size; ValueError, before any launch,
         with `fused=False` or a decoder the step kernels are not built for.  `ancestry=True` (include/singa_hip_ancestry.h): the
         decoder owns an ancestry table `anc` [max_positions, rows] int32 - the identity after `reset` -, `advance` hands it to every
         layer's self-attention, and `follow_ancestry(src)` re-ranks the rows by updating the table: the caches are never moved
-        and no second cache buffer is needed.  The fused step only (ValueError otherwise), one position for all rows."""
+        and no second cache buffer is needed.  The fused step only (ValueError otherwise), one position for all rows.
+        `precision="bf16"` (include/singa_hip_dec_bf16.h; `tiles=True` only, ValueError otherwise): every layer's weight matrices
+        are packed as bf16 once, here, and the row-tiled step multiplies with them on the bf16 matrix cores; the f32 weights stay
+        for everything else, and caches, encoder keys / values and the logits projection keep their type."""
         self.dec, self.proj, self.beams, self.V = decoder, projection, beams, vocab_size
+        self.precision = ops.check_precision(precision)
+        if self.precision == "bf16" and not tiles:
+            raise ValueError("KVDecoder: precision='bf16' is a form of the row-tiled step: tiles=True")
         a0, f0 = decoder.layers[0].dec_self_attn, decoder.layers[0].pos_ffn
         # the step kernels are built for the shipped decoder geometry; anything else takes the library path
         geometry = bool(a0.hidden_channels == 256 and a0.key_channels == 128 and a0.num_heads == 4
@@ -125,6 +131,8 @@ class KVDecoder:
                 "ffn": dict(w1_t=tr(f.conv1.weight[:, :, 0]), b1=f.conv1.bias.detach(), w2_t=tr(f.conv2.weight[:, :, 0]),
                             b2=f.conv2.bias.detach(), gamma=f.layer_norm.weight.detach(), beta=f.layer_norm.bias.detach(),
                             eps=f.layer_norm.eps)})
+            if self.precision == "bf16":
+                ops.dec_bf16_pack_layer(self.w[-1])
         n = len(decoder.layers)
         self.k = torch.zeros(n, self.R, self.heads, max_positions, self.dk, device=dev)
         self.v = torch.zeros(n, self.R, self.heads, max_positions, self.dv, device=dev)
@@ -180,14 +188,15 @@ class KVDecoder:
                 raise ValueError("KVDecoder.advance: one position per row needs the k17 step kernels (fused)")
             for l in range(len(self.dec.layers)):
                 x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], row_pos, self.cross_k[l], self.cross_v[l],
-                                       self.pad_u8, self.beams, per_row=True, tiles=self.tiles)
+                                       self.pad_u8, self.beams, per_row=True, tiles=self.tiles, precision=self.precision)
             return x
         if self.fused:
             # three hand-written launches per layer (singa_dec_*): q/k/v + cache append + attention + projection + LayerNorm,
             # encoder-decoder attention, feed-forward - instead of ~33 library / elementwise launches on 20-row operands
             for l in range(len(self.dec.layers)):
                 x = ops.dec_layer_step(x.contiguous(), self.w[l], k[l], v[l], self.pos, self.cross_k[l],
-                                       self.cross_v[l], self.pad_u8, self.beams, tiles=self.tiles, anc=self.anc)
+                                       self.cross_v[l], self.pad_u8, self.beams, tiles=self.tiles, anc=self.anc,
+                                       precision=self.precision)
             self.pos += 1
             return x
         R, B, H = self.R, self.B, self.heads
@@ -312,13 +321,14 @@ def _select(cand_score, cand_flat, prefixes, hyps, done, num_beams, vocab_size, 
 
 @torch.no_grad()
 def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", trace=None,
-                graph=True, fused=True, tiles=False):
+                graph=True, fused=True, tiles=False, decoder_precision="f32"):
     """BS:38-175.  `model`: SINGA (uses model.model.encoder / decoder / projection); `example`: attribute bag with
     protein_element_batch, protein_atom_feature, protein_pos, protein_atom_laplacian (gen.py:176-181) and, optionally,
     protein_knn (a precomputed [2,E] kNN list; otherwise drawn on the GPU); `prop` [batch_size*num_beams, num_props].
     `graph=False` launches the step's kernels one by one instead of replaying the captured HIP graph (same numbers);
     `fused=False` evaluates the decoder layers with library GEMMs / elementwise ops instead of the k17 step kernels;
-    `tiles=True` evaluates them with the row-tiled step kernels (`KVDecoder`), and `trace["path"]` says which path ran.
+    `tiles=True` evaluates them with the row-tiled step kernels (`KVDecoder`), and `trace["path"]` says which path ran;
+    `decoder_precision="bf16"` (with `tiles=True` only) takes their bf16 matrix-core form (include/singa_hip_dec_bf16.h).
     Returns the decoded int64 token matrix [batch_size*topk, T] on `device`."""
     tf = model.model
     vocab_size = len(smiVoc)
@@ -326,12 +336,14 @@ def beam_search(model, smiVoc, num_beams, batch_size, max_length, topk, example,
     sos, eos, pad = voc.index("&"), voc.index("$"), voc.index("^")
     dev = torch.device(device)
     num = 1 if tf.decoder.num_props else 0
+    from .Sampling import check_decoder_precision, check_tiles
+    check_decoder_precision("beam_search", decoder_precision, tiles)
     if tiles:
-        from .Sampling import check_tiles
         check_tiles("beam_search", tf.decoder, max_length + num, fused)
     enc_outputs, enc_pad_mask = encode_pockets(tf, example, batch_size)
     rows = batch_size * num_beams
-    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_beams, max_length + num, vocab_size, fused, tiles=tiles)
+    kv = KVDecoder(tf.decoder, tf.projection, enc_outputs, enc_pad_mask, num_beams, max_length + num, vocab_size, fused, tiles=tiles,
+                   precision=decoder_precision)
     if graph:
         kv.capture()
     if num:
@@ -387,7 +399,8 @@ BEAM_MAX_K = 1024       # slots per pocket singa_beam_select is built for
 
 @torch.no_grad()
 def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, example, prop=None, device="cuda", grammar=None,
-                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None, tiles=False, cache="copy"):
+                       suppress=(), length_penalty=0.7, graph=True, trace=None, forced=None, tiles=False, cache="copy",
+                       decoder_precision="f32"):
     """`beam_search` with the selection on the device (include/singa_hip_beam.h states the rule: `_select` and `BeamHypotheses`
     as kernels, ties ranked by slot, then token), which can therefore be constrained: `grammar` None, "smiles" or "valence"
     and `suppress` as in `Sampling.sample`.  Under a grammar every stored hypothesis is a string the rule accepts, ended by its
@@ -417,11 +430,14 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
 
     `cache`: "copy" (the default) or "ancestry", as in `Sampling.sample_distinct`: with "ancestry" the caches are one buffer that
     is never moved, the self-attention kernels read a row's past through a table (include/singa_hip_ancestry.h) that
-    `ops.anc_follow` updates, and the step is captured once.  Same result, bit for bit.  Anything else is a ValueError."""
+    `ops.anc_follow` updates, and the step is captured once.  Same result, bit for bit.  Anything else is a ValueError.
+
+    `decoder_precision` as in `Sampling.sample`: "bf16", with `tiles=True` only, is the step of include/singa_hip_dec_bf16.h."""
     from . import Sampling as S
     from .. import smiles
     if cache not in ("copy", "ancestry"):
         raise ValueError(f"beam_search_device: cache is 'copy' or 'ancestry', got {cache!r}")
+    S.check_decoder_precision("beam_search_device", decoder_precision, tiles)
     ancestry = cache == "ancestry"
     if not 1 <= topk <= num_beams <= BEAM_MAX_K:
         raise ValueError(f"beam_search_device: 1 <= topk <= num_beams <= {BEAM_MAX_K} (got topk {topk}, num_beams {num_beams})")
@@ -446,7 +462,7 @@ def beam_search_device(model, smiVoc, num_beams, batch_size, max_length, topk, e
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
-                   tiles=tiles, ancestry=ancestry)
+                   tiles=tiles, ancestry=ancestry, precision=decoder_precision)
     bufs = ((kv.k, kv.v), (kv.k, kv.v) if ancestry else (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     state = {"score": new(rows, torch.float32), "length": new(rows, torch.int32), "tokens": new((rows, T), torch.int64),

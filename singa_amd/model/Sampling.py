@@ -91,6 +91,15 @@ def check_tiles(fn, decoder, positions, fused):
         raise ValueError(f"{fn}: tiles=True needs the shipped decoder geometry and at most 256 positions")
 
 
+def check_decoder_precision(fn, precision, tiles):
+    """`decoder_precision` of `fn` before any device work: "f32" or "bf16" (`ops.check_precision`), and "bf16" - the row-tiled
+    step with its weight products on the bf16 matrix cores, include/singa_hip_dec_bf16.h - is a form of `tiles=True` that is
+    never chosen for the caller: without it a ValueError."""
+    if ops.check_precision(precision) == "bf16" and not tiles:
+        raise ValueError(f"{fn}: decoder_precision='bf16' is a form of the row-tiled step: tiles=True")
+    return precision
+
+
 def _prologue(fn, model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress):
     """What `sample` and `sample_distinct` (`fn`: the caller's name, for the messages) check and work out alike before they
     differ -> (device, transformer, vocabulary, (sos, eos, pad), rows, 1 with a property prompt else 0, cache positions, free
@@ -140,7 +149,7 @@ def _decode(replays, max_steps, live, each=None):
 @torch.no_grad()
 def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0, top_k=0,
            top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, fused=None, trace=None, grammar=None, forced=None,
-           tiles=False):
+           tiles=False, decoder_precision="f32"):
     """`num_samples` sequences for each of the `batch_size` pockets of `example`, drawn token by token from the model's own
     distribution reshaped by `temperature` (0 = greedy), `top_k` (0 = off) and `top_p` (1 = off).
 
@@ -150,7 +159,8 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     `graph=False` launches the step's kernels one by one (same tokens).  `fused`: True = k17 step kernels, False = library
     GEMMs, None = k17 wherever the k17 kernels' limits allow (it is the faster one at every row count measured).  `tiles=True`:
     the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17 - no limit on the pocket's atoms; a ValueError with
-    `fused=False` or another decoder geometry.
+    `fused=False` or another decoder geometry.  `decoder_precision="bf16"` (with `tiles=True` only, a ValueError otherwise): the
+    row-tiled step multiplies with bf16 weights on the bf16 matrix cores (include/singa_hip_dec_bf16.h); never chosen for the caller.
 
     Returns the int64 token matrix [batch_size * num_samples, max_length], pocket-major: a row starts with '&', ends with
     '$' if the model ended it before `max_length`, and is padded with '^'.  `trace`, if a dict, receives `lengths` (int32:
@@ -186,6 +196,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
         if forced.shape[0] != batch_size * num_samples:
             raise ValueError(f"sample: forced has {forced.shape[0]} rows, expected {batch_size * num_samples} (or one per pocket: "
                              f"{batch_size})")
+    check_decoder_precision("sample", decoder_precision, tiles)
     if tiles:
         check_tiles("sample", tf.decoder, positions, fused)
     need = cache_bytes(tf.decoder, rows, positions)
@@ -202,7 +213,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
     uniforms = uniforms.to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), num_samples, positions, len(voc),
-                   fused is None or bool(fused), search_buffers=False, tiles=tiles)
+                   fused is None or bool(fused), search_buffers=False, tiles=tiles, precision=decoder_precision)
     if fused and not kv.fused:
         raise ValueError("sample: fused=True needs the shipped decoder geometry, at most 256 positions and 1024 pocket atoms")
     state = {"tokens": torch.empty(rows, max_length, dtype=torch.int64, device=dev),
@@ -259,7 +270,7 @@ def sample(model, smiVoc, num_samples, batch_size, max_length, example, prop=Non
 
 
 def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda", max_length=None, grammar=None, fused=None,
-          rows_per_pocket=None, tiles=False):
+          rows_per_pocket=None, tiles=False, decoder_precision="f32"):
     """The model's own log-likelihood of given molecules: `molecules[b]` is the list of SMILES strings (or token lists, as
     `smiles.encode` takes them) to score for pocket b of `example`; the lists may differ in length.  Every molecule is one row
     of `sample` with all its columns forced up to and including '$', so a score comes from the same kernels, in the same
@@ -277,7 +288,8 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     the rows, not of the library, and a row that has ended a short molecule starts the pocket's next one.  The same dict comes
     back, bit for bit.  `prop` is then one prompt per pocket ([num_props] or [batch_size, num_props]); a prompt per molecule is
     a ValueError (a row keeps its cache position 0 across molecules), and `fused` is not consulted (the k17 step kernels are
-    that mode's only path).  `tiles`: handed to `sample` / `sample_stream`; with it the returned dict also holds `path`: "tiles"."""
+    that mode's only path).  `tiles`: handed to `sample` / `sample_stream`; with it the returned dict also holds `path`: "tiles".
+    `decoder_precision`: handed on likewise."""
     dev = torch.device(device)
     if dev.type != "cuda" or not example.protein_atom_feature.is_cuda:
         raise RuntimeError("score runs on the GPU only (no CPU fallback): device and the example's tensors must be cuda")
@@ -308,10 +320,10 @@ def score(model, smiVoc, molecules, batch_size, example, prop=None, device="cuda
     uniforms = torch.zeros(max_length, batch_size * per)
     if rows_per_pocket is not None:
         sample_stream(model, smiVoc, per, batch_size, max_length, example, prop, rows_per_pocket, device=device, uniforms=uniforms,
-                      trace=tr, grammar=grammar, forced=forced, tiles=tiles)
+                      trace=tr, grammar=grammar, forced=forced, tiles=tiles, decoder_precision=decoder_precision)
     else:
         sample(model, smiVoc, per, batch_size, max_length, example, prop, device=device, uniforms=uniforms, fused=fused, trace=tr,
-               grammar=grammar, forced=forced, tiles=tiles)
+               grammar=grammar, forced=forced, tiles=tiles, decoder_precision=decoder_precision)
     keys = {"token_logp": "token_logp", "rank": "rank"}
     if grammar is not None:
         keys["allowed_logp"] = "allowed_logp"
@@ -335,7 +347,7 @@ STREAM_MAX_ROWS = 2048  # rows per pocket singa_stream_refill is built for
 @torch.no_grad()
 def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, rows_per_pocket=64, device="cuda",
                   temperature=1.0, top_k=0, top_p=1.0, suppress=(), generator=None, uniforms=None, graph=True, trace=None,
-                  grammar=None, forced=None, tiles=False):
+                  grammar=None, forced=None, tiles=False, decoder_precision="f32"):
     """`sample` on a fixed budget of rows: `num_samples` molecules for each of the `batch_size` pockets of `example`, decoded on
     batch_size * `rows_per_pocket` rows; a row that has ended its molecule ('$', or the last column) starts the pocket's next
     one in the following step, until the pocket has none left (include/singa_hip_stream.h states the rule).  Rows that have
@@ -365,9 +377,10 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
     per-molecule buffers (`forced` and `rank` included) do not fit the free memory.
 
     `tiles=True`: the row-tiled step kernels (include/singa_hip_dec_tiles.h) instead of k17; the limit on the pocket's atoms does
-    not apply to them, and `trace["path"]` says "tiles"."""
+    not apply to them, and `trace["path"]` says "tiles".  `decoder_precision` as in `sample`."""
     dev, tf, voc, (sos, eos, pad), mols, num, positions, free, cls, allowed = _prologue(
         "sample_stream", model, smiVoc, num_samples, batch_size, max_length, example, device, grammar, suppress)
+    check_decoder_precision("sample_stream", decoder_precision, tiles)
     R, V = int(rows_per_pocket), len(voc)
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError(f"sample_stream: temperature >= 0, top_k >= 0, 0 < top_p <= 1 (got {temperature}, {top_k}, {top_p})")
@@ -407,7 +420,7 @@ def sample_stream(model, smiVoc, num_samples, batch_size, max_length, example, p
     uniforms = uniforms.to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), R, positions, V, True, search_buffers=False,
-                   tiles=tiles)
+                   tiles=tiles, precision=decoder_precision)
     if not kv.fused:
         raise ValueError("sample_stream: unsupported decoder geometry for the k17 step kernels")
     i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
@@ -476,7 +489,8 @@ SWOR_MAX_K = 2048       # slots per pocket singa_swor_select is built for
 
 @torch.no_grad()
 def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example, prop=None, device="cuda", temperature=1.0,
-                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None, tiles=False, cache="copy"):
+                    suppress=(), grammar=None, seed=0, streams=None, graph=True, trace=None, forced=None, tiles=False, cache="copy",
+                    decoder_precision="f32"):
     """Up to `num_samples` pairwise DISTINCT sequences for each of the `batch_size` pockets of `example`: a sample without
     replacement from the model's distribution reshaped by `temperature` (> 0), `suppress` and `grammar` ("smiles", as in `sample`;
     "valence" is a ValueError here), by
@@ -513,9 +527,12 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
     prefixes move from one to the other after every token (`ops.swor_follow`), the step is captured once per direction.
     "ancestry" (include/singa_hip_ancestry.h): one buffer that is never moved, a table [positions, rows] int32 names the slot that
     holds each position of a row's prefix, the self-attention kernels gather through it and `ops.anc_follow` updates it - 4 bytes
-    per row and position instead of about 9 KB; one captured step.  Same result, bit for bit.  Anything else is a ValueError."""
+    per row and position instead of about 9 KB; one captured step.  Same result, bit for bit.  Anything else is a ValueError.
+
+    `decoder_precision` as in `sample`."""
     if cache not in ("copy", "ancestry"):
         raise ValueError(f"sample_distinct: cache is 'copy' or 'ancestry', got {cache!r}")
+    check_decoder_precision("sample_distinct", decoder_precision, tiles)
     ancestry = cache == "ancestry"
     if grammar == "valence":
         raise ValueError("sample_distinct: grammar='valence' is unsupported (the selection gathers one state word per row); use "
@@ -550,7 +567,7 @@ def sample_distinct(model, smiVoc, num_samples, batch_size, max_length, example,
         forced = torch.as_tensor(smiles.check_prefix(forced, smiVoc, batch_size, max_length, grammar)).to(dev).contiguous()
 
     kv = KVDecoder(tf.decoder, tf.projection, *encode_pockets(tf, example, batch_size), k, positions, V, True, search_buffers=False,
-                   tiles=tiles, ancestry=ancestry)
+                   tiles=tiles, ancestry=ancestry, precision=decoder_precision)
     bufs = ((kv.k, kv.v), (kv.k, kv.v) if ancestry else (torch.zeros_like(kv.k), torch.zeros_like(kv.v)))
     f32 = dict(dtype=torch.float32, device=dev)
     state = {"gumbel": torch.empty(rows, **f32), "prop_logp": torch.empty(rows, **f32), "sum_logp": torch.empty(rows, **f32),

@@ -894,7 +894,8 @@ def ln_silu(x, gamma, beta, eps=1e-5):
     return _LnSilu.apply(x, gamma, beta, eps)
 
 
-def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, per_row=False, tiles=False, anc=None):
+def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, per_row=False, tiles=False, anc=None,
+                   precision="f32"):
     """One decoder layer for one new position of every beam-search row (k17; inference only, no autograd): three launches.
     `w`: dict of the layer's transposed weights as built by BeamSearch.KVDecoder; k_cache [R,4,P,32], v_cache [R,4,P,64];
     pos: int64 device scalar; cross_k [B,4,32,S], cross_v [B,4,S,64], pad [B,S] uint8.  `pos` of shape [R] (more than one
@@ -902,9 +903,14 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, pe
     include/singa_hip_stream.h, the other two launches do not depend on the position.  `tiles=True`: the three launches are the
     row-tiled ones of include/singa_hip_dec_tiles.h (one workgroup per 16 rows of a pocket, any number of encoder positions).
     `anc`: int32 [P, R] ancestry table (include/singa_hip_ancestry.h states the rule): the self-attention launch of the chosen path
-    is its `_anc` form, which reads cached position p of row r from slot anc[p, r]; ValueError together with `per_row`."""
+    is its `_anc` form, which reads cached position p of row r from slot anc[p, r]; ValueError together with `per_row`.
+    `precision="bf16"` (with `tiles=True` only, ValueError otherwise, before any launch): the three launches are those of
+    include/singa_hip_dec_bf16.h - the products with a weight matrix on the bf16 matrix cores, everything else as the f32 tile
+    kernels have it - and read the packed weights `w[...]["bf16"]` that `dec_bf16_pack_layer` made once."""
     if anc is not None and per_row:
         raise ValueError("dec_layer_step: an ancestry table goes with one position for all rows, not with per_row=True")
+    if check_precision(precision) == "bf16" and not tiles:
+        raise ValueError("dec_layer_step: precision='bf16' is a form of the row-tiled step: tiles=True")
     _dev(x, k_cache, v_cache, cross_k, cross_v)
     lib, st = _lib.lib(), _stream()
     R, P, S = x.shape[0], k_cache.shape[2], cross_v.shape[2]
@@ -915,6 +921,17 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, pe
     _check_views("dec_layer_step", ((anc, torch.int32, (P, R)),))
     self_args = (_p(x), _p(a["wqkv_t"]), _p(a["bqkv"]), _p(a["wo_t"]), _p(a["bo"]), _p(a["gamma"]), _p(a["beta"]), _p(k_cache),
                  _p(v_cache), _p(pos))
+    if tiles and precision == "bf16":
+        pa, pc, pf = a["bf16"], c["bf16"], f["bf16"]
+        _chk(lib.singa_dec_bf16_tile_self_attn(_p(x), _p(pa["wqkv_t"]), _p(a["bqkv"]), _p(pa["wo_t"]), _p(a["bo"]), _p(a["gamma"]),
+                                               _p(a["beta"]), _p(k_cache), _p(v_cache), _p(pos), 1 if per_row else 0, R, beams, P,
+                                               _p(y), a["eps"], _p(anc), st), "singa_dec_bf16_tile_self_attn")
+        _chk(lib.singa_dec_bf16_tile_cross_attn(_p(y), _p(pc["wq_t"]), _p(c["bq"]), _p(cross_k), _p(cross_v), _p(pad), _p(pc["wo_t"]),
+                                                _p(c["bo"]), _p(c["gamma"]), _p(c["beta"]), R, beams, S, _p(z), c["eps"], st),
+             "singa_dec_bf16_tile_cross_attn")
+        _chk(lib.singa_dec_bf16_tile_ffn(_p(z), _p(pf["w1_t"]), _p(f["b1"]), _p(pf["w2_t"]), _p(f["b2"]), _p(f["gamma"]), _p(f["beta"]),
+                                         R, _p(out), f["eps"], st), "singa_dec_bf16_tile_ffn")
+        return out
     if tiles:
         if anc is not None:
             _chk(lib.singa_dec_tile_self_attn_anc(*self_args, 0, R, beams, P, _p(y), a["eps"], _p(anc), st),
@@ -939,6 +956,25 @@ def dec_layer_step(x, w, k_cache, v_cache, pos, cross_k, cross_v, pad, beams, pe
     _chk(lib.singa_dec_ffn(_p(z), _p(f["w1_t"]), _p(f["b1"]), _p(f["w2_t"]), _p(f["b2"]), _p(f["gamma"]), _p(f["beta"]), R, _p(out),
                            f["eps"], st), "singa_dec_ffn")
     return out
+
+
+def dec_bf16_pack(w_t):
+    """w_t [K, N] f32 (a transposed weight matrix, K a multiple of 32, N of 16) -> int16 [K * N]: its values rounded to bf16,
+    ties to even, in the fragment order the step kernels of include/singa_hip_dec_bf16.h read (`singa_dec_bf16_pack`)."""
+    _dev(w_t)
+    _check_views("dec_bf16_pack", ((w_t, torch.float32, None),))
+    K, N = w_t.shape
+    out = torch.empty(K * N, dtype=torch.int16, device=w_t.device)
+    _chk(_lib.lib().singa_dec_bf16_pack(_p(w_t), K, N, _p(out), _stream()), "singa_dec_bf16_pack")
+    return out
+
+
+def dec_bf16_pack_layer(w):
+    """The weight matrices of one layer's dict `w` (as `BeamSearch.KVDecoder` builds it) packed once for
+    `dec_layer_step(..., precision="bf16")`: every sub-block gains the entry "bf16", a dict of its packed matrices."""
+    for block, names in (("self", ("wqkv_t", "wo_t")), ("cross", ("wq_t", "wo_t")), ("ffn", ("w1_t", "w2_t"))):
+        w[block]["bf16"] = {n: dec_bf16_pack(w[block][n]) for n in names}
+    return w
 
 
 def _check_views(what, items):

@@ -66,7 +66,10 @@ def main():
     ap.add_argument("--tiles", action="store_true", help="time the search on the k17 and on the row-tiled decoder step, interleaved")
     ap.add_argument("--ancestry", action="store_true",
                     help="--select device: time the search with copied caches and with the ancestry table, interleaved")
+    ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
+                    help="--tiles: bf16 = time the search on the row-tiled step under decoder_precision f32 and bf16, interleaved")
     args = ap.parse_args()
+    assert args.precision == "f32" or (args.tiles and not args.ancestry), "--precision bf16 is a form of the row-tiled step: --tiles"
     assert not args.ancestry or args.select == "device", "--ancestry is about the rows re-ranked on the device: --select device"
     assert not args.prefix_baseline or args.batch == 1, "--prefix-baseline re-runs one pocket: --batch 1"
     import __graft_entry__
@@ -124,6 +127,25 @@ def main():
                                               "ancestry_ms_per_step": round(float(np.median(an)), 4),
                                               "copy_runs_ms": [round(x, 4) for x in cp], "ancestry_runs_ms": [round(x, 4) for x in an],
                                               "ancestry_faster": max(an) < min(cp), "copy_faster": max(cp) < min(an)}]}))
+        return
+    if args.tiles and args.precision == "bf16":
+        def timed(precision):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = search(model, voc, args.beams, args.batch, args.max_length, 1, pockets[0], prop, device=dev, graph=not args.no_graph,
+                       tiles=True, decoder_precision=precision).shape[1]
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (n - 1)
+        timed("f32"), timed("bf16")
+        f32, b16 = [], []
+        for _ in range(3):
+            f32.append(timed("f32"))
+            b16.append(timed("bf16"))
+        print(json.dumps({"select": args.select, "num_beams": args.beams, "pockets_per_call": args.batch, "max_length": args.max_length,
+                          "dec_bf16_table": [{"rows": args.beams * args.batch, "f32_ms_per_step": round(float(np.median(f32)), 4),
+                                              "bf16_ms_per_step": round(float(np.median(b16)), 4),
+                                              "f32_runs_ms": [round(x, 4) for x in f32], "bf16_runs_ms": [round(x, 4) for x in b16],
+                                              "bf16_faster": max(b16) < min(f32), "f32_faster": max(f32) < min(b16)}]}))
         return
     if args.tiles:
         def timed(tiles):

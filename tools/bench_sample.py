@@ -75,6 +75,9 @@ def main():
                          "2048 (tiles_table, tiles_distinct)")
     ap.add_argument("--tiles-only", type=int, default=0, metavar="ROWS",
                     help="nothing but two sample(tiles=True) generations of ROWS rows: the run to take a kernel trace of")
+    ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
+                    help="--tiles: bf16 = nothing but sample(tiles=True) under decoder_precision f32 and bf16, alternated three times "
+                         "at rows = 128, 512, 2048 (dec_bf16_table); --tiles-only: the decoder_precision of the two generations")
     ap.add_argument("--score-stream", action="store_true",
                     help="nothing but score on a row budget against score in chunks, and the forced step of the two slot searches")
     args = ap.parse_args()
@@ -117,11 +120,12 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / steps
 
-    def run_sample(rows, fused, grammar=None, forced=None, tiles=False):
+    def run_sample(rows, fused, grammar=None, forced=None, tiles=False, precision="f32"):
         tr = {}
         prop = torch.ones(rows, 3, device=dev)
         sample(model, voc, rows, 1, T, ex, prop, device=dev, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar, forced=forced, tiles=tiles)
+               suppress=() if grammar else ("$",), generator=gen, fused=fused, trace=tr, grammar=grammar, forced=forced, tiles=tiles,
+               decoder_precision=precision)
         run_sample.path = tr["path"]
         return tr["steps"]
 
@@ -133,8 +137,23 @@ def main():
                 "sequences_per_s": round(rows / (ms * (T - 1)) * 1e3, 2)}
 
     if args.tiles_only:
-        ms = [timed(lambda: run_sample(args.tiles_only, True, tiles=True)) for _ in range(2)]
-        print(json.dumps({"tiles_only_rows": args.tiles_only, "path": run_sample.path, "ms_per_step": [round(x, 4) for x in ms]}))
+        ms = [timed(lambda: run_sample(args.tiles_only, True, tiles=True, precision=args.precision)) for _ in range(2)]
+        print(json.dumps({"tiles_only_rows": args.tiles_only, "path": run_sample.path, "precision": args.precision,
+                          "ms_per_step": [round(x, 4) for x in ms]}))
+        return
+    if args.tiles and args.precision == "bf16":
+        table = []
+        for rows in (128, 512, 2048):
+            run = lambda p: run_sample(rows, True, tiles=True, precision=p)
+            run("f32"), run("bf16")                                            # one warm-up each, then three generations each, alternated
+            f32, b16 = [], []
+            for _ in range(3):
+                f32.append(timed(lambda: run("f32")))
+                b16.append(timed(lambda: run("bf16")))
+            table.append({"rows": rows, "f32_ms_per_step": round(statistics.median(f32), 4), "bf16_ms_per_step": round(statistics.median(b16), 4),
+                          "f32_runs_ms": [round(x, 4) for x in f32], "bf16_runs_ms": [round(x, 4) for x in b16],
+                          "bf16_faster": max(b16) < min(f32), "f32_faster": max(f32) < min(b16)})  # faster = the runs do not overlap
+        print(json.dumps({"max_length": T, "dec_bf16_table": table}))
         return
     if args.tiles:
         def both(fn, reps):
